@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the turbdiff denoising-diffusion hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one DDPM training step of the full turbdiff U-Net (dim 32, 4 levels, GroupNorm(8),
 c_local 4; 55.2 M parameters) on one synthetic batch of 192x64x48 (u, p) volumes:
@@ -9,6 +9,7 @@ GaussianDiffusion.forward (t ~ randint, q_sample, U-Net forward, masked l2 loss)
 + gradient all-reduce (N > 1) + clip-by-norm 0.1 + RAdam -- BASELINE.json configs[1] / [2].
 Inputs are resident in HBM before the timed region.  One JSON line is printed by rank 0:
   value        whole-job voxels/s = N * B * 192*64*48 * K / (max over ranks of the K-step time)
+  ms_per_step  milliseconds of one timed step (the same K-step time / K)
   roofline     the dominant kernel (MFMA implicit-GEMM 3x3x3 conv, forward launches): algorithmic
                FLOPs of all its launches / their HIP-event time, against the dense MFMA peak of the mode
   cpu_baseline the CPU oracle (a PyTorch-CPU port of the reference math, fp32) timed on the host cores on
@@ -23,6 +24,9 @@ Inputs are resident in HBM before the timed region.  One JSON line is printed by
                real_grid: the dataset's 194x50x50 grid at the reference batch (bf16, f32s);
                N > 1: overlap report of the gradient all-reduce and the sharded
                sampling leg of BASELINE configs[3] (8 trajectories per GPU)
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, roofline and kernels from the events
+of the timed region, traffic from the committed PMC file of this tree's kernels); cpu_baseline, live roofline.traffic and
+every extra leg run only with --full.  --dump-outputs DIR writes what the last timed step left its caller (dump_outputs).
 """
 
 import argparse
@@ -619,6 +623,26 @@ def deterministic_leg(diff, x, C, md, mode, B, cell_idx):
             "note": "TDX_DETERMINISTIC=1: ordered merges instead of fp32 atomics in the backward pass; two identical backward passes compared bit for bit"}
 
 
+DUMP_PARAM_SAMPLE = 1 << 22  # indices drawn for params_sample.npy (4.04 M distinct of the model's 55.2 M values: 16 MB of float32)
+
+
+def dump_outputs(out_dir, diff, loss, t):
+    """--dump-outputs: what the timed path's last step handed its caller -- diff(x, C, md) -> (loss, t), and the parameters the
+    optimiser step updated in place -- as out_dir/<name>.npy: loss.npy (float64, shape (1,)), t.npy (the diffusion times drawn,
+    float64, shape (B,)) and params_sample.npy (float32: DUMP_PARAM_SAMPLE values at fixed indices, drawn from a generator seeded
+    with 0 (repeats dropped, ascending), of all parameters flattened one after the other in named_parameters() order)."""
+    import numpy as np
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    flat = torch.cat([p.detach().float().flatten() for _, p in diff.named_parameters()])
+    idx = torch.randint(0, flat.numel(), (min(DUMP_PARAM_SAMPLE, flat.numel()),), generator=torch.Generator().manual_seed(0))
+    arrays = {"loss": loss.detach().double().reshape(1).cpu().numpy(), "t": t.detach().double().cpu().numpy(),
+              "params_sample": flat[idx.unique().to(flat.device)].cpu().numpy()}
+    del flat
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def _parse_cpulist(text):
     out = []
     for part in text.strip().split(","):
@@ -715,7 +739,18 @@ def main():
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not measure roofline.traffic in this run (two rocprofv3 --pmc child passes, ~1 min); quote the committed "
                          "PMC file of this tree's kernels instead")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline steps: CPU baseline + accuracy probe, live roofline.traffic, the "
+                         "instrumented per-kernel leg, parity modes, captured step, forward-only and sampling legs, cfg1, real grid, "
+                         "deterministic switch, cfg5 attention, stock PyTorch-ROCm leg, N > 1 overlap report (the --no-* options "
+                         "still drop legs from it).  Without it: set-up, warm-up, the timed steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (loss, diffusion times) and a fixed sample of the "
+                         "parameters it left as DIR/<name>.npy (float64 / float32, ~16 MB)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: the headline steps and their line only
+        args.no_cpu_baseline = args.no_extra = args.no_live_traffic = True
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC (RCCL's intra-node transport on this driver): before HIP starts
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -835,7 +870,7 @@ def main():
         scale_loss = getattr(opt, "scale_loss", lambda l: l)
 
         def train_step():
-            loss, _ = diff(x, C, md, None)
+            loss, t = diff(x, C, md, None)
             if ddp.timing:
                 ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
                 ev[0].record()
@@ -849,7 +884,7 @@ def main():
                 torch.nn.utils.clip_grad_norm_(diff.parameters(), 0.1)
             opt.step()
             opt.zero_grad(set_to_none=True)
-            return loss.detach()
+            return loss.detach(), t
 
         for _ in range(warmup):
             train_step()
@@ -861,7 +896,7 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
-            loss = train_step()
+            loss, t_last = train_step()
         run_mode.host_enqueue_ms = 1e3 * (time.perf_counter() - t0) / steps  # this rank's wall time to ISSUE a step
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
@@ -871,6 +906,7 @@ def main():
         if hasattr(opt, "settle"):
             opt.settle()
             run_mode.skipped = opt.skipped_steps  # fp16: steps whose gradients overflowed (0 = every timed step updated)
+        run_mode.last = (loss, t_last)  # what the last timed step returned (--dump-outputs)
         return elapsed, (kern, timer), loss.item(), train_step
 
     leg_done("build_model_and_accuracy_probe")
@@ -880,6 +916,8 @@ def main():
     elapsed, (kern, timer), last_loss, train_step = run_mode(args.dtype, K, Wm + 1, calls=FWD_CALLS, ddp_timing=False)
     headline_enqueue_ms = run_mode.host_enqueue_ms
     headline_skipped = getattr(run_mode, "skipped", None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), diff, *run_mode.last)
     leg_done("headline_steps")
     instrumented_ms = None
     if not args.no_extra:

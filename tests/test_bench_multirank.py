@@ -45,7 +45,7 @@ def test_bench_two_ranks_one_gpu():
     env = dict(os.environ, TDX_BENCH_BACKEND="gloo", TDX_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "1",
-           "--no-cpu-baseline", "--sample-steps", "3", "--sample-batch", "1"]
+           "--full", "--no-cpu-baseline", "--sample-steps", "3", "--sample-batch", "1"]
     out = _run_bench(cmd, env)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
@@ -70,7 +70,7 @@ def test_bench_bare_command_launches_its_own_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "1",
-           "--no-cpu-baseline", "--sample-steps", "0"]
+           "--full", "--no-cpu-baseline", "--sample-steps", "0"]
     out = _run_bench(cmd, env)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
@@ -106,7 +106,7 @@ def test_bench_data_parallel_legs_over_rccl_at_world_size_one():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         env["MASTER_PORT"] = str(s.getsockname()[1])
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline",
            "--sample-steps", "3", "--sample-batch", "1"]
     out = _run_bench(cmd, env)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -128,16 +128,17 @@ def test_bench_data_parallel_legs_over_rccl_at_world_size_one():
     assert d["extra"]["sampling"]["ddpm_samples_per_s_T1000"] > 0
 
 
-def test_bench_single_gpu_line_keeps_its_contract():
+def test_bench_single_gpu_line_keeps_its_contract(tmp_path):
     """`python bench.py` at N = 1 (short: no CPU baseline, no extra legs, traffic from the committed PMC file): ONE JSON line with
     the keys and meanings the driver reads -- BASELINE configs[1]'s metric on its workload, whole-job voxels/s consistent with
-    ms_per_step, the roofline block of the dominant kernel measured in the timed region."""
+    ms_per_step, the roofline block of the dominant kernel measured in the timed region; --dump-outputs writes the last timed
+    step's loss, diffusion times and parameter sample as float .npy files."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TDX_BENCH_FORCE_DDP", "TDX_BENCH_BACKEND",
               "TDX_BENCH_ONE_DEVICE"):
         env.pop(k, None)
     cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-extra",
-           "--no-live-traffic"]
+           "--no-live-traffic", "--dump-outputs", str(tmp_path / "dump")]
     out = _run_bench(cmd, env)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
@@ -155,3 +156,13 @@ def test_bench_single_gpu_line_keeps_its_contract():
     assert r["launches"] == 16 * 4 and r["avg_launch_ms"] > 0  # the brick / ring forward launches of the 4 timed steps
     assert r["algorithmic_bytes_per_launch"] > 1e8 and (r["traffic"] is None or r["traffic"] > r["algorithmic_bytes_per_launch"] * 0.9)
     assert 5.0 < d["ms_per_step"] < 200.0 and abs(d["loss"]) < 10.0
+    # a plain run carries none of the --full legs
+    assert "cpu_baseline" not in d and not set(d.get("extra", {})) - {"wall_s"}, sorted(d.get("extra", {}))
+    import numpy as np
+
+    dump = {f.stem: np.load(f) for f in (tmp_path / "dump").glob("*.npy")}
+    assert set(dump) == {"loss", "t", "params_sample"} and all(a.dtype in (np.float32, np.float64) for a in dump.values())
+    assert sum(a.nbytes for a in dump.values()) <= 64 << 20
+    assert dump["loss"].shape == (1,) and abs(dump["loss"][0] - d["loss"]) <= 1e-6 * abs(d["loss"])
+    assert dump["t"].shape == (6,) and ((dump["t"] >= 0) & (dump["t"] < 500)).all()
+    assert 4e6 < dump["params_sample"].size <= 1 << 22 and np.isfinite(dump["params_sample"]).all()

@@ -2,9 +2,9 @@
 # round-6 evidence: fp32-MFMA conv path and the ingress/egress kernels.  GPU box: bash tools/r06_profiles.sh
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r06; mkdir -p $O
 cd $R
-python bench.py --steps 5 --warmup 2 > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/r06_bench.json
-python bench.py --dtype f32 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_f32.log 2>&1; tail -1 $O/bench_f32.log > $O/r06_bench_f32.json
-python bench.py --dtype f32s --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_f32s.log 2>&1; tail -1 $O/bench_f32s.log > $O/r06_bench_f32s.json
+python bench.py --full --steps 5 --warmup 2 > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/r06_bench.json
+python bench.py --full --dtype f32 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_f32.log 2>&1; tail -1 $O/bench_f32.log > $O/r06_bench_f32.json
+python bench.py --full --dtype f32s --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_f32s.log 2>&1; tail -1 $O/bench_f32s.log > $O/r06_bench_f32s.json
 python tools/conv_bench.py --dtype f32 > $O/r06_conv3_f32_table.txt 2>&1
 python tools/conv_bench.py --dtype f32 --impl split > $O/r06_conv3_f32s_table.txt 2>&1
 python tests/report_accuracy.py > $O/r06_accuracy.txt 2>&1

@@ -2,7 +2,7 @@
 # Round-3 evidence (GPU box: bash tools/r10_profiles.sh): rocprofv3 stats + PMC passes of the bench command in the bf16 and
 # f32s modes (tools/collect_profiles.sh -> gpurun_out/prof_r10*; the weight gradients on the launching stream there, so that
 # every kernel's duration and counters are its own), the config-5 attention profile with fp16 operands, the per-layer conv
-# table, and two bench.py lines (default flags; --steps 20 --warmup 5 without the CPU / parity / PyTorch legs).
+# table, and two bench.py --full lines (default flags; --steps 20 --warmup 5 without the CPU / parity / PyTorch legs).
 # Summaries: python tools/summarize_profiles.py r10bf16 (and r10f32s) -> profiles/.
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r10p; mkdir -p $O
 cd $R
@@ -37,6 +37,6 @@ for k, c in pm.items():
           f"= {100*busy:.1f} % of the SIMD-cycles, clock {clk:.2f} GHz, HBM read {2*fetch*1024/1e6:.1f} MB = {2*fetch*1024/max(d,1):.3f} GB/s ({100*2*fetch*1024/max(d,1)/8000:.3f} % of 8 TB/s)")
 PY
 cd $R
-python bench.py > $O/r10_bench.json 2> $O/r10_bench.err
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-parity-modes --no-torch-baseline > $O/r10_bench_steps20_fullT.json 2> $O/r10_bench20.err
+python bench.py --full > $O/r10_bench.json 2> $O/r10_bench.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-parity-modes --no-torch-baseline > $O/r10_bench_steps20_fullT.json 2> $O/r10_bench20.err
 ls $O
