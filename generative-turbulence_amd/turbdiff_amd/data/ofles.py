@@ -101,6 +101,23 @@ class OpenFOAMMetadata:
         return Path(self.file).parent.name
 
     @property
+    def two_dimensional(self):
+        # because of the padding, one cell is actually three (ofles.py:121-124)
+        return int(np.min(self.cell_counts)) == 3
+
+    @property
+    def unpadded_cell_counts(self):
+        return np.asarray(self.cell_counts) - 2
+
+    @property
+    def unpadded_cell_idx(self):
+        """Flat indices of the in-domain cells into the unpadded (X-2, Y-2, Z-2) grid (ofles.py:131-139)."""
+        X, Y, Z = (int(c) for c in self.cell_counts)
+        idx = self.cell_idx.long()
+        x, y, z = idx // (Y * Z), (idx // Z) % Y, idx % Z
+        return ((x - 1) * (Y - 2) + (y - 1)) * (Z - 2) + (z - 1)
+
+    @property
     def inside_mask(self):
         mask = torch.zeros(tuple(int(c) for c in self.cell_counts), device=self.device, dtype=torch.bool)
         mask.flatten()[self.cell_idx] = True
@@ -378,6 +395,9 @@ class InMemoryRepository:
 
     def reset_caches(self):
         pass
+
+    def read_metadata(self, file_idx: int):
+        return self.cases[file_idx][0]
 
     def read(self, file_idx: int, samples):
         meta, times, fields = self.cases[file_idx]

@@ -5,8 +5,11 @@
 The spectrum's FFT is rocFFT (``torch.fft.fftn``); everything around it is two HIP kernels
 (``tdx_tke_energy``, ``tdx_tke_sphere``: csrc/tdx_metrics.hip).  The Lebedev rule comes from
 ``scipy.integrate.lebedev_rule`` (the same 5810 nodes and weights as the reference's ``numgrids.pickle`` up to
-their order; a reference checkpoint overwrites the ``p`` / ``w`` buffers with its own copy).  The Wasserstein
-part of the reference's metrics (POT's EMD) stays where it is: on the CPU, outside this package.
+their order; a reference checkpoint overwrites the ``p`` / ``w`` buffers with its own copy).
+
+The paper's sample metrics (``WassersteinTKE``, ``WassersteinMetric``, ``MaxMeanTKEPositionMetric`` under
+``SampleMetricsCollection``, metrics.py:122-196, 381-611) follow below; the exact W2 of their many large inner problems
+is the batched HIP auction of ``turbdiff_amd.ot`` (POT's EMD is not needed).
 """
 
 from __future__ import annotations
@@ -230,3 +233,251 @@ def _open_h5py(path, mode="r"):
         raise ImportError("HDF5 sample files need h5py (pip install h5py), or pass opener= (an object with h5py's File "
                           "interface); SampleStore.save('x.npz') needs nothing") from e
     return h5py.File(path, mode)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Sample-quality metrics of the paper (turbdiff/models/metrics.py:122-196, 381-581)
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _log():
+    import logging
+
+    return logging.getLogger("turbdiff_amd.metrics")
+
+
+def _side(metric, data, name: str, load):
+    """Side data of a case: ``metric.side[case_name][name]`` when given in memory, else ``load(path)`` of the file
+    ``name`` next to the case's data file (the reference's layout), else None."""
+    from pathlib import Path
+
+    per_case = (getattr(metric, "side", None) or {}).get(data.metadata.case_name, {})
+    if name in per_case:
+        return per_case[name]
+    path = Path(data.metadata.file).parent / name
+    return load(path) if path.is_file() else None
+
+
+def _load_mean_flow(path):
+    try:
+        import h5py
+    except ImportError:
+        _log().warning(f"Mean flow file {path} needs h5py, which is missing")
+        return None
+    with h5py.File(path, "r") as f:
+        import numpy as np
+
+        return np.array(f["data/u"])
+
+
+def wasserstein2_squared(D):
+    """``ot.emd2([], [], D**2)`` exactly, for a (small) matrix of distances D."""
+    import numpy as np
+
+    from ..ot import exact_emd2
+
+    return exact_emd2(np.asarray(D, dtype=np.float64) ** 2)
+
+
+def _wasserstein2(D):
+    import numpy as np
+
+    return np.sqrt(wasserstein2_squared(D))
+
+
+class WassersteinTKE(nn.Module):
+    """W2 between the log-TKE spectra of samples and data in three channel cubes (front, middle, back) and jointly
+    (metrics.py:381-476).  ``side``: optional {case_name: {"mean-flow.h5": (n_cells, 3) array}}."""
+
+    def __init__(self, side=None):
+        super().__init__()
+        from collections import defaultdict
+
+        self.distance = LogTKESpectrumL2Distance(TurbulentKineticEnergySpectrum())
+        self.case_data = defaultdict(dict)
+        self.side = side
+
+    def is_expensive(self):
+        return False
+
+    def forward(self, samples, data, stats):
+        import numpy as np
+
+        from ..data.ofles import OpenFOAMData
+        from ..data.ofles import Variable as V
+
+        if samples.two_dimensional:
+            return {}  # handling the 2D case everywhere is too much of a hassle (reference)
+        u_sample = samples.grid_embedding((V.U,))
+        u_data = data.grid_embedding((V.U,))
+        mean = _side(self, data, "mean-flow.h5", _load_mean_flow)
+        if mean is not None:
+            u_mean_data = u_sample.new_tensor(np.asarray(mean)).reshape(1, -1, 3)
+            u_mean = OpenFOAMData(data.metadata, samples.t[:1], {V.U: u_mean_data}).grid_embedding((V.U,))
+        else:
+            _log().warning(f"Mean flow file of case {data.metadata.case_name} is missing! Estimating mean from data samples.")
+            if u_data.shape[0] == 1:
+                _log().warning(f"Only a single data sample for case {data.metadata.case_name}. "
+                               "Mean flow estimate will be useless for TKE!")
+            u_mean = u_data.mean(dim=0)
+
+        u_sample = u_sample[..., 1:-1, 1:-1, 1:-1]
+        u_data = u_data[..., 1:-1, 1:-1, 1:-1]
+        u_mean = u_mean[..., 1:-1, 1:-1, 1:-1]
+        offset_multiplier = {"front": 3, "middle": 2, "back": 1}
+        width, length = min(u_sample.shape[-2:]), u_sample.shape[-3]
+        D_regions, distances = [], {}
+        for region in ["front", "middle", "back"]:
+            start = length - offset_multiplier[region] * width
+            cut = lambda t: torch.narrow(t, dim=-3, start=start, length=width).contiguous()
+            D_region, log_tke_sample, log_tke_data, k = self.distance(cut(u_sample), cut(u_data), cut(u_mean))
+            D_region = D_region.cpu().double().numpy()
+            self.case_data[region][data.metadata.case_name] = (log_tke_sample.cpu(), log_tke_data.cpu(), k.cpu())
+            distances[f"tke-{region}"] = torch.tensor(_wasserstein2(D_region))
+            D_regions.append(D_region)
+        D_combined = np.sqrt((np.stack(D_regions) ** 2).sum(axis=0))
+        distances["tke"] = torch.tensor(_wasserstein2(D_combined))
+        return distances
+
+
+class WassersteinMetric(nn.Module):
+    """Per-cell W2 over the regions of ``regions.npz`` with features u, curl u, p (metrics.py:479-567), the paper's
+    headline sample metric.  The n x m x K inner problems run in ONE batched device auction (``ot.auction_w2``); the
+    host gets n*m*K numbers back and solves the small outer n x m problem exactly.
+    ``side``: optional {case_name: {"regions.npz": (n_cells,) region assignments}}."""
+
+    def __init__(self, side=None, rel_eps=None):
+        super().__init__()
+        self.side = side
+        self.rel_eps = rel_eps
+
+    def is_expensive(self):
+        return True
+
+    def forward(self, samples, data, stats):
+        import numpy as np
+
+        regions_data = _side(self, data, "regions.npz", lambda p: np.load(p)["assignments"])
+        if regions_data is None:
+            _log().warning(f"Regions file of case {data.metadata.case_name} is missing, can't compute Wasserstein metric!")
+            return {}
+        D = self.region_distances(samples, data, stats, np.asarray(regions_data))
+        counts = np.bincount(np.asarray(regions_data))
+        weights = counts.astype(float) / counts.sum()
+        D = np.sqrt(np.einsum("ijk,k -> ij", D, weights))
+        return {"wasserstein": torch.tensor(_wasserstein2(D))}
+
+    def region_distances(self, samples, data, stats, regions):
+        """(n, m, K) W2^2 of every (sample, data sample, region); regions of weight 0 stay 0."""
+        import numpy as np
+
+        from .. import ot
+
+        regions = np.asarray(regions).astype(np.int64)
+        counts = np.bincount(regions)
+        order = np.argsort(regions, kind="stable")
+        offsets = np.concatenate(([0], np.cumsum(counts)))
+        n, m, K = samples.n_samples, data.n_samples, len(counts)
+        jobs = np.array([(i, j, k) for k in range(K) if counts[k] > 0 for i in range(n) for j in range(m)], dtype=np.int64)
+        D = np.zeros((n, m, K))
+        if len(jobs):
+            kw = {} if self.rel_eps is None else {"rel_eps": self.rel_eps}
+            res = ot.auction_w2(self.features(samples, stats), self.features(data, stats), order, offsets, jobs, **kw)
+            D[jobs[:, 0], jobs[:, 1], jobs[:, 2]] = res.primal
+            self.last_jobs, self.last_result = jobs, res  # per-job bids, certificate (tools/ot_bench.py)
+        return D
+
+    def features(self, data, stats):
+        """Normalised per-cell features [u, curl u, p] / std, (S, n_cells, 8) with a zero 8th lane (the reference's
+        (S, n_cells, 7) padded for 32-byte rows)."""
+        from .. import ot
+        from ..data.ofles import Variable as V
+
+        _, std = stats.normalizers((V.U, V.CURL, V.P), mode="u:norm-std;curl:norm-std;p:mean-std")
+        dev = data.samples[V.U].device
+        return ot.features(data.grid_embedding((V.U,)), data.samples[V.U], data.samples[V.P],
+                           data.metadata.unpadded_cell_idx.to(dev), std.to(dev), data.metadata.h)
+
+
+class MaxMeanTKEPositionMetric(nn.Module):
+    """Squared error of the position of the maximum of the mean TKE profile behind the obstacle (metrics.py:584-611).
+    ``side``: optional {case_name: {"max-mean-tke.npy": float}}."""
+
+    def __init__(self, side=None):
+        super().__init__()
+        self.side = side
+
+    def is_expensive(self):
+        return False
+
+    def forward(self, samples, data, stats):
+        import numpy as np
+
+        from ..data.ofles import Variable as V
+
+        gt = _side(self, data, "max-mean-tke.npy", np.load)
+        if gt is None:
+            _log().warning(f"Ground-truth max-mean-TKE file of case {data.metadata.case_name} is missing!")
+            return {}
+        gt = float(np.asarray(gt))
+        u_sample = samples.grid_embedding((V.U,))
+        u_mean = u_sample.mean(dim=0)  # estimating the mean flow is part of the task: from the samples
+        u_fluc = (u_sample - u_mean)[..., 24:, :, :]
+        tke = 0.5 * (u_fluc**2).sum(dim=-4)
+        estimate = tke.mean(dim=(-1, -2)).argmax(dim=1).float().mean() + 24
+        return {"max-mean-tke-pos": (gt - estimate) ** 2}
+
+
+class SampleMetricsCollection(nn.Module):
+    """Metrics over the samples of a ``SampleStore`` against data samples of each case (metrics.py:122-196).
+    ``repository(case_name)`` gives the case's data repository (default: ``OpenFOAMDataRepository`` on
+    ``data_dir/case_name/data.h5``; an ``InMemoryRepository`` works as well)."""
+
+    def __init__(self, prefix: str = "val", data_dir=None, metrics=(), repository=None):
+        super().__init__()
+        self.prefix = prefix
+        self.data_dir = data_dir
+        self.metrics = nn.ModuleList(metrics)
+        self.repository = repository
+
+    def _repository(self, case_name, variables):
+        from pathlib import Path
+
+        from ..data.ofles import OpenFOAMDataRepository
+
+        if self.repository is not None:
+            return self.repository(case_name)
+        return OpenFOAMDataRepository([Path(self.data_dir) / case_name / "data.h5"], variables)
+
+    def compute(self, sample_store, stats, device, *, expensive_metrics: bool = True):
+        import numpy as np
+
+        from ..data.ofles import OpenFOAMData
+
+        values, metric_names = {}, set()
+        case_names = sample_store.case_names
+        stats = stats.to(device)
+        for case_name in case_names:
+            repo = self._repository(case_name, sample_store.variables)
+            samples = sample_store.load_samples(repo.read_metadata(0))
+            if samples.n_samples == 0:
+                continue
+            # data samples evenly spread over the second half of the simulation (fully developed turbulence)
+            n_data = len(repo.times[0])
+            data_idx = np.round(np.linspace(n_data // 2, n_data - 1, num=samples.n_samples)).astype(int)
+            data = repo.read(0, data_idx)
+            to_dev = lambda d: OpenFOAMData(d.metadata.to(device), d.t.to(device),
+                                            {v: s.to(device) for v, s in d.samples.items()})
+            data, samples = to_dev(data), to_dev(samples)
+            for metric in self.metrics:
+                if not expensive_metrics and metric.is_expensive():
+                    continue
+                for name, value in metric(samples, data, stats).items():
+                    values[self.log_name(case_name, name)] = value
+                    metric_names.add(name)
+        for metric_name in metric_names:
+            per_case = [values[self.log_name(c, metric_name)] for c in case_names if self.log_name(c, metric_name) in values]
+            values[f"{self.prefix}/{metric_name}"] = torch.mean(torch.stack([torch.as_tensor(v).to(device) for v in per_case]))
+        return values
+
+    def log_name(self, case: str, metric: str):
+        return f"{self.prefix}/{case}/{metric}"

@@ -46,25 +46,18 @@ ACTFNS = {"silu": nn.SiLU, "gelu": nn.GELU, "relu": nn.ReLU, "softplus": nn.Soft
 N_CELL_TYPES = 6  # inside, outside, walls, inlets, outlets, empties (cell_type_embeddings.py:30-38)
 
 
-class _Holder(nn.Module):
-    """Empty module used to reproduce nested state_dict paths."""
-
-
 def _metric_placeholders():
-    """`{val,test}_sample_metrics.metrics.0.distance.*` buffers of the reference task
-    (models/metrics.py); evaluation metrics are out of scope, the buffers only keep checkpoints
-    strict-loadable (legendre_* hold the real Gauss-Legendre rule, tke_spectrum the device implementation of
-    the reference's TurbulentKineticEnergySpectrum with the same Lebedev rule)."""
-    nodes, weights = np.polynomial.legendre.leggauss(64)
-    coll = _Holder()
-    coll.metrics = nn.ModuleList([_Holder()])
-    dist = _Holder()
-    dist.register_buffer("legendre_nodes", torch.tensor(nodes, dtype=torch.float32))
-    dist.register_buffer("legendre_weights", torch.tensor(weights, dtype=torch.float32))
-    from .models.metrics import TurbulentKineticEnergySpectrum
+    """The reference task's sample metrics, ``SampleMetricsCollection([WassersteinTKE(), WassersteinMetric(),
+    MaxMeanTKEPositionMetric()])`` (models/metrics.py): their state is the `{val,test}_sample_metrics.metrics.0.distance.*`
+    buffers that keep the reference's checkpoints strict-loadable (legendre_* the Gauss-Legendre rule, tke_spectrum the
+    device implementation of TurbulentKineticEnergySpectrum with the same Lebedev rule)."""
+    from .models.metrics import MaxMeanTKEPositionMetric, SampleMetricsCollection, WassersteinMetric, WassersteinTKE
 
-    dist.tke_spectrum = TurbulentKineticEnergySpectrum()  # 5810-node Lebedev rule, the device spectrum (§8 f3)
-    coll.metrics[0].distance = dist
+    coll = SampleMetricsCollection(metrics=[WassersteinTKE(), WassersteinMetric(), MaxMeanTKEPositionMetric()])
+    nodes, weights = np.polynomial.legendre.leggauss(64)  # the values this task has always carried
+    dist = coll.metrics[0].distance
+    dist.legendre_nodes.copy_(torch.tensor(nodes, dtype=torch.float32))
+    dist.legendre_weights.copy_(torch.tensor(weights, dtype=torch.float32))
     return coll
 
 

@@ -397,6 +397,41 @@ int tdx_tke_energy(const float* u, float* tke, int B, int64_t V, void* stream);
 int tdx_tke_sphere(const float* fft, const float* p, const float* w, const float* k, float* E, int B, int X, int Y, int Z,
                    int N, int K, void* stream);
 
+/* Finite differences of turbdiff/metrics.py:9-92 (tdx_fd.hip).  u: padded velocity grid (B, 3, X, Y, Z) f32, X, Y, Z >= 3;
+ * every derivative is the centred (u[i+1] - u[i-1]) / two_h[axis] (two_h = fp32(2 h)) at the unpadded interior:
+ *   TDX_FD_CURL       out (B, 3, X-2, Y-2, Z-2) = (duz/dy - duy/dz, dux/dz - duz/dx, duy/dx - dux/dy)
+ *   TDX_FD_DIVERGENCE out (B, 1, X-2, Y-2, Z-2) = dux/dx + duy/dy + duz/dz
+ *   TDX_FD_ENSTROPHY  out (B, 1, X-2, Y-2, Z-2) = |curl u|^2 * dv   (dv = prod(h), the cell volume)
+ * tdx_ot_features: WassersteinMetric.features (turbdiff/models/metrics.py:570-586) for S samples: out (S, n_cells, 8) =
+ * [u_cells (S, n_cells, 3), curl u at unpadded_idx (n_cells, flat index into (X-2, Y-2, Z-2)), p_cells (S, n_cells, 1)]
+ * divided lane by lane by scale[0..6], lane 7 = 0.  The curl is evaluated at the listed cells only. */
+#define TDX_FD_CURL 0
+#define TDX_FD_DIVERGENCE 1
+#define TDX_FD_ENSTROPHY 2
+int tdx_fd(const float* u, float* out, int B, int X, int Y, int Z, float two_hx, float two_hy, float two_hz, float dv,
+           int mode, void* stream);
+int tdx_ot_features(const float* u_grid, const float* u_cells, const float* p_cells, const int64_t* unpadded_idx,
+                    const float* scale, float* out, int S, int64_t n_cells, int X, int Y, int Z, float two_hx, float two_hy,
+                    float two_hz, void* stream);
+
+/* Batched exact W2^2 by the epsilon-scaling auction (tdx_ot.hip).  fa (Sa, n_cells, 8), fb (Sb, n_cells, 8) f32 features;
+ * region k = cells idx[offsets[k] .. offsets[k+1]) (int32, every idx < n_cells); jobs (J, 3) int32 (i, j, k).  Job (i, j, k)
+ * assigns region k of fa[i] to region k of fb[j] at cost c_pq = ||fa[i, p] - fb[j, q]||^2 (fp32, never materialised).
+ * out (J, 4) f64: [primal (1/n) sum c_{p sigma(p)}, dual bound (1/n)[sum_p min_q (c_pq + pi_q) - sum_q pi_q], eps_final,
+ * bids]; 0 <= primal - dual <= eps_final = rel_eps * S, S = (1/n) sum over both sets of |x - pooled mean|^2.
+ * status (J) int32: TDX_OT_OK, or the cap that stopped the job (max_rounds rounds in one phase, max_bids bids in the
+ * job; primal and dual are then NaN).  workspace: tdx_ot_workspace_bytes(max_n, slots) bytes, max_n >= the largest
+ * region, slots = workgroups (each walks the job list with its own slice); results do not depend on slots. */
+#define TDX_OT_OK 0
+#define TDX_OT_ROUND_CAP 1
+#define TDX_OT_BID_CAP 2
+#define TDX_OT_BAD_JOB 3
+#define TDX_OT_NONFINITE 4
+size_t tdx_ot_workspace_bytes(int max_n, int slots);
+int tdx_ot_auction(const float* fa, const float* fb, int64_t n_cells, const int* idx, const int* offsets, int K,
+                   const int* jobs, int J, int Sa, int Sb, double rel_eps, int max_rounds, int64_t max_bids,
+                   void* workspace, int max_n, int slots, double* out, int* status, void* stream);
+
 /* Counter-based N(0,1) generator (Philox4x32-10 + Box-Muller), graph-replay safe: the
  * 64-bit offset is read from device memory and advanced by the kernel itself.
  * Replaces torch.randn_like (ddpm.py:777,801,810,835) inside captured sampling graphs.

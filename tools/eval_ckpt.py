@@ -11,8 +11,13 @@ Flow, step for step as in the reference: load the checkpoint -> take the run con
 Differences, all on the I/O side (no h5py / POT in this image): validation cases come from ``--cases`` (a
 ``torch.save``d list of ``(OpenFOAMMetadata, times, {Variable: (T, n_cells, dims)})`` tuples plus the statistics, see
 ``turbdiff_amd.data.ofles.InMemoryRepository``) or are synthesised; the store lives in memory and is written as one
-``.npz``; of the reference's metrics the log-TKE-spectrum L2 distance runs here (on the device), the Wasserstein
-ones need POT.
+``.npz``.  By default it prints the log-TKE-spectrum L2 distance (``val/log_tke_l2``, computed on the device), which no
+paper table reports; ``--sample-metrics`` adds the reference's own ``SampleMetricsCollection`` metrics without the
+expensive one (``tke-front``, ``tke-middle``, ``tke-back``, ``tke``, ``max-mean-tke-pos``, as the reference's
+eval_ckpt.py computes them with ``expensive_metrics=False``), ``--expensive-metrics`` also ``wasserstein`` (exact W2 by
+the batched device auction).  Their side files (``regions.npz``, ``max-mean-tke.npy``, ``mean-flow.h5``) come from an
+optional ``side`` entry of the ``--cases`` blob, ``{case_name: {file name: value}}``; ``--synthetic`` cases bring their
+own (channel-aligned region blocks, a nominal max-mean-TKE position).
 """
 
 import argparse
@@ -77,6 +82,50 @@ def synthetic_cases(n_cases, grid=(48, 32, 32), n_times=12, seed=0):
     return cases, stats
 
 
+def synthetic_side(cases, n_regions=8):
+    """Side data of synthetic cases: regions = ``n_regions`` contiguous blocks of cells along the channel, the
+    max-mean-TKE position at a third of the channel length."""
+    from turbdiff_amd.data.ofles import Variable
+
+    side = {}
+    for meta, _, fields in cases:
+        n = fields[Variable.U].shape[1]
+        side[meta.case_name] = {"regions.npz": (np.arange(n) * n_regions // n).astype(np.int64),
+                                "max-mean-tke.npy": float(int(meta.cell_counts[0]) // 3)}
+    return side
+
+
+def add_curl_statistics(cases, stats, device):
+    """The ``norm(curl)`` record of the statistics (WassersteinMetric's feature scale), from every sample of the cases."""
+    from turbdiff_amd.data.ofles import OpenFOAMData, Variable
+    from turbdiff_amd.metrics import curl
+
+    norms = []
+    for meta, times, fields in cases:
+        m = meta.to(device)
+        d = OpenFOAMData(m, torch.as_tensor(times, device=device), {v: f.to(device) for v, f in fields.items()})
+        c = curl(d.grid_embedding((Variable.U,)), meta.h).flatten(-3)[..., m.unpadded_cell_idx]  # (T, 3, n_cells)
+        norms.append(c.norm(dim=1).reshape(-1).cpu())
+    n = torch.cat(norms)
+    stats.stats["norm(curl)"] = {"mean": n.mean(), "std": n.std(), "min": n.min(), "max": n.max()}
+    stats._normalizers.clear()
+    return stats
+
+
+def sample_metrics(store, cases, stats, device, *, side=None, expensive=False, prefix="val"):
+    """The reference's SampleMetricsCollection over the stored samples, the case data held in memory."""
+    from turbdiff_amd.data.ofles import InMemoryRepository
+    from turbdiff_amd.models.metrics import (MaxMeanTKEPositionMetric, SampleMetricsCollection, WassersteinMetric,
+                                             WassersteinTKE)
+
+    repos = {c[0].case_name: InMemoryRepository([c]) for c in cases}
+    coll = SampleMetricsCollection(prefix, None, [WassersteinTKE(side=side), WassersteinMetric(side=side),
+                                                  MaxMeanTKEPositionMetric(side=side)], repository=repos.__getitem__).to(device)
+    if "norm(curl)" not in stats.stats:
+        stats = add_curl_statistics(cases, stats, device)
+    return {k: float(v) for k, v in coll.compute(store, stats, device, expensive_metrics=expensive).items()}
+
+
 def evaluate(ckpt: dict, cases, stats, device, *, overrides=(), seed=2883413570083077179, samples_path=None,
              eval_batch_size=None, val_samples=2, discard_first_seconds=0.0, start_from=None, compute_mode=None):
     """The body of eval_ckpt.py:43-76.  Returns (store, metrics dict, task)."""
@@ -138,6 +187,8 @@ def main():
     ap.add_argument("--synthetic", type=int, default=0, help="evaluate on N synthetic cases instead")
     ap.add_argument("--start-from", type=int, default=None, help="start the reverse process at this step (smoke runs)")
     ap.add_argument("--compute-mode", default=None, choices=[None, "f32", "f32s", "bf16", "fp16"])
+    ap.add_argument("--sample-metrics", action="store_true", help="also print the reference's cheap sample metrics")
+    ap.add_argument("--expensive-metrics", action="store_true", help="with --sample-metrics, also the Wasserstein metric")
     ap.add_argument("ckpt", help="Path to .ckpt file")
     ap.add_argument("samples_path", help=".npz file for storing samples")
     ap.add_argument("overrides", nargs="*")
@@ -149,11 +200,18 @@ def main():
         from turbdiff_amd.data.ofles import OpenFOAMStats
 
         blob = torch.load(args.cases, weights_only=False)
-        cases, stats = blob["cases"], OpenFOAMStats(blob["stats"])
+        cases, stats, side = blob["cases"], OpenFOAMStats(blob["stats"]), blob.get("side")
+    elif args.sample_metrics or args.expensive_metrics:
+        # long enough for WassersteinTKE's three channel cubes and the max-mean-TKE window behind x = 24
+        cases, stats = synthetic_cases(max(args.synthetic, 1), grid=(64, 18, 18))
+        side = synthetic_side(cases)
     else:
         cases, stats = synthetic_cases(max(args.synthetic, 1))
-    _, metrics, _ = evaluate(ckpt, cases, stats, torch.device(args.device), overrides=args.overrides, seed=args.seed,
-                             samples_path=samples_path, start_from=args.start_from, compute_mode=args.compute_mode)
+    device = torch.device(args.device)
+    store, metrics, _ = evaluate(ckpt, cases, stats, device, overrides=args.overrides, seed=args.seed,
+                                 samples_path=samples_path, start_from=args.start_from, compute_mode=args.compute_mode)
+    if args.sample_metrics or args.expensive_metrics:
+        metrics.update(sample_metrics(store, cases, stats, device, side=side, expensive=args.expensive_metrics))
     for key in sorted(metrics):
         print(f"{key}: {metrics[key]}")
 
