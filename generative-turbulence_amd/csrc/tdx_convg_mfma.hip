@@ -40,10 +40,12 @@ struct ConvGM {
 // the accumulator row rho = 8 j + 4 hh + i (register 4 j + i of lane half hh) holds channel 16 hh + 4 j + i
 __device__ __forceinline__ int cgm_row_channel(int rho) { return 16 * ((rho >> 2) & 1) + 4 * (rho >> 3) + (rho & 3); }
 
-template <bool TRANSPOSED, int NT>
+// EPI: the fused epilogues of the DilResNet chain (TdxConvgEpilogue, include/tdx.h; tdx_convg_chain.hip); EPI = false is the
+// plain `acc + bias` store of tdx_convg_apply
+template <bool TRANSPOSED, int NT, bool EPI>
 __global__ void __launch_bounds__(256, 2)
 convg_mfma_kernel(const bf16* __restrict__ in, const float* __restrict__ w, const float* __restrict__ bias, bf16* __restrict__ out,
-                  ConvGM g) {
+                  ConvGM g, TdxConvgEpilogue e) {
     constexpr int BN = 32 * NT;
     constexpr int WBUF = (CGM_KCH / 8) * BN * 16;  // one weight stage: [k group][channel][8] bf16
     __shared__ __attribute__((aligned(16))) unsigned char sW[2 * WBUF];
@@ -188,6 +190,88 @@ convg_mfma_kernel(const bf16* __restrict__ in, const float* __restrict__ w, cons
     }
 
     // ---- epilogue: lane (r, hh) holds channels n0 + 32 nt + 16 hh + (0..15) of its voxel in registers 0..15
+    if constexpr (EPI) {
+        const int64_t V = (int64_t)g.Eo[0] * g.Eo[1] * g.Eo[2];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int ch = n0 + 32 * nt + 16 * hh;
+            if (ch >= g.Cout) continue;
+            float bv[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) bv[i] = (bias != nullptr && ch + i < g.Cout) ? bias[ch + i] : 0.f;
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                if (!live[mt]) continue;
+                const int64_t vox = orow[mt];
+                if (e.x != nullptr) {
+                    // rollout update (the host guarantees Cout <= 16, so channels 0..15 sit in the lanes with ch == 0):
+                    // x_next = inside ? x + dx_mean + dx_std (acc + bias) : x in fp32, and its bf16 copy padded with zeros
+                    if (ch != 0) continue;
+                    const bool upd = e.inside[vox % V] != 0;
+                    const float* xs = e.x + vox * e.F;
+                    float* xn = e.x_next + vox * e.F;
+                    float nx[16];
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        nx[i] = 0.f;
+                        if (i < e.F) {
+                            const float xv = xs[i];
+                            nx[i] = upd ? xv + (e.dx_mean[i] + e.dx_std[i] * (acc[nt][mt][i] + bv[i])) : xv;
+                            xn[i] = nx[i];
+                        }
+                    }
+#pragma unroll
+                    for (int h8 = 0; h8 < 2; ++h8) {
+                        if (8 * h8 >= g.Cout) continue;
+                        Vec8<bf16> v;
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) v.v[i] = nx[8 * h8 + i];
+                        v.store(out + vox * g.Cout + 8 * h8);
+                    }
+                    continue;
+                }
+#pragma unroll
+                for (int h8 = 0; h8 < 2; ++h8) {
+                    if (ch + 8 * h8 >= g.Cout) continue;
+                    const int64_t off = vox * g.Cout + ch + 8 * h8;
+                    float v[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        v[i] = acc[nt][mt][8 * h8 + i] + bv[8 * h8 + i];
+                        if (e.relu) v[i] = fmaxf(v[i], 0.f);
+                    }
+                    if (e.h != nullptr) {
+                        Vec8<bf16> hv;
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) hv.v[i] = v[i];
+                        hv.store(reinterpret_cast<bf16*>(e.h) + off);
+                    }
+                    const void* adds[2] = {e.add0, e.add1};
+#pragma unroll
+                    for (int a = 0; a < 2; ++a) {
+                        if (adds[a] == nullptr) continue;
+                        const int64_t aoff = ((e.add_bcast >> a) & 1) ? (vox % V) * g.Cout + ch + 8 * h8 : off;
+                        Vec8<bf16> av;
+                        av.load(reinterpret_cast<const bf16*>(adds[a]) + aoff);
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) v[i] += av.v[i];
+                    }
+                    if (e.out_f32) {
+                        Vec8<float> ov;
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) ov.v[i] = v[i];
+                        ov.store(reinterpret_cast<float*>(out) + off);
+                    } else {
+                        Vec8<bf16> ov;
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) ov.v[i] = v[i];
+                        ov.store(out + off);
+                    }
+                }
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         const int ch = n0 + 32 * nt + 16 * hh;
@@ -210,8 +294,9 @@ convg_mfma_kernel(const bf16* __restrict__ in, const float* __restrict__ w, cons
     }
 }
 
-int convg_mfma_apply(const void* in, const float* w, const float* bias, void* out, int B, const int* Ei, const int* Eo, int Cin,
-                     int Cout, int k, int stride, int dil, int pad, int replicate, int transposed, hipStream_t st) {
+static int convg_mfma_launch(const void* in, const float* w, const float* bias, void* out, int B, const int* Ei, const int* Eo,
+                             int Cin, int Cout, int k, int stride, int dil, int pad, int replicate, int transposed,
+                             const TdxConvgEpilogue* ep, hipStream_t st) {
     ConvGM g;
     g.B = B;
     for (int a = 0; a < 3; ++a) { g.Ei[a] = Ei[a]; g.Eo[a] = Eo[a]; }
@@ -222,12 +307,26 @@ int convg_mfma_apply(const void* in, const float* w, const float* bias, void* ou
     g.cls_blocks = ceil_div(mc, CGM_ROWS);
     const int nt = Cout > 32 ? 2 : 1;
     dim3 grid((unsigned)(g.cls_blocks * g.cs * g.cs * g.cs), (unsigned)ceil_div(Cout, 32 * nt));
-#define CGM_GO(TR, NTV) \
-    hipLaunchKernelGGL((convg_mfma_kernel<TR, NTV>), grid, dim3(256), 0, st, (const bf16*)in, w, bias, (bf16*)out, g)
-    if (transposed) { if (nt == 2) CGM_GO(true, 2); else CGM_GO(true, 1); }
-    else            { if (nt == 2) CGM_GO(false, 2); else CGM_GO(false, 1); }
+    TdxConvgEpilogue e = {};
+    if (ep != nullptr) e = *ep;
+#define CGM_GO(TR, NTV, EP) \
+    hipLaunchKernelGGL((convg_mfma_kernel<TR, NTV, EP>), grid, dim3(256), 0, st, (const bf16*)in, w, bias, (bf16*)out, g, e)
+    if (ep != nullptr) { if (nt == 2) CGM_GO(false, 2, true); else CGM_GO(false, 1, true); }
+    else if (transposed) { if (nt == 2) CGM_GO(true, 2, false); else CGM_GO(true, 1, false); }
+    else                 { if (nt == 2) CGM_GO(false, 2, false); else CGM_GO(false, 1, false); }
 #undef CGM_GO
     return tdx_launch_status();
+}
+
+int convg_mfma_apply(const void* in, const float* w, const float* bias, void* out, int B, const int* Ei, const int* Eo, int Cin,
+                     int Cout, int k, int stride, int dil, int pad, int replicate, int transposed, hipStream_t st) {
+    return convg_mfma_launch(in, w, bias, out, B, Ei, Eo, Cin, Cout, k, stride, dil, pad, replicate, transposed, nullptr, st);
+}
+
+// gather form (stride 1) with a fused epilogue: the caller (tdx_convg_apply_fused) has checked the options
+int convg_mfma_apply_epilogue(const void* in, const float* w, const float* bias, void* out, int B, const int* Ei, const int* Eo,
+                              int Cin, int Cout, int k, int dil, int pad, int replicate, const TdxConvgEpilogue* ep, hipStream_t st) {
+    return convg_mfma_launch(in, w, bias, out, B, Ei, Eo, Cin, Cout, k, 1, dil, pad, replicate, 0, ep, st);
 }
 
 // ------------------------------------------------------------------------------------------ weight gradient

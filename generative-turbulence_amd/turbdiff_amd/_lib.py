@@ -89,6 +89,8 @@ SIGNATURES = {
     "tdx_convg_apply": (_i, [_vp, _vp, _vp, _vp] + [_i] * 16 + [_vp]),
     "tdx_convg_fold_clamp": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "tdx_convg_bwd_weight": (_i, [_vp, _vp, _vp, _vp] + [_i] * 15 + [_vp]),
+    "tdx_convg_apply_fused": (_i, [_vp, _vp, _vp, _vp] + [_i] * 13 + [_vp, _i, _vp]),
+    "tdx_convg_fold_fused": (_i, [_vp] * 6 + [_i] * 7 + [_vp]),
     "tdx_film_supported": (_i, [_i, _i]),
     "tdx_film_fwd": (_i, [_vp, _i, _i, _vp, _i, _vp]),
     "tdx_film_bwd_workspace_bytes": (_sz, [_i, _i, _vp, _i]),

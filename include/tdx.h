@@ -567,6 +567,45 @@ int tdx_convg_bwd_weight(const void* in, const void* dy, float* dw, float* dbias
                          int Xo, int Yo, int Zo, int Cout, int k, int stride, int dilation, int pad, int replicate,
                          int dtype, void* stream);
 
+/* ------------------------------------------------------------------ DilResNet chain (tdx_convg_chain.hip)
+ * Fused epilogues of the replicate-padded gather conv (stride 1, bf16 tensors, matrix cores) for the DilResNet baseline
+ * (dilresnet.py:47-94).  With z = acc + bias (fp32) at every output voxel and channel:
+ *     r    = relu ? max(z, 0) : z
+ *     h    = r                       (bf16 copy, when h != NULL: the block's last layer keeps it for its ReLU mask)
+ *     out  = r + add0 + add1         (each addend bf16 NDHWC (B, Xo, Yo, Zo, Cout); with bit a of add_bcast set, addend a is
+ *                                     one (Xo, Yo, Zo, Cout) grid shared by the batch), stored fp32 when out_f32 != 0
+ * Rollout-update mode (x != NULL; Cout <= 16, F <= Cout; relu / addends / h ignored), the decode conv of
+ * DilResNetTraining._predict_x (dilresnet.py:191-197):
+ *     x_next[b, o, f] = inside[o] ? x + dx_mean[f] + dx_std[f] z[f] : x      f < F, fp32 NDHWC (B, Xo, Yo, Zo, F)
+ *     out[b, o, :]    = bf16 (x_next, zeros up to Cout): the next step's encode input.  x_next may equal x. */
+typedef struct TdxConvgEpilogue {
+    int relu;
+    const void* add0;
+    const void* add1;
+    int add_bcast;
+    void* h;
+    int out_f32;
+    const float* x;
+    float* x_next;
+    const unsigned char* inside; /* (Xo, Yo, Zo), nonzero = updated */
+    const float* dx_mean;
+    const float* dx_std;
+    int F;
+} TdxConvgEpilogue;
+/* out = epilogue(gather(in, w) + bias), stride 1, bf16 only (TDX_EDTYPE otherwise); ep == NULL is tdx_convg_apply. */
+int tdx_convg_apply_fused(const void* in, const float* w, const float* bias, void* out, int B, int Xi, int Yi, int Zi, int Cin,
+                          int Xo, int Yo, int Zo, int Cout, int k, int dilation, int pad, int replicate,
+                          const TdxConvgEpilogue* ep, int dtype, void* stream);
+/* Backward fold of a replicate-padded conv with the chain's elementwise tail, bf16 tensors, fp32 arithmetic:
+ *     t[b, i]   = sum of dpad[b, q] over the padded positions q (grid E + 2 pad) that clamp onto i   (tdx_convg_fold_clamp)
+ *                 + res[b, i]                                 (res != NULL: the residual path's gradient)
+ *     dx        = t                                           (bf16, when dx != NULL)
+ *     dx_masked = mask_src[b, i] > 0 ? t : 0                  (bf16, when mask_src != NULL: ReLU backward of the producer)
+ *     acc[i]   += sum over b of t[b, i]                       (fp32 (X, Y, Z, C), when acc != NULL; batch order, no atomics)
+ * All tensors NDHWC with C % 8 == 0. */
+int tdx_convg_fold_fused(const void* dpad, const void* res, const void* mask_src, void* dx, void* dx_masked, float* acc, int B,
+                         int X, int Y, int Z, int pad, int C, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
