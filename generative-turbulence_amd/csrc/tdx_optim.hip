@@ -224,12 +224,15 @@ __global__ void __launch_bounds__(OPT_THREADS) stage_scaled_kernel(const StageAr
 extern "C" int tdx_stage_scaled(const TdxStageItem* items, int n_items, float scale, void* stream) {
     TDX_CHECK_ARG(items || n_items == 0);
     TDX_CHECK_ARG(n_items >= 0);
-    for (int base = 0; base < n_items; base += TDX_STAGE_MAX_ITEMS) {
+    // one launch per TDX_STAGE_MAX_ITEMS NON-EMPTY items; `next` is where the last launch stopped reading (empty items take no
+    // slot, so a pass may read more than TDX_STAGE_MAX_ITEMS inputs: every input is staged exactly once -- an in-place item
+    // staged twice would be scaled twice)
+    for (int next = 0; next < n_items;) {
         StageArgs a;
         a.n = 0;
         a.scale = scale;
         int blocks = 0;
-        for (int i = base; i < n_items && a.n < TDX_STAGE_MAX_ITEMS; ++i) {
+        for (int& i = next; i < n_items && a.n < TDX_STAGE_MAX_ITEMS; ++i) {
             TDX_CHECK_ARG(items[i].n >= 0 && (items[i].dst || items[i].n == 0));
             if (items[i].n == 0) continue;
             const int64_t nb = (items[i].n + STAGE_CHUNK - 1) / STAGE_CHUNK;

@@ -10,7 +10,8 @@ fp32 state) through ``tdx_grad_norm`` / ``tdx_radam_step`` (csrc/tdx_optim.hip).
 It is a ``torch.optim.Optimizer``: ``param_groups[i]["lr"]`` is honoured every step (LR schedulers
 work), and the per-parameter state uses torch's RAdam keys (``step``, ``exp_avg``, ``exp_avg_sq``) with
 per-parameter step counts (parameters at different counts are updated in one launch per count), so
-optimizer state_dicts move between the two implementations.
+optimizer state_dicts move between the two implementations (``state_dict()`` settles the step counts first and carries
+the loss-scaling state under a top-level key of its own, ``loss_scaling``, which torch's ``load_state_dict`` ignores).
 
 Loss scaling (fp16 training, ``loss_scale=``): the backward pass runs on ``scale_loss(loss) = S * loss`` (S a power of two) so
 that fp16 activation gradients stay representable; the stored fp32 parameter gradients are then S times the true ones.
@@ -88,6 +89,38 @@ class ClipRAdam(torch.optim.Optimizer):
         `skipped_steps` and the per-parameter step counts reflect all steps taken."""
         if self.loss_scale is not None:
             self._settle_flags(self._step_index + 1, wait=True)
+
+    def state_dict(self):
+        """torch's layout (``state`` with ``step`` / ``exp_avg`` / ``exp_avg_sq`` per parameter, ``param_groups``), settled first:
+        the step counts saved are those of the steps that happened, also within the two-step lag behind an overflow.  The
+        loss-scaling state travels under a third top-level key, ``loss_scaling``, which ``torch.optim.Optimizer.load_state_dict``
+        does not read: the same dictionary loads into ``torch.optim.RAdam``.  Like ``settle()``, this waits for the
+        outstanding flags, so a run that checkpoints continues from settled counters -- as the run resumed from the checkpoint does."""
+        self.settle()
+        sd = super().state_dict()
+        # (the live step counters are views into one tensor that step() increments in place: hand out copies)
+        sd["state"] = {k: {n: (v.clone() if n == "step" and torch.is_tensor(v) else v) for n, v in st.items()}
+                       for k, st in sd["state"].items()}
+        if self.loss_scale is not None:
+            sd["loss_scaling"] = {"loss_scale": float(self.loss_scale), "clean_steps": int(self._clean_steps),
+                                  "skipped_steps": int(self.skipped_steps), "step_index": int(self._step_index)}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """A ``state_dict()`` of this class or of ``torch.optim.RAdam``.  With loss scaling on, ``loss_scaling`` (if the dictionary
+        has it) restores the scale, the clean-step count towards its next doubling, the skipped-step count and the step index;
+        a dictionary without it (torch's) leaves them as they are.  Flags of steps taken before the call are dropped: they
+        belong to the state that is being replaced."""
+        for _, _, ev, _ in self._flags:
+            ev.synchronize()  # (their pinned landing slots are reused by the steps to come)
+        self._flags.clear()
+        super().load_state_dict(state_dict)
+        extra = state_dict.get("loss_scaling")
+        if extra is not None and self.loss_scale is not None:
+            self.loss_scale = float(extra["loss_scale"])
+            self._clean_steps = int(extra["clean_steps"])
+            self.skipped_steps = int(extra["skipped_steps"])
+            self._step_index = int(extra["step_index"])
 
     # one plan per parameter group: chunk tables (static) + pointer table (refreshed every step)
     def _plan(self, gi, group):

@@ -302,10 +302,27 @@ class BucketedDataParallel:
         flag = torch.zeros(16, dtype=torch.int32).pin_memory()
         self._cap = {"gen": gen, "flag": flag, "order": []}
 
+    def capture_flush(self):
+        """Still inside the capture, behind the captured backward: capture the staging kernel of every bucket that received
+        gradients but did not fill up -- a bucket that also holds a parameter whose gradient arrives eagerly after the replay
+        (the learned cell-type table, chained behind the graph) or a parameter that receives none.  Every replay then
+        refreshes those slices from the gradients the graph has just written; the eager hook, or finish(), stages the rest
+        of the bucket and launches it."""
+        if self._cap is None:
+            return
+        for b in range(len(self._buckets)):
+            if b not in self._launched:
+                self._flush(b)
+
     def end_capture(self):
         """-> the plan replay_launch() needs for every replay of the graph just captured (None when inactive)."""
         if self._cap is None:
             return None
+        if any(self._staged):
+            # (gradient, slice) pairs left here would be staged ONCE, by the first eager launch of their bucket, and never
+            # again: from the second replay on the bucket would carry -- and all-reduce again -- an old step's gradients
+            raise RuntimeError("BucketedDataParallel.end_capture: gradients staged during the capture were not captured; call "
+                               "capture_flush() inside the capture, after backward()")
         cap, self._cap = self._cap, None
         per_bucket = {}
         for i in self._seen:

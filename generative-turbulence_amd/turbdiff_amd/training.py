@@ -541,6 +541,10 @@ class GraphedTrainingStep:
                 if ddp is not None:
                     slot.gen.add_(1)
                 slot.loss = body().detach()  # (no autograd graph outlives the capture: its nodes belong to this stream)
+                if ddp is not None:
+                    # the bucket the chained parameters (or parameters without a gradient) share with captured ones does not
+                    # fill up in here: its staging is captured now, so that every replay refreshes it
+                    ddp.capture_flush()
         finally:
             ops.WGRAD_STREAM = fork
         if ddp is not None:

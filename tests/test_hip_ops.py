@@ -958,6 +958,151 @@ def test_clip_radam_loss_scaling_unscales_skips_and_adapts():
     assert all(abs(n - (part if i % 2 else full)) < 1e-4 for i, n in zip([0, 1, 2, 5, 6, 7, 8, 9, 10, 11], norms)), norms
 
 
+_LS_SHAPES = [(5,), (17, 3), (40000,), (9, 2)]
+_LS_BAD = {3: float("inf"), 4: float("nan")}  # the overflow steps of the 12-step schedule
+
+
+def _ls_schedule(d):
+    """The synthetic schedule of the test above: 12 steps of unscaled gradients, alternately large and small."""
+    gen = torch.Generator().manual_seed(9)
+    return [[(torch.randn(s, generator=gen) * (2.0 if step % 2 else 0.02)).to(d) for s in _LS_SHAPES] for step in range(12)]
+
+
+def _ls_scaled_step(opt, params, grads, step):
+    """One step of the loss-scaling optimiser: gradients S times too large, parameter 3 only on even steps, an overflow in
+    parameter 2 on the bad steps."""
+    S = opt.loss_scale
+    for k, (p, g) in enumerate(zip(params, grads[step])):
+        p.grad = None if (k == 3 and step % 2 == 1) else g * S
+    if step in _LS_BAD:
+        params[2].grad[123] = _LS_BAD[step]
+    opt.step()
+
+
+def _ls_reference_step(opt, params, grads, step):
+    """The reference: clip_grad_norm_ + torch.optim.RAdam on the unscaled gradients; an overflow step does not happen."""
+    if step in _LS_BAD:
+        return
+    for k, (p, g) in enumerate(zip(params, grads[step])):
+        p.grad = None if (k == 3 and step % 2 == 1) else g.clone()
+    torch.nn.utils.clip_grad_norm_(params, 0.5)
+    opt.step()
+
+
+def _ls_params(d):
+    gen = torch.Generator().manual_seed(4)
+    return [torch.randn(s, generator=gen).to(d).requires_grad_() for s in _LS_SHAPES]
+
+
+def _through_a_file(sd):
+    """What a checkpoint does to a state_dict: torch.save / torch.load (no tensor shared with the live optimiser)."""
+    import io
+
+    buf = io.BytesIO()
+    torch.save(sd, buf)
+    buf.seek(0)
+    return torch.load(buf)
+
+
+def _ls_optimizer(params, loss_scale=2.0**12):
+    from turbdiff_amd.optim import ClipRAdam
+
+    return ClipRAdam(params, lr=1e-2, max_norm=0.5, loss_scale=loss_scale, scale_growth_interval=4)  # lazy flags (the default)
+
+
+@pytest.mark.parametrize("k", [5, 8])
+def test_clip_radam_state_dict_holds_settled_step_counts(k):
+    """A state_dict() taken after step k of the schedule -- k = 5: right behind the two overflows, inside the two-step lag of
+    their flags -- holds the step counts torch.optim.RAdam holds at that point (the skipped steps taken out), and the
+    loss-scaling state of all k steps."""
+    d = torch.device("cuda:0")
+    grads = _ls_schedule(d)
+    pa, pb = _ls_params(d), _ls_params(d)
+    oa, ob = torch.optim.RAdam(pa, lr=1e-2), _ls_optimizer(pb)
+    for step in range(k):
+        _ls_reference_step(oa, pa, grads, step)
+        _ls_scaled_step(ob, pb, grads, step)
+    sa, sb = oa.state_dict(), ob.state_dict()
+    want = {5: [3, 3, 3, 2], 8: [6, 6, 6, 3]}[k]
+    assert [int(sa["state"][i]["step"]) for i in range(4)] == want
+    assert [float(sb["state"][i]["step"]) for i in range(4)] == [float(w) for w in want]
+    # k = 5: flags 1-3 clean, 4 and 5 skipped; k = 8: three more clean steps
+    assert sb["loss_scaling"] == {"loss_scale": 2.0**10, "clean_steps": {5: 0, 8: 3}[k], "skipped_steps": 2, "step_index": k}
+    for i in range(4):
+        assert torch.allclose(sa["state"][i]["exp_avg_sq"], sb["state"][i]["exp_avg_sq"], rtol=1e-4, atol=1e-12)
+
+
+@pytest.mark.parametrize("k", [5, 8])
+def test_clip_radam_resumed_from_a_checkpoint_equals_the_run_that_went_on(k):
+    """Loss-scaling mode, flags read lazily: a run takes a checkpoint (state_dict() + parameters) after step k and goes on; a
+    fresh optimiser on copies of the parameters loads the checkpoint and runs the remaining steps.  The arithmetic is the
+    same, so everything is EQUAL: parameters after every step, moments, per-parameter step counts, loss scale, skipped and
+    clean step counts.  (state_dict() settles the outstanding flags -- the run that goes on continues from settled counters,
+    like the resumed one; k = 5 is inside the two-step lag behind the overflows of steps 3 and 4.)"""
+    d = torch.device("cuda:0")
+    grads = _ls_schedule(d)
+    pa = _ls_params(d)
+    oa = _ls_optimizer(pa)
+    trace = {}
+    for step in range(12):
+        if step == k:
+            saved = _through_a_file(oa.state_dict())
+            saved_params = [p.detach().clone() for p in pa]
+        _ls_scaled_step(oa, pa, grads, step)
+        trace[step] = [p.detach().clone() for p in pa]
+    pb = [p.clone().requires_grad_() for p in saved_params]
+    ob = _ls_optimizer(pb)  # starts at the initial scale; the checkpoint must bring the scale of step k
+    ob.load_state_dict(saved)
+    for step in range(k, 12):
+        _ls_scaled_step(ob, pb, grads, step)
+        for i, (b, a) in enumerate(zip(pb, trace[step])):
+            assert torch.equal(b.detach(), a), (step, i, (b.detach() - a).abs().max().item())
+    oa.settle()
+    ob.settle()
+    assert (ob.loss_scale, ob.skipped_steps, ob._clean_steps) == (oa.loss_scale, oa.skipped_steps, oa._clean_steps) == (2.0**11, 2, 3)
+    for i, (a, b) in enumerate(zip(pa, pb)):
+        sa, sb = oa.state[a], ob.state[b]
+        assert float(sa["step"]) == float(sb["step"]) == [10, 10, 10, 5][i], (i, float(sa["step"]), float(sb["step"]))
+        assert torch.equal(sa["exp_avg"], sb["exp_avg"]) and torch.equal(sa["exp_avg_sq"], sb["exp_avg_sq"]), i
+
+
+def test_clip_radam_state_dicts_interchange_with_torch_radam_under_loss_scaling():
+    """The module's promise with loss scaling on, at k = 5 (behind the overflows): (a) a ClipRAdam state_dict loads into
+    torch.optim.RAdam -- its loss-scaling entry sits where torch does not look -- and torch goes on as the reference that
+    ran from the start does; (b) a torch.optim.RAdam state_dict loads into a loss-scaling ClipRAdam, which goes on as torch
+    does and keeps its own scale (the dictionary has none)."""
+    d = torch.device("cuda:0")
+    grads = _ls_schedule(d)
+    k = 5
+    pr, pc = _ls_params(d), _ls_params(d)
+    ref, oc = torch.optim.RAdam(pr, lr=1e-2), _ls_optimizer(pc)
+    for step in range(k):
+        _ls_reference_step(ref, pr, grads, step)
+        _ls_scaled_step(oc, pc, grads, step)
+    from_clip, from_torch = _through_a_file(oc.state_dict()), _through_a_file(ref.state_dict())
+    # (a) ClipRAdam -> torch
+    pt = [p.detach().clone().requires_grad_() for p in pc]
+    ot = torch.optim.RAdam(pt, lr=1e-2)
+    ot.load_state_dict(from_clip)
+    # (b) torch -> ClipRAdam, at a scale of its own
+    pd = [p.detach().clone().requires_grad_() for p in pr]
+    od = _ls_optimizer(pd, loss_scale=2.0**10)
+    od.load_state_dict(from_torch)
+    for step in range(k, 12):
+        _ls_reference_step(ref, pr, grads, step)
+        _ls_reference_step(ot, pt, grads, step)
+        _ls_scaled_step(od, pd, grads, step)
+        for i, r in enumerate(pr):
+            assert torch.allclose(pt[i], r, rtol=3e-6, atol=2e-7), ("clip->torch", step, i, (pt[i] - r).abs().max().item())
+            assert torch.allclose(pd[i], r, rtol=3e-6, atol=2e-7), ("torch->clip", step, i, (pd[i] - r).abs().max().item())
+    od.settle()
+    assert od.loss_scale == 2.0**11 and od.skipped_steps == 0 and od._clean_steps == 3  # seven clean steps from 2^10
+    for i, r in enumerate(pr):
+        assert float(ref.state[r]["step"]) == float(ot.state[pt[i]]["step"]) == float(od.state[pd[i]]["step"]) == [10, 10, 10, 5][i], i
+        for other in (ot.state[pt[i]], od.state[pd[i]]):
+            assert torch.allclose(ref.state[r]["exp_avg_sq"], other["exp_avg_sq"], rtol=1e-4, atol=1e-12), i
+
+
 def test_clip_radam_with_bucket_view_gradients():
     """Gradients that are views into a flat all-reduce bucket (parallel.BucketedDataParallel.finish) are
     only 4-byte aligned: the fused optimiser must not assume 16-byte alignment."""
@@ -1019,6 +1164,76 @@ def test_stage_scaled_moves_a_bucket_in_one_launch():
         bad = (L.StageItem * 1)()
         bad[0].src, bad[0].dst, bad[0].n = srcs[0].data_ptr(), None, 1
         L.call("tdx_stage_scaled", bad, 1, 1.0, L.stream())
+
+
+def _stage_case(kinds, sizes, scale, d):
+    """One tdx_stage_scaled call over items of the given kinds ("copy": src != dst, "inplace": src == dst, "null": src NULL ->
+    zeros, "empty": n == 0) whose destinations are slices of one NaN-filled buffer at odd element offsets (4-byte alignment
+    only) with one NaN guard element between neighbours; every slice bit-exact against torch.mul, every guard still NaN."""
+    from turbdiff_amd import _lib as L
+
+    assert len(kinds) == len(sizes)
+    gen = torch.Generator().manual_seed(len(kinds))
+    sizes = [0 if kind == "empty" else n for kind, n in zip(kinds, sizes)]
+    flat = torch.full((1 + sum(n + 1 for n in sizes),), float("nan"), device=d)
+    guard = torch.ones(flat.numel(), dtype=torch.bool)
+    tab, checks, off = (L.StageItem * len(kinds))(), [], 1
+    for k, (kind, n) in enumerate(zip(kinds, sizes)):
+        v = flat[off : off + n]
+        guard[off : off + n] = False
+        off += n + 1
+        g = torch.randn(n, generator=gen).to(d)
+        if kind == "inplace":
+            v.copy_(g)
+            tab[k].src = v.data_ptr()
+        elif kind == "null":
+            v.fill_(7.0)  # must be overwritten with zeros
+            tab[k].src = None
+        else:
+            tab[k].src = g.data_ptr()
+        tab[k].dst, tab[k].n = v.data_ptr(), n
+        checks.append((k, kind, v, torch.zeros_like(g) if kind == "null" else torch.mul(g, scale), g))  # (g: the source stays alive)
+    L.call("tdx_stage_scaled", tab, len(kinds), scale, L.stream())
+    torch.cuda.synchronize()
+    wrong = [(k, kind, v.numel()) for k, kind, v, want, _ in checks if not torch.equal(v, want)]
+    assert not wrong, f"items staged wrongly (position, kind, size): {wrong}"
+    assert torch.isnan(flat[guard.to(d)]).all(), "written outside the slices"
+
+
+@pytest.mark.parametrize("n_empty", [1, 2, 3, 70])
+def test_stage_scaled_scales_in_place_items_once_across_launch_boundaries(n_empty):
+    """A launch holds 64 NON-EMPTY items; empty items take no slot, so a pass reads more than 64 inputs when some are empty,
+    and the next pass has to go on where this one stopped -- not 64 inputs after its start, which stages the overlap a
+    second time.  For src != dst that is invisible; a gradient that already lives in its slice (src == dst) would be scaled
+    twice.  In-place items at and around input positions 63, 64, 65, 127 and 128, `n_empty` empty items in front of them in
+    the first pass, scale 1 / 3 (not idempotent): every one scaled exactly once."""
+    d = torch.device("cuda:0")
+    around = {p + o for p in (63, 64, 65, 127, 128) for o in (-1, 0, 1)} | set(range(n_empty + 60, n_empty + 70))
+    n_items = 140 + n_empty
+    empties = set(range(2, 2 + n_empty)) - around if n_empty < 10 else set(range(40, 40 + n_empty)) - around
+    assert len(empties) >= min(n_empty, 20) and max(empties) < 63 + n_empty
+    kinds = ["empty" if k in empties else "inplace" if k in around else "copy" for k in range(n_items)]
+    sizes = [5 + 7 * (k % 11) if k % 9 else 8192 + k for k in range(n_items)]
+    _stage_case(kinds, sizes, 1.0 / 3.0, d)
+
+
+@pytest.mark.parametrize("kinds", [["empty"] * 65, ["empty"] * 200, ["inplace", "copy"] + ["empty"] * 130,
+                                   ["copy"] * 64 + ["empty"] * 3, ["empty"] * 64 + ["inplace"], ["empty"] * 100 + ["inplace"] * 70 + ["empty"]],
+                         ids=["65-empty", "200-empty", "ends-in-130-empty", "full-launch-then-empty", "64-empty-then-one", "empty-both-ends"])
+def test_stage_scaled_lists_of_empty_items(kinds):
+    """More than 64 empty items in a row (alone, in front of and behind real items), lists that end in empty items."""
+    _stage_case(kinds, [33 + k for k in range(len(kinds))], 1.0 / 3.0, torch.device("cuda:0"))
+
+
+def test_stage_scaled_mixed_list_of_250_items():
+    """250 items mixing missing gradients (src NULL), in-place, ordinary and empty items, 4-byte alignment only, sizes on both
+    sides of a block's 8192 elements; the NaN guard elements between the slices stay NaN."""
+    gen = torch.Generator().manual_seed(5)
+    pick = torch.randint(0, 8, (250,), generator=gen).tolist()
+    kinds = [("null", "inplace", "inplace", "empty", "copy", "copy", "copy", "inplace")[p] for p in pick]
+    assert min(kinds.count(k) for k in ("null", "inplace", "empty", "copy")) >= 15
+    sizes = [[1, 3, 17, 8191, 8192, 8193, 260, 20001][(k * 5 + p) % 8] for k, p in enumerate(pick)]
+    _stage_case(kinds, sizes, 1.0 / 3.0, torch.device("cuda:0"))
 
 
 @pytest.mark.parametrize("C,src,dst", [(24, (5, 4, 3), (9, 9, 17)), (8, (3, 3, 3), (20, 7, 30)), (64, (13, 9, 10), (6, 4, 5)),
