@@ -14,9 +14,14 @@
 //               dS^T = exp2(S^T - lse) o (dP^T - delta)          per-lane lse, delta
 //               dQ^T += K^T dS^T        (K^T fragments: transposed LDS reads of the row-major K tile)
 //   dK/dV kernel  workgroup = 256 keys, walks the queries in staged tiles of 64 (Q, dO, lse, delta):
-//               S  = Q K^T,  dP = dO V^T   (K pre-scaled and V resident as B operands)
+//               S  = Q K^T,  dP = dO V^T   (K and V resident as B operands; Q pre-scaled by log2(e)/sqrt(D) when staged)
 //               P  = exp2(S - lse_row),  dS = P o (dP - delta_row)     per-register lse, delta
 //               dV^T += dO^T P,  dK^T += Q^T dS   (dO^T / Q^T fragments: transposed LDS reads)
+//
+// The operand that carries log2(e)/sqrt(D), rounded to the format once more, is Q in ALL kernels, with the forward's own
+// expression: the saved log-sum-exp belongs to the forward's scores, and exp2(S' - lse) is a row of probabilities only if S'
+// are those scores bit for bit in their operands.  (Scaling K in the dK/dV pass instead would move every score by an
+// independent 2^-9 |s| in bf16: with |s| ~ 50-200 the recomputed rows sum to 1 +- 0.2 -- tests/test_attention_backward.py.)
 //
 // 6 + 8 MFMAs per 32 x 32 tile against the forward's 4; no atomics, no running maximum.
 #include "tdx_common.h"
@@ -99,6 +104,12 @@ __device__ __forceinline__ typename E::V8 fb_row_frag(const typename E::T* row, 
 #pragma unroll
     for (int e = 0; e < 4; ++e) w[e] = E::pack2(v.v[2 * e] * scale, v.v[2 * e + 1] * scale);
     return __builtin_bit_cast(typename E::V8, make_uint4(w[0], w[1], w[2], w[3]));
+}
+
+// one staged 16-B piece (8 elements) times `scale`, rounded to the format: the forward's expression on Q, so the bits agree
+template <typename E>
+__device__ __forceinline__ uint4 fb_scale_piece(const uint4& piece, float scale) {
+    return __builtin_bit_cast(uint4, fb_row_frag<E>(reinterpret_cast<const typename E::T*>(&piece), scale));
 }
 
 // ------------------------------------------------------------------ dQ ---------------------------
@@ -236,16 +247,17 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
     const int ld = 3 * H * FB_D;
     const typename E::T* base = qkv + (int64_t)b * N * ld;
     const int j0 = blockIdx.x * FB_RB + wave * RW;
-    const float sm_scale = rsqrtf((float)FB_D);
+    const float qscale = FB_LOG2E * rsqrtf((float)FB_D);
+    const float dk_scale = 0.6931471805599453f;  // ln 2 = (1/sqrt(D)) / (log2(e)/sqrt(D)): the staged Q carries the rest
 
-    typename E::V8 kf[TW][2], vf[TW][2];  // K (pre-scaled) and V as B operands: col = key r, k = d
+    typename E::V8 kf[TW][2], vf[TW][2];  // K and V as stored, as B operands: col = key r, k = d
     f32x16 dk[TW], dv[TW];        // dK^T[d][key], dV^T[d][key]
 #pragma unroll
     for (int kt = 0; kt < TW; ++kt) {
         const int key = min(j0 + kt * 32 + r, N - 1);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            kf[kt][ks] = fb_row_frag<E>(base + (int64_t)key * ld + H * FB_D + h * FB_D + ks * 16 + hh * 8, FB_LOG2E * sm_scale);
+            kf[kt][ks] = fb_row_frag<E>(base + (int64_t)key * ld + H * FB_D + h * FB_D + ks * 16 + hh * 8, 1.0f);
             vf[kt][ks] = fb_row_frag<E>(base + (int64_t)key * ld + 2 * H * FB_D + h * FB_D + ks * 16 + hh * 8, 1.0f);
         }
 #pragma unroll
@@ -271,8 +283,11 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
     load_tile(0);
     for (int i0 = 0; i0 < N; i0 += T) {
         __syncthreads();
-        *reinterpret_cast<uint4*>(sQ + fb_sw64(st_row, st_c)) = qreg;
-        *reinterpret_cast<uint4*>(sQp + st_row * 64 + st_c * 16) = qreg;
+        // Q enters LDS as the forward's operand, round(q * log2(e)/sqrt(D)): the scores are the forward's, and the Q^T
+        // fragments of dK^T += Q^T dS carry the factor too (taken out again in the epilogue)
+        const uint4 qs = fb_scale_piece<E>(qreg, qscale);
+        *reinterpret_cast<uint4*>(sQ + fb_sw64(st_row, st_c)) = qs;
+        *reinterpret_cast<uint4*>(sQp + st_row * 64 + st_c * 16) = qs;
         *reinterpret_cast<uint4*>(sG + fb_sw64(st_row, st_c)) = greg;
         *reinterpret_cast<uint4*>(sGp + st_row * 64 + st_c * 16) = greg;
         if (tid < T) { sL[tid] = lreg; sD[tid] = dreg; }
@@ -327,7 +342,7 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
             }
         }
     }
-    // dK[key][..] = scale * dK^T, dV[key][..] = dV^T;  lane holds d = (i & 3) + 8 (i >> 2) + 4 hh
+    // dK[key][..] = ln 2 * dK^T (Q^T was pre-scaled), dV[key][..] = dV^T;  lane holds d = (i & 3) + 8 (i >> 2) + 4 hh
 #pragma unroll
     for (int kt = 0; kt < TW; ++kt) {
         const int key = j0 + kt * 32 + r;
@@ -337,8 +352,8 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 *reinterpret_cast<uint2*>(okp + 8 * j + 4 * hh) =
-                    make_uint2(E::pack2(dk[kt][4 * j] * sm_scale, dk[kt][4 * j + 1] * sm_scale),
-                               E::pack2(dk[kt][4 * j + 2] * sm_scale, dk[kt][4 * j + 3] * sm_scale));
+                    make_uint2(E::pack2(dk[kt][4 * j] * dk_scale, dk[kt][4 * j + 1] * dk_scale),
+                               E::pack2(dk[kt][4 * j + 2] * dk_scale, dk[kt][4 * j + 3] * dk_scale));
                 *reinterpret_cast<uint2*>(ovp + 8 * j + 4 * hh) =
                     make_uint2(E::pack2(dv[kt][4 * j], dv[kt][4 * j + 1]), E::pack2(dv[kt][4 * j + 2], dv[kt][4 * j + 3]));
             }

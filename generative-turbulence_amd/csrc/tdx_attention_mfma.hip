@@ -61,12 +61,10 @@ struct AttnF16 {
     typedef f16 T;
     typedef f16x8 V8;
     static __device__ __forceinline__ unsigned pack2(float a, float b) { return pack_f16x2(a, b); }
-    // probabilities (in [0, 1], consumed at once by the next MFMA): one v_cvt_pkrtz_f16_f32 -- the kernel is bound by
-    // its vector-ALU work, round-to-nearest costs three instructions per pair
-    static __device__ __forceinline__ unsigned packp(float a, float b) {
-        const auto h = __builtin_amdgcn_cvt_pkrtz(a, b);
-        return *reinterpret_cast<const unsigned*>(&h);
-    }
+    // probabilities: round to nearest, one v_cvt_pk_f16_f32 per pair on gfx950.  Not v_cvt_pkrtz_f16_f32: truncation makes
+    // every row sum, and with it the exported log-sum-exp, 3.5e-4 too small -- that cancels in O, but the backward normalises
+    // its round-to-nearest probabilities by that lse and its rows would sum to 1 + 3.5e-4 (test_attention_backward.py)
+    static __device__ __forceinline__ unsigned packp(float a, float b) { return pack_f16x2(a, b); }
     static __device__ __forceinline__ f32x16 mfma(V8 a, V8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ f32x4 mfma16(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ float unpack_lo(unsigned w) {

@@ -43,7 +43,7 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
     return *reinterpret_cast<const unsigned*>(&h);
 }
 
-// two floats -> packed fp16 pair, round to nearest even (v_cvt_f16_f32 x2 + v_pack_b32_f16)
+// two floats -> packed fp16 pair, round to nearest even: one v_cvt_pk_f16_f32 on gfx950
 __device__ __forceinline__ unsigned pack_f16x2(float lo, float hi) {
     typedef __attribute__((ext_vector_type(2))) float f32x2_t;
     typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;

@@ -12,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from attention_cases import growing_scores_qkv
 from conftest import rel_l2
 from oracle import turbdiff_oracle as O
 
@@ -689,14 +690,7 @@ def test_attention_growing_scores_and_loose_norm_bound(dtype, tol, N, monkeypatc
     from turbdiff_amd import ops
 
     B, H, D = 2, 4, 32
-    g = torch.Generator().manual_seed(5)
-    q = torch.randn(B, N, H, D, generator=g) * torch.logspace(-1, 0.7, N).reshape(1, N, 1, 1)[:, torch.randperm(N, generator=g)]
-    u = torch.nn.functional.normalize(torch.randn(B, 1, H, D, generator=g), dim=-1)
-    ramp = torch.linspace(-6.0, 6.0, N).reshape(1, N, 1, 1)
-    k = torch.randn(B, N, H, D, generator=g) * 0.3 + u * ramp          # scores grow with the key index for q along +u
-    q = q + 2.0 * u * (torch.rand(B, N, H, 1, generator=g) > 0.5)       # half of the queries look along +u
-    k[:, N // 3] = 40.0 * torch.nn.functional.normalize(torch.randn(B, H, D, generator=g), dim=-1)  # the outlier
-    v = torch.randn(B, N, H, D, generator=g)
+    q, k, v = growing_scores_qkv(B, N, H, D, seed=5)
     qkv = torch.cat([t.reshape(B, N, H * D) for t in (q, k, v)], dim=-1).to(dtype)
     qd, kd, vd = (t.reshape(B, N, H, D).transpose(1, 2).double() for t in qkv.chunk(3, dim=-1))
     ref = O.sdpa(qd, kd, vd).transpose(1, 2).reshape(B, N, H * D)
