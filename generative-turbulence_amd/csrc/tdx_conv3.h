@@ -1,8 +1,8 @@
-// Internal interface between tdx_conv3_direct.hip (entry points, vector-ALU kernels) and
-// tdx_conv3_mfma.hip (bf16 MFMA implicit-GEMM kernels).
+// Internal interface of the 3x3x3 convolution: the route (which kernel serves a call), the call records the launchers
+// take, and the launchers of every kernel family.  tdx_conv3_entry.hip holds the entry points of include/tdx.h and the
+// route; tdx_conv3_direct.hip weight packing and the vector-ALU kernels; every other tdx_conv3_*.hip one kernel family.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "tdx_common.h"
 
 struct Conv3Geom {
     int B;
@@ -25,15 +25,7 @@ static inline int conv3_layout_kc(int dtype, int K, int N) {
     return conv3_mfma_f32_supported(K, 0, N) ? 8 : 0;
 }
 static inline bool conv3_uses_mfma_layout(int dtype, int K, int N) { return (dtype == 1 || dtype == 3) && conv3_mfma_supported(K, 0, N); }
-// split-precision (bf16 hi + lo) MFMA forward / zero-padded data gradient for fp32 tensors (tdx_conv3_mfma_split.hip)
 bool conv3_mfma_split_supported(int C1, int C2, int Cout);
-int conv3_mfma_split_launch(const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* y,
-                            const Conv3Geom& g, int Cout, bool zero_pad, hipStream_t st, double* gn_acc = nullptr,
-                            void* d1 = nullptr, int D1 = 0, void* d2 = nullptr, const void* a1 = nullptr, const void* a2 = nullptr);
-// fp32 MFMA forward / zero-padded data gradient (tdx_conv3_mfma_f32.hip)
-int conv3_mfma_f32_launch(const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* y,
-                          const Conv3Geom& g, int Cout, bool zero_pad, hipStream_t st, double* gn_acc = nullptr,
-                          void* d1 = nullptr, int D1 = 0, void* d2 = nullptr, const void* a1 = nullptr, const void* a2 = nullptr);
 
 // optional extras of the MFMA forward: input row strides (0: dense) and a tensor the accumulators
 // start from ([B][V][Cout] bf16, or [V][Cout] shared by the batch)
@@ -42,48 +34,167 @@ struct Conv3Ext {
     const void* init;
     bool init_shared;
 };
-int conv3_mfma_launch(const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* y,
-                      const Conv3Geom& g, int Cout, bool zero_pad, hipStream_t st, double* gn_acc = nullptr,
-                      void* d1 = nullptr, int D1 = 0, void* d2 = nullptr, const void* a1 = nullptr,
-                      const void* a2 = nullptr, const Conv3Ext* ext = nullptr, const int* slabs_beyond = nullptr,
-                      bool hf = false);
-// hf (here and in the launchers below): the tensors and the packed operand are IEEE half instead of bfloat16 (TDX_F16):
-// same kernels, same layouts, v_mfma_f32_32x32x16_f16 and half rounding of the results (H16<HF>, tdx_common.h)
-// slabs_beyond = {mx, my, mz}: another kernel has computed the region [0, mx) x [0, my) x [0, mz) of the output; launch
-// only the thin-brick kernel on the remainder slabs beyond it (1-2 voxels thick per axis).
 
-// persistent LDS-DMA ring kernel (tdx_conv3_ring.hip; bf16): forward or main term of the data gradient on grids whose
-// whole 8 x 8 x 8 bricks fill the chip and leave remainders of at most 2 voxels per axis (those go to the thin-brick kernel
-// of tdx_conv3_mfma.hip in a second launch: the reference's 194 x 50 x 50 and its 97 x 25 x 25 level); TDX_ESHAPE = not such a case, take conv3_mfma_launch (results equal up to the
-// fp32 summation order: ~1 bf16 ulp on a few % of the elements)
-bool conv3_ring_supported(int C1, int C2, int Cout, int B, int X, int Y, int Z);
-int conv3_ring_launch(const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* y, int B, int X,
-                      int Y, int Z, int Cout, bool zero_pad, hipStream_t st, double* gn_acc = nullptr, void* d1 = nullptr,
-                      int D1 = 0, void* d2 = nullptr, const void* a1 = nullptr, const void* a2 = nullptr, bool hf = false);
+// One forward or data-gradient call, as every launcher below takes it.  Forward: y = conv3([x1 | x2]) + bias with N output
+// channels.  Data gradient (zero_pad): x1 = dy (C2 = 0), wp = the data-gradient operand, the N result channels are split
+// over d1 (channels [0, D1)) and d2, each plus its addend a1 / a2 where given.
+struct Conv3Call {
+    const void* x1; int C1;
+    const void* x2; int C2;
+    const void* wp;          // packed operand in the layout of `fmt` (tdx_conv3_pack_weight)
+    const float* bias;
+    void* y;                 // forward result; vector-ALU data gradient: the padded workspace
+    int B, X, Y, Z, N;
+    bool zero_pad;           // sources outside the grid read zero (data gradient) instead of the clamped voxel
+    double* gn_acc;          // forward: per-channel f64 moments are added here (tdx_conv3_fwd_gn)
+    void* d1; int D1; void* d2;
+    const void* a1; const void* a2;
+    hipStream_t st;
+    int fmt;                 // TDX_BF16 / TDX_F16 / TDX_F32 / TDX_F32_SPLIT: tensors and operand (split: fp32 tensors)
+    const Conv3Ext* ext;     // conv3_mfma_launch only
+    // conv3_mfma_launch only: {mx, my, mz} = another kernel has computed the region [0, mx) x [0, my) x [0, mz) of the
+    // output; launch only the thin-brick kernel on the remainder slabs beyond it (1-2 voxels thick per axis)
+    const int* slabs_beyond;
+    // TDX_F16: the tensors and the packed operand are IEEE half instead of bfloat16: same kernels, same layouts,
+    // v_mfma_f32_32x32x16_f16 and half rounding of the results (H16<HF>, tdx_common.h)
+    bool hf() const { return fmt == TDX_F16; }
+    Conv3Geom geom() const { return Conv3Geom{B, X, Y, Z, X, Y, Z, 0}; }
+};
 
-// small-grid conv (tdx_conv3_small.hip; bf16 tensors, or fp32 tensors with split-precision products when split): forward
-// or data gradient (then x1 = dy, result split over out1 / out2 with addends, halo fold included); TDX_ESHAPE = not a
-// small-grid case, take the brick kernels.  Needs the scratch arena.
-int conv3_small_launch(const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* out1, int D1,
-                       void* out2, const void* add1, const void* add2, int B, int X, int Y, int Z, int N, bool data_gradient,
-                       bool split, hipStream_t st, bool hf = false);
-bool conv3_small_applies(int C1, int C2, int B, int X, int Y, int Z, int N, bool data_gradient, bool split);
-// packed-K weight gradient for small grids (tdx_conv3_wgrad_small.hip, bf16); same contract as conv3_wgrad_mfma_launch,
-// TDX_ESHAPE = not a small-grid case
-int conv3_wgrad_small_launch(const void* x1, int C1, const void* x2, int C2, const void* dy, float* dwp, float* dbias, int B,
-                             int X, int Y, int Z, int Cout, hipStream_t st, float* slabs, int max_slabs, int* nslab_out,
-                             bool hf = false);
-// producer / consumer weight gradient, 64- and 32-wide output tiles (tdx_conv3_wgrad_ring.hip, bf16: 8 computing + 4 loader
-// waves per workgroup); same contract as conv3_wgrad_mfma_launch, TDX_ESHAPE = not a case for it
-int conv3_wgrad_ring_launch(const void* x1, int C1, const void* x2, int C2, const void* dy, float* dwp, float* dbias, int B, int X,
-                            int Y, int Z, int Cout, hipStream_t st, float* slabs, int max_slabs, int* nslab_out, bool hf = false);
+// launch geometry of the small-grid kernel (tdx_conv3_small_kernel.h)
+struct SmallGeom {
+    int B;
+    int Ev[3];     // virtual grid (rows)
+    int Es[3];     // source grid
+    int off;       // source coordinate = virtual coordinate - off
+    int clamp;     // 1: clamp sources into the grid (forward), 0: zero outside (data gradient)
+    int nbg;       // samples per row group (1 when a sample is cut into x slabs)
+    int xs;        // virtual x planes per row group
+    int gx;        // x slabs per sample
+    int Ix, Iy, Iz;  // LDS image per sample of a group: (xs + 2) x (Ev[1] + 2) x (Ev[2] + 2) entries
+    int K, N;      // channels of the source tensor(s) / of the result
+    int per_split; // K slices per split
+    int nsplit;
+};
+struct Conv3SmallPlan {
+    SmallGeom g;
+    size_t lds;
+    int mtw;  // M tiles per wave
+};
+
+// Which kernel serves a call: the ONE place that decides it.  fmt: the arithmetic and operand layout (TDX_BF16 / TDX_F16:
+// 16-bit MFMA, TDX_F32: fp32-IEEE MFMA, TDX_F32_SPLIT: split-precision MFMA; with family TDX_KERNEL_DIRECT the tensors'
+// dtype, on the vector ALU).  family: TDX_KERNEL_* of include/tdx.h.  status: TDX_OK, or what the entry point returns for
+// this combination (family is then what tdx_conv3_fwd_kernel reports).  The plan of the chosen family rides along, so
+// that "would this launcher take the call" and the launch itself are one computation.
+struct Conv3Route {
+    int fmt, family, status;
+    int ring_depth;        // TDX_KERNEL_RING: 8- or 4-deep bricks
+    Conv3SmallPlan small;  // TDX_KERNEL_SMALL
+};
+// C1 | C2: channels of the conv's inputs, N of its result (data gradient: C1 = Cout, C2 = 0, N = Cin); impl: TDX_CONV_*
+// (flag bits above 0xff are ignored).  Pure host code: reads the environment switches and the arena's size, launches nothing.
+Conv3Route conv3_route(int dtype, int impl, int C1, int C2, int N, int B, int X, int Y, int Z, bool data_gradient);
+
+// The launchers.  Each serves the calls the route gives it and returns an error for any other: none is a fall-through.
+// brick kernels: 16-bit (tdx_conv3_mfma.hip), split-precision (tdx_conv3_mfma_split.hip), fp32-IEEE (tdx_conv3_mfma_f32.hip)
+int conv3_mfma_launch(const Conv3Call& c);
+int conv3_mfma_split_launch(const Conv3Call& c);
+int conv3_mfma_f32_launch(const Conv3Call& c);
+// vector-ALU kernel (tdx_conv3_direct.hip); zero_pad: the adjoint on the padded grid (X + 2)(Y + 2)(Z + 2) into c.y
+int conv3_direct_launch(const Conv3Call& c);
+// halo fold of that adjoint (the same call): d1 | d2 = fold(c.y) (+ a1 | a2)
+int conv3_fold_launch(const Conv3Call& c);
+
+// persistent LDS-DMA ring kernel (tdx_conv3_ring.hip; 16-bit): forward or main term of the data gradient on grids whose
+// whole 8 x 8 x 8 (or 4-deep) bricks fill the chip and leave remainders of at most 2 voxels per axis (those go to the
+// thin-brick kernel of tdx_conv3_mfma.hip in a second launch: the reference's 194 x 50 x 50 and its 97 x 25 x 25 level).
+// Results equal the brick kernel's up to the fp32 summation order: ~1 bf16 ulp on a few % of the elements.
+// conv3_ring_depth: brick depth the kernel would run this call with, 0 = not a case for it (the data gradient also needs
+// the arena's zero block)
+int conv3_ring_depth(int C1, int C2, int N, int B, int X, int Y, int Z, bool data_gradient);
+int conv3_ring_launch(const Conv3Call& c, int depth);
+
+// small-grid conv (tdx_conv3_small.hip; 16-bit tensors, or fp32 tensors with split-precision products): forward or data
+// gradient (halo fold included).  Needs the scratch arena.  conv3_small_plan: false = not a small-grid case.
+bool conv3_small_plan(Conv3SmallPlan& p, int C1, int C2, int N, int B, int X, int Y, int Z, bool data_gradient, bool split);
+int conv3_small_launch(const Conv3Call& c, const Conv3SmallPlan& p);
+
+// One weight-gradient call: dwp [27][Cin][Cout] (+)= x^T dy, dbias (+)= column sums of dy (nullptr: not wanted).
+// slabs / max_slabs: optional region of max_slabs x 27*Cin*Cout floats; when the launch uses at most max_slabs K-splits
+// every split stores its partial tiles there (no atomics) and *nslab tells the caller how many slabs to add up (0: the
+// result was accumulated into dwp)
+struct Conv3WgradCall {
+    const void* x1; int C1;
+    const void* x2; int C2;
+    const void* dy;
+    float* dwp;
+    float* dbias;
+    int B, X, Y, Z, Cout;
+    hipStream_t st;
+    float* slabs; int max_slabs; int* nslab;
+    bool hf;
+};
+// TDX_DETERMINISTIC=1 in the environment (read per call): the fp32 atomic merges of the backward's small parameter gradients are
+// replaced by per-split partials added in a fixed order (tdx_ordered.hip), the halo shell takes its ordered route
+bool tdx_deterministic();
+// where a launch of nsplit K-splits puts its partial tiles: returns the base (slabs or dwp) and the slab stride (0: atomics
+// into dwp), reports the slab count.  Slab mode: every (tile, split) pair stores its whole partial tile, so the slabs need no
+// zeroing.  TDX_DETERMINISTIC: never the atomic merge -- nsplit is held to the slabs the workspace has (added in order by
+// the unpack kernel)
+static inline float* conv3_wgrad_merge(const Conv3WgradCall& c, int& nsplit, int64_t& slab_stride) {
+    if (tdx_deterministic() && c.slabs != nullptr && nsplit > c.max_slabs) nsplit = c.max_slabs > 0 ? c.max_slabs : 1;
+    const bool use_slabs = c.slabs != nullptr && nsplit <= c.max_slabs;
+    slab_stride = use_slabs ? (int64_t)27 * (c.C1 + c.C2) * c.Cout : 0;
+    if (c.nslab) *c.nslab = use_slabs ? nsplit : 0;
+    return use_slabs ? c.slabs : c.dwp;
+}
+// The six weight-gradient launchers.  16-bit tensors: conv3_wgrad_mfma_launch (tdx_conv3_wgrad_mfma.hip) hands the deep
+// U-Net levels to the packed-K kernel for small grids (tdx_conv3_wgrad_small.hip) and the fine levels to the producer /
+// consumer form (tdx_conv3_wgrad_ring.hip: 8 computing + 4 loader waves per workgroup, 64- and 32-wide output tiles),
+// each of which answers TDX_ESHAPE when the call is not a case for it.  fp32 tensors: split-precision
+// (tdx_conv3_wgrad_mfma_split.hip, which tries its producer / consumer form tdx_conv3_wgrad_split_ring.hip first: 2 x 8 x 8
+// bricks) or fp32-IEEE products (tdx_conv3_wgrad_mfma_f32.hip).
+// The launch geometry of the brick weight-gradient kernels: bricks of bx x by x bz voxels in the kernel's LOCAL axes, the
+// short axis on the grid axis that leaves the fewest bricks (permute false: the grid's own order).  Fills a Wgrad*View
+// (every kernel's has these fields) and returns the number of bricks.
+template <typename View>
+static inline int conv3_wgrad_view(View& g, const Conv3WgradCall& c, int bx, int by, int bz, bool permute = true) {
+    const int E[3] = {c.X, c.Y, c.Z}, gs[3] = {c.Y * c.Z, c.Z, 1}, gw[3] = {9, 3, 1}, bdim[3] = {bx, by, bz};
+    const int cand[3][3] = {{0, 1, 2}, {1, 0, 2}, {2, 0, 1}};
+    int best = 0;
+    int64_t best_n = -1;
+    for (int k = 0; k < (permute ? 3 : 1); ++k) {
+        const int64_t n = (int64_t)ceil_div(E[cand[k][0]], bx) * ceil_div(E[cand[k][1]], by) * ceil_div(E[cand[k][2]], bz);
+        if (best_n < 0 || n < best_n) { best_n = n; best = k; }
+    }
+    g.B = c.B; g.batch = c.X * c.Y * c.Z;
+    for (int k = 0; k < 3; ++k) {
+        const int a = cand[best][k];
+        g.E[k] = E[a]; g.s[k] = gs[a]; g.ws[k] = gw[a]; g.nb[k] = ceil_div(E[a], bdim[k]);
+    }
+    return c.B * g.nb[0] * g.nb[1] * g.nb[2];
+}
+bool conv3_wgrad_mfma_supported(int C1, int C2, int Cout);
+bool conv3_wgrad_mfma_split_supported(int C1, int C2, int Cout);
+bool conv3_wgrad_mfma_f32_supported(int C1, int C2, int Cout);
+int conv3_wgrad_mfma_launch(const Conv3WgradCall& c);
+int conv3_wgrad_small_launch(const Conv3WgradCall& c);
+int conv3_wgrad_ring_launch(const Conv3WgradCall& c);
+int conv3_wgrad_mfma_split_launch(const Conv3WgradCall& c);
+int conv3_wgrad_split_ring_launch(const Conv3WgradCall& c);
+int conv3_wgrad_mfma_f32_launch(const Conv3WgradCall& c);
+// vector-ALU weight gradient (tdx_conv3_direct.hip), atomics into dwp; max_slabs > 0 (deterministic runs): at most that many
+// voxel chunks, chunk k stores into slab k
+int conv3_wgrad_direct_launch(const Conv3WgradCall& c, int dtype);
+// after the launch of c: dwp [27][Cin][Cout] (or the sum of its *nslab slabs) -> dw (Cout, Cin, 27); the bias-gradient
+// accumulator dbw -> dbias.  The accumulators are left all-zero.  many: the per-tap summing kernel for more slabs than the
+// tiled one walks.
+int conv3_unpack_wgrad_launch(const Conv3WgradCall& c, float* dw, float* dbw, float* dbias, bool many);
 // CUs the persistent one-workgroup-per-CU kernels (ring conv, producer / consumer weight gradient) may occupy:
 // TDX_PERSISTENT_CUS in the environment (read per call), a multiple of 8 in [8, 256], default 256.  A data-parallel run
 // sets it below 256 to leave CUs to RCCL's kernels.
 int tdx_persistent_cus();
-// TDX_DETERMINISTIC=1 in the environment (read per call): the fp32 atomic merges of the backward's small parameter gradients are
-// replaced by per-split partials added in a fixed order (tdx_ordered.hip), the halo shell takes its ordered route
-bool tdx_deterministic();
 // dst[r * ld + c] (+)= sum_{k < nslab} slabs[k * stride + r * cols + c], k ascending
 int ordered_sum_launch(const float* slabs, int nslab, int64_t stride, float* dst, int rows, int cols, int64_t ld, bool add,
                        hipStream_t st);
@@ -95,27 +206,6 @@ int bias_grad_ordered_launch(const void* dy, int64_t nvox, int C, int dtype, flo
 void* tdx_scratch_ptr();
 size_t tdx_scratch_bytes();
 
-bool conv3_wgrad_mfma_supported(int C1, int C2, int Cout);
-bool conv3_wgrad_mfma_split_supported(int C1, int C2, int Cout);
-int conv3_wgrad_mfma_split_launch(const void* x1, int C1, const void* x2, int C2, const void* dy, float* dwp, float* dbias,
-                                  int B, int X, int Y, int Z, int Cout, hipStream_t st, float* slabs, int max_slabs,
-                                  int* nslab_out);
-// producer / consumer form of the split-precision weight gradient (tdx_conv3_wgrad_split_ring.hip: 8 computing + 4 loader
-// waves, 2 x 8 x 8 bricks); same contract, TDX_ESHAPE = not a case for it
-int conv3_wgrad_split_ring_launch(const void* x1, int C1, const void* x2, int C2, const void* dy, float* dwp, float* dbias,
-                                  int B, int X, int Y, int Z, int Cout, hipStream_t st, float* slabs, int max_slabs,
-                                  int* nslab_out);
-bool conv3_wgrad_mfma_f32_supported(int C1, int C2, int Cout);
-int conv3_wgrad_mfma_f32_launch(const void* x1, int C1, const void* x2, int C2, const void* dy, float* dwp,
-                                float* dbias, int B, int X, int Y, int Z, int Cout, hipStream_t st, float* slabs,
-                                int max_slabs, int* nslab_out);
-// slabs / max_slabs: optional region of max_slabs x 27*Cin*Cout floats; when the launch uses at most
-// max_slabs K-splits every split stores its partial tiles there (no atomics) and *nslab_out tells the
-// caller how many slabs to add up (0: the result was accumulated into dwp)
-int conv3_wgrad_mfma_launch(const void* x1, int C1, const void* x2, int C2, const void* dy, float* dwp, float* dbias,
-                            int B, int X, int Y, int Z, int Cout, hipStream_t st, float* slabs = nullptr,
-                            int max_slabs = 0, int* nslab_out = nullptr, bool hf = false);
-
 // halo-shell term of the data gradient, added onto dx with atomics (tdx_conv3_shell.hip); mode 0 bf16, 1 fp32 MFMA,
 // 2 split-precision, 3 fp16; wb = the packed data-gradient operand for (K -> N) in that mode's layout
 // sbuf: conv3_shell_buffer_bytes() of scratch, used when TDX_SHELL_DETERMINISTIC=1 (positions stored, then folded in a
@@ -123,9 +213,6 @@ int conv3_wgrad_mfma_launch(const void* x1, int C1, const void* x2, int C2, cons
 size_t conv3_shell_buffer_bytes(int B, int X, int Y, int Z, int N);
 int conv3_shell_launch(const void* dy, const void* wb, void* d1, int D1, void* d2, int B, int X, int Y, int Z, int K, int N,
                        int mode, hipStream_t st, void* sbuf = nullptr);
-
-int conv3_direct_launch(const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* y,
-                        const Conv3Geom& g, int Cout, int dtype, bool zero_pad, hipStream_t st);
 
 // tdx_groupnorm.hip: (mean, rstd) per (b, group) from per-channel f64 (sum, sumsq)
 #define TDX_GN_REPLICAS 32  // == GN_REPLICAS in tdx_groupnorm.hip (sizes tdx_gn_workspace_bytes)

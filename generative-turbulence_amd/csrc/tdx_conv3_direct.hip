@@ -1,9 +1,8 @@
-// 3x3x3 convolution on NDHWC activations: weight packing, the vector-ALU implicit-GEMM
-// kernels (any dtype, exact f32 accumulation -- the f32 parity path and the cross-check
-// for the MFMA kernels), the halo fold of the data gradient, and the public entry points
-// that dispatch between this file and tdx_conv3_mfma.hip.
+// 3x3x3 convolution on NDHWC activations: weight packing and unpacking, and the vector-ALU implicit-GEMM kernels (any
+// dtype, exact f32 accumulation -- the f32 parity path and the cross-check for the MFMA kernels) with the halo fold of
+// their data gradient.  The entry points and the choice between these kernels and the MFMA families: tdx_conv3_entry.hip.
 //
-// Geometry shared by both implementations: an "output grid" (Xo,Yo,Zo) is produced from an
+// Geometry shared by all implementations: an "output grid" (Xo,Yo,Zo) is produced from an
 // "input grid" (Xi,Yi,Zi); output voxel o reads input voxel o + off + e for the 27 taps
 // e in {-1,0,1}^3, either clamped to the grid (replicate padding, forward: off = 0, grids
 // equal) or treated as zero outside (data gradient: the adjoint is evaluated on the padded
@@ -335,6 +334,17 @@ conv3_unpack_sum_kernel(float* __restrict__ dw, float* __restrict__ dbw, float* 
     }
 }
 
+int conv3_unpack_wgrad_launch(const Conv3WgradCall& c, float* dw, float* dbw, float* dbias, bool many) {
+    const int Cin = c.C1 + c.C2, Cout = c.Cout;
+    if (many)
+        hipLaunchKernelGGL(conv3_unpack_sum_kernel, dim3(ceil_div(Cin, 8), ceil_div(Cout, 32), 27), dim3(256), 0, c.st, dw, dbw,
+                           dbias, Cin, Cout, c.slabs, *c.nslab);
+    else
+        hipLaunchKernelGGL(conv3_unpack_wgrad_kernel, dim3(ceil_div(Cin, 16), ceil_div(Cout, 16)), dim3(256), 0, c.st, c.dwp, dw,
+                           dbw, dbias, Cin, Cout, c.slabs, *c.nslab);
+    return tdx_launch_status();
+}
+
 // ------------------------------------------------------------------ direct implicit GEMM -
 #define D3_BM 64
 #define D3_BN 64
@@ -431,19 +441,20 @@ conv3_direct_kernel(const T* __restrict__ x1, int C1, const T* __restrict__ x2, 
     }
 }
 
-int conv3_direct_launch(const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* y,
-                        const Conv3Geom& g, int Cout, int dtype, bool zero_pad, hipStream_t st) {
-    if ((C1 % 8) || (C2 % 8)) return TDX_ESHAPE;
+int conv3_direct_launch(const Conv3Call& c) {
+    if ((c.C1 % 8) || (c.C2 % 8)) return TDX_ESHAPE;
+    // data gradient: the adjoint on the padded grid, dpad[p'] = sum_e wb[e] dy_zero[p' - 1 + e]
+    const Conv3Geom g = c.zero_pad ? Conv3Geom{c.B, c.X, c.Y, c.Z, c.X + 2, c.Y + 2, c.Z + 2, -1} : c.geom();
     const int64_t nvox = (int64_t)g.B * g.Xo * g.Yo * g.Zo;
-    dim3 grid(ceil_div(nvox, D3_BM), ceil_div(Cout, D3_BN));
-    const int ml = conv3_layout_kc(dtype, C1 + C2, Cout);
-    TDX_DISPATCH_DTYPE(dtype, {
-        if (zero_pad)
-            hipLaunchKernelGGL((conv3_direct_kernel<T, true>), grid, dim3(256), 0, st, (const T*)x1, C1, (const T*)x2,
-                               C2, (const T*)wp, bias, (T*)y, g, Cout, ml);
+    dim3 grid(ceil_div(nvox, D3_BM), ceil_div(c.N, D3_BN));
+    const int ml = conv3_layout_kc(c.fmt, c.C1 + c.C2, c.N);
+    TDX_DISPATCH_DTYPE(c.fmt, {
+        if (c.zero_pad)
+            hipLaunchKernelGGL((conv3_direct_kernel<T, true>), grid, dim3(256), 0, c.st, (const T*)c.x1, c.C1, (const T*)c.x2,
+                               c.C2, (const T*)c.wp, c.bias, (T*)c.y, g, c.N, ml);
         else
-            hipLaunchKernelGGL((conv3_direct_kernel<T, false>), grid, dim3(256), 0, st, (const T*)x1, C1,
-                               (const T*)x2, C2, (const T*)wp, bias, (T*)y, g, Cout, ml);
+            hipLaunchKernelGGL((conv3_direct_kernel<T, false>), grid, dim3(256), 0, c.st, (const T*)c.x1, c.C1,
+                               (const T*)c.x2, c.C2, (const T*)c.wp, c.bias, (T*)c.y, g, c.N, ml);
     });
     return tdx_launch_status();
 }
@@ -500,6 +511,14 @@ conv3_fold_kernel(const T* __restrict__ dpad, T* __restrict__ dx1, int C1, T* __
         for (int j = 0; j < 8; ++j) o.v[j] = acc[j];
     }
     o.store(dst);
+}
+
+int conv3_fold_launch(const Conv3Call& c) {
+    const int64_t total = (int64_t)c.B * c.X * c.Y * c.Z * (c.N / 8);
+    TDX_DISPATCH_DTYPE(c.fmt, hipLaunchKernelGGL((conv3_fold_kernel<T>), dim3(ceil_div(total, 256)), dim3(256), 0, c.st,
+                                                  (const T*)c.y, (T*)c.d1, c.D1, (T*)c.d2, c.N - c.D1, (const T*)c.a1,
+                                                  (const T*)c.a2, c.B, c.X, c.Y, c.Z, total));
+    return tdx_launch_status();
 }
 
 // ------------------------------------------------------------------ direct weight grad ---
@@ -588,342 +607,20 @@ conv3_wgrad_direct_kernel(const T* __restrict__ x1, int C1, const T* __restrict_
     if (do_bias && tid < D3_BN && co0 + tid < Cout) atomicAdd(&dbias[co0 + tid], bsum);
 }
 
-// ------------------------------------------------------------------ scratch arena --------
-// caller-provided transient workspace of kernels whose entry points have no argument for one (the K-split slabs of
-// the small-grid conv, tdx_conv3_small.hip).  The first 64 bytes must be zero and stay zero.
-int tdx_persistent_cus() {
-    const char* env = getenv("TDX_PERSISTENT_CUS");
-    int n = env ? atoi(env) : 256;
-    n = n < 8 ? 8 : (n > 256 ? 256 : n);
-    return n & ~7;
-}
-static void* g_scratch = nullptr;
-static size_t g_scratch_bytes = 0;
-void* tdx_scratch_ptr() { return g_scratch; }
-size_t tdx_scratch_bytes() { return g_scratch_bytes; }
-extern "C" int tdx_set_scratch(void* ptr, size_t bytes) {
-    if (ptr != nullptr && bytes < 64) return TDX_EINVAL;  // at least the zero block
-    g_scratch = ptr;
-    g_scratch_bytes = ptr ? bytes : 0;
-    return TDX_OK;
-}
-
-// ------------------------------------------------------------------ entry points ---------
-// the matrix-core kernels of the 16-bit formats (bf16 and fp16 tensors share them: H16<HF>, tdx_common.h)
-static bool mfma_ok(int dtype, int Cin1, int Cin2, int Cout) {
-    return tdx_is_h16(dtype) && conv3_mfma_supported(Cin1, Cin2, Cout);
-}
-
-extern "C" int tdx_conv3_fwd(const void* x1, int C1, const void* x2, int C2, const void* wf, const float* bias,
-                             void* y, int B, int X, int Y, int Z, int Cout, int dtype, int impl, void* stream) {
-    TDX_CHECK_ARG(x1 && wf && y && B > 0 && X > 0 && Y > 0 && Z > 0 && C1 > 0 && C2 >= 0 && Cout > 0);
-    TDX_CHECK_ARG(C2 == 0 || x2);
-    Conv3Geom g = {B, X, Y, Z, X, Y, Z, 0};
-    if (dtype == TDX_F32 && impl == TDX_CONV_SPLIT && conv3_mfma_split_supported(C1 + C2, 0, Cout)) {
-        // the operand was packed as split images (layout is a function of (K, N)); both inputs must be sliceable
-        if (!conv3_mfma_split_supported(C1, C2, Cout)) return TDX_ESHAPE;
-        int rs = conv3_small_launch(x1, C1, x2, C2, wf, bias, y, Cout, nullptr, nullptr, nullptr, B, X, Y, Z, Cout, false, true,
-                                    as_stream(stream));
-        if (rs != TDX_ESHAPE) return rs;
-        return conv3_mfma_split_launch(x1, C1, x2, C2, wf, bias, y, g, Cout, false, as_stream(stream));
+int conv3_wgrad_direct_launch(const Conv3WgradCall& c, int dtype) {
+    const int64_t nvox = (int64_t)c.B * c.X * c.Y * c.Z;
+    const int Cin = c.C1 + c.C2, nci = ceil_div(Cin, D3_BM), nco = ceil_div(c.Cout, D3_BN);
+    int64_t vpb = D3W_VOX, slab_stride = 0;
+    float* out = c.dwp;
+    if (c.max_slabs > 0) {  // at most max_slabs voxel chunks, one slab each
+        vpb = (ceil_div(nvox, c.max_slabs) + D3_BK - 1) / D3_BK * D3_BK;
+        slab_stride = (int64_t)27 * Cin * c.Cout;
+        out = c.slabs;
+        *c.nslab = ceil_div(nvox, vpb);
     }
-    if (dtype == TDX_F32 && impl != TDX_CONV_DIRECT && conv3_mfma_f32_supported(C1, C2, Cout))
-        return conv3_mfma_f32_launch(x1, C1, x2, C2, wf, bias, y, g, Cout, false, as_stream(stream));
-    const bool use_mfma = impl == TDX_CONV_MFMA || (impl == TDX_CONV_AUTO && mfma_ok(dtype, C1, C2, Cout));
-    if (use_mfma) {
-        if (!mfma_ok(dtype, C1, C2, Cout)) return TDX_ESHAPE;
-        // deep U-Net levels: the small-grid kernel (packed M tiles, split K); TDX_ESHAPE = not such a case
-        const bool hf = dtype == TDX_F16;
-        int rs = conv3_small_launch(x1, C1, x2, C2, wf, bias, y, Cout, nullptr, nullptr, nullptr, B, X, Y, Z, Cout, false,
-                                    false, as_stream(stream), hf);
-        if (rs != TDX_ESHAPE) return rs;
-        // the two finest levels: persistent LDS-DMA ring kernel (same products, fp32 sums in another order: equal to the brick
-        // kernel up to ~1 bf16 ulp on a few % of the elements, tdx_conv3_ring.hip)
-        rs = conv3_ring_launch(x1, C1, x2, C2, wf, bias, y, B, X, Y, Z, Cout, false, as_stream(stream), nullptr, nullptr, 0,
-                               nullptr, nullptr, nullptr, hf);
-        if (rs != TDX_ESHAPE) return rs;
-        return conv3_mfma_launch(x1, C1, x2, C2, wf, bias, y, g, Cout, false, as_stream(stream), nullptr, nullptr, 0, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, hf);
-    }
-    return conv3_direct_launch(x1, C1, x2, C2, wf, bias, y, g, Cout, dtype, false, as_stream(stream));
-}
-
-// Which kernel family tdx_conv3_fwd / tdx_conv3_fwd_gn run for this call (mirrors the dispatch above)
-extern "C" int tdx_conv3_fwd_kernel(int C1, int C2, int Cout, int B, int X, int Y, int Z, int dtype, int impl) {
-    impl &= 0xff;
-    if (dtype == TDX_F32 && impl == TDX_CONV_SPLIT && conv3_mfma_split_supported(C1 + C2, 0, Cout))
-        return conv3_small_applies(C1, C2, B, X, Y, Z, Cout, false, true) ? TDX_KERNEL_SMALL : TDX_KERNEL_BRICK;
-    if (dtype == TDX_F32 && impl != TDX_CONV_DIRECT && conv3_mfma_f32_supported(C1, C2, Cout)) return TDX_KERNEL_BRICK;
-    if (impl == TDX_CONV_MFMA || (impl == TDX_CONV_AUTO && mfma_ok(dtype, C1, C2, Cout))) {
-        if (!mfma_ok(dtype, C1, C2, Cout)) return TDX_KERNEL_DIRECT;
-        if (conv3_small_applies(C1, C2, B, X, Y, Z, Cout, false, false)) return TDX_KERNEL_SMALL;
-        return conv3_ring_supported(C1, C2, Cout, B, X, Y, Z) ? TDX_KERNEL_RING : TDX_KERNEL_BRICK;
-    }
-    return TDX_KERNEL_DIRECT;
-}
-
-extern "C" int tdx_conv3_fwd_gn(const void* x1, int C1, const void* x2, int C2, const void* wf, const float* bias,
-                                void* y, float* stats, int G, float eps, void* gn_workspace, int B, int X, int Y, int Z,
-                                int Cout, int dtype, int impl, void* stream) {
-    TDX_CHECK_ARG(x1 && wf && y && stats && gn_workspace && B > 0 && X > 0 && Y > 0 && Z > 0 && C1 > 0 && C2 >= 0);
-    TDX_CHECK_ARG(Cout > 0 && G > 0 && (Cout % G) == 0 && (C2 == 0 || x2));
-    const bool clean = (impl & TDX_WS_CLEAN) != 0;
-    if (tdx_deterministic()) {
-        // the conv kernels' epilogues merge their moments with f64 atomics in arrival order; deterministic runs take the conv and
-        // then the statistics pass over its result, whose block partials are exact in f64 (gn_stats_launch)
-        int rc = tdx_conv3_fwd(x1, C1, x2, C2, wf, bias, y, B, X, Y, Z, Cout, dtype, impl & 0xff, stream);
-        if (rc != TDX_OK) return rc;
-        return gn_stats_launch(y, stats, B, (int64_t)X * Y * Z, Cout, G, eps, dtype, gn_workspace, clean, as_stream(stream));
-    }
-    impl &= 0xff;
-    const bool use_mfma =
-        tdx_is_h16(dtype) && (impl == TDX_CONV_MFMA || (impl == TDX_CONV_AUTO && mfma_ok(dtype, C1, C2, Cout)));
-    const bool hf = dtype == TDX_F16;
-    const bool f32_split = dtype == TDX_F32 && impl == TDX_CONV_SPLIT && conv3_mfma_split_supported(C1 + C2, 0, Cout);
-    const bool f32_mfma = dtype == TDX_F32 && !f32_split && impl != TDX_CONV_DIRECT && conv3_mfma_f32_supported(C1, C2, Cout);
-    if (f32_split || f32_mfma) {  // fp32 tensors: the MFMA kernels accumulate the moments in their store loop too
-        if (f32_split && !conv3_mfma_split_supported(C1, C2, Cout)) return TDX_ESHAPE;
-        hipStream_t st = as_stream(stream);
-        if (f32_split) {  // deep U-Net levels: small-grid conv, then the statistics pass over its (tiny) result
-            int rs = conv3_small_launch(x1, C1, x2, C2, wf, bias, y, Cout, nullptr, nullptr, nullptr, B, X, Y, Z, Cout, false, true, st);
-            if (rs == TDX_OK) return gn_stats_launch(y, stats, B, (int64_t)X * Y * Z, Cout, G, eps, dtype, gn_workspace, clean, st);
-            if (rs != TDX_ESHAPE) return rs;
-        }
-        double* acc = (double*)gn_workspace;
-        if (!clean) {
-            int e = tdx_zero_async(acc, (size_t)TDX_GN_REPLICAS * B * Cout * 2 * sizeof(double), st);
-            if (e != TDX_OK) return e;
-        }
-        Conv3Geom g = {B, X, Y, Z, X, Y, Z, 0};
-        int rc = f32_split ? conv3_mfma_split_launch(x1, C1, x2, C2, wf, bias, y, g, Cout, false, st, acc)
-                           : conv3_mfma_f32_launch(x1, C1, x2, C2, wf, bias, y, g, Cout, false, st, acc);
-        if (rc != TDX_OK) return rc;
-        return gn_finalize_launch(acc, stats, B, Cout, G, (int64_t)X * Y * Z, eps, TDX_GN_REPLICAS, st);
-    }
-    if (!use_mfma) {  // unfused: conv, then the streaming statistics pass
-        int rc = tdx_conv3_fwd(x1, C1, x2, C2, wf, bias, y, B, X, Y, Z, Cout, dtype, impl, stream);
-        if (rc != TDX_OK) return rc;
-        return tdx_gn_stats(y, stats, B, (int64_t)X * Y * Z, Cout, G, eps, dtype, gn_workspace, stream);
-    }
-    if (!mfma_ok(dtype, C1, C2, Cout)) return tdx_is_h16(dtype) ? TDX_ESHAPE : TDX_EDTYPE;
-    hipStream_t st = as_stream(stream);
-    {   // deep U-Net levels: small-grid conv, then the statistics pass over its (tiny) result
-        int rs = conv3_small_launch(x1, C1, x2, C2, wf, bias, y, Cout, nullptr, nullptr, nullptr, B, X, Y, Z, Cout, false, false, st, hf);
-        if (rs == TDX_OK) return gn_stats_launch(y, stats, B, (int64_t)X * Y * Z, Cout, G, eps, dtype, gn_workspace, clean, st);
-        if (rs != TDX_ESHAPE) return rs;
-    }
-    double* acc = (double*)gn_workspace;
-    if (!clean) {
-        int e = tdx_zero_async(acc, (size_t)TDX_GN_REPLICAS * B * Cout * 2 * sizeof(double), st);
-        if (e != TDX_OK) return e;
-    }
-    Conv3Geom g = {B, X, Y, Z, X, Y, Z, 0};
-    int rc = conv3_ring_launch(x1, C1, x2, C2, wf, bias, y, B, X, Y, Z, Cout, false, st, acc, nullptr, 0, nullptr, nullptr, nullptr, hf);
-    if (rc == TDX_ESHAPE)
-        rc = conv3_mfma_launch(x1, C1, x2, C2, wf, bias, y, g, Cout, false, st, acc, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                               nullptr, hf);
-    if (rc != TDX_OK) return rc;
-    return gn_finalize_launch(acc, stats, B, Cout, G, (int64_t)X * Y * Z, eps, TDX_GN_REPLICAS, st);
-}
-
-// Forward with a strided first input and accumulators that start from a precomputed partial
-// convolution (bf16 MFMA path only): y = conv3(x1[..., :C1] with row stride ld1, wf) + bias + init.
-extern "C" int tdx_conv3_fwd_partial(const void* x1, int C1, int ld1, const void* wf, const float* bias,
-                                     const void* init, int init_shared, void* y, float* stats, int G, float eps,
-                                     void* gn_workspace, int B, int X, int Y, int Z, int Cout, int dtype, int impl,
-                                     void* stream) {
-    TDX_CHECK_ARG(x1 && wf && y && B > 0 && X > 0 && Y > 0 && Z > 0 && C1 > 0 && Cout > 0 && ld1 >= C1 && (ld1 % 8) == 0);
-    TDX_CHECK_ARG(stats == nullptr || (gn_workspace && G > 0 && (Cout % G) == 0));
-    const bool clean = (impl & TDX_WS_CLEAN) != 0;
-    if (!mfma_ok(dtype, C1, 0, Cout)) return tdx_is_h16(dtype) ? TDX_ESHAPE : TDX_EDTYPE;
-    hipStream_t st = as_stream(stream);
-    const bool det = tdx_deterministic();  // then: conv, and the ordered statistics pass over its result (as tdx_conv3_fwd_gn)
-    double* acc = (stats && !det) ? (double*)gn_workspace : nullptr;
-    if (acc && !clean) {
-        int e = tdx_zero_async(acc, (size_t)TDX_GN_REPLICAS * B * Cout * 2 * sizeof(double), st);
-        if (e != TDX_OK) return e;
-    }
-    Conv3Geom g = {B, X, Y, Z, X, Y, Z, 0};
-    Conv3Ext ext = {ld1, 0, init, init_shared != 0};
-    int rc = conv3_mfma_launch(x1, C1, nullptr, 0, wf, bias, y, g, Cout, false, st, acc, nullptr, 0, nullptr, nullptr, nullptr,
-                               &ext, nullptr, dtype == TDX_F16);
-    if (rc != TDX_OK || !stats) return rc;
-    if (det) return gn_stats_launch(y, stats, B, (int64_t)X * Y * Z, Cout, G, eps, dtype, gn_workspace, clean, st);
-    return gn_finalize_launch(acc, stats, B, Cout, G, (int64_t)X * Y * Z, eps, TDX_GN_REPLICAS, st);
-}
-
-extern "C" size_t tdx_conv3_bwd_data_workspace_bytes(int B, int X, int Y, int Z, int Cin, int dtype, int impl) {
-    // the padded tensor of the vector-ALU path (shapes the MFMA kernels do not cover, TDX_CONV_DIRECT); which path a
-    // call takes also depends on Cout, so the size is the same for all; the MFMA paths use it only for the position buffer
-    // of the deterministic halo-shell route
-    (void)impl;
-    const size_t padded = (size_t)B * (X + 2) * (Y + 2) * (Z + 2) * Cin * (tdx_is_h16(dtype) ? 2 : 4);
-    const size_t shell = conv3_shell_buffer_bytes(B, X, Y, Z, Cin);  // TDX_SHELL_DETERMINISTIC=1: one fp32 row per shell position
-    return (padded > shell ? padded : shell) + 256;
-}
-
-// dx = adjoint of the replicate-padded conv.  MFMA paths: main term = zero-padded correlation on the original grid
-// (the conv kernel, epilogue writes dx incl. the fused addend), then the halo-shell term added by
-// conv3_shell_launch.  Vector-ALU path: correlation on the padded grid into the workspace, then the fold.
-static int conv3_bwd_data_impl(const void* dy, const void* wb, void* dx1, int C1, void* dx2, int C2, const void* add1,
-                               const void* add2, int B, int X, int Y, int Z, int Cout, int dtype, int impl,
-                               void* workspace, void* stream) {
-    TDX_CHECK_ARG(dy && wb && dx1 && workspace && B > 0 && X > 0 && Y > 0 && Z > 0 && C1 > 0 && C2 >= 0 && Cout > 0);
-    TDX_CHECK_ARG(C2 == 0 || dx2);
-    const int Cin = C1 + C2;
-    if ((C1 % 8) || (C2 % 8) || (Cout % 8)) return TDX_ESHAPE;
-    hipStream_t st = as_stream(stream);
-    const Conv3Geom g0 = {B, X, Y, Z, X, Y, Z, 0};
-    const bool use_mfma = tdx_is_h16(dtype) && (impl == TDX_CONV_MFMA || (impl == TDX_CONV_AUTO && mfma_ok(dtype, Cout, 0, Cin)));
-    const bool hf = dtype == TDX_F16;
-    int rc;
-    if (use_mfma) {
-        if (!mfma_ok(dtype, Cout, 0, Cin)) return TDX_ESHAPE;
-        // deep U-Net levels: adjoint on the padded grid by the small-grid kernel, halo fold in its reduce pass
-        rc = conv3_small_launch(dy, Cout, nullptr, 0, wb, nullptr, dx1, C1, dx2, add1, add2, B, X, Y, Z, Cin, true, false, st, hf);
-        if (rc != TDX_ESHAPE) return rc;
-        rc = conv3_ring_launch(dy, Cout, nullptr, 0, wb, nullptr, nullptr, B, X, Y, Z, Cin, true, st, nullptr, dx1, C1, dx2, add1, add2,
-                               hf);
-        if (rc == TDX_ESHAPE)
-            rc = conv3_mfma_launch(dy, Cout, nullptr, 0, wb, nullptr, nullptr, g0, Cin, true, st, nullptr, dx1, C1, dx2, add1, add2,
-                                   nullptr, nullptr, hf);
-        if (rc != TDX_OK) return rc;
-        return conv3_shell_launch(dy, wb, dx1, C1, dx2, B, X, Y, Z, Cout, Cin, hf ? 3 : 0, st, workspace);
-    } else if (dtype == TDX_F32 && impl != TDX_CONV_DIRECT &&
-               ((impl == TDX_CONV_SPLIT && conv3_mfma_split_supported(Cout, 0, Cin)) || conv3_mfma_f32_supported(Cout, 0, Cin))) {
-        const bool split = impl == TDX_CONV_SPLIT && conv3_mfma_split_supported(Cout, 0, Cin);
-        if (split) {
-            rc = conv3_small_launch(dy, Cout, nullptr, 0, wb, nullptr, dx1, C1, dx2, add1, add2, B, X, Y, Z, Cin, true, true, st);
-            if (rc != TDX_ESHAPE) return rc;
-        }
-        rc = split ? conv3_mfma_split_launch(dy, Cout, nullptr, 0, wb, nullptr, nullptr, g0, Cin, true, st, nullptr, dx1, C1, dx2,
-                                             add1, add2)
-                   : conv3_mfma_f32_launch(dy, Cout, nullptr, 0, wb, nullptr, nullptr, g0, Cin, true, st, nullptr, dx1, C1, dx2,
-                                           add1, add2);
-        if (rc != TDX_OK) return rc;
-        return conv3_shell_launch(dy, wb, dx1, C1, dx2, B, X, Y, Z, Cout, Cin, split ? 2 : 1, st, workspace);
-    }
-    // adjoint on the padded grid: dpad[p'] = sum_e wb[e] dy_zero[p' - 1 + e]
-    const Conv3Geom g = {B, X, Y, Z, X + 2, Y + 2, Z + 2, -1};
-    rc = conv3_direct_launch(dy, Cout, nullptr, 0, wb, nullptr, workspace, g, Cin, dtype, true, st);
-    if (rc != TDX_OK) return rc;
-    const int64_t total = (int64_t)B * X * Y * Z * (Cin / 8);
-    TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv3_fold_kernel<T>), dim3(ceil_div(total, 256)), dim3(256), 0, st,
-                                                  (const T*)workspace, (T*)dx1, C1, (T*)dx2, C2, (const T*)add1, (const T*)add2,
-                                                  B, X, Y, Z, total));
+    dim3 grid(ceil_div(nvox, vpb), 27, nci * nco);
+    TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv3_wgrad_direct_kernel<T>), grid, dim3(256), 0, c.st, (const T*)c.x1, c.C1,
+                                                  (const T*)c.x2, c.C2, (const T*)c.dy, out, c.dbias, c.B, c.X, c.Y, c.Z, c.Cout,
+                                                  nci, vpb, slab_stride));
     return tdx_launch_status();
-}
-
-extern "C" int tdx_conv3_bwd_data(const void* dy, const void* wb, void* dx1, int C1, void* dx2, int C2,
-                                  int accumulate, int B, int X, int Y, int Z, int Cout, int dtype, int impl,
-                                  void* workspace, void* stream) {
-    return conv3_bwd_data_impl(dy, wb, dx1, C1, dx2, C2, accumulate ? dx1 : nullptr, accumulate ? dx2 : nullptr, B, X, Y, Z,
-                               Cout, dtype, impl, workspace, stream);
-}
-
-extern "C" int tdx_conv3_bwd_data_add(const void* dy, const void* wb, void* dx1, int C1, void* dx2, int C2,
-                                      const void* add1, const void* add2, int B, int X, int Y, int Z, int Cout, int dtype,
-                                      int impl, void* workspace, void* stream) {
-    return conv3_bwd_data_impl(dy, wb, dx1, C1, dx2, C2, add1, add2, B, X, Y, Z, Cout, dtype, impl, workspace, stream);
-}
-
-#define W3_MAX_SLABS 8
-// per-split slabs a workspace holds: 8 for the wide layers (few K splits), up to 512 for the narrow ones of the fine
-// levels, whose launches split K over 32-512 workgroups -- about 2 MB x 27 of slabs either way
-static int w3_slab_capacity(int Cin, int Cout) {
-    const int64_t c = ((int64_t)1 << 19) / ((int64_t)Cin * Cout);
-    return (int)(c < W3_MAX_SLABS ? W3_MAX_SLABS : (c > 512 ? 512 : c));
-}
-extern "C" size_t tdx_conv3_bwd_weight_workspace_bytes(int Cin, int Cout, int impl) {
-    (void)impl;
-    // dw + dbias accumulators (the part covered by TDX_WS_CLEAN), then the partial-sum slabs (scratch, never needs zeroing)
-    return (size_t)(1 + w3_slab_capacity(Cin, Cout)) * 27 * Cin * Cout * sizeof(float) + (size_t)Cout * sizeof(float) + 512;
-}
-
-extern "C" int tdx_conv3_bwd_weight(const void* x1, int C1, const void* x2, int C2, const void* dy, float* dw,
-                                    float* dbias, int B, int X, int Y, int Z, int Cout, int dtype, int impl,
-                                    void* workspace, void* stream) {
-    TDX_CHECK_ARG(x1 && dy && dw && workspace && B > 0 && X > 0 && Y > 0 && Z > 0 && C1 > 0 && C2 >= 0 && Cout > 0);
-    TDX_CHECK_ARG(C2 == 0 || x2);
-    const int Cin = C1 + C2;
-    if ((C1 % 8) || (C2 % 8) || (Cout % 8)) return TDX_ESHAPE;
-    hipStream_t st = as_stream(stream);
-    const bool clean = (impl & TDX_WS_CLEAN) != 0;
-    impl &= 0xff;
-    float* dwp = (float*)workspace;
-    float* dbw = dwp + (size_t)27 * Cin * Cout;  // bias-gradient accumulator
-    if (!clean) {
-        int e = tdx_zero_async(dwp, ((size_t)27 * Cin * Cout + Cout) * sizeof(float), st);
-        if (e != TDX_OK) return e;
-    }
-    const bool use_mfma = impl == TDX_CONV_MFMA || (impl == TDX_CONV_AUTO && tdx_is_h16(dtype) &&
-                                                     conv3_wgrad_mfma_supported(C1, C2, Cout));
-    int nslab = 0;
-    const float* slab_ptr = nullptr;
-    // TDX_DETERMINISTIC: no bias-gradient atomics inside the weight-gradient kernels -- the bias gradient is summed from dy in a
-    // fixed order afterwards (partials in the slab region, free again once the unpack kernel has read it); the launchers hold
-    // their K splits to the slab capacity (per-split slabs added in order: their default for few splits)
-    const bool det = tdx_deterministic();
-    float* bias_acc = (dbias && !det) ? dbw : nullptr;
-    float* slab_base = dbw + ((Cout + 63) / 64) * 64;
-    auto ordered_bias = [&]() -> int {
-        if (!det || !dbias) return TDX_OK;
-        return bias_grad_ordered_launch(dy, (int64_t)B * X * Y * Z, Cout, dtype, dbias, slab_base,
-                                        (size_t)W3_MAX_SLABS * 27 * Cin * Cout, st);
-    };
-    // the fp32-tensor kernels split K 256-fold on the fine levels and merge with atomics by default (8 slabs); deterministic runs
-    // give them the slab capacity the 16-bit kernels use
-    const int cap_f32 = det ? w3_slab_capacity(Cin, Cout) : W3_MAX_SLABS;
-    auto many_slabs = [&]() -> int {  // more slabs than the 16 x 16 unpack kernel walks: the per-tap summing unpack
-        hipLaunchKernelGGL(conv3_unpack_sum_kernel, dim3(ceil_div(Cin, 8), ceil_div(Cout, 32), 27), dim3(256), 0, st, dw, dbw, dbias,
-                           Cin, Cout, slab_ptr, nslab);
-        const int rc2 = tdx_launch_status();
-        return rc2 != TDX_OK ? rc2 : ordered_bias();
-    };
-    if (dtype == TDX_F32 && impl == TDX_CONV_SPLIT && conv3_wgrad_mfma_split_supported(C1, C2, Cout)) {
-        float* slabs = dbw + ((Cout + 63) / 64) * 64;
-        int rc = conv3_wgrad_mfma_split_launch(x1, C1, x2, C2, dy, dwp, bias_acc, B, X, Y, Z, Cout, st, slabs,
-                                               cap_f32, &nslab);
-        slab_ptr = slabs;
-        if (rc != TDX_OK) return rc;
-        if (nslab > W3_MAX_SLABS) return many_slabs();
-    } else if (dtype == TDX_F32 && impl != TDX_CONV_DIRECT && conv3_wgrad_mfma_f32_supported(C1, C2, Cout)) {
-        float* slabs = dbw + ((Cout + 63) / 64) * 64;
-        int rc = conv3_wgrad_mfma_f32_launch(x1, C1, x2, C2, dy, dwp, bias_acc, B, X, Y, Z, Cout, st, slabs,
-                                             cap_f32, &nslab);
-        slab_ptr = slabs;
-        if (rc != TDX_OK) return rc;
-        if (nslab > W3_MAX_SLABS) return many_slabs();
-    } else if (use_mfma) {
-        if (!tdx_is_h16(dtype)) return TDX_EDTYPE;
-        if (!conv3_wgrad_mfma_supported(C1, C2, Cout)) return TDX_ESHAPE;
-        float* slabs = dbw + ((Cout + 63) / 64) * 64;
-        const int cap = w3_slab_capacity(Cin, Cout);
-        int rc = conv3_wgrad_mfma_launch(x1, C1, x2, C2, dy, dwp, bias_acc, B, X, Y, Z, Cout, st, slabs, cap, &nslab,
-                                         dtype == TDX_F16);
-        slab_ptr = slabs;
-        if (rc != TDX_OK) return rc;
-        if (nslab > W3_MAX_SLABS) return many_slabs();
-    } else {
-        const int64_t nvox = (int64_t)B * X * Y * Z;
-        const int nci = ceil_div(Cin, D3_BM), nco = ceil_div(Cout, D3_BN);
-        int64_t vpb = D3W_VOX, slab_stride = 0;
-        float* out = dwp;
-        if (det) {  // at most min(capacity, 64) voxel chunks, one slab each
-            const int chunks = std::min(w3_slab_capacity(Cin, Cout), 64);
-            vpb = (ceil_div(nvox, chunks) + D3_BK - 1) / D3_BK * D3_BK;
-            slab_stride = (int64_t)27 * Cin * Cout;
-            out = slab_base;
-            nslab = ceil_div(nvox, vpb);
-            slab_ptr = slab_base;
-        }
-        dim3 grid(ceil_div(nvox, vpb), 27, nci * nco);
-        TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv3_wgrad_direct_kernel<T>), grid, dim3(256), 0, st,
-                                                      (const T*)x1, C1, (const T*)x2, C2, (const T*)dy, out,
-                                                      bias_acc, B, X, Y, Z, Cout, nci, vpb, slab_stride));
-    }
-    hipLaunchKernelGGL(conv3_unpack_wgrad_kernel, dim3(ceil_div(Cin, 16), ceil_div(Cout, 16)), dim3(256), 0, st, dwp, dw,
-                       dbw, dbias, Cin, Cout, slab_ptr, nslab);
-    const int rc_unpack = tdx_launch_status();
-    return rc_unpack != TDX_OK ? rc_unpack : ordered_bias();
 }

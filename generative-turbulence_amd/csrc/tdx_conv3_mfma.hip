@@ -371,9 +371,7 @@ conv3_mfma_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restrict__ 
 }
 
 template <int NT, bool XT, bool ZP, bool PERM, bool EXT, bool HF>
-static int launch_view_h(const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* y,
-                       const ConvViews& v, int Cout, hipStream_t st, double* gn_acc, void* d1, int D1, void* d2,
-                       const void* a1, const void* a2, const void* init) {
+static int launch_view_h(const Conv3Call& c, const ConvViews& v) {
     constexpr int BN = NT * 32;
     constexpr int HXv = (XT ? 2 : 4) + 2, HYv = (XT ? 16 : 8) + 2, SZv = XT ? 10 : 12;
     const size_t lds = (size_t)2 * (HXv * HYv * SZv * 16 + 64) + (size_t)27 * BN * 32 + 128;
@@ -384,24 +382,25 @@ static int launch_view_h(const void* x1, int C1, const void* x2, int C2, const v
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    dim3 grid((unsigned)v.start[3], Cout / BN);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const bf16*)x1, C1, (const bf16*)x2, C2, (const bf16*)wp, bias,
-                       (bf16*)y, v, Cout, gn_acc, (bf16*)d1, D1, (bf16*)d2, (const bf16*)a1, (const bf16*)a2, (const bf16*)init);
+    dim3 grid((unsigned)v.start[3], c.N / BN);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, c.st, (const bf16*)c.x1, c.C1, (const bf16*)c.x2, c.C2, (const bf16*)c.wp, c.bias,
+                       (bf16*)c.y, v, c.N, c.gn_acc, (bf16*)c.d1, c.D1, (bf16*)c.d2, (const bf16*)c.a1, (const bf16*)c.a2,
+                       (const bf16*)(EXT ? c.ext->init : nullptr));
     return tdx_launch_status();
 }
 template <int NT, bool XT, bool ZP, bool PERM, bool EXT = false>
-static int launch_view(const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* y,
-                       const ConvViews& v, int Cout, hipStream_t st, double* gn_acc, void* d1, int D1, void* d2,
-                       const void* a1, const void* a2, const void* init, bool hf) {
-    if (hf) return launch_view_h<NT, XT, ZP, PERM, EXT, true>(x1, C1, x2, C2, wp, bias, y, v, Cout, st, gn_acc, d1, D1, d2, a1, a2, init);
-    return launch_view_h<NT, XT, ZP, PERM, EXT, false>(x1, C1, x2, C2, wp, bias, y, v, Cout, st, gn_acc, d1, D1, d2, a1, a2, init);
+static int launch_view(const Conv3Call& c, const ConvViews& v) {
+    return c.hf() ? launch_view_h<NT, XT, ZP, PERM, EXT, true>(c, v) : launch_view_h<NT, XT, ZP, PERM, EXT, false>(c, v);
 }
 
-int conv3_mfma_launch(const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* y,
-                      const Conv3Geom& g, int Cout, bool zero_pad, hipStream_t st, double* gn_acc, void* d1, int D1,
-                      void* d2, const void* a1, const void* a2, const Conv3Ext* ext, const int* slabs_beyond, bool hf) {
-    const int NT = (Cout % 64 == 0) ? 2 : 1;
-    const void* init = ext ? ext->init : nullptr;
+int conv3_mfma_launch(const Conv3Call& c) {
+    if (!tdx_is_h16(c.fmt)) return TDX_EINVAL;
+    const Conv3Geom g = c.geom();
+    const int C1 = c.C1, C2 = c.C2;
+    const bool zero_pad = c.zero_pad;
+    const Conv3Ext* ext = c.ext;
+    const int* slabs_beyond = c.slabs_beyond;
+    const int NT = (c.N % 64 == 0) ? 2 : 1;
     if ((int64_t)g.Xi * g.Yi * g.Zi * 2 >= (1ll << 31) || (int64_t)g.Xo * g.Yo * g.Zo >= (1ll << 31)) return TDX_ESHAPE;
     static const bool no_thin = getenv("TDX_CONV3_THIN") && atoi(getenv("TDX_CONV3_THIN")) == 0;  // A/B switch
 
@@ -448,18 +447,10 @@ int conv3_mfma_launch(const void* x1, int C1, const void* x2, int C2, const void
     };
     auto launch = [&](const ConvViews& vs, bool xt, bool permuted) -> int {
         if (vs.start[3] == 0) return TDX_OK;
-#define M3_GO(NTV, XTV, PV)                                                                                             \
-    (zero_pad ? launch_view<NTV, XTV, true, PV>(x1, C1, x2, C2, wp, bias, y, vs, Cout, st, gn_acc, d1, D1, d2, a1, a2,  \
-                                                nullptr, hf)                                                           \
-              : launch_view<NTV, XTV, false, PV>(x1, C1, x2, C2, wp, bias, y, vs, Cout, st, gn_acc, d1, D1, d2, a1, a2, \
-                                                 nullptr, hf))
+#define M3_GO(NTV, XTV, PV) (zero_pad ? launch_view<NTV, XTV, true, PV>(c, vs) : launch_view<NTV, XTV, false, PV>(c, vs))
         if (ext != nullptr) {  // strided input / init tensor: forward main bricks only
             if (zero_pad || xt || permuted) return TDX_ESHAPE;
-            if (NT == 2)
-                return launch_view<2, false, false, false, true>(x1, C1, x2, C2, wp, bias, y, vs, Cout, st, gn_acc, d1, D1, d2,
-                                                                 a1, a2, init, hf);
-            return launch_view<1, false, false, false, true>(x1, C1, x2, C2, wp, bias, y, vs, Cout, st, gn_acc, d1, D1, d2, a1,
-                                                             a2, init, hf);
+            return NT == 2 ? launch_view<2, false, false, false, true>(c, vs) : launch_view<1, false, false, false, true>(c, vs);
         }
         if (NT == 2) return xt ? M3_GO(2, true, false) : (permuted ? M3_GO(2, false, true) : M3_GO(2, false, false));
         return xt ? M3_GO(1, true, false) : (permuted ? M3_GO(1, false, true) : M3_GO(1, false, false));

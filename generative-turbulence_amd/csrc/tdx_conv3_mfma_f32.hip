@@ -253,9 +253,11 @@ conv3_mfma_f32_kernel(const float* __restrict__ x1, int C1, const float* __restr
     }
 }
 
-int conv3_mfma_f32_launch(const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* y,
-                          const Conv3Geom& g, int Cout, bool zero_pad, hipStream_t st, double* gn_acc, void* d1, int D1, void* d2,
-                          const void* a1, const void* a2) {
+int conv3_mfma_f32_launch(const Conv3Call& c) {
+    if (c.fmt != TDX_F32) return TDX_EINVAL;
+    const Conv3Geom g = c.geom();
+    const bool zero_pad = c.zero_pad;
+    const int Cout = c.N;
     if ((int64_t)g.Xi * g.Yi * g.Zi * 2 >= (1ll << 31) || (int64_t)g.Xo * g.Yo * g.Zo >= (1ll << 31)) return TDX_ESHAPE;
     static const bool no_thin = getenv("TDX_CONV3_THIN") && atoi(getenv("TDX_CONV3_THIN")) == 0;  // A/B switch
     const int NT = (Cout % 64 == 0) ? 2 : 1;
@@ -278,9 +280,9 @@ int conv3_mfma_f32_launch(const void* x1, int C1, const void* x2, int C2, const 
             attr_set = true;                                                                                            \
         }                                                                                                               \
         dim3 grid((unsigned)(REG).start[(REG).n], Cout / BNV);                                                          \
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const float*)x1, C1, (const float*)x2, C2, (const float*)wp, \
-                           bias, (float*)y, REG, Cout, gn_acc, (float*)d1, D1, (float*)d2, (const float*)a1,             \
-                           (const float*)a2);                                                                           \
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, c.st, (const float*)c.x1, c.C1, (const float*)c.x2, c.C2,        \
+                           (const float*)c.wp, c.bias, (float*)c.y, REG, Cout, c.gn_acc, (float*)c.d1, c.D1,            \
+                           (float*)c.d2, (const float*)c.a1, (const float*)c.a2);                                       \
     } while (0)
     const bool perm = main.v[0].perm[0] != 0;
     if (NT == 2) {

@@ -47,39 +47,24 @@ int conv3_mfma_split_go_1rmp(SPLIT_GO_ARGS);
 int conv3_mfma_split_go_1rmn(SPLIT_GO_ARGS);
 int conv3_mfma_split_go_1ztp(SPLIT_GO_ARGS);
 
-int conv3_mfma_split_launch(const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* y,
-                            const Conv3Geom& g, int Cout, bool zero_pad, hipStream_t st, double* gn_acc, void* d1, int D1, void* d2,
-                            const void* a1, const void* a2) {
+int conv3_mfma_split_launch(const Conv3Call& c) {
+    if (c.fmt != TDX_F32_SPLIT) return TDX_EINVAL;
+    const Conv3Geom g = c.geom();
+    const bool zero_pad = c.zero_pad;
     if ((int64_t)g.Xi * g.Yi * g.Zi * 2 >= (1ll << 31) || (int64_t)g.Xo * g.Yo * g.Zo >= (1ll << 31)) return TDX_ESHAPE;
     static const bool no_thin = getenv("TDX_CONV3_THIN") && atoi(getenv("TDX_CONV3_THIN")) == 0;  // A/B switch
-    const int NT = (Cout % 64 == 0) ? 2 : 1;
+    const int NT = (c.N % 64 == 0) ? 2 : 1;
     // 32-wide output tiles: 8 x 8 x 8 bricks (four M tiles per wave) where the grid is large enough to fill the chip
     const bool big = NT == 1 && (int64_t)g.B * ceil_div(g.Xo, 8) * ceil_div(g.Yo, 8) * ceil_div(g.Zo, 8) >= 1024;
     BrickRegions main, thin;
     brick_plan(g, zero_pad, !no_thin, main, thin, big ? BRICK_BIG : BRICK_MAIN);
-    const int64_t lo_offset = (int64_t)27 * (C1 + C2) * Cout;  // elements between the hi and the lo weight image
     const bool perm = main.v[0].perm[0] != 0;  // forward on ragged grids: the short brick edge on another axis
-    auto go_main = [&]() -> int {
-        if (NT == 2) {
-            if (zero_pad && perm) { return conv3_mfma_split_go_2zmp(x1, C1, x2, C2, wp, bias, y, main, Cout, lo_offset, gn_acc, d1, D1, d2, a1, a2, st); }
-            if (zero_pad) { return conv3_mfma_split_go_2zmn(x1, C1, x2, C2, wp, bias, y, main, Cout, lo_offset, gn_acc, d1, D1, d2, a1, a2, st); }
-            if (perm) { return conv3_mfma_split_go_2rmp(x1, C1, x2, C2, wp, bias, y, main, Cout, lo_offset, gn_acc, d1, D1, d2, a1, a2, st); }
-            return conv3_mfma_split_go_2rmn(x1, C1, x2, C2, wp, bias, y, main, Cout, lo_offset, gn_acc, d1, D1, d2, a1, a2, st);
-        }
-        if (big) {
-            if (zero_pad && perm) { return conv3_mfma_split_go_1zbp(x1, C1, x2, C2, wp, bias, y, main, Cout, lo_offset, gn_acc, d1, D1, d2, a1, a2, st); }
-            if (zero_pad) { return conv3_mfma_split_go_1zbn(x1, C1, x2, C2, wp, bias, y, main, Cout, lo_offset, gn_acc, d1, D1, d2, a1, a2, st); }
-            if (perm) { return conv3_mfma_split_go_1rbp(x1, C1, x2, C2, wp, bias, y, main, Cout, lo_offset, gn_acc, d1, D1, d2, a1, a2, st); }
-            return conv3_mfma_split_go_1rbn(x1, C1, x2, C2, wp, bias, y, main, Cout, lo_offset, gn_acc, d1, D1, d2, a1, a2, st);
-        }
-        if (zero_pad && perm) { return conv3_mfma_split_go_1zmp(x1, C1, x2, C2, wp, bias, y, main, Cout, lo_offset, gn_acc, d1, D1, d2, a1, a2, st); }
-        if (zero_pad) { return conv3_mfma_split_go_1zmn(x1, C1, x2, C2, wp, bias, y, main, Cout, lo_offset, gn_acc, d1, D1, d2, a1, a2, st); }
-        if (perm) { return conv3_mfma_split_go_1rmp(x1, C1, x2, C2, wp, bias, y, main, Cout, lo_offset, gn_acc, d1, D1, d2, a1, a2, st); }
-        return conv3_mfma_split_go_1rmn(x1, C1, x2, C2, wp, bias, y, main, Cout, lo_offset, gn_acc, d1, D1, d2, a1, a2, st);
-    };
-    int rc = go_main();
+    // instantiation <tiles><z: zero-padded, r: replicate><b: big, m: main bricks><p: permuted, n: not>
+#define SP_GO(T, S) (zero_pad ? (perm ? conv3_mfma_split_go_##T##z##S##p(c, main) : conv3_mfma_split_go_##T##z##S##n(c, main)) \
+                              : (perm ? conv3_mfma_split_go_##T##r##S##p(c, main) : conv3_mfma_split_go_##T##r##S##n(c, main)))
+    const int rc = NT == 2 ? SP_GO(2, m) : (big ? SP_GO(1, b) : SP_GO(1, m));
+#undef SP_GO
     if (rc != TDX_OK) return rc;
     // remainder slabs of the padded grid: 2 x 16 x 8 bricks, 32-wide tiles
-    if (thin.n > 0) { return conv3_mfma_split_go_1ztp(x1, C1, x2, C2, wp, bias, y, thin, Cout, lo_offset, gn_acc, d1, D1, d2, a1, a2, st); }
-    return TDX_OK;
+    return thin.n > 0 ? conv3_mfma_split_go_1ztp(c, thin) : TDX_OK;
 }

@@ -324,9 +324,7 @@ conv3_mfma_split_kernel(const float* __restrict__ x1, int C1, const float* __res
     }
 }
 
-#define SPLIT_GO_ARGS const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* y,          \
-                      const BrickRegions& reg, int Cout, int64_t lo_offset, double* gn_acc, void* d1, int D1, void* d2,       \
-                      const void* a1, const void* a2, hipStream_t st
+#define SPLIT_GO_ARGS const Conv3Call& c, const BrickRegions& reg
 template <int NTV, bool ZP, int TH, bool PM>
 static int split_go(SPLIT_GO_ARGS) {
     constexpr int BNV = NTV * 32;
@@ -338,10 +336,12 @@ static int split_go(SPLIT_GO_ARGS) {
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    dim3 grid((unsigned)reg.start[reg.n], Cout / BNV);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const float*)x1, C1, (const float*)x2, C2, (const bf16*)wp, bias, (float*)y,
-                       reg, Cout, lo_offset, gn_acc, (float*)d1, D1, (float*)d2, (const float*)a1, (const float*)a2);
+    dim3 grid((unsigned)reg.start[reg.n], c.N / BNV);
+    const int64_t lo_offset = (int64_t)27 * (c.C1 + c.C2) * c.N;  // elements between the hi and the lo weight image
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, c.st, (const float*)c.x1, c.C1, (const float*)c.x2, c.C2, (const bf16*)c.wp, c.bias,
+                       (float*)c.y, reg, c.N, lo_offset, c.gn_acc, (float*)c.d1, c.D1, (float*)c.d2, (const float*)c.a1,
+                       (const float*)c.a2);
     return tdx_launch_status();
 }
 #define SPLIT_INSTANCE(NTV, ZP, TH, PM, NAME) \
-    int NAME(SPLIT_GO_ARGS) { return split_go<NTV, ZP, TH, PM>(x1, C1, x2, C2, wp, bias, y, reg, Cout, lo_offset, gn_acc, d1, D1, d2, a1, a2, st); }
+    int NAME(SPLIT_GO_ARGS) { return split_go<NTV, ZP, TH, PM>(c, reg); }

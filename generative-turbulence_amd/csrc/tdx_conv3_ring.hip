@@ -35,7 +35,7 @@
 // is the brick depth (Z4: 8 MT x 8 x 4 bricks for grids like 48 x 16 x 12 -- see RingShape).
 //
 // Same products and the same fp32 accumulation as the brick kernel up to summation order (taps in pairs, bias first).
-// Used when the grid's whole bricks fill the chip and leave at most 2 voxels per axis (conv3_ring_supported; those
+// Used when the grid's whole bricks fill the chip and leave at most 2 voxels per axis (conv3_ring_depth; those
 // remainder slabs go to the thin-brick kernel in a second launch); everything else stays on the brick kernel.
 #include "tdx_common.h"
 #include "tdx_conv3.h"
@@ -567,8 +567,10 @@ static int ring_brick_depth(int C1, int C2, int Cout, int B, int X, int Y, int Z
     if (ring_z8_supported(C1, C2, Cout, B, X, Y, Z, mode)) return 8;
     return ring_z4_supported(C1, C2, Cout, B, X, Y, Z, mode) ? 4 : 0;
 }
-bool conv3_ring_supported(int C1, int C2, int Cout, int B, int X, int Y, int Z) {
-    return ring_brick_depth(C1, C2, Cout, B, X, Y, Z) != 0;
+// the route's question and the launcher's precondition: the data gradient reads its zero-padding from the arena's zero block
+int conv3_ring_depth(int C1, int C2, int N, int B, int X, int Y, int Z, bool data_gradient) {
+    if (data_gradient && (tdx_scratch_ptr() == nullptr || tdx_scratch_bytes() < 16)) return 0;
+    return ring_brick_depth(C1, C2, N, B, X, Y, Z);
 }
 static bool ring_z8_supported(int C1, int C2, int Cout, int B, int X, int Y, int Z, int mode) {
     const int NT = Cout % 64 == 0 ? 2 : 1, bx = NT == 2 ? 8 : 16;
@@ -616,23 +618,23 @@ static int ring_go(const RingArgs& a, hipStream_t st) {
     return tdx_launch_status();
 }
 
-// forward (zero_pad = false: y, bias, gn_acc) or main term of the data gradient (zero_pad = true: d1 / d2 / a1 / a2);
-// TDX_ESHAPE = not a case for this kernel, take the brick kernel
-int conv3_ring_launch(const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* y, int B, int X,
-                      int Y, int Z, int Cout, bool zero_pad, hipStream_t st, double* gn_acc, void* d1, int D1, void* d2,
-                      const void* a1, const void* a2, bool hf) {
-    const int depth = ring_brick_depth(C1, C2, Cout, B, X, Y, Z);
-    if (depth == 0) return TDX_ESHAPE;
-    if (zero_pad && (tdx_scratch_ptr() == nullptr || tdx_scratch_bytes() < 16)) return TDX_ESHAPE;  // zero source
-    const int NT = Cout % 64 == 0 ? 2 : 1;
+// forward (zero_pad = false: y, bias, gn_acc) or main term of the data gradient (zero_pad = true: d1 / d2 / a1 / a2) with
+// bricks of depth = conv3_ring_depth of this call
+int conv3_ring_launch(const Conv3Call& c, int depth) {
+    if ((depth != 4 && depth != 8) || !tdx_is_h16(c.fmt)) return TDX_EINVAL;
+    if (c.zero_pad && (tdx_scratch_ptr() == nullptr || tdx_scratch_bytes() < 16)) return TDX_EINVAL;  // zero source
+    const int X = c.X, Y = c.Y, Z = c.Z;
+    const bool zero_pad = c.zero_pad, hf = c.hf();
+    hipStream_t st = c.st;
+    const int NT = c.N % 64 == 0 ? 2 : 1;
     const int bxr = (NT == 2 ? 8 : 16) * (depth == 4 ? 2 : 1);  // brick extent along x
     RingArgs a;
-    a.x1 = (const bf16*)x1; a.x2 = (const bf16*)x2; a.C1 = C1; a.C2 = C2;
-    a.wp = (const bf16*)wp; a.bias = bias; a.y = (bf16*)y;
-    a.B = B; a.X = X; a.Y = Y; a.Z = Z; a.Cout = Cout;
-    a.nbx = X / bxr; a.nby = Y / 8; a.nbz = Z / depth; a.ntn = Cout / (32 * NT);
-    a.gn_acc = gn_acc;
-    a.d1 = (bf16*)d1; a.d2 = (bf16*)d2; a.D1 = D1; a.a1 = (const bf16*)a1; a.a2 = (const bf16*)a2;
+    a.x1 = (const bf16*)c.x1; a.x2 = (const bf16*)c.x2; a.C1 = c.C1; a.C2 = c.C2;
+    a.wp = (const bf16*)c.wp; a.bias = c.bias; a.y = (bf16*)c.y;
+    a.B = c.B; a.X = X; a.Y = Y; a.Z = Z; a.Cout = c.N;
+    a.nbx = X / bxr; a.nby = Y / 8; a.nbz = Z / depth; a.ntn = c.N / (32 * NT);
+    a.gn_acc = c.gn_acc;
+    a.d1 = (bf16*)c.d1; a.d2 = (bf16*)c.d2; a.D1 = c.D1; a.a1 = (const bf16*)c.a1; a.a2 = (const bf16*)c.a2;
     a.zeros = tdx_scratch_ptr();
     a.stamps = nullptr;
 #ifdef RG_STAMPS
@@ -660,12 +662,13 @@ int conv3_ring_launch(const void* x1, int C1, const void* x2, int C2, const void
     // the 1-2 voxel remainder slabs beyond the whole bricks: thin 2 x 16 x 8 bricks, all slabs in one launch (same
     // operands, same epilogue incl. the statistics accumulators and the data gradient's split / addends)
     const int beyond[3] = {X - X % bxr, Y - Y % 8, Z - Z % depth};
-    const Conv3Geom g = {B, X, Y, Z, X, Y, Z, 0};
-    return conv3_mfma_launch(x1, C1, x2, C2, wp, bias, y, g, Cout, zero_pad, st, gn_acc, d1, D1, d2, a1, a2, nullptr, beyond, hf);
+    Conv3Call rest = c;
+    rest.slabs_beyond = beyond;
+    return conv3_mfma_launch(rest);
 }
 
 extern "C" int tdx_conv3_uses_ring(int C1, int C2, int Cout, int B, int X, int Y, int Z) {
-    return conv3_ring_supported(C1, C2, Cout, B, X, Y, Z) ? 1 : 0;
+    return ring_brick_depth(C1, C2, Cout, B, X, Y, Z) != 0 ? 1 : 0;
 }
 extern "C" int tdx_conv3_ring_brick_depth(int C1, int C2, int Cout, int B, int X, int Y, int Z) {
     return ring_brick_depth(C1, C2, Cout, B, X, Y, Z);

@@ -187,64 +187,49 @@ int conv3_small_go_5h(SMALL_GO_ARGS);
 int conv3_small_go_6h(SMALL_GO_ARGS);
 int conv3_small_go_7h(SMALL_GO_ARGS);
 
-// FMT: 0 bf16 tensors, 1 split-precision fp32 tensors, 2 fp16 tensors
-template <int FMT>
-static int small_dispatch(int mtw, SMALL_GO_ARGS) {
-#define GO(M) (FMT == 1 ? conv3_small_go_##M##s(x1, C1, x2, C2, wp, slab, zero16, g, lds, lo_offset, st)   \
-               : FMT == 2 ? conv3_small_go_##M##h(x1, C1, x2, C2, wp, slab, zero16, g, lds, lo_offset, st) \
-                          : conv3_small_go_##M##b(x1, C1, x2, C2, wp, slab, zero16, g, lds, lo_offset, st))
-    switch (mtw) {
+static int small_dispatch(SMALL_GO_ARGS) {
+#define GO(M) (c.fmt == TDX_F32_SPLIT ? conv3_small_go_##M##s(c, p, slab, zero16, lo_offset)   \
+               : c.hf() ? conv3_small_go_##M##h(c, p, slab, zero16, lo_offset) \
+                        : conv3_small_go_##M##b(c, p, slab, zero16, lo_offset))
+    switch (p.mtw) {
         case 1: case 2: case 3: return GO(3);
         case 4: return GO(4);
         case 5: return GO(5);
         case 6: return GO(6);
         case 7: return GO(7);
-        default: return TDX_ESHAPE;  // more than 28 M tiles per row group: not a launch small_plan produces
+        default: return TDX_ESHAPE;  // more than 28 M tiles per row group: not a launch conv3_small_plan produces
     }
 #undef GO
 }
 
-// would conv3_small_launch take this call? (bookkeeping: tdx_conv3_fwd_kernel)
-bool conv3_small_applies(int C1, int C2, int B, int X, int Y, int Z, int N, bool data_gradient, bool split) {
+// Plan the call; false = not a small-grid case (no arena, shapes, grid too large, arena too small): the route then takes the
+// next family.  split: fp32 tensors with split-precision products.
+bool conv3_small_plan(Conv3SmallPlan& p, int C1, int C2, int N, int B, int X, int Y, int Z, bool data_gradient, bool split) {
     if (tdx_scratch_ptr() == nullptr || (C1 % SM_KC) || (C2 % SM_KC)) return false;
-    SmallGeom g;
-    size_t lds = 0;
-    if (!small_plan(g, B, X, Y, Z, C1 + C2, N, data_gradient, split, tdx_scratch_bytes(), lds)) return false;
-    return ceil_div(ceil_div(g.nbg * g.xs * g.Ev[1] * g.Ev[2], 32), 4) <= SM_MAX_TILES / 4;
+    if (!small_plan(p.g, B, X, Y, Z, C1 + C2, N, data_gradient, split, tdx_scratch_bytes(), p.lds)) return false;
+    p.mtw = ceil_div(ceil_div(p.g.nbg * p.g.xs * p.g.Ev[1] * p.g.Ev[2], 32), 4);
+    return p.mtw <= SM_MAX_TILES / 4;  // never drop rows silently
 }
 
-// Forward (data_gradient == false: y = conv3([x1 | x2]) + bias, N = Cout) or data gradient (x1 = dy with K = C1
-// channels, x2 unused; result N channels split over out1 [0, D1) / out2, plus addends).  split == false: bf16 tensors,
-// wp = the bf16 packed weight; split == true: fp32 tensors, wp = the split-precision packed weight (hi image, lo image).
-// Returns TDX_ESHAPE when the launch is not a small-grid case (the caller then takes the brick kernels).
-int conv3_small_launch(const void* x1, int C1, const void* x2, int C2, const void* wp, const float* bias, void* out1, int D1,
-                       void* out2, const void* add1, const void* add2, int B, int X, int Y, int Z, int N, bool data_gradient,
-                       bool split, hipStream_t st, bool hf) {
+// Forward (c.zero_pad == false: y = conv3([x1 | x2]) + bias) or data gradient (x1 = dy with K = C1 channels, x2 unused;
+// result N channels split over d1 [0, D1) / d2, plus addends).  TDX_BF16 / TDX_F16: 16-bit tensors and packed weight;
+// TDX_F32_SPLIT: fp32 tensors, wp = the split-precision packed weight (hi image, lo image).  p: conv3_small_plan of this call.
+int conv3_small_launch(const Conv3Call& c, const Conv3SmallPlan& p) {
     char* arena = (char*)tdx_scratch_ptr();
-    if (arena == nullptr) return TDX_ESHAPE;
-    if ((C1 % SM_KC) || (C2 % SM_KC)) return TDX_ESHAPE;
-    SmallGeom g;
-    size_t lds = 0;
-    if (!small_plan(g, B, X, Y, Z, C1 + C2, N, data_gradient, split, tdx_scratch_bytes(), lds)) return TDX_ESHAPE;
+    const bool split = c.fmt == TDX_F32_SPLIT;
+    if (arena == nullptr || !(split || tdx_is_h16(c.fmt))) return TDX_EINVAL;
     float* slab = reinterpret_cast<float*>(arena + 64);
-    const int rows = g.nbg * g.xs * g.Ev[1] * g.Ev[2];
-    const int mtw = ceil_div(ceil_div(rows, 32), 4);
-    if (mtw > SM_MAX_TILES / 4) return TDX_ESHAPE;  // never drop rows silently: the brick kernels take the call
-    const int64_t lo = (int64_t)27 * (C1 + C2) * N;  // elements between the hi and the lo weight image
-    if (split && hf) return TDX_EINVAL;
-    const int rc = split ? small_dispatch<1>(mtw, x1, C1, x2, C2, wp, slab, arena, g, lds, lo, st)
-                   : hf ? small_dispatch<2>(mtw, x1, C1, x2, C2, wp, slab, arena, g, lds, 0, st)
-                         : small_dispatch<0>(mtw, x1, C1, x2, C2, wp, slab, arena, g, lds, 0, st);
+    const int N = c.N, D1 = c.zero_pad ? c.D1 : N, fold = c.zero_pad ? 1 : 0;
+    void* out1 = c.zero_pad ? c.d1 : c.y;
+    const int rc = small_dispatch(c, p, slab, arena, split ? (int64_t)27 * (c.C1 + c.C2) * N : 0);
     if (rc != TDX_OK) return rc;
-    const int64_t total = (int64_t)B * X * Y * Z * (N / 8);
-    if (split)
-        hipLaunchKernelGGL(conv3_small_reduce_kernel<float>, dim3(ceil_div(total, 256)), dim3(256), 0, st, slab, bias, (float*)out1,
-                           D1, (float*)out2, (const float*)add1, (const float*)add2, B, X, Y, Z, N, g.nsplit, data_gradient ? 1 : 0);
-    else if (hf)
-        hipLaunchKernelGGL(conv3_small_reduce_kernel<f16>, dim3(ceil_div(total, 256)), dim3(256), 0, st, slab, bias, (f16*)out1,
-                           D1, (f16*)out2, (const f16*)add1, (const f16*)add2, B, X, Y, Z, N, g.nsplit, data_gradient ? 1 : 0);
-    else
-        hipLaunchKernelGGL(conv3_small_reduce_kernel<bf16>, dim3(ceil_div(total, 256)), dim3(256), 0, st, slab, bias, (bf16*)out1,
-                           D1, (bf16*)out2, (const bf16*)add1, (const bf16*)add2, B, X, Y, Z, N, g.nsplit, data_gradient ? 1 : 0);
+    const int64_t total = (int64_t)c.B * c.X * c.Y * c.Z * (N / 8);
+#define SM_REDUCE(T)                                                                                                          \
+    hipLaunchKernelGGL(conv3_small_reduce_kernel<T>, dim3(ceil_div(total, 256)), dim3(256), 0, c.st, slab, c.bias, (T*)out1, D1, \
+                       (T*)c.d2, (const T*)c.a1, (const T*)c.a2, c.B, c.X, c.Y, c.Z, N, p.g.nsplit, fold)
+    if (split) SM_REDUCE(float);
+    else if (c.hf()) SM_REDUCE(f16);
+    else SM_REDUCE(bf16);
+#undef SM_REDUCE
     return tdx_launch_status();
 }

@@ -2,7 +2,6 @@
 #pragma once
 #include "tdx_common.h"
 #include "tdx_conv3.h"
-#include "tdx_conv3.h"
 #include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -12,20 +11,7 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 #define SM_BN 32
 #define SM_MAX_TILES 28
 
-struct SmallGeom {
-    int B;
-    int Ev[3];     // virtual grid (rows)
-    int Es[3];     // source grid
-    int off;       // source coordinate = virtual coordinate - off
-    int clamp;     // 1: clamp sources into the grid (forward), 0: zero outside (data gradient)
-    int nbg;       // samples per row group (1 when a sample is cut into x slabs)
-    int xs;        // virtual x planes per row group
-    int gx;        // x slabs per sample
-    int Ix, Iy, Iz;  // LDS image per sample of a group: (xs + 2) x (Ev[1] + 2) x (Ev[2] + 2) entries
-    int K, N;      // channels of the source tensor(s) / of the result
-    int per_split; // K slices per split
-    int nsplit;
-};
+// SmallGeom, the launch geometry: tdx_conv3.h
 
 // SPLIT = false: bf16 tensors.  SPLIT = true: fp32 tensors with split-precision products (every operand as bf16 hi + lo,
 // x w ~ xh wh + xl wh + xh wl, as tdx_conv3_mfma_split.hip): the image is staged as raw fp32 (four 16-B quarter planes of
@@ -282,25 +268,25 @@ conv3_small_kernel(const void* __restrict__ x1_, int C1, const void* __restrict_
 // host-side launch of one instantiation; every (MTW, SPLIT) pair lives in its own translation unit
 // (tdx_conv3_small_i*.hip: the 27-tap x MTW-tile loop is fully unrolled and takes minutes to compile, so the ten
 // instantiations build in parallel), declared here for the dispatcher in tdx_conv3_small.hip
-#define SMALL_GO_ARGS const void* x1, int C1, const void* x2, int C2, const void* wp, float* slab, const void* zero16, \
-                      const SmallGeom& g, size_t lds, int64_t lo_offset, hipStream_t st
+// slab: the K-split partial tiles; zero16: a zeroed 16-B block; lo_offset: elements between the hi and the lo weight image
+#define SMALL_GO_ARGS const Conv3Call& c, const Conv3SmallPlan& p, float* slab, const void* zero16, int64_t lo_offset
 template <int MTW, bool SPLIT, bool HF = false>
 static int small_go(SMALL_GO_ARGS) {
     static_assert(!(SPLIT && HF), "split precision has bf16 halves");
     auto kern = conv3_small_kernel<MTW, SPLIT, HF>;
     static size_t attr = 0;
-    if (lds > attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (p.lds > attr) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
         if (e != hipSuccess) return (int)e;
-        attr = lds;
+        attr = p.lds;
     }
+    const SmallGeom& g = p.g;
     const int ngroups = ceil_div(g.B, g.nbg) * g.gx;
-    hipLaunchKernelGGL(kern, dim3(g.N / SM_BN, ngroups, g.nsplit), dim3(256 + 64 * SM_LOADERS), lds, st, x1, C1, x2, C2, (const bf16*)wp, slab,
-                       zero16, g, lo_offset);
+    hipLaunchKernelGGL(kern, dim3(g.N / SM_BN, ngroups, g.nsplit), dim3(256 + 64 * SM_LOADERS), p.lds, c.st, c.x1, c.C1, c.x2, c.C2,
+                       (const bf16*)c.wp, slab, zero16, g, lo_offset);
     return tdx_launch_status();
 }
 #define SMALL_INSTANCE(MTW, SPLIT, NAME) \
-    int NAME(SMALL_GO_ARGS) { return small_go<MTW, SPLIT>(x1, C1, x2, C2, wp, slab, zero16, g, lds, lo_offset, st); }
+    int NAME(SMALL_GO_ARGS) { return small_go<MTW, SPLIT>(c, p, slab, zero16, lo_offset); }
 #define SMALL_INSTANCE_F16(MTW, NAME) \
-    int NAME(SMALL_GO_ARGS) { return small_go<MTW, false, true>(x1, C1, x2, C2, wp, slab, zero16, g, lds, lo_offset, st); }
-
+    int NAME(SMALL_GO_ARGS) { return small_go<MTW, false, true>(c, p, slab, zero16, lo_offset); }

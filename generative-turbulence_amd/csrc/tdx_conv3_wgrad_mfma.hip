@@ -333,38 +333,23 @@ conv3_wgrad_mfma_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
     }
 }
 
-int conv3_wgrad_mfma_launch(const void* x1, int C1, const void* x2, int C2, const void* dy, float* dwp, float* dbias,
-                            int B, int X, int Y, int Z, int Cout, hipStream_t st, float* slabs, int max_slabs,
-                            int* nslab_out, bool hf) {
+int conv3_wgrad_mfma_launch(const Conv3WgradCall& c) {
+    const int Cout = c.Cout;
     {   // deep U-Net levels: packed-K kernel (tdx_conv3_wgrad_small.hip); TDX_ESHAPE = not such a case
-        int rs = conv3_wgrad_small_launch(x1, C1, x2, C2, dy, dwp, dbias, B, X, Y, Z, Cout, st, slabs, max_slabs, nslab_out, hf);
+        int rs = conv3_wgrad_small_launch(c);
         if (rs != TDX_ESHAPE) return rs;
 #ifndef W3_STAMPS
         // fine levels: the producer / consumer form (8 computing + 4 loader waves)
-        rs = conv3_wgrad_ring_launch(x1, C1, x2, C2, dy, dwp, dbias, B, X, Y, Z, Cout, st, slabs, max_slabs, nslab_out, hf);
+        rs = conv3_wgrad_ring_launch(c);
         if (rs != TDX_ESHAPE) return rs;
 #endif
     }
-    const int Cin = C1 + C2;
+    const int Cin = c.C1 + c.C2;
     const int NT = (Cout % 64 == 0) ? 2 : 1;
     // local axes: brick 4 x 8 x 8; the short axis goes where it leaves the fewest bricks
-    const int E[3] = {X, Y, Z}, gs[3] = {Y * Z, Z, 1}, gw[3] = {9, 3, 1};
-    const int cand[3][3] = {{0, 1, 2}, {1, 0, 2}, {2, 0, 1}};
     static const bool no_perm = getenv("TDX_CONV3_PERM") && atoi(getenv("TDX_CONV3_PERM")) == 0;  // A/B switch
-    int best = 0;
-    int64_t best_n = -1;
-    for (int c = 0; c < (no_perm ? 1 : 3); ++c) {
-        const int64_t n = (int64_t)ceil_div(E[cand[c][0]], W3_BX) * ceil_div(E[cand[c][1]], W3_BY) * ceil_div(E[cand[c][2]], W3_BZ);
-        if (best_n < 0 || n < best_n) { best_n = n; best = c; }
-    }
     WgradView g;
-    g.B = B; g.batch = X * Y * Z;
-    const int bdim[3] = {W3_BX, W3_BY, W3_BZ};
-    for (int k = 0; k < 3; ++k) {
-        const int a = cand[best][k];
-        g.E[k] = E[a]; g.s[k] = gs[a]; g.ws[k] = gw[a]; g.nb[k] = ceil_div(E[a], bdim[k]);
-    }
-    const int nbricks = B * g.nb[0] * g.nb[1] * g.nb[2];
+    const int nbricks = conv3_wgrad_view(g, c, W3_BX, W3_BY, W3_BZ, !no_perm);
     const int n_ci = (Cin + 31) / 32, n_co = Cout / (32 * NT);
     const int ntiles = n_ci * n_co;
     // one workgroup per CU (224 accumulator registers -> one wave per SIMD): aim at 256
@@ -373,28 +358,23 @@ int conv3_wgrad_mfma_launch(const void* x1, int C1, const void* x2, int C2, cons
     int nsplit = ((NT == 2 ? 256 : 512) + ntiles - 1) / ntiles;
     if (nsplit > nbricks) nsplit = nbricks;
     if (nsplit < 1) nsplit = 1;
-    // TDX_DETERMINISTIC: never the atomic merge -- hold the K splits to the slabs the workspace has (added in order by the unpack kernel)
-    if (tdx_deterministic() && slabs != nullptr && nsplit > max_slabs) nsplit = max_slabs > 0 ? max_slabs : 1;
+    int64_t slab_stride;
+    float* out = conv3_wgrad_merge(c, nsplit, slab_stride);  // may lower nsplit (TDX_DETERMINISTIC)
     size_t lds = W3_XBYTES + (size_t)NT * W3_GPLANE;
 #ifdef W3_STAMPS
     lds += 4 * W3_NSTAMP * 8;
 #endif
     dim3 grid((unsigned)(ntiles * nsplit));
-    // slab mode: every (tile, split) pair stores its whole partial tile, so the slabs need no zeroing
-    const bool use_slabs = slabs != nullptr && nsplit <= max_slabs;
-    const int64_t slab_stride = use_slabs ? (int64_t)27 * Cin * Cout : 0;
-    float* out = use_slabs ? slabs : dwp;
-    if (nslab_out) *nslab_out = use_slabs ? nsplit : 0;
 #define W3_LAUNCH(NTV, HFV)                                                                                          \
     do {                                                                                                             \
         auto kern = conv3_wgrad_mfma_kernel<NTV, HFV>;                                                                  \
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         if (e != hipSuccess) return (int)e;                                                                          \
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const bf16*)x1, C1, (const bf16*)x2, C2, (const bf16*)dy, \
-                           out, dbias, g, Cout, nsplit, n_ci, slab_stride);                               \
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, c.st, (const bf16*)c.x1, c.C1, (const bf16*)c.x2, c.C2,       \
+                           (const bf16*)c.dy, out, c.dbias, g, Cout, nsplit, n_ci, slab_stride);                     \
     } while (0)
-    if (NT == 2) { if (hf) W3_LAUNCH(2, true); else W3_LAUNCH(2, false); }
-    else { if (hf) W3_LAUNCH(1, true); else W3_LAUNCH(1, false); }
+    if (NT == 2) { if (c.hf) W3_LAUNCH(2, true); else W3_LAUNCH(2, false); }
+    else { if (c.hf) W3_LAUNCH(1, true); else W3_LAUNCH(1, false); }
 #undef W3_LAUNCH
     return tdx_launch_status();
 }

@@ -273,47 +273,28 @@ conv3_wgrad_mfma_split_kernel(const float* __restrict__ x1, int C1, const float*
     }
 }
 
-int conv3_wgrad_mfma_split_launch(const void* x1, int C1, const void* x2, int C2, const void* dy, float* dwp, float* dbias,
-                                  int B, int X, int Y, int Z, int Cout, hipStream_t st, float* slabs, int max_slabs,
-                                  int* nslab_out) {
+int conv3_wgrad_mfma_split_launch(const Conv3WgradCall& c) {
+    const int Cout = c.Cout;
     {   // grids that give every workgroup several bricks: the producer / consumer form
-        const int rs = conv3_wgrad_split_ring_launch(x1, C1, x2, C2, dy, dwp, dbias, B, X, Y, Z, Cout, st, slabs, max_slabs, nslab_out);
+        const int rs = conv3_wgrad_split_ring_launch(c);
         if (rs != TDX_ESHAPE) return rs;
     }
-    const int Cin = C1 + C2;
-    const int E[3] = {X, Y, Z}, gs[3] = {Y * Z, Z, 1}, gw[3] = {9, 3, 1};
-    const int cand[3][3] = {{0, 1, 2}, {1, 0, 2}, {2, 0, 1}};
-    int best = 0;
-    int64_t best_n = -1;
-    for (int c = 0; c < 3; ++c) {
-        const int64_t n = (int64_t)ceil_div(E[cand[c][0]], WS_BX) * ceil_div(E[cand[c][1]], WS_BY) * ceil_div(E[cand[c][2]], WS_BZ);
-        if (best_n < 0 || n < best_n) { best_n = n; best = c; }
-    }
+    const int Cin = c.C1 + c.C2;
     WgradViewS g;
-    g.B = B; g.batch = X * Y * Z;
-    const int bdim[3] = {WS_BX, WS_BY, WS_BZ};
-    for (int k = 0; k < 3; ++k) {
-        const int a = cand[best][k];
-        g.E[k] = E[a]; g.s[k] = gs[a]; g.ws[k] = gw[a]; g.nb[k] = ceil_div(E[a], bdim[k]);
-    }
-    const int nbricks = B * g.nb[0] * g.nb[1] * g.nb[2];
+    const int nbricks = conv3_wgrad_view(g, c, WS_BX, WS_BY, WS_BZ);
     const int n_ci = (Cin + 31) / 32, n_co = Cout / 32;
     const int ntiles = n_ci * n_co;
     int nsplit = (256 + ntiles - 1) / ntiles;  // one workgroup per CU: one resident wave of workgroups
     if (nsplit > nbricks) nsplit = nbricks;
     if (nsplit < 1) nsplit = 1;
-    // TDX_DETERMINISTIC: never the atomic merge -- hold the K splits to the slabs the workspace has (added in order by the unpack kernel)
-    if (tdx_deterministic() && slabs != nullptr && nsplit > max_slabs) nsplit = max_slabs > 0 ? max_slabs : 1;
+    int64_t slab_stride;
+    float* out = conv3_wgrad_merge(c, nsplit, slab_stride);  // may lower nsplit (TDX_DETERMINISTIC)
     const size_t lds = (size_t)2 * WS_XBYTES + 2 * WS_GBYTES;
     dim3 grid((unsigned)(ntiles * nsplit));
-    const bool use_slabs = slabs != nullptr && nsplit <= max_slabs;
-    const int64_t slab_stride = use_slabs ? (int64_t)27 * Cin * Cout : 0;
-    float* out = use_slabs ? slabs : dwp;
-    if (nslab_out) *nslab_out = use_slabs ? nsplit : 0;
     auto kern = conv3_wgrad_mfma_split_kernel;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const float*)x1, C1, (const float*)x2, C2, (const float*)dy, out, dbias,
-                       g, Cout, nsplit, n_ci, slab_stride);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, c.st, (const float*)c.x1, c.C1, (const float*)c.x2, c.C2, (const float*)c.dy, out,
+                       c.dbias, g, Cout, nsplit, n_ci, slab_stride);
     return tdx_launch_status();
 }

@@ -322,27 +322,13 @@ bool conv3_wgrad_ring_supported(int C1, int C2, int Cout) {
 }
 
 // same contract as conv3_wgrad_mfma_launch; TDX_ESHAPE = not a case for this kernel
-int conv3_wgrad_ring_launch(const void* x1, int C1, const void* x2, int C2, const void* dy, float* dwp, float* dbias, int B, int X,
-                            int Y, int Z, int Cout, hipStream_t st, float* slabs, int max_slabs, int* nslab_out, bool hf) {
-    if (!conv3_wgrad_ring_supported(C1, C2, Cout)) return TDX_ESHAPE;
-    const int Cin = C1 + C2;
+int conv3_wgrad_ring_launch(const Conv3WgradCall& c) {
+    const int Cout = c.Cout;
+    if (!conv3_wgrad_ring_supported(c.C1, c.C2, Cout)) return TDX_ESHAPE;
+    const int Cin = c.C1 + c.C2;
     // local axes: brick 4 x 8 x 8; the short axis goes where it leaves the fewest bricks
-    const int E[3] = {X, Y, Z}, gs[3] = {Y * Z, Z, 1}, gw[3] = {9, 3, 1};
-    const int cand[3][3] = {{0, 1, 2}, {1, 0, 2}, {2, 0, 1}};
-    int best = 0;
-    int64_t best_n = -1;
-    for (int c = 0; c < 3; ++c) {
-        const int64_t n = (int64_t)ceil_div(E[cand[c][0]], WR_BX) * ceil_div(E[cand[c][1]], WR_BY) * ceil_div(E[cand[c][2]], WR_BZ);
-        if (best_n < 0 || n < best_n) { best_n = n; best = c; }
-    }
     WgradRingView g;
-    g.B = B; g.batch = X * Y * Z;
-    const int bdim[3] = {WR_BX, WR_BY, WR_BZ};
-    for (int k = 0; k < 3; ++k) {
-        const int a = cand[best][k];
-        g.E[k] = E[a]; g.s[k] = gs[a]; g.ws[k] = gw[a]; g.nb[k] = ceil_div(E[a], bdim[k]);
-    }
-    const int nbricks = B * g.nb[0] * g.nb[1] * g.nb[2];
+    const int nbricks = conv3_wgrad_view(g, c, WR_BX, WR_BY, WR_BZ);
     const int NTN = (Cout % 64) == 0 ? 2 : 1;
     {
         const char* env = getenv("TDX_WGRAD_RING");  // A/B switch: 2 = 64-wide tiles only (round 4's rule)
@@ -357,12 +343,8 @@ int conv3_wgrad_ring_launch(const void* x1, int C1, const void* x2, int C2, cons
     // a workgroup should walk several bricks, or the double buffering has nothing to overlap
     if (nbricks < 4 * nsplit) return TDX_ESHAPE;
     const size_t lds = (size_t)2 * WR_XBUF + (size_t)2 * WR_GBUF(NTN);
-    // TDX_DETERMINISTIC: never the atomic merge -- hold the K splits to the slabs the workspace has (added in order by the unpack kernel)
-    if (tdx_deterministic() && slabs != nullptr && nsplit > max_slabs) nsplit = max_slabs > 0 ? max_slabs : 1;
-    const bool use_slabs = slabs != nullptr && nsplit <= max_slabs;
-    const int64_t slab_stride = use_slabs ? (int64_t)27 * Cin * Cout : 0;
-    float* out = use_slabs ? slabs : dwp;
-    if (nslab_out) *nslab_out = use_slabs ? nsplit : 0;
+    int64_t slab_stride;
+    float* out = conv3_wgrad_merge(c, nsplit, slab_stride);  // may lower nsplit (TDX_DETERMINISTIC)
     static bool attr_set[2][2] = {{false, false}, {false, false}};
 #define WR_GO(NTNV, HFV)                                                                                                          \
     do {                                                                                                                          \
@@ -372,11 +354,12 @@ int conv3_wgrad_ring_launch(const void* x1, int C1, const void* x2, int C2, cons
             if (e != hipSuccess) return (int)e;                                                                                   \
             attr_set[NTNV - 1][HFV] = true;                                                                                       \
         }                                                                                                                         \
-        hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles * nsplit)), dim3(768), lds, st, (const bf16*)x1, C1, (const bf16*)x2, C2, \
-                           (const bf16*)dy, out, dbias, g, Cout, nsplit, n_ci, slab_stride, tdx_scratch_ptr());                   \
+        hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles * nsplit)), dim3(768), lds, c.st, (const bf16*)c.x1, c.C1,                \
+                           (const bf16*)c.x2, c.C2, (const bf16*)c.dy, out, c.dbias, g, Cout, nsplit, n_ci, slab_stride,          \
+                           tdx_scratch_ptr());                                                                                    \
     } while (0)
-    if (NTN == 2) { if (hf) WR_GO(2, true); else WR_GO(2, false); }
-    else { if (hf) WR_GO(1, true); else WR_GO(1, false); }
+    if (NTN == 2) { if (c.hf) WR_GO(2, true); else WR_GO(2, false); }
+    else { if (c.hf) WR_GO(1, true); else WR_GO(1, false); }
 #undef WR_GO
     return tdx_launch_status();
 }

@@ -252,12 +252,12 @@ conv3_wgrad_small_kernel(const bf16* __restrict__ x1, int C1, const bf16* __rest
 }
 
 // Launch if this is a small-grid case; TDX_ESHAPE otherwise (the caller then takes the brick kernel).
-int conv3_wgrad_small_launch(const void* x1, int C1, const void* x2, int C2, const void* dy, float* dwp, float* dbias, int B,
-                             int X, int Y, int Z, int Cout, hipStream_t st, float* slabs, int max_slabs, int* nslab_out, bool hf) {
+int conv3_wgrad_small_launch(const Conv3WgradCall& c) {
+    const int B = c.B, X = c.X, Y = c.Y, Z = c.Z, Cout = c.Cout;
     static const int mode = getenv("TDX_WGRAD_SMALL") ? atoi(getenv("TDX_WGRAD_SMALL")) : 1;  // A/B switch
     if (mode == 0) return TDX_ESHAPE;
-    const int Cin = C1 + C2;
-    if ((C1 % 32) || (C2 % 32) || (Cout % 32) || Cin < 128) return TDX_ESHAPE;
+    const int Cin = c.C1 + c.C2;
+    if ((c.C1 % 32) || (c.C2 % 32) || (Cout % 32) || Cin < 128) return TDX_ESHAPE;
     const char* env_rows = getenv("TDX_WGRAD_SMALL_ROWS");  // row gate (tests, A/B runs; read per call)
     const int64_t rows_total = (int64_t)B * X * Y * Z;
     if (rows_total > (env_rows ? atoi(env_rows) : 8000)) return TDX_ESHAPE;
@@ -285,12 +285,8 @@ int conv3_wgrad_small_launch(const void* x1, int C1, const void* x2, int C2, con
     const int n_ci = Cin / 32, n_co = Cout / (32 * NT);
     const int ntiles = n_ci * n_co;
     int nsplit = std::max(1, std::min(g.ngroups, ceil_div(256, ntiles)));
-    // TDX_DETERMINISTIC: never the atomic merge -- hold the K splits to the slabs the workspace has (added in order by the unpack kernel)
-    if (tdx_deterministic() && slabs != nullptr && nsplit > max_slabs) nsplit = max_slabs > 0 ? max_slabs : 1;
-    const bool use_slabs = slabs != nullptr && nsplit <= max_slabs;
-    const int64_t slab_stride = use_slabs ? (int64_t)27 * Cin * Cout : 0;
-    float* out = use_slabs ? slabs : dwp;
-    if (nslab_out) *nslab_out = use_slabs ? nsplit : 0;
+    int64_t slab_stride;
+    float* out = conv3_wgrad_merge(c, nsplit, slab_stride);  // may lower nsplit (TDX_DETERMINISTIC)
     dim3 grid((unsigned)(ntiles * nsplit));
 #define WS_LAUNCH(NTV, HFV)                                                                                           \
     do {                                                                                                              \
@@ -301,11 +297,11 @@ int conv3_wgrad_small_launch(const void* x1, int C1, const void* x2, int C2, con
             if (e != hipSuccess) return (int)e;                                                                       \
             attr = lds;                                                                                               \
         }                                                                                                             \
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const bf16*)x1, C1, (const bf16*)x2, C2, (const bf16*)dy, out, \
-                           dbias, g, Cout, nsplit, n_ci, slab_stride);                                                \
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, c.st, (const bf16*)c.x1, c.C1, (const bf16*)c.x2, c.C2,        \
+                           (const bf16*)c.dy, out, c.dbias, g, Cout, nsplit, n_ci, slab_stride);                      \
     } while (0)
-    if (NT == 2) { if (hf) WS_LAUNCH(2, true); else WS_LAUNCH(2, false); }
-    else { if (hf) WS_LAUNCH(1, true); else WS_LAUNCH(1, false); }
+    if (NT == 2) { if (c.hf) WS_LAUNCH(2, true); else WS_LAUNCH(2, false); }
+    else { if (c.hf) WS_LAUNCH(1, true); else WS_LAUNCH(1, false); }
 #undef WS_LAUNCH
     return tdx_launch_status();
 }

@@ -273,31 +273,17 @@ conv3_wgrad_split_ring_kernel(const float* __restrict__ x1, int C1, const float*
     }
 }
 
-int conv3_wgrad_split_ring_launch(const void* x1, int C1, const void* x2, int C2, const void* dy, float* dwp, float* dbias, int B,
-                                  int X, int Y, int Z, int Cout, hipStream_t st, float* slabs, int max_slabs, int* nslab_out) {
+int conv3_wgrad_split_ring_launch(const Conv3WgradCall& c) {
+    const int Cout = c.Cout;
     {
         const char* env = getenv("TDX_WGRAD_SPLIT_RING");  // A/B switch, read per call: 0 = off
         if (env && atoi(env) == 0) return TDX_ESHAPE;
     }
-    if (!conv3_wgrad_mfma_split_supported(C1, C2, Cout)) return TDX_ESHAPE;
-    const int Cin = C1 + C2;
+    if (!conv3_wgrad_mfma_split_supported(c.C1, c.C2, Cout)) return TDX_ESHAPE;
+    const int Cin = c.C1 + c.C2;
     // local axes: brick 2 x 8 x 8; the short axis goes where it leaves the fewest bricks
-    const int E[3] = {X, Y, Z}, gs[3] = {Y * Z, Z, 1}, gw[3] = {9, 3, 1};
-    const int cand[3][3] = {{0, 1, 2}, {1, 0, 2}, {2, 0, 1}};
-    int best = 0;
-    int64_t best_n = -1;
-    for (int c = 0; c < 3; ++c) {
-        const int64_t n = (int64_t)ceil_div(E[cand[c][0]], SR_BX) * ceil_div(E[cand[c][1]], SR_BY) * ceil_div(E[cand[c][2]], SR_BZ);
-        if (best_n < 0 || n < best_n) { best_n = n; best = c; }
-    }
     WgradSplitRingView g;
-    g.B = B; g.batch = X * Y * Z;
-    const int bdim[3] = {SR_BX, SR_BY, SR_BZ};
-    for (int k = 0; k < 3; ++k) {
-        const int a = cand[best][k];
-        g.E[k] = E[a]; g.s[k] = gs[a]; g.ws[k] = gw[a]; g.nb[k] = ceil_div(E[a], bdim[k]);
-    }
-    const int nbricks = B * g.nb[0] * g.nb[1] * g.nb[2];
+    const int nbricks = conv3_wgrad_view(g, c, SR_BX, SR_BY, SR_BZ);
     const int n_ci = (Cin + 31) / 32, n_co = Cout / 32;
     const int ntiles = n_ci * n_co;
     const int cus = tdx_persistent_cus();
@@ -307,19 +293,15 @@ int conv3_wgrad_split_ring_launch(const void* x1, int C1, const void* x2, int C2
     // a workgroup should walk several bricks, or the double buffering has nothing to overlap
     if (nbricks < 4 * nsplit) return TDX_ESHAPE;
     const size_t lds = (size_t)2 * SR_SET;
-    // TDX_DETERMINISTIC: never the atomic merge -- hold the K splits to the slabs the workspace has (added in order by the unpack kernel)
-    if (tdx_deterministic() && slabs != nullptr && nsplit > max_slabs) nsplit = max_slabs > 0 ? max_slabs : 1;
-    const bool use_slabs = slabs != nullptr && nsplit <= max_slabs;
-    const int64_t slab_stride = use_slabs ? (int64_t)27 * Cin * Cout : 0;
-    float* out = use_slabs ? slabs : dwp;
-    if (nslab_out) *nslab_out = use_slabs ? nsplit : 0;
+    int64_t slab_stride;
+    float* out = conv3_wgrad_merge(c, nsplit, slab_stride);  // may lower nsplit (TDX_DETERMINISTIC)
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void*)conv3_wgrad_split_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    hipLaunchKernelGGL(conv3_wgrad_split_ring_kernel, dim3((unsigned)(ntiles * nsplit)), dim3(768), lds, st, (const float*)x1, C1,
-                       (const float*)x2, C2, (const float*)dy, out, dbias, g, Cout, nsplit, n_ci, slab_stride);
+    hipLaunchKernelGGL(conv3_wgrad_split_ring_kernel, dim3((unsigned)(ntiles * nsplit)), dim3(768), lds, c.st, (const float*)c.x1, c.C1,
+                       (const float*)c.x2, c.C2, (const float*)c.dy, out, c.dbias, g, Cout, nsplit, n_ci, slab_stride);
     return tdx_launch_status();
 }

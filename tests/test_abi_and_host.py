@@ -499,3 +499,53 @@ def test_library_sources_zero_with_kernels_not_memsets():
             if re.search(r"\bhipMemset\w*\s*\(", code):
                 offenders.append(f"{f.name}:{k}: {line.strip()}")
     assert not offenders, "\n".join(offenders)
+
+
+# (C1, C2, Cout, B, X, Y, Z) -> families for (bf16, auto), (fp16, auto), (f32, auto), (f32, split), (bf16, direct), (f32, direct)
+# without an arena, the same with a 96 MB arena, tdx_conv3_ring_brick_depth.  Recorded from a build of the commit before
+# the route function existed (146fb94); never regenerated from the code under test.
+_R4, _B4, _D6 = "ring ring brick brick direct direct", "brick brick brick brick direct direct", "direct " * 6
+_S4 = "small small brick small direct direct"
+_CONV3_ROUTES = [
+    ((64, 0, 64, 6, 192, 64, 48), _R4, _R4, 8),
+    ((64, 64, 64, 6, 192, 64, 48), _R4, _R4, 8),
+    ((128, 0, 128, 6, 96, 32, 24), _R4, _R4, 8),
+    ((256, 0, 256, 6, 48, 16, 12), _R4, _R4, 4),
+    ((512, 0, 512, 6, 24, 8, 6), _B4, _S4, 0),
+    ((512, 0, 512, 6, 12, 4, 3), _B4, _S4, 0),
+    ((512, 512, 256, 6, 24, 8, 6), _B4, _S4, 0),
+    ((64, 0, 64, 6, 194, 50, 50), _R4, _R4, 8),
+    ((128, 0, 128, 6, 97, 25, 25), _R4, _R4, 8),
+    ((8, 0, 8, 2, 48, 32, 32), _D6, _D6, 0),
+    ((4, 0, 64, 6, 192, 64, 48), _D6, _D6, 0),
+]
+
+
+def test_conv3_routing_is_pinned(monkeypatch):
+    """Which kernel family serves a forward call (tdx_conv3_fwd_kernel: the conv route, pure host code) did not move.  The
+    small-grid route needs the scratch arena: tdx_set_scratch only stores the pointer, so a host buffer with a claimed size
+    stands in for it.  Nothing is launched."""
+    import ctypes
+
+    from turbdiff_amd import _lib as L
+
+    for v in ("TDX_CONV3_RING", "TDX_RING_Z4", "TDX_RING_RAGGED", "TDX_RING_MIN_ITEMS", "TDX_PERSISTENT_CUS",
+              "TDX_CONV3_SMALL_ROWS", "TDX_CONV_IMPL"):
+        monkeypatch.delenv(v, raising=False)
+    names = {L.KERNEL_DIRECT: "direct", L.KERNEL_BRICK: "brick", L.KERNEL_SMALL: "small", L.KERNEL_RING: "ring"}
+    modes = [(L.BF16, L.CONV_AUTO), (L.F16, L.CONV_AUTO), (L.F32, L.CONV_AUTO), (L.F32, L.CONV_SPLIT),
+             (L.BF16, L.CONV_DIRECT), (L.F32, L.CONV_DIRECT)]
+    lib = L.load()
+    fake = ctypes.create_string_buffer(256)  # zeroed; never dereferenced by the queries
+    try:
+        for arena_bytes, column in ((0, 1), (96 << 20, 2)):
+            assert lib.tdx_set_scratch(ctypes.addressof(fake) if arena_bytes else None, arena_bytes) == 0
+            for row in _CONV3_ROUTES:
+                shape = row[0]
+                got = [names[L.query("tdx_conv3_fwd_kernel", *shape, dt, impl)] for dt, impl in modes]
+                assert got == row[column].split(), (shape, arena_bytes)
+                assert L.query("tdx_conv3_ring_brick_depth", *shape) == row[3], shape
+                assert bool(L.query("tdx_conv3_uses_ring", *shape)) == (row[3] != 0), shape
+    finally:
+        lib.tdx_set_scratch(None, 0)
+        L._ACTIVE = None  # a later GPU test in this process binds its real arena again

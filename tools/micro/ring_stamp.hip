@@ -13,6 +13,8 @@ static void* g_scratch = nullptr;
 void* tdx_scratch_ptr() { return g_scratch; }
 size_t tdx_scratch_bytes() { return 1 << 20; }
 bool conv3_mfma_supported(int C1, int C2, int Cout) { return C1 > 0 && (C1 % 16) == 0 && (C2 % 16) == 0 && (Cout % 32) == 0; }
+int tdx_persistent_cus() { return 256; }
+int conv3_mfma_launch(const Conv3Call&) { return TDX_ESHAPE; }  // remainder slabs: whole-brick grids only here
 
 __global__ void fill_rand(unsigned* p, size_t n, unsigned seed, unsigned expo) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -41,10 +43,11 @@ int main(int argc, char** argv) {
     hipMalloc(&rg_stamp_buffer, nrec * 8);
     hipMemset(rg_stamp_buffer, 0, nrec * 8);
     double* gn; hipMalloc(&gn, (size_t)32 * B * Cout * 2 * 8); hipMemset(gn, 0, (size_t)32 * B * Cout * 2 * 8);
-    auto go = [&]() {
-        return zp ? conv3_ring_launch(x, Cin, nullptr, 0, w, nullptr, nullptr, B, X, Y, Z, Cout, true, 0, nullptr, y, Cout, nullptr, nullptr, nullptr)
-                  : conv3_ring_launch(x, Cin, nullptr, 0, w, nullptr, y, B, X, Y, Z, Cout, false, 0, gn);
-    };
+    Conv3Call c = {};
+    c.x1 = x; c.C1 = Cin; c.wp = w; c.B = B; c.X = X; c.Y = Y; c.Z = Z; c.N = Cout; c.zero_pad = zp; c.fmt = TDX_BF16;
+    if (zp) { c.d1 = y; c.D1 = Cout; } else { c.y = y; c.gn_acc = gn; }
+    const int depth = conv3_ring_depth(Cin, 0, Cout, B, X, Y, Z, zp);  // 0: not a grid for this kernel, the launch refuses
+    auto go = [&]() { return conv3_ring_launch(c, depth); };
     int rc = go();
     if (rc != 0) { printf("launch failed: %d\n", rc); return 1; }
     for (int it = 0; it < 40; ++it) go();

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <vector>
 #include <algorithm>
+bool tdx_deterministic() { return false; }
 
 __global__ void fill_rand(unsigned* p, size_t n, unsigned seed, unsigned expo) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;

@@ -7,7 +7,8 @@
 #include <cstdio>
 #include <vector>
 #include <algorithm>
-int conv3_wgrad_small_launch(const void*, int, const void*, int, const void*, float*, float*, int, int, int, int, int, hipStream_t, float*, int, int*) { return TDX_ESHAPE; }
+bool tdx_deterministic() { return false; }
+int conv3_wgrad_small_launch(const Conv3WgradCall&) { return TDX_ESHAPE; }
 
 __global__ void fill_rand(unsigned* p, size_t n, unsigned seed, unsigned expo) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -34,7 +35,8 @@ int main(int argc, char** argv) {
     (void)hipMalloc(&buf, nrec * 8);
     (void)hipMemset(buf, 0, nrec * 8);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(w3_stamps_dev), &buf, sizeof(buf));
-    auto go = [&]() { return conv3_wgrad_mfma_launch(x, Cin, nullptr, 0, dy, dw, db, B, X, Y, Z, Cout, 0, nullptr, 0, nullptr); };
+    const Conv3WgradCall c = {x, Cin, nullptr, 0, dy, dw, db, B, X, Y, Z, Cout, 0, nullptr, 0, nullptr, false};
+    auto go = [&]() { return conv3_wgrad_mfma_launch(c); };
     int rc = go();
     if (rc != 0) { printf("launch failed %d\n", rc); return 1; }
     for (int it = 0; it < 20; ++it) go();
