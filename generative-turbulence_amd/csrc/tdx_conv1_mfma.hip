@@ -20,12 +20,7 @@
 //   reduces its own 64 rows of every 256-row chunk into a private (32*MT) x (32*NT) tile;
 //   tiles are merged with f32 atomics.
 #include "tdx_common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+#include "tdx_mfma.h"
 
 #define C1M_ROWS 256
 #define C1M_KC 32
@@ -243,13 +238,6 @@ int conv1_mfma_fwd_launch(const void* x1, int C1, const void* x2, int C2, const 
 }
 
 // ------------------------------------------------------------------ weight gradient ------
-__device__ __forceinline__ bf16x8 tr_frag8(const unsigned char* lo, const unsigned char* hi) {
-    s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lo));
-    s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(hi));
-    s16x8 rr = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, rr);
-}
-
 bool conv1_wgrad_mfma_supported(int Cin, int Cout) { return (Cin % 32) == 0 && (Cout % 32) == 0; }
 
 #define C1W_PLANE (C1M_ROWS * 64)  // one [256][32] bf16 plane
@@ -340,12 +328,12 @@ conv1_wgrad_mfma_kernel(const bf16* __restrict__ x, int Cin, const bf16* __restr
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 const unsigned char* ap = sX + m * C1W_PLANE + row * 64 + col_off;
-                af[m] = tr_frag8(ap, ap + 4 * 64);
+                af[m] = tr_frag(ap, ap + 4 * 64);
             }
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
                 const unsigned char* bp = sG + n * C1W_PLANE + row * 64 + col_off;
-                bfv[n] = tr_frag8(bp, bp + 4 * 64);
+                bfv[n] = tr_frag(bp, bp + 4 * 64);
             }
 #pragma unroll
             for (int m = 0; m < MT; ++m)

@@ -155,26 +155,8 @@ static inline float* conv3_wgrad_merge(const Conv3WgradCall& c, int& nsplit, int
 // each of which answers TDX_ESHAPE when the call is not a case for it.  fp32 tensors: split-precision
 // (tdx_conv3_wgrad_mfma_split.hip, which tries its producer / consumer form tdx_conv3_wgrad_split_ring.hip first: 2 x 8 x 8
 // bricks) or fp32-IEEE products (tdx_conv3_wgrad_mfma_f32.hip).
-// The launch geometry of the brick weight-gradient kernels: bricks of bx x by x bz voxels in the kernel's LOCAL axes, the
-// short axis on the grid axis that leaves the fewest bricks (permute false: the grid's own order).  Fills a Wgrad*View
-// (every kernel's has these fields) and returns the number of bricks.
-template <typename View>
-static inline int conv3_wgrad_view(View& g, const Conv3WgradCall& c, int bx, int by, int bz, bool permute = true) {
-    const int E[3] = {c.X, c.Y, c.Z}, gs[3] = {c.Y * c.Z, c.Z, 1}, gw[3] = {9, 3, 1}, bdim[3] = {bx, by, bz};
-    const int cand[3][3] = {{0, 1, 2}, {1, 0, 2}, {2, 0, 1}};
-    int best = 0;
-    int64_t best_n = -1;
-    for (int k = 0; k < (permute ? 3 : 1); ++k) {
-        const int64_t n = (int64_t)ceil_div(E[cand[k][0]], bx) * ceil_div(E[cand[k][1]], by) * ceil_div(E[cand[k][2]], bz);
-        if (best_n < 0 || n < best_n) { best_n = n; best = k; }
-    }
-    g.B = c.B; g.batch = c.X * c.Y * c.Z;
-    for (int k = 0; k < 3; ++k) {
-        const int a = cand[best][k];
-        g.E[k] = E[a]; g.s[k] = gs[a]; g.ws[k] = gw[a]; g.nb[k] = ceil_div(E[a], bdim[k]);
-    }
-    return c.B * g.nb[0] * g.nb[1] * g.nb[2];
-}
+// What the brick kernels among them share on the device, and their launch geometry (WgradView, conv3_wgrad_view):
+// tdx_conv3_wgrad.h.
 bool conv3_wgrad_mfma_supported(int C1, int C2, int Cout);
 bool conv3_wgrad_mfma_split_supported(int C1, int C2, int Cout);
 bool conv3_wgrad_mfma_f32_supported(int C1, int C2, int Cout);

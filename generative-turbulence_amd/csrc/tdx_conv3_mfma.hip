@@ -43,10 +43,8 @@
 // per MFMA, two co-resident workgroups hide more than a deeper pipeline in one.
 #include "tdx_common.h"
 #include "tdx_conv3.h"
+#include "tdx_mfma.h"
 #include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define M3_KC 16
 

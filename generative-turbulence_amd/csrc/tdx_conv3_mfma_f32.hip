@@ -18,9 +18,9 @@
 #include "tdx_common.h"
 #include "tdx_conv3.h"
 #include "tdx_conv3_brick.h"
+#include "tdx_mfma.h"
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define F3_KC 8
 

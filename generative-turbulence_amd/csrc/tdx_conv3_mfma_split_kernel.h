@@ -6,32 +6,14 @@
 #include "tdx_common.h"
 #include "tdx_conv3.h"
 #include "tdx_conv3_brick.h"
+#include "tdx_mfma.h"
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 #define SP_KC 16
-
-
 
 template <int BN>
 __device__ __forceinline__ int outs_addr(int v, int c) {
     return v * (BN * 4) + ((c ^ (v & (BN / 4 - 1))) << 4);
-}
-
-// 8 fp32 -> 8 bf16 hi and 8 bf16 lo
-__device__ __forceinline__ void split8(const float4& a, const float4& b, uint4& hi, uint4& lo) {
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        h[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
-        const float r0 = v[2 * i] - __uint_as_float(h[i] << 16), r1 = v[2 * i + 1] - __uint_as_float(h[i] & 0xffff0000u);
-        l[i] = pack_bf16x2(r0, r1);
-    }
-    hi = make_uint4(h[0], h[1], h[2], h[3]);
-    lo = make_uint4(l[0], l[1], l[2], l[3]);
 }
 
 // LDS image of one 8-channel slice: activations [part = hi, lo][halo voxel, z stride 12][8 ch] (16-B entries), weights
@@ -45,7 +27,7 @@ template <int SHAPE, int BN> struct SplitLds {
     static constexpr int BYTES = STAGE > OUT ? STAGE : OUT;
 };
 
-// 4 fp32 -> 4 bf16 hi and 4 bf16 lo
+// 4 fp32 -> 4 bf16 hi and 4 bf16 lo (split8 of tdx_mfma.h for one float4)
 __device__ __forceinline__ void split4(const float4& a, uint2& hi, uint2& lo) {
     const float v[4] = {a.x, a.y, a.z, a.w};
     unsigned h[2], l[2];

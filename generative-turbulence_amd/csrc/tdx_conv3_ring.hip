@@ -39,11 +39,9 @@
 // remainder slabs go to the thin-brick kernel in a second launch); everything else stays on the brick kernel.
 #include "tdx_common.h"
 #include "tdx_conv3.h"
+#include "tdx_mfma.h"
 #include <stdlib.h>
 #include <algorithm>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define RG_HY 10
 #define RG_SZ 12                        // padded z stride of the LDS brick image (conflict-free 16-B fragment reads)
@@ -66,15 +64,7 @@ struct RingArgs {
     unsigned long long* stamps;          // diagnostic builds only
 };
 
-// One LDS-DMA instruction: every lane copies 16 B from its own global address to LDS byte address lds + 16 * lane.
-// Inline assembly, not the builtin: the compiler would order every later ds_read behind the copy with vmcnt(0).
-__device__ __forceinline__ void rg_dma(const void* gsrc, unsigned lds) {
-    lds = __builtin_amdgcn_readfirstlane(lds);
-    unsigned keep;  // M0 is compiler-reserved: saved and restored inside the statement instead of a clobber the compiler does not honour
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds) : "memory");
-}
-// the same with a uniform 64-bit base and a 32-bit per-lane byte offset
+// lds_dma16 (tdx_mfma.h) with a uniform 64-bit base and a 32-bit per-lane byte offset
 __device__ __forceinline__ void rg_dma_off(const void* sbase, unsigned voff, unsigned lds) {
     lds = __builtin_amdgcn_readfirstlane(lds);
     unsigned keep;
@@ -82,11 +72,6 @@ __device__ __forceinline__ void rg_dma_off(const void* sbase, unsigned voff, uns
                  : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds) : "memory");
 }
 #define RG_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-__device__ __forceinline__ void rg_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS stores are performed before the others proceed
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // Diagnostic builds only (tools/micro/ring_stamp.hip defines RG_STAMPS): s_memtime stamps of bricks RG_STAMP_B0 .. +1
 // of every wave, kept in LDS (the statistics scratch: such builds run without the statistics flush) and dumped to
@@ -195,7 +180,7 @@ __global__ void __launch_bounds__(512 + 64 * LW, LW ? 3 : 2) conv3_ring_kernel(R
 
     if (tid < BN) sBias[tid] = A.bias ? A.bias[n0 + tid] : 0.f;
     if (tid < 16) reinterpret_cast<unsigned*>(sZ)[tid] = 0u;
-    rg_barrier();
+    lds_barrier();
 
     // ---- per-lane DMA geometry (fixed for the kernel)
     // brick piece i of this wave: pi = wave * BPW + i -> entries 64 pi .. 64 pi + 63 of the image
@@ -289,7 +274,7 @@ __global__ void __launch_bounds__(512 + 64 * LW, LW ? 3 : 2) conv3_ring_kernel(R
         const unsigned dst = pi < S::APIECES ? ldsA + buf * S::ABUF + pi * 1024 : ldsD;
         if (ZP) {
             const bf16* src = vox[i] >= 0 ? base + (int64_t)vox[i] * Cs : reinterpret_cast<const bf16*>(A.zeros);
-            rg_dma(src, dst);
+            lds_dma16(src, dst);
         } else {
             rg_dma_off(base, (unsigned)(vox[i] * Cs) * 2u, dst);
         }
@@ -323,7 +308,7 @@ __global__ void __launch_bounds__(512 + 64 * LW, LW ? 3 : 2) conv3_ring_kernel(R
                 sRed[(wave * BN + lane * 8 + e) * 2 + 1] = s2[e];
             }
         }
-        rg_barrier();
+        lds_barrier();
         if (tid < BN * 2) {
             float t = 0.f;
 #pragma unroll
@@ -331,7 +316,7 @@ __global__ void __launch_bounds__(512 + 64 * LW, LW ? 3 : 2) conv3_ring_kernel(R
             const int rep = blockIdx.x & (TDX_GN_REPLICAS - 1);
             atomicAdd(&A.gn_acc[(((size_t)rep * A.B + b) * A.Cout + n0) * 2 + tid], (double)t);
         }
-        rg_barrier();
+        lds_barrier();
 #pragma unroll
         for (int e = 0; e < 4; ++e) p1[e] = p2[e] = f32x2{0.f, 0.f};
     };
@@ -357,7 +342,7 @@ __global__ void __launch_bounds__(512 + 64 * LW, LW ? 3 : 2) conv3_ring_kernel(R
         for (int ord = 0; ord < nmine; ++ord) {
             for (int c8 = 0; c8 < nun; ++c8, ++u) {
                 RG_VMCNT(WPW);
-                rg_barrier();
+                lds_barrier();
 #pragma unroll
                 for (int i = 0; i < BPW; ++i) issue_brick_piece(qs, (u + 1) & 1, i);
 #pragma unroll
@@ -371,7 +356,7 @@ __global__ void __launch_bounds__(512 + 64 * LW, LW ? 3 : 2) conv3_ring_kernel(R
                 int b, nb = -1, t0, t1, t2;
                 brick_coords(ord, b, t0, t1, t2);
                 if (ord + 1 < nmine) brick_coords(ord + 1, nb, t0, t1, t2);
-                if (nb != b) { rg_barrier(); rg_barrier(); }
+                if (nb != b) { lds_barrier(); lds_barrier(); }
             }
 #endif
         }
@@ -405,7 +390,7 @@ __global__ void __launch_bounds__(512 + 64 * LW, LW ? 3 : 2) conv3_ring_kernel(R
             if (LW == 0) { if (stores_behind) RG_VMCNT(WPW + NST); else RG_VMCNT(WPW); }
             stores_behind = false;
             RG_T();  // this wave's copies have landed
-            rg_barrier();
+            lds_barrier();
             RG_T();  // everybody's have
 
             const unsigned char* bufA = sA + (u & 1) * S::ABUF;

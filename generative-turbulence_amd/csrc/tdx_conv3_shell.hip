@@ -30,12 +30,11 @@
 // split-precision (bf16 hi + lo, three MFMAs per product) on fp32 tensors.
 #include "tdx_common.h"
 #include "tdx_conv3.h"
+#include "tdx_mfma.h"
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define SH_BF16 0
 #define SH_F32 1
@@ -78,20 +77,6 @@ struct ShellRegions {
     int pstart[4];  // first row of region r in the position buffer; rows of a region: [b][face][position 1][position 2]
     int B;
 };
-
-// 8 fp32 -> 8 bf16 hi and 8 bf16 lo (as tdx_conv3_mfma_split.hip)
-__device__ __forceinline__ void sh_split8(const float4& a, const float4& b, uint4& hi, uint4& lo) {
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        h[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
-        const float r0 = v[2 * i] - __uint_as_float(h[i] << 16), r1 = v[2 * i + 1] - __uint_as_float(h[i] & 0xffff0000u);
-        l[i] = pack_bf16x2(r0, r1);
-    }
-    hi = make_uint4(h[0], h[1], h[2], h[3]);
-    lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
 
 template <int MODE, int NT, int S>
 __global__ void __launch_bounds__(256, 2)
@@ -207,7 +192,7 @@ conv3_shell_kernel(const void* __restrict__ dy_, const void* __restrict__ wb_, v
                 if (MODE == SH_SPLIT) {
                     uint4 hi, lo;
                     const uint4 u0 = areg[i][0], u1 = areg[i][MODE == SH_SPLIT ? 1 : 0];
-                    sh_split8(make_float4(__uint_as_float(u0.x), __uint_as_float(u0.y), __uint_as_float(u0.z), __uint_as_float(u0.w)),
+                    split8(make_float4(__uint_as_float(u0.x), __uint_as_float(u0.y), __uint_as_float(u0.z), __uint_as_float(u0.w)),
                               make_float4(__uint_as_float(u1.x), __uint_as_float(u1.y), __uint_as_float(u1.z), __uint_as_float(u1.w)),
                               hi, lo);
                     *reinterpret_cast<uint4*>(sA + a_dst[i]) = hi;

@@ -2,10 +2,8 @@
 #pragma once
 #include "tdx_common.h"
 #include "tdx_conv3.h"
+#include "tdx_mfma.h"
 #include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define SM_KC 16
 #define SM_BN 32
@@ -161,19 +159,6 @@ conv3_small_kernel(const void* __restrict__ x1_, int C1, const void* __restrict_
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
 
-    // 8 fp32 -> 8 bf16 hi and 8 bf16 lo
-    auto split8 = [](const float4& a, const float4& b, bf16x8& hi, bf16x8& lo) {
-        const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        unsigned h[4], l[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            h[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
-            l[i] = pack_bf16x2(v[2 * i] - __uint_as_float(h[i] << 16), v[2 * i + 1] - __uint_as_float(h[i] & 0xffff0000u));
-        }
-        const uint4 uh = make_uint4(h[0], h[1], h[2], h[3]), ul = make_uint4(l[0], l[1], l[2], l[3]);
-        hi = *reinterpret_cast<const bf16x8*>(&uh);
-        lo = *reinterpret_cast<const bf16x8*>(&ul);
-    };
     __syncthreads();  // the first slice has landed (the loader waves waited for it)
     for (int c = c_first; c < c_end; ++c) {
         const int buf = SPLIT ? 0 : ((c - c_first) & 1);
@@ -206,8 +191,9 @@ conv3_small_kernel(const void* __restrict__ x1_, int C1, const void* __restrict_
 #pragma unroll
             for (int i = 0; i < MTW; ++i) {
                 if (SPLIT) {
-                    bf16x8 xh, xl;
-                    split8(f.xa[SPLIT ? i : 0], f.xb[SPLIT ? i : 0], xh, xl);
+                    uint4 uh, ul;
+                    split8(f.xa[SPLIT ? i : 0], f.xb[SPLIT ? i : 0], uh, ul);
+                    const bf16x8 xh = __builtin_bit_cast(bf16x8, uh), xl = __builtin_bit_cast(bf16x8, ul);
                     acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.w, xh, acc[i], 0, 0, 0);
                     acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.w, xl, acc[i], 0, 0, 0);
                     acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.wl, xh, acc[i], 0, 0, 0);

@@ -18,53 +18,18 @@
 // atomics (128-B contiguous per half-wave) into dwp[27][Cin][Cout].  The bias gradient is summed
 // from the dy staging registers (a thread always stages the same 8 channels).  The brick's short
 // axis is put on the grid axis that leaves the fewest bricks (WgradView: local axes).
-#include "tdx_common.h"
-#include "tdx_conv3.h"
+#include "tdx_conv3_wgrad.h"
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-#define W3_BX 4
-#define W3_BY 8
-#define W3_BZ 8
-#define W3_HY 10
-#define W3_HZ 10
-#define W3_NVOX (W3_BX * W3_BY * W3_BZ)              // 256 voxels per brick
-#define W3_NSTEPS (W3_NVOX / 16)                     // K-steps of 16 voxels
-#define W3_NHALO ((W3_BX + 2) * W3_HY * W3_HZ)        // 1000
-#define W3_XBYTES (W3_NHALO * 64)   // 64000
-#define W3_GPLANE (W3_NVOX * 64)    // one 32-channel dy plane
+typedef WgradBrick<4> W3;                            // 4 x 8 x 8 bricks, 64-B rows
+#define W3_NSTEPS (W3::NVOX / 16)                    // K-steps of 16 voxels
 #define W3_TAPS_PER_WAVE 7
-
-// grid in the kernel's local axes (local axis k = global axis perm[k]; the brick is 4 x 8 x 8 in local
-// axes, and the short axis is put where it leaves the fewest bricks)
-struct WgradView {
-    int B;
-    int E[3];     // extents
-    int s[3];     // voxel strides
-    int ws[3];    // weight-tap strides: global tap = sum_k (e_k + 1) * ws[k]
-    int nb[3];    // bricks per axis
-    int batch;    // voxels per sample
-};
 
 // a single input may end in a half-filled 32-channel tile (C1 % 16 == 0): its missing channels are
 // staged as zeros and their rows of dW are not written
 bool conv3_wgrad_mfma_supported(int C1, int C2, int Cout) {
     const bool c1_ok = (C1 % 32) == 0 || (C2 == 0 && (C1 % 16) == 0);
     return C1 > 0 && c1_ok && (C2 % 32) == 0 && (Cout % 32) == 0;
-}
-
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* base_lo, const unsigned char* base_hi) {
-    // two transposed 4-row reads -> 8 consecutive k for this lane's column
-    s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base_lo));
-    s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base_hi));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    s16x8 r = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, r);
 }
 
 // Diagnostic builds only (tools/micro/wgrad_stamp.hip defines W3_STAMPS): s_memtime stamps of brick iterations 4 .. 11
@@ -92,7 +57,7 @@ conv3_wgrad_mfma_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
                         int Cout, int nsplit, int n_ci_tiles, int64_t slab_stride) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* sX = smem;
-    unsigned char* sG = smem + W3_XBYTES;
+    unsigned char* sG = smem + W3::XBYTES;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -107,10 +72,8 @@ conv3_wgrad_mfma_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
 
     const int nbricks = gv.B * gv.nb[0] * gv.nb[1] * gv.nb[2];
 
-    // ---- fragment lane geometry (see file header)
-    const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-    const int col_off = (16 * (g & 1) + 4 * p) * 2;   // byte offset of this lane's 4 columns in a 64-B row
-    const int kh = g >> 1;                            // which 8-voxel half of the 16-voxel K-step
+    const WgradLane L = wgrad_lane(lane);  // fragment lane geometry
+    const int q = L.q, kh = L.kh, col_off = L.col_off;
 
     f32x16 acc[W3_TAPS_PER_WAVE][NT];
 #pragma unroll
@@ -127,40 +90,29 @@ conv3_wgrad_mfma_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
     // halo offsets (in voxels) of this wave's taps
     int toff[W3_TAPS_PER_WAVE];
 #pragma unroll
-    for (int t = 0; t < W3_TAPS_PER_WAVE; ++t) {
-        const int tap = min(wave + 4 * t, 26);
-        const int ex = tap / 9 - 1, ey = (tap / 3) % 3 - 1, ez = tap % 3 - 1;
-        toff[t] = (ex * W3_HY + ey) * W3_HZ + ez;
-    }
-
-    // per-tap fragment base address of this lane at step 0: halo voxel (1, kh + 1, q + 1) + tap
+    for (int t = 0; t < W3_TAPS_PER_WAVE; ++t) toff[t] = W3::tap_offset(min(wave + 4 * t, 26));
+    // per-tap fragment base address of this lane at step 0
     const unsigned char* a_base[W3_TAPS_PER_WAVE];
 #pragma unroll
-    for (int t = 0; t < W3_TAPS_PER_WAVE; ++t)
-        a_base[t] = sX + ((W3_HY + kh + 1) * W3_HZ + (q + 1) + toff[t]) * 64 + col_off;
+    for (int t = 0; t < W3_TAPS_PER_WAVE; ++t) a_base[t] = sX + wgrad_x_frag_row<W3>(L, toff[t]) * 64 + col_off;
 
-    constexpr int XP = (W3_NHALO * 4 + 255) / 256;  // 16 pieces of 16 B per thread
-    constexpr int GP = (W3_NVOX * 4 * NT) / 256;     // 8*NT pieces per thread
+    constexpr int XP = (W3::NHALO * 4 + 255) / 256;  // 16 pieces of 16 B per thread
+    constexpr int GP = (W3::NVOX * 4 * NT) / 256;     // 8*NT pieces per thread
     uint4 xreg[XP], greg[GP];
 
     auto load_brick = [&](int brick) {
-        int bb = brick;
-        const int bz = bb % gv.nb[2]; bb /= gv.nb[2];
-        const int by = bb % gv.nb[1]; bb /= gv.nb[1];
-        const int bx = bb % gv.nb[0]; bb /= gv.nb[0];
-        const int b = bb;
-        const int ox0 = bx * W3_BX, oy0 = by * W3_BY, oz0 = bz * W3_BZ;
+        int bx, by, bz;
+        const int b = wgrad_brick_coords(gv, brick, bx, by, bz);
+        const int ox0 = bx * W3::BX, oy0 = by * W3::BY, oz0 = bz * W3::BZ;
 #pragma unroll
         for (int i = 0; i < XP; ++i) {
             const int pc = tid + i * 256;
             xreg[i] = make_uint4(0, 0, 0, 0);
-            if (pc < W3_NHALO * 4 && cbase + (pc & 3) * 8 < Cs) {
-                const int hv = pc >> 2, q4 = pc & 3;
-                const int hx = hv / (W3_HY * W3_HZ), rem = hv - hx * (W3_HY * W3_HZ);
-                const int hy = rem / W3_HZ, hz = rem - hy * W3_HZ;
-                const int sx = min(max(ox0 + hx - 1, 0), gv.E[0] - 1), sy = min(max(oy0 + hy - 1, 0), gv.E[1] - 1),
-                          sz = min(max(oz0 + hz - 1, 0), gv.E[2] - 1);
-                const int64_t vox = (int64_t)b * gv.batch + sx * gv.s[0] + sy * gv.s[1] + sz * gv.s[2];
+            if (pc < W3::NHALO * 4 && cbase + (pc & 3) * 8 < Cs) {
+                const int q4 = pc & 3;
+                int hx, hy, hz;
+                W3::halo_coords(pc >> 2, hx, hy, hz);
+                const int64_t vox = W3::halo_source(gv, b, bx, by, bz, hx, hy, hz);
                 xreg[i] = *reinterpret_cast<const uint4*>(xs + vox * Cs + cbase + q4 * 8);
             }
         }
@@ -171,7 +123,7 @@ conv3_wgrad_mfma_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
             const int vx = ox0 + (v >> 6), vy = oy0 + ((v >> 3) & 7), vz = oz0 + (v & 7);
             greg[i] = make_uint4(0, 0, 0, 0);
             if (vx < gv.E[0] && vy < gv.E[1] && vz < gv.E[2]) {
-                const int64_t vox = (int64_t)b * gv.batch + vx * gv.s[0] + vy * gv.s[1] + vz * gv.s[2];
+                const int64_t vox = wgrad_voxel(gv, b, vx, vy, vz);
                 greg[i] = *reinterpret_cast<const uint4*>(dy + vox * Cout + co0 + q8 * 8);
             }
         }
@@ -180,13 +132,13 @@ conv3_wgrad_mfma_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
 #pragma unroll
         for (int i = 0; i < XP; ++i) {
             const int pc = tid + i * 256;
-            if (pc < W3_NHALO * 4) *reinterpret_cast<uint4*>(sX + pc * 16) = xreg[i];
+            if (pc < W3::NHALO * 4) *reinterpret_cast<uint4*>(sX + pc * 16) = xreg[i];
         }
 #pragma unroll
         for (int i = 0; i < GP; ++i) {
             const int pc = tid + i * 256;
             const int v = pc / (4 * NT), q8 = pc - v * (4 * NT);
-            *reinterpret_cast<uint4*>(sG + (q8 >> 2) * W3_GPLANE + v * 64 + (q8 & 3) * 16) = greg[i];
+            *reinterpret_cast<uint4*>(sG + (q8 >> 2) * W3::GPLANE + v * 64 + (q8 & 3) * 16) = greg[i];
             if (do_bias) {
                 const unsigned wds[4] = {greg[i].x, greg[i].y, greg[i].z, greg[i].w};
 #pragma unroll
@@ -199,7 +151,7 @@ conv3_wgrad_mfma_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
     };
 
 #ifdef W3_STAMPS
-    unsigned long long* sStamp_ = reinterpret_cast<unsigned long long*>(smem + W3_XBYTES + NT * W3_GPLANE);
+    unsigned long long* sStamp_ = reinterpret_cast<unsigned long long*>(smem + W3::XBYTES + NT * W3::GPLANE);
     int nst_ = 0, it_ = 0;
 #endif
     int brick = split;
@@ -226,10 +178,10 @@ conv3_wgrad_mfma_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
         auto read_b = [&](int s, bf16x8 (&bf)[NT]) {
             const unsigned char* bp = sG + (16 * s + 8 * kh + q) * 64 + col_off;
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) bf[nt] = tr_frag(bp + nt * W3_GPLANE, bp + nt * W3_GPLANE + 4 * 64);
+            for (int nt = 0; nt < NT; ++nt) bf[nt] = tr_frag(bp + nt * W3::GPLANE, bp + nt * W3::GPLANE + 4 * 64);
         };
         // byte offset of step s inside the halo brick (x = s >> 2, y = 2 (s & 3))
-        auto step_off = [&](int s) { return ((s >> 2) * W3_HY + 2 * (s & 3)) * W3_HZ * 64; };
+        auto step_off = [&](int s) { return wgrad_x_step_offset<W3>(s); };
         auto read_a = [&](int soff, int t) {
             const unsigned char* ap = a_base[t] + soff;
             return tr_frag(ap, ap + 4 * 64);
@@ -302,7 +254,7 @@ conv3_wgrad_mfma_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
     for (int t = 0; t < W3_TAPS_PER_WAVE; ++t) {
         const int ltap = wave + 4 * t;  // tap in local axes -> tap of the weight tensor
         if (ltap < 27) {
-            const int tap = (ltap / 9) * gv.ws[0] + ((ltap / 3) % 3) * gv.ws[1] + (ltap % 3) * gv.ws[2];
+            const int tap = wgrad_global_tap(gv, ltap);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -349,7 +301,7 @@ int conv3_wgrad_mfma_launch(const Conv3WgradCall& c) {
     // local axes: brick 4 x 8 x 8; the short axis goes where it leaves the fewest bricks
     static const bool no_perm = getenv("TDX_CONV3_PERM") && atoi(getenv("TDX_CONV3_PERM")) == 0;  // A/B switch
     WgradView g;
-    const int nbricks = conv3_wgrad_view(g, c, W3_BX, W3_BY, W3_BZ, !no_perm);
+    const int nbricks = conv3_wgrad_view(g, c, W3::BX, W3::BY, W3::BZ, !no_perm);
     const int n_ci = (Cin + 31) / 32, n_co = Cout / (32 * NT);
     const int ntiles = n_ci * n_co;
     // one workgroup per CU (224 accumulator registers -> one wave per SIMD): aim at 256
@@ -360,7 +312,7 @@ int conv3_wgrad_mfma_launch(const Conv3WgradCall& c) {
     if (nsplit < 1) nsplit = 1;
     int64_t slab_stride;
     float* out = conv3_wgrad_merge(c, nsplit, slab_stride);  // may lower nsplit (TDX_DETERMINISTIC)
-    size_t lds = W3_XBYTES + (size_t)NT * W3_GPLANE;
+    size_t lds = W3::XBYTES + (size_t)NT * W3::GPLANE;
 #ifdef W3_STAMPS
     lds += 4 * W3_NSTAMP * 8;
 #endif

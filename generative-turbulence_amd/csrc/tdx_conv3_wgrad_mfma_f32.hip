@@ -14,30 +14,13 @@
 // step s+1 read during step s) are an order of magnitude cheaper, relatively, than in the bf16 kernel.
 // Products and sums are IEEE fp32.  Partial tiles: f32 atomics into dwp[27][Cin][Cout], or plain stores
 // into per-split slabs when there are few splits.
-#include "tdx_common.h"
-#include "tdx_conv3.h"
+#include "tdx_conv3_wgrad.h"
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 // brick BX x 8 x 8 with BX = 4 for NT = 1 and BX = 2 for NT = 2 (224 accumulator registers: the
-// smaller brick keeps the prefetch registers of the next brick inside the 512-register budget)
-#define WF_BX(NT) ((NT) == 2 ? 2 : 4)
-#define WF_BY 8
-#define WF_BZ 8
-#define WF_HY 10
-#define WF_HZ 10
-#define WF_ROW 128                                 // bytes of a 32-channel fp32 voxel row
+// smaller brick keeps the prefetch registers of the next brick inside the 512-register budget); 128-B rows (32 fp32 channels)
+template <int NT> using WF = WgradBrick<NT == 2 ? 2 : 4, 128>;
 #define WF_TAPS_PER_WAVE 7
-
-struct WgradViewF {
-    int B;
-    int E[3];   // extents in the kernel's local axes
-    int s[3];   // voxel strides
-    int ws[3];  // weight-tap strides
-    int nb[3];  // bricks per axis
-    int batch;  // voxels per sample
-};
 
 bool conv3_wgrad_mfma_f32_supported(int C1, int C2, int Cout) {
     const bool c1_ok = (C1 % 32) == 0 || (C2 == 0 && (C1 % 8) == 0);
@@ -48,16 +31,12 @@ template <int NT>
 __global__ void __launch_bounds__(256, 1)
 conv3_wgrad_mfma_f32_kernel(const float* __restrict__ x1, int C1, const float* __restrict__ x2, int C2,
                             const float* __restrict__ dy, float* __restrict__ dwp, float* __restrict__ dbias,
-                            WgradViewF gv, int Cout, int nsplit, int n_ci_tiles, int64_t slab_stride) {
-    constexpr int BX = WF_BX(NT);
-    constexpr int WF_NVOX = BX * WF_BY * WF_BZ;          // voxels per brick
-    constexpr int WF_NSTEPS = WF_NVOX / 2;               // K-steps of 2 voxels
-    constexpr int WF_NHALO = (BX + 2) * WF_HY * WF_HZ;
-    constexpr int WF_XBYTES = WF_NHALO * WF_ROW;
-    constexpr int WF_GPLANE = WF_NVOX * WF_ROW;          // one 32-channel dy plane
+                            WgradView gv, int Cout, int nsplit, int n_ci_tiles, int64_t slab_stride) {
+    using BR = WF<NT>;
+    constexpr int WF_NSTEPS = BR::NVOX / 2;              // K-steps of 2 voxels
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* sX = smem;
-    unsigned char* sG = smem + WF_XBYTES;
+    unsigned char* sG = smem + BR::XBYTES;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -87,35 +66,28 @@ conv3_wgrad_mfma_f32_kernel(const float* __restrict__ x1, int C1, const float* _
     const unsigned char* a_base[WF_TAPS_PER_WAVE];
 #pragma unroll
     for (int t = 0; t < WF_TAPS_PER_WAVE; ++t) {
-        const int tap = min(wave + 4 * t, 26);
-        const int ex = tap / 9 - 1, ey = (tap / 3) % 3 - 1, ez = tap % 3 - 1;
-        const int toff = (ex * WF_HY + ey) * WF_HZ + ez;
-        a_base[t] = sX + ((WF_HY + 1) * WF_HZ + 1 + hh + toff) * WF_ROW + r * 4;
+        const int toff = BR::tap_offset(min(wave + 4 * t, 26));
+        a_base[t] = sX + ((BR::HY + 1) * BR::HZ + 1 + hh + toff) * BR::ROW + r * 4;
     }
-    const unsigned char* b_base = sG + hh * WF_ROW + r * 4;
+    const unsigned char* b_base = sG + hh * BR::ROW + r * 4;
 
-    constexpr int XP = (WF_NHALO * 8 + 255) / 256;  // 16-B pieces per thread
-    constexpr int GP = (WF_NVOX * 8 * NT) / 256;
+    constexpr int XP = (BR::NHALO * 8 + 255) / 256;  // 16-B pieces per thread
+    constexpr int GP = (BR::NVOX * 8 * NT) / 256;
     float4 xreg[XP], greg[GP];
 
     auto load_brick = [&](int brick) {
-        int bb = brick;
-        const int bz = bb % gv.nb[2]; bb /= gv.nb[2];
-        const int by = bb % gv.nb[1]; bb /= gv.nb[1];
-        const int bx = bb % gv.nb[0]; bb /= gv.nb[0];
-        const int b = bb;
-        const int ox0 = bx * BX, oy0 = by * WF_BY, oz0 = bz * WF_BZ;
+        int bx, by, bz;
+        const int b = wgrad_brick_coords(gv, brick, bx, by, bz);
+        const int ox0 = bx * BR::BX, oy0 = by * BR::BY, oz0 = bz * BR::BZ;
 #pragma unroll
         for (int i = 0; i < XP; ++i) {
             const int pc = tid + i * 256;
             xreg[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (pc < WF_NHALO * 8 && cbase + (pc & 7) * 4 < Cs) {
-                const int hv = pc >> 3, q4 = pc & 7;
-                const int hx = hv / (WF_HY * WF_HZ), rem = hv - hx * (WF_HY * WF_HZ);
-                const int hy = rem / WF_HZ, hz = rem - hy * WF_HZ;
-                const int sx = min(max(ox0 + hx - 1, 0), gv.E[0] - 1), sy = min(max(oy0 + hy - 1, 0), gv.E[1] - 1),
-                          sz = min(max(oz0 + hz - 1, 0), gv.E[2] - 1);
-                const int64_t vox = (int64_t)b * gv.batch + sx * gv.s[0] + sy * gv.s[1] + sz * gv.s[2];
+            if (pc < BR::NHALO * 8 && cbase + (pc & 7) * 4 < Cs) {
+                const int q4 = pc & 7;
+                int hx, hy, hz;
+                BR::halo_coords(pc >> 3, hx, hy, hz);
+                const int64_t vox = BR::halo_source(gv, b, bx, by, bz, hx, hy, hz);
                 xreg[i] = *reinterpret_cast<const float4*>(xs + vox * Cs + cbase + q4 * 4);
             }
         }
@@ -126,7 +98,7 @@ conv3_wgrad_mfma_f32_kernel(const float* __restrict__ x1, int C1, const float* _
             const int vx = ox0 + (v >> 6), vy = oy0 + ((v >> 3) & 7), vz = oz0 + (v & 7);
             greg[i] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (vx < gv.E[0] && vy < gv.E[1] && vz < gv.E[2]) {
-                const int64_t vox = (int64_t)b * gv.batch + vx * gv.s[0] + vy * gv.s[1] + vz * gv.s[2];
+                const int64_t vox = wgrad_voxel(gv, b, vx, vy, vz);
                 greg[i] = *reinterpret_cast<const float4*>(dy + vox * Cout + co0 + q4 * 4);
             }
         }
@@ -135,23 +107,23 @@ conv3_wgrad_mfma_f32_kernel(const float* __restrict__ x1, int C1, const float* _
 #pragma unroll
         for (int i = 0; i < XP; ++i) {
             const int pc = tid + i * 256;
-            if (pc < WF_NHALO * 8) *reinterpret_cast<float4*>(sX + pc * 16) = xreg[i];
+            if (pc < BR::NHALO * 8) *reinterpret_cast<float4*>(sX + pc * 16) = xreg[i];
         }
 #pragma unroll
         for (int i = 0; i < GP; ++i) {
             const int pc = tid + i * 256;
             const int v = pc / (8 * NT), q4 = pc - v * (8 * NT);
-            *reinterpret_cast<float4*>(sG + (q4 >> 3) * WF_GPLANE + v * WF_ROW + (q4 & 7) * 16) = greg[i];
+            *reinterpret_cast<float4*>(sG + (q4 >> 3) * BR::GPLANE + v * BR::ROW + (q4 & 7) * 16) = greg[i];
             if (do_bias) { bs[0] += greg[i].x; bs[1] += greg[i].y; bs[2] += greg[i].z; bs[3] += greg[i].w; }
         }
     };
 
     // K-step s: voxels (x = s >> 5, y = (s >> 2) & 7, z = 2 (s & 3) + hh)
-    auto step_off = [&](int s) { return (((s >> 5) * WF_HY + ((s >> 2) & 7)) * WF_HZ + 2 * (s & 3)) * WF_ROW; };
+    auto step_off = [&](int s) { return (((s >> 5) * BR::HY + ((s >> 2) & 7)) * BR::HZ + 2 * (s & 3)) * BR::ROW; };
     auto read_a = [&](int soff, int t) { return *reinterpret_cast<const float*>(a_base[t] + soff); };
     auto read_b = [&](int s, float (&bf)[NT]) {
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) bf[nt] = *reinterpret_cast<const float*>(b_base + nt * WF_GPLANE + 2 * s * WF_ROW);
+        for (int nt = 0; nt < NT; ++nt) bf[nt] = *reinterpret_cast<const float*>(b_base + nt * BR::GPLANE + 2 * s * BR::ROW);
     };
 
     int brick = split;
@@ -202,7 +174,7 @@ conv3_wgrad_mfma_f32_kernel(const float* __restrict__ x1, int C1, const float* _
     for (int t = 0; t < WF_TAPS_PER_WAVE; ++t) {
         const int ltap = wave + 4 * t;  // tap in local axes -> tap of the weight tensor
         if (ltap < 27) {
-            const int tap = (ltap / 9) * gv.ws[0] + ((ltap / 3) % 3) * gv.ws[1] + (ltap % 3) * gv.ws[2];
+            const int tap = wgrad_global_tap(gv, ltap);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -236,8 +208,8 @@ int conv3_wgrad_mfma_f32_launch(const Conv3WgradCall& c) {
     const int Cin = c.C1 + c.C2;
     const int NT = (Cout % 64 == 0) ? 2 : 1;
     // local axes: brick 4 x 8 x 8; the short axis goes where it leaves the fewest bricks
-    WgradViewF g;
-    const int nbricks = conv3_wgrad_view(g, c, WF_BX(NT), WF_BY, WF_BZ);
+    WgradView g;
+    const int nbricks = conv3_wgrad_view(g, c, NT == 2 ? WF<2>::BX : WF<1>::BX, WF<1>::BY, WF<1>::BZ);
     const int n_ci = (Cin + 31) / 32, n_co = Cout / (32 * NT);
     const int ntiles = n_ci * n_co;
     // one workgroup per CU (LDS): one resident wave of workgroups, at most one split per brick
@@ -246,7 +218,7 @@ int conv3_wgrad_mfma_f32_launch(const Conv3WgradCall& c) {
     if (nsplit < 1) nsplit = 1;
     int64_t slab_stride;
     float* out = conv3_wgrad_merge(c, nsplit, slab_stride);  // may lower nsplit (TDX_DETERMINISTIC)
-    const size_t lds = (size_t)(WF_BX(NT) + 2) * WF_HY * WF_HZ * WF_ROW + (size_t)NT * WF_BX(NT) * WF_BY * WF_BZ * WF_ROW;
+    const size_t lds = NT == 2 ? WF<2>::XBYTES + 2 * WF<2>::GPLANE : WF<1>::XBYTES + WF<1>::GPLANE;  // x image + NT dy planes
     dim3 grid((unsigned)(ntiles * nsplit));
 #define WF_LAUNCH(NTV)                                                                                               \
     do {                                                                                                             \

@@ -12,68 +12,27 @@
 // (tap, K-step) issues three MFMAs, the output tile is 32 channels wide (NT = 1: the second register set of
 // the double-buffered fragments takes the room of the second accumulator tile), and the bias gradient is
 // summed from the fp32 staging registers, i.e. exactly.
-#include "tdx_common.h"
-#include "tdx_conv3.h"
+#include "tdx_conv3_wgrad.h"
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-#define WS_BX 4
-#define WS_BY 8
-#define WS_BZ 8
-#define WS_HY 10
-#define WS_HZ 10
-#define WS_NVOX (WS_BX * WS_BY * WS_BZ)              // 256
-#define WS_NSTEPS (WS_NVOX / 16)                     // K-steps of 16 voxels
-#define WS_NHALO ((WS_BX + 2) * WS_HY * WS_HZ)        // 600
-#define WS_XBYTES (WS_NHALO * 64)                    // one image of the halo brick (32 bf16 channels per voxel)
-#define WS_GBYTES (WS_NVOX * 64)                     // one image of the dy brick
+typedef WgradBrick<4> WS;                            // 4 x 8 x 8 bricks; an image (hi or lo) has 64-B rows of 32 bf16 channels
+#define WS_NSTEPS (WS::NVOX / 16)                    // K-steps of 16 voxels
 #define WS_TAPS 7
-
-struct WgradViewS {
-    int B;
-    int E[3], s[3], ws[3], nb[3];
-    int batch;
-};
 
 bool conv3_wgrad_mfma_split_supported(int C1, int C2, int Cout) {
     const bool c1_ok = (C1 % 32) == 0 || (C2 == 0 && (C1 % 8) == 0);
     return C1 > 0 && c1_ok && (C2 % 32) == 0 && (Cout % 32) == 0;
 }
 
-__device__ __forceinline__ bf16x8 tr_frag_s(const unsigned char* base_lo, const unsigned char* base_hi) {
-    s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base_lo));
-    s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base_hi));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    s16x8 r = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, r);
-}
-
-__device__ __forceinline__ void split8w(const float4& a, const float4& b, uint4& hi, uint4& lo) {
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        h[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
-        const float r0 = v[2 * i] - __uint_as_float(h[i] << 16), r1 = v[2 * i + 1] - __uint_as_float(h[i] & 0xffff0000u);
-        l[i] = pack_bf16x2(r0, r1);
-    }
-    hi = make_uint4(h[0], h[1], h[2], h[3]);
-    lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
 __global__ void __launch_bounds__(256, 1)
 conv3_wgrad_mfma_split_kernel(const float* __restrict__ x1, int C1, const float* __restrict__ x2, int C2,
-                              const float* __restrict__ dy, float* __restrict__ dwp, float* __restrict__ dbias, WgradViewS gv,
+                              const float* __restrict__ dy, float* __restrict__ dwp, float* __restrict__ dbias, WgradView gv,
                               int Cout, int nsplit, int n_ci_tiles, int64_t slab_stride) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* sXh = smem;
-    unsigned char* sXl = smem + WS_XBYTES;
-    unsigned char* sGh = smem + 2 * WS_XBYTES;
-    unsigned char* sGl = sGh + WS_GBYTES;
+    unsigned char* sXl = smem + WS::XBYTES;
+    unsigned char* sGh = smem + 2 * WS::XBYTES;
+    unsigned char* sGl = sGh + WS::GPLANE;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -88,10 +47,8 @@ conv3_wgrad_mfma_split_kernel(const float* __restrict__ x1, int C1, const float*
 
     const int nbricks = gv.B * gv.nb[0] * gv.nb[1] * gv.nb[2];
 
-    // fragment lane geometry (as the bf16 kernel)
-    const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-    const int col_off = (16 * (g & 1) + 4 * p) * 2;
-    const int kh = g >> 1;
+    const WgradLane L = wgrad_lane(lane);  // fragment lane geometry
+    const int q = L.q, kh = L.kh, col_off = L.col_off;
 
     f32x16 acc[WS_TAPS];
 #pragma unroll
@@ -106,34 +63,26 @@ conv3_wgrad_mfma_split_kernel(const float* __restrict__ x1, int C1, const float*
     int a_off[WS_TAPS];  // byte offset inside an x image of this lane's fragment at step 0, per tap
 #pragma unroll
     for (int t = 0; t < WS_TAPS; ++t) {
-        const int tap = min(wave + 4 * t, 26);
-        const int ex = tap / 9 - 1, ey = (tap / 3) % 3 - 1, ez = tap % 3 - 1;
-        const int toff = (ex * WS_HY + ey) * WS_HZ + ez;
-        a_off[t] = ((WS_HY + kh + 1) * WS_HZ + (q + 1) + toff) * 64 + col_off;
+        a_off[t] = wgrad_x_frag_row<WS>(L, WS::tap_offset(min(wave + 4 * t, 26))) * 64 + col_off;
     }
 
-    constexpr int XP = (WS_NHALO * 4 + 255) / 256;  // pieces of 8 fp32 channels per thread (10)
-    constexpr int GP = (WS_NVOX * 4) / 256;          // 4
+    constexpr int XP = (WS::NHALO * 4 + 255) / 256;  // pieces of 8 fp32 channels per thread (10)
+    constexpr int GP = (WS::NVOX * 4) / 256;          // 4
     float4 xreg[XP][2], greg[GP][2];
 
     auto load_brick = [&](int brick) {
-        int bb = brick;
-        const int bz = bb % gv.nb[2]; bb /= gv.nb[2];
-        const int by = bb % gv.nb[1]; bb /= gv.nb[1];
-        const int bx = bb % gv.nb[0]; bb /= gv.nb[0];
-        const int b = bb;
-        const int ox0 = bx * WS_BX, oy0 = by * WS_BY, oz0 = bz * WS_BZ;
+        int bx, by, bz;
+        const int b = wgrad_brick_coords(gv, brick, bx, by, bz);
+        const int ox0 = bx * WS::BX, oy0 = by * WS::BY, oz0 = bz * WS::BZ;
 #pragma unroll
         for (int i = 0; i < XP; ++i) {
             const int pc = tid + i * 256;
             xreg[i][0] = xreg[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (pc < WS_NHALO * 4 && cbase + (pc & 3) * 8 < Cs) {
-                const int hv = pc >> 2, q4 = pc & 3;
-                const int hx = hv / (WS_HY * WS_HZ), rem = hv - hx * (WS_HY * WS_HZ);
-                const int hy = rem / WS_HZ, hz = rem - hy * WS_HZ;
-                const int sx = min(max(ox0 + hx - 1, 0), gv.E[0] - 1), sy = min(max(oy0 + hy - 1, 0), gv.E[1] - 1),
-                          sz = min(max(oz0 + hz - 1, 0), gv.E[2] - 1);
-                const int64_t vox = (int64_t)b * gv.batch + sx * gv.s[0] + sy * gv.s[1] + sz * gv.s[2];
+            if (pc < WS::NHALO * 4 && cbase + (pc & 3) * 8 < Cs) {
+                const int q4 = pc & 3;
+                int hx, hy, hz;
+                WS::halo_coords(pc >> 2, hx, hy, hz);
+                const int64_t vox = WS::halo_source(gv, b, bx, by, bz, hx, hy, hz);
                 const float4* src = reinterpret_cast<const float4*>(xs + vox * Cs + cbase + q4 * 8);
                 xreg[i][0] = src[0];
                 xreg[i][1] = src[1];
@@ -146,7 +95,7 @@ conv3_wgrad_mfma_split_kernel(const float* __restrict__ x1, int C1, const float*
             const int vx = ox0 + (v >> 6), vy = oy0 + ((v >> 3) & 7), vz = oz0 + (v & 7);
             greg[i][0] = greg[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (vx < gv.E[0] && vy < gv.E[1] && vz < gv.E[2]) {
-                const int64_t vox = (int64_t)b * gv.batch + vx * gv.s[0] + vy * gv.s[1] + vz * gv.s[2];
+                const int64_t vox = wgrad_voxel(gv, b, vx, vy, vz);
                 const float4* src = reinterpret_cast<const float4*>(dy + vox * Cout + co0 + q8 * 8);
                 greg[i][0] = src[0];
                 greg[i][1] = src[1];
@@ -157,9 +106,9 @@ conv3_wgrad_mfma_split_kernel(const float* __restrict__ x1, int C1, const float*
 #pragma unroll
         for (int i = 0; i < XP; ++i) {
             const int pc = tid + i * 256;
-            if (pc < WS_NHALO * 4) {
+            if (pc < WS::NHALO * 4) {
                 uint4 hi, lo;
-                split8w(xreg[i][0], xreg[i][1], hi, lo);
+                split8(xreg[i][0], xreg[i][1], hi, lo);
                 *reinterpret_cast<uint4*>(sXh + pc * 16) = hi;
                 *reinterpret_cast<uint4*>(sXl + pc * 16) = lo;
             }
@@ -168,7 +117,7 @@ conv3_wgrad_mfma_split_kernel(const float* __restrict__ x1, int C1, const float*
         for (int i = 0; i < GP; ++i) {
             const int pc = tid + i * 256;
             uint4 hi, lo;
-            split8w(greg[i][0], greg[i][1], hi, lo);
+            split8(greg[i][0], greg[i][1], hi, lo);
             *reinterpret_cast<uint4*>(sGh + pc * 16) = hi;
             *reinterpret_cast<uint4*>(sGl + pc * 16) = lo;
             if (do_bias) {
@@ -178,16 +127,16 @@ conv3_wgrad_mfma_split_kernel(const float* __restrict__ x1, int C1, const float*
         }
     };
 
-    auto step_off = [&](int s) { return ((s >> 2) * WS_HY + 2 * (s & 3)) * WS_HZ * 64; };
+    auto step_off = [&](int s) { return wgrad_x_step_offset<WS>(s); };
     auto read_a = [&](int soff, int t, bf16x8& h, bf16x8& l) {
         const int o = a_off[t] + soff;
-        h = tr_frag_s(sXh + o, sXh + o + 4 * 64);
-        l = tr_frag_s(sXl + o, sXl + o + 4 * 64);
+        h = tr_frag(sXh + o, sXh + o + 4 * 64);
+        l = tr_frag(sXl + o, sXl + o + 4 * 64);
     };
     auto read_b = [&](int s, bf16x8& h, bf16x8& l) {
         const int o = (16 * s + 8 * kh + q) * 64 + col_off;
-        h = tr_frag_s(sGh + o, sGh + o + 4 * 64);
-        l = tr_frag_s(sGl + o, sGl + o + 4 * 64);
+        h = tr_frag(sGh + o, sGh + o + 4 * 64);
+        l = tr_frag(sGl + o, sGl + o + 4 * 64);
     };
 
     int brick = split;
@@ -246,7 +195,7 @@ conv3_wgrad_mfma_split_kernel(const float* __restrict__ x1, int C1, const float*
     for (int t = 0; t < WS_TAPS; ++t) {
         const int ltap = wave + 4 * t;
         if (ltap < 27) {
-            const int tap = (ltap / 9) * gv.ws[0] + ((ltap / 3) % 3) * gv.ws[1] + (ltap % 3) * gv.ws[2];
+            const int tap = wgrad_global_tap(gv, ltap);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int ci = ci0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
@@ -280,8 +229,8 @@ int conv3_wgrad_mfma_split_launch(const Conv3WgradCall& c) {
         if (rs != TDX_ESHAPE) return rs;
     }
     const int Cin = c.C1 + c.C2;
-    WgradViewS g;
-    const int nbricks = conv3_wgrad_view(g, c, WS_BX, WS_BY, WS_BZ);
+    WgradView g;
+    const int nbricks = conv3_wgrad_view(g, c, WS::BX, WS::BY, WS::BZ);
     const int n_ci = (Cin + 31) / 32, n_co = Cout / 32;
     const int ntiles = n_ci * n_co;
     int nsplit = (256 + ntiles - 1) / ntiles;  // one workgroup per CU: one resident wave of workgroups
@@ -289,7 +238,7 @@ int conv3_wgrad_mfma_split_launch(const Conv3WgradCall& c) {
     if (nsplit < 1) nsplit = 1;
     int64_t slab_stride;
     float* out = conv3_wgrad_merge(c, nsplit, slab_stride);  // may lower nsplit (TDX_DETERMINISTIC)
-    const size_t lds = (size_t)2 * WS_XBYTES + 2 * WS_GBYTES;
+    const size_t lds = (size_t)2 * WS::XBYTES + 2 * WS::GPLANE;
     dim3 grid((unsigned)(ntiles * nsplit));
     auto kern = conv3_wgrad_mfma_split_kernel;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -31,77 +31,34 @@
 // feeds ONE MFMA here, so a K step reads 10 fragments per wave for 3-4 MFMAs (LDS array ~70 % busy at full MFMA rate): it
 // gains less than the 64-wide form did: 32 -> 32 at 192 x 64 x 48 x 6: 0.255 -> 0.218 ms, 128 -> 32: 0.90 -> 0.82 ms,
 // training step -0.22 ms (TDX_WGRAD_RING=2 restores the brick kernel for these layers).
-#include "tdx_common.h"
-#include "tdx_conv3.h"
+#include "tdx_conv3_wgrad.h"
 #include <stdlib.h>
 #include <algorithm>
 #include <type_traits>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-#define WR_BX 4
-#define WR_BY 8
-#define WR_BZ 8
-#define WR_HY 10
-#define WR_HZ 10
-#define WR_NVOX 256
-#define WR_NSTEPS 16                                  // K steps of 16 voxels
-#define WR_NHALO ((WR_BX + 2) * WR_HY * WR_HZ)         // 600 halo'd voxels, 64-B rows (32 channels)
-#define WR_XPIECES ((WR_NHALO * 4 + 63) / 64)          // 38 DMA pieces of 1 KiB
+typedef WgradBrick<4> WR;                             // 4 x 8 x 8 bricks, 600 halo'd voxels, 64-B rows (32 channels)
+#define WR_NSTEPS (WR::NVOX / 16)                     // K steps of 16 voxels
+#define WR_XPIECES ((WR::NHALO * 4 + 63) / 64)         // 38 DMA pieces of 1 KiB
 #define WR_XBUF (WR_XPIECES * 1024)
 #define WR_XPW ((WR_XPIECES + 3) / 4)                  // 10 per loader wave
-#define WR_GPLANE (WR_NVOX * 64)                       // one 32-channel dy plane: 16 pieces
 #define WR_CW 8                                        // computing waves
 // NTN = N tiles of 32 output channels per workgroup (2: 64-wide, 1: 32-wide): dy planes per buffer, dy pieces per loader
 // wave, accumulator tiles per computing wave
-#define WR_GBUF(NTN) ((NTN) * WR_GPLANE)
+#define WR_GBUF(NTN) ((NTN) * WR::GPLANE)            // a dy plane (32 channels) is 16 pieces
 #define WR_GPW(NTN) (4 * (NTN))
 #define WR_SLOTS(NTN) ((NTN) == 2 ? 7 : 4)
-
-struct WgradRingView {
-    int B;
-    int E[3];     // extents in the kernel's local axes (brick 4 x 8 x 8)
-    int s[3];     // voxel strides
-    int ws[3];    // weight-tap strides: global tap = sum_k (e_k + 1) * ws[k]
-    int nb[3];    // bricks per axis
-    int batch;    // voxels per sample
-};
-
-__device__ __forceinline__ bf16x8 wr_tr_frag(const unsigned char* lo, const unsigned char* hi) {
-    s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lo));
-    s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(hi));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    s16x8 r = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, r);
-}
-
-// one LDS-DMA instruction (inline assembly: see tdx_conv3_ring.hip)
-__device__ __forceinline__ void wr_dma(const void* gsrc, unsigned lds) {
-    lds = __builtin_amdgcn_readfirstlane(lds);
-    unsigned keep;  // M0 is compiler-reserved: saved and restored inside the statement (no "m0" clobber)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds) : "memory");
-}
-__device__ __forceinline__ void wr_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // HF: operand format (H16<HF>: bf16 or fp16 words behind the bf16-typed pointers)
 template <int NTN, bool HF>
 __global__ void __launch_bounds__(768, 3)
 conv3_wgrad_ring_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restrict__ x2, int C2, const bf16* __restrict__ dy,
-                        float* __restrict__ dwp, float* __restrict__ dbias, WgradRingView gv, int Cout, int nsplit, int n_ci_tiles,
+                        float* __restrict__ dwp, float* __restrict__ dbias, WgradView gv, int Cout, int nsplit, int n_ci_tiles,
                         int64_t slab_stride, const void* __restrict__ zeros) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     unsigned char* sX = smem;                        // [2][WR_XBUF]
     unsigned char* sG = smem + 2 * WR_XBUF;           // [2][WR_GBUF(NTN)]
     constexpr int GBUF = WR_GBUF(NTN), GPW = WR_GPW(NTN), SLOTS = WR_SLOTS(NTN);
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) const void*)smem;
+    const unsigned lds0 = lds_addr(smem);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -121,44 +78,43 @@ conv3_wgrad_ring_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
         int xh[WR_XPW];  // hx | hy << 8 | hz << 16 | quarter << 24 | channels exist << 30
 #pragma unroll
         for (int i = 0; i < WR_XPW; ++i) {
-            const int pc = min(min(lw * WR_XPW + i, WR_XPIECES - 1) * 64 + lane, WR_NHALO * 4 - 1);
+            const int pc = min(min(lw * WR_XPW + i, WR_XPIECES - 1) * 64 + lane, WR::NHALO * 4 - 1);
             const int hv = pc >> 2, q4 = pc & 3;
-            const int hx = hv / (WR_HY * WR_HZ), rem = hv - hx * (WR_HY * WR_HZ);
-            const int hy = rem / WR_HZ, hz = rem - hy * WR_HZ;
+            int hx, hy, hz;
+            WR::halo_coords(hv, hx, hy, hz);
             xh[i] = hx | (hy << 8) | (hz << 16) | (q4 << 24) | ((cbase + q4 * 8 < Cs) ? (1 << 30) : 0);
         }
         // dy piece j of this wave: gp = lw * GPW + j -> plane gp / 16, chunks e = (gp % 16) * 64 + lane = (voxel e >> 2, quarter e & 3)
         const int g_plane = (lw * GPW) / 16, g_p0 = (lw * GPW) % 16;
         const int g_e0 = g_p0 * 64 + lane;
         auto issue = [&](int brick, int buf) {
-            int bb = brick;
-            const int bz = bb % gv.nb[2]; bb /= gv.nb[2];
-            const int by = bb % gv.nb[1]; bb /= gv.nb[1];
-            const int bx = bb % gv.nb[0]; bb /= gv.nb[0];
+            int bx, by, bz;
+            const int bb = wgrad_brick_coords(gv, brick, bx, by, bz);
 #pragma unroll
             for (int i = 0; i < WR_XPW; ++i) {
-                const int sx = min(max(bx * WR_BX + (xh[i] & 0xff) - 1, 0), gv.E[0] - 1);
-                const int sy = min(max(by * WR_BY + ((xh[i] >> 8) & 0xff) - 1, 0), gv.E[1] - 1);
-                const int sz = min(max(bz * WR_BZ + ((xh[i] >> 16) & 0xff) - 1, 0), gv.E[2] - 1);
+                // WR::halo_source, written out: through the helper the compiler orders this loop differently
+                const int sx = min(max(bx * WR::BX + (xh[i] & 0xff) - 1, 0), gv.E[0] - 1);
+                const int sy = min(max(by * WR::BY + ((xh[i] >> 8) & 0xff) - 1, 0), gv.E[1] - 1);
+                const int sz = min(max(bz * WR::BZ + ((xh[i] >> 16) & 0xff) - 1, 0), gv.E[2] - 1);
                 const int64_t vox = (int64_t)bb * gv.batch + sx * gv.s[0] + sy * gv.s[1] + sz * gv.s[2];
                 const bf16* src = (xh[i] >> 30) & 1 ? xs + vox * Cs + cbase + ((xh[i] >> 24) & 3) * 8 : reinterpret_cast<const bf16*>(zeros);
-                wr_dma(src, lds0 + buf * WR_XBUF + min(lw * WR_XPW + i, WR_XPIECES - 1) * 1024);
+                lds_dma16(src, lds0 + buf * WR_XBUF + min(lw * WR_XPW + i, WR_XPIECES - 1) * 1024);
             }
 #pragma unroll
             for (int j = 0; j < GPW; ++j) {
                 const int e = g_e0 + 64 * j, v = e >> 2, c4 = e & 3;
-                const int vx = bx * WR_BX + (v >> 6), vy = by * WR_BY + ((v >> 3) & 7), vz = bz * WR_BZ + (v & 7);
+                const int vx = bx * WR::BX + (v >> 6), vy = by * WR::BY + ((v >> 3) & 7), vz = bz * WR::BZ + (v & 7);
                 const bool ok = vx < gv.E[0] && vy < gv.E[1] && vz < gv.E[2];
-                const int64_t vox = (int64_t)bb * gv.batch + vx * gv.s[0] + vy * gv.s[1] + vz * gv.s[2];
+                const int64_t vox = wgrad_voxel(gv, bb, vx, vy, vz);
                 const bf16* src = ok ? dy + vox * Cout + co0 + g_plane * 32 + c4 * 8 : reinterpret_cast<const bf16*>(zeros);
-                wr_dma(src, lds0 + 2 * WR_XBUF + buf * GBUF + g_plane * WR_GPLANE + (g_p0 + j) * 1024);
+                lds_dma16(src, lds0 + 2 * WR_XBUF + buf * GBUF + g_plane * WR::GPLANE + (g_p0 + j) * 1024);
             }
         };
         int brick = split, it = 0;
         if (brick < nbricks) issue(brick, 0);
         for (; brick < nbricks; brick += nsplit, ++it) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // brick `it` has landed
-            wr_barrier();                                     // ... and the computing waves are done with brick it - 1
+            lds_barrier();                                    // ... and the computing waves are done with brick it - 1
             if (brick + nsplit < nbricks) issue(brick + nsplit, (it + 1) & 1);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -174,17 +130,12 @@ conv3_wgrad_ring_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
     const int a0 = NTN == 2 ? first >> 1 : first;
     const bool odd = NTN == 2 && (first & 1) != 0;  // slot 0 is N tile 1 of tap a; else slots (0, 1) are tap a
 
-    // fragment lane geometry (tdx_conv3_wgrad_mfma.hip): a K step is 16 voxels; lane group g of 16 lanes reads voxel rows
-    // 8 kh + q and + 4, columns 16 (g & 1) + 4 p .. + 3
-    const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-    const int col_off = (16 * (g & 1) + 4 * p) * 2;
-    const int kh = g >> 1;
+    const WgradLane L = wgrad_lane(lane);  // fragment lane geometry
+    const int q = L.q, kh = L.kh, col_off = L.col_off;
     int a_off[4];  // byte offset of this lane's x fragment at K step 0 for the wave's four taps
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        const int tap = min(a0 + t, 26);
-        const int ex = tap / 9 - 1, ey = (tap / 3) % 3 - 1, ez = tap % 3 - 1;
-        a_off[t] = ((WR_HY + kh + 1) * WR_HZ + (q + 1) + (ex * WR_HY + ey) * WR_HZ + ez) * 64 + col_off;
+        a_off[t] = wgrad_x_frag_row<WR>(L, WR::tap_offset(min(a0 + t, 26))) * 64 + col_off;
     }
     const int b_row = (8 * kh + q) * 64 + col_off;
 
@@ -205,17 +156,17 @@ conv3_wgrad_ring_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
         constexpr bool ODD = decltype(odd_c)::value;  // NTN = 1: "the fourth slot is used"
         int it = 0;
         for (int brick = split; brick < nbricks; brick += nsplit, ++it) {
-            wr_barrier();  // brick `it` is in LDS (the loaders waited for it), everybody is done with brick it - 1
+            lds_barrier();  // brick `it` is in LDS (the loaders waited for it), everybody is done with brick it - 1
             const unsigned char* bX = sX + (it & 1) * WR_XBUF;
             const unsigned char* bG = sG + (it & 1) * GBUF + b_row;
-            auto step_off = [&](int s) { return ((s >> 2) * WR_HY + 2 * (s & 3)) * WR_HZ * 64; };
+            auto step_off = [&](int s) { return wgrad_x_step_offset<WR>(s); };
             auto read_a = [&](int s, int t) {
                 const unsigned char* ap = bX + a_off[t] + step_off(s);
-                return wr_tr_frag(ap, ap + 4 * 64);
+                return tr_frag(ap, ap + 4 * 64);
             };
             auto read_b = [&](int s, int nt) {
-                const unsigned char* bp = bG + nt * WR_GPLANE + s * (16 * 64);
-                return wr_tr_frag(bp, bp + 4 * 64);
+                const unsigned char* bp = bG + nt * WR::GPLANE + s * (16 * 64);
+                return tr_frag(bp, bp + 4 * 64);
             };
             bf16x8 A[4], Bq[2][NTN];
 #pragma unroll
@@ -299,7 +250,7 @@ conv3_wgrad_ring_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
         const int T = first + i;
         if (i < cnt) {
             const int ltap = T / NTN, nt = T % NTN;  // tap in local axes -> tap of the weight tensor
-            const int tap = (ltap / 9) * gv.ws[0] + ((ltap / 3) % 3) * gv.ws[1] + (ltap % 3) * gv.ws[2];
+            const int tap = wgrad_global_tap(gv, ltap);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int ci = ci0 + (e & 3) + 8 * (e >> 2) + 4 * hh;
@@ -327,8 +278,8 @@ int conv3_wgrad_ring_launch(const Conv3WgradCall& c) {
     if (!conv3_wgrad_ring_supported(c.C1, c.C2, Cout)) return TDX_ESHAPE;
     const int Cin = c.C1 + c.C2;
     // local axes: brick 4 x 8 x 8; the short axis goes where it leaves the fewest bricks
-    WgradRingView g;
-    const int nbricks = conv3_wgrad_view(g, c, WR_BX, WR_BY, WR_BZ);
+    WgradView g;
+    const int nbricks = conv3_wgrad_view(g, c, WR::BX, WR::BY, WR::BZ);
     const int NTN = (Cout % 64) == 0 ? 2 : 1;
     {
         const char* env = getenv("TDX_WGRAD_RING");  // A/B switch: 2 = 64-wide tiles only (round 4's rule)

@@ -13,14 +13,8 @@
 // 32 (ci) x 32 NT (co) tile of all 27 taps, wave w the taps w, w + 4, ...; transposed fragment reads
 // (ds_read_b64_tr_b16) of voxel-major rows; partial tiles go to per-split slabs (summed by the unpack kernel) or are
 // merged with f32 atomics.
-#include "tdx_common.h"
-#include "tdx_conv3.h"
+#include "tdx_conv3_wgrad.h"
 #include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 #define WS_MAXROWS 256        // voxels per row group (16 K steps)
 #define WS_TAPS_PER_WAVE 7
@@ -35,26 +29,8 @@ struct WsGeom {
     int grows;      // dy rows per buffer (multiple of 16)
 };
 
-__device__ __forceinline__ bf16x8 ws_tr_frag(const unsigned char* lo, const unsigned char* hi) {
-    s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lo));
-    s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(hi));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    s16x8 r = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, r);
-}
-
-// One LDS-DMA instruction (global_load_lds_dwordx4: every lane copies 16 B from its own global address to LDS byte
-// address `lds` + 16 lane), issued as inline assembly: the compiler treats the builtin form as a store to LDS that any
-// later ds_read might alias and puts s_waitcnt vmcnt(0) in front of the NEXT fragment read -- which serialises the
-// copy of group i + 1 with the MFMAs of group i, the opposite of double buffering.  The kernel orders the copies
-// itself (s_waitcnt vmcnt(0) + barrier before a buffer is read); it issues no other vector-memory loads.
-__device__ __forceinline__ void ws_dma16(const void* gsrc, const unsigned char* lds) {
-    const unsigned a = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) const void*)lds);
-    unsigned keep;  // M0 is compiler-reserved: saved and restored inside the statement (no "m0" clobber)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(a) : "memory");
-}
-
+// The kernel issues no vector-memory loads besides its LDS-DMA copies (lds_dma16) and orders those itself: s_waitcnt
+// vmcnt(0) + barrier before a buffer is read.
 // HF: operand format (H16<HF>: bf16 or fp16 words behind the bf16-typed pointers)
 template <int NT, bool HF>
 __global__ void __launch_bounds__(256, 1)
@@ -104,11 +80,8 @@ conv3_wgrad_small_kernel(const bf16* __restrict__ x1, int C1, const bf16* __rest
     }
     __syncthreads();
 
-    // ---- fragment lane geometry (as tdx_conv3_wgrad_mfma.hip): a K step is 16 rows; lane group g4 of 16 lanes reads
-    // rows 8 kh + q and + 4, columns 16 (g4 & 1) + 4 p .. + 3
-    const int g4 = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-    const int col_off = (16 * (g4 & 1) + 4 * p) * 2;
-    const int kh = g4 >> 1;
+    const WgradLane L = wgrad_lane(lane);  // fragment lane geometry: a K step is 16 rows of the packed K axis
+    const int q = L.q, kh = L.kh, col_off = L.col_off;
 
     f32x16 acc[WS_TAPS_PER_WAVE][NT];
 #pragma unroll
@@ -149,7 +122,7 @@ conv3_wgrad_small_kernel(const bf16* __restrict__ x1, int C1, const bf16* __rest
             const int s0 = min(max(x0 + ix - 1, 0), g.E[0] - 1);
             const int64_t vox = (int64_t)(b0 + bl) * V + s0 * plane + yz;
             const bf16* src = xs_ + vox * Cs + cbase + q4 * 8;
-            ws_dma16(src, dX + pc * 1024);
+            lds_dma16(src, lds_addr(dX + pc * 1024));
         }
         unsigned char* dG = sG + buf * gbytes;
         const int nrows = nb * nx * plane, npg = (g.grows >> 4) * NT;
@@ -161,7 +134,7 @@ conv3_wgrad_small_kernel(const bf16* __restrict__ x1, int C1, const bf16* __rest
                 // the rows of a group are contiguous voxels: whole samples b0 .., or planes x0 .. of sample b0
                 const int64_t vox = (int64_t)b0 * V + (int64_t)x0 * plane + row;
                 const bf16* src = dy + vox * Cout + co0 + pl * 32 + q4 * 8;
-                ws_dma16(src, dst);
+                lds_dma16(src, lds_addr(dst));
             } else {
                 *reinterpret_cast<uint4*>(dst + lane * 16) = make_uint4(0, 0, 0, 0);  // K padding: zero dy rows
             }
@@ -184,7 +157,7 @@ conv3_wgrad_small_kernel(const bf16* __restrict__ x1, int C1, const bf16* __rest
         auto read_b = [&](int s, bf16x8 (&bf)[NT]) {
             const unsigned char* bp = G + (16 * s + 8 * kh + q) * 64;
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) bf[nt] = ws_tr_frag(bp + nt * g.grows * 64, bp + nt * g.grows * 64 + 4 * 64);
+            for (int nt = 0; nt < NT; ++nt) bf[nt] = tr_frag(bp + nt * g.grows * 64, bp + nt * g.grows * 64 + 4 * 64);
         };
         // fragments of step s + 1 are read while the MFMAs of step s issue (two register sets); the table entries of
         // a step are fetched one step before its fragments, so no fragment read waits for its address
@@ -193,8 +166,8 @@ conv3_wgrad_small_kernel(const bf16* __restrict__ x1, int C1, const bf16* __rest
         unsigned e1 = tab[krow], e2 = tab[krow + 4];
         auto read_a = [&](int s_next, bf16x8 (&A)[WS_TAPS_PER_WAVE]) {
 #pragma unroll
-            for (int t = 0; t < WS_TAPS_PER_WAVE - 1; ++t) A[t] = ws_tr_frag(X + e1 + toff[t], X + e2 + toff[t]);
-            A[WS_TAPS_PER_WAVE - 1] = ones_slot ? ones : ws_tr_frag(X + e1 + toff[WS_TAPS_PER_WAVE - 1], X + e2 + toff[WS_TAPS_PER_WAVE - 1]);
+            for (int t = 0; t < WS_TAPS_PER_WAVE - 1; ++t) A[t] = tr_frag(X + e1 + toff[t], X + e2 + toff[t]);
+            A[WS_TAPS_PER_WAVE - 1] = ones_slot ? ones : tr_frag(X + e1 + toff[WS_TAPS_PER_WAVE - 1], X + e2 + toff[WS_TAPS_PER_WAVE - 1]);
             e1 = tab[16 * s_next + krow];
             e2 = tab[16 * s_next + krow + 4];
         };

@@ -16,71 +16,21 @@
 //     stall), then the tap's x fragments are re-read for the next step; wave 7's spare slot multiplies ones with dy_hi and
 //     dy_lo: the bias gradient.
 // Same contract as conv3_wgrad_mfma_split_launch; TDX_ESHAPE = not a case for it (too few bricks per workgroup).
-#include "tdx_common.h"
-#include "tdx_conv3.h"
+#include "tdx_conv3_wgrad.h"
 #include <stdlib.h>
 #include <algorithm>
 #include <type_traits>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-#define SR_BX 2
-#define SR_BY 8
-#define SR_BZ 8
-#define SR_HY 10
-#define SR_HZ 10
-#define SR_NVOX (SR_BX * SR_BY * SR_BZ)                // 128
-#define SR_NSTEPS (SR_NVOX / 16)                       // 8 K steps of 16 voxels
-#define SR_NHALO ((SR_BX + 2) * SR_HY * SR_HZ)          // 400 halo'd voxels, 64-B rows (32 bf16 channels)
-#define SR_XBYTES (SR_NHALO * 64)                      // one image (hi or lo) of the x brick
-#define SR_GBYTES (SR_NVOX * 64)                       // one image of the dy brick
-#define SR_SET (2 * SR_XBYTES + 2 * SR_GBYTES)         // 67 584 B
+typedef WgradBrick<2> SR;                              // 2 x 8 x 8 bricks: 128 voxels, 400 halo'd; 64-B rows (32 bf16 channels)
+#define SR_NSTEPS (SR::NVOX / 16)                      // 8 K steps of 16 voxels
+#define SR_SET (2 * SR::XBYTES + 2 * SR::GPLANE)       // hi and lo image of the x brick and of the dy brick: 67 584 B
 #define SR_CW 8                                        // computing waves
 #define SR_LT 256                                      // loader threads
-
-struct WgradSplitRingView {
-    int B;
-    int E[3];     // extents in the kernel's local axes (brick 2 x 8 x 8)
-    int s[3];     // voxel strides
-    int ws[3];    // weight-tap strides: global tap = sum_k (e_k + 1) * ws[k]
-    int nb[3];    // bricks per axis
-    int batch;    // voxels per sample
-};
-
-__device__ __forceinline__ bf16x8 sr_tr_frag(const unsigned char* lo, const unsigned char* hi) {
-    s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lo));
-    s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(hi));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    s16x8 r = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, r);
-}
-
-__device__ __forceinline__ void sr_split8(const float4& a, const float4& b, uint4& hi, uint4& lo) {
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        h[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
-        const float r0 = v[2 * i] - __uint_as_float(h[i] << 16), r1 = v[2 * i + 1] - __uint_as_float(h[i] & 0xffff0000u);
-        l[i] = pack_bf16x2(r0, r1);
-    }
-    hi = make_uint4(h[0], h[1], h[2], h[3]);
-    lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
-__device__ __forceinline__ void sr_barrier() {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 __global__ void __launch_bounds__(768, 3)
 conv3_wgrad_split_ring_kernel(const float* __restrict__ x1, int C1, const float* __restrict__ x2, int C2,
                               const float* __restrict__ dy, float* __restrict__ dwp, float* __restrict__ dbias,
-                              WgradSplitRingView gv, int Cout, int nsplit, int n_ci_tiles, int64_t slab_stride) {
+                              WgradView gv, int Cout, int nsplit, int n_ci_tiles, int64_t slab_stride) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2 sets][x hi | x lo | dy hi | dy lo]
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -96,32 +46,27 @@ conv3_wgrad_split_ring_kernel(const float* __restrict__ x1, int C1, const float*
         const float* xs;
         int Cs, cbase;
         if (ci0 < C1) { xs = x1; Cs = C1; cbase = ci0; } else { xs = x2; Cs = C2; cbase = ci0 - C1; }
-        constexpr int XP = (SR_NHALO * 4 + SR_LT - 1) / SR_LT;  // pieces (halo voxel, 8 fp32 channels) per thread: 7
-        constexpr int GP = (SR_NVOX * 4) / SR_LT;                // 2
+        constexpr int XP = (SR::NHALO * 4 + SR_LT - 1) / SR_LT;  // pieces (halo voxel, 8 fp32 channels) per thread: 7
+        constexpr int GP = (SR::NVOX * 4) / SR_LT;                // 2
         int xh[XP];  // hx | hy << 8 | hz << 16 | channels exist << 30
 #pragma unroll
         for (int i = 0; i < XP; ++i) {
             const int pc = lt + i * SR_LT;
-            const int hv = min(pc >> 2, SR_NHALO - 1), q4 = pc & 3;
-            const int hx = hv / (SR_HY * SR_HZ), rem = hv - hx * (SR_HY * SR_HZ);
-            const int hy = rem / SR_HZ, hz = rem - hy * SR_HZ;
+            const int hv = min(pc >> 2, SR::NHALO - 1), q4 = pc & 3;
+            int hx, hy, hz;
+            SR::halo_coords(hv, hx, hy, hz);
             xh[i] = hx | (hy << 8) | (hz << 16) | ((cbase + q4 * 8 < Cs) ? (1 << 30) : 0);
         }
         auto stage = [&](int brick, int set) {
-            int bb = brick;
-            const int bz = bb % gv.nb[2]; bb /= gv.nb[2];
-            const int by = bb % gv.nb[1]; bb /= gv.nb[1];
-            const int bx = bb % gv.nb[0]; bb /= gv.nb[0];
+            int bx, by, bz;
+            const int bb = wgrad_brick_coords(gv, brick, bx, by, bz);
             float4 xr[XP][2], gr[GP][2];
 #pragma unroll
             for (int i = 0; i < XP; ++i) {
                 const int pc = lt + i * SR_LT;
                 xr[i][0] = xr[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (pc < SR_NHALO * 4 && ((xh[i] >> 30) & 1)) {
-                    const int sx = min(max(bx * SR_BX + (xh[i] & 0xff) - 1, 0), gv.E[0] - 1);
-                    const int sy = min(max(by * SR_BY + ((xh[i] >> 8) & 0xff) - 1, 0), gv.E[1] - 1);
-                    const int sz = min(max(bz * SR_BZ + ((xh[i] >> 16) & 0xff) - 1, 0), gv.E[2] - 1);
-                    const int64_t vox = (int64_t)bb * gv.batch + sx * gv.s[0] + sy * gv.s[1] + sz * gv.s[2];
+                if (pc < SR::NHALO * 4 && ((xh[i] >> 30) & 1)) {
+                    const int64_t vox = SR::halo_source(gv, bb, bx, by, bz, xh[i] & 0xff, (xh[i] >> 8) & 0xff, (xh[i] >> 16) & 0xff);
                     const float4* src = reinterpret_cast<const float4*>(xs + vox * Cs + cbase + (pc & 3) * 8);
                     xr[i][0] = src[0];
                     xr[i][1] = src[1];
@@ -131,40 +76,40 @@ conv3_wgrad_split_ring_kernel(const float* __restrict__ x1, int C1, const float*
             for (int i = 0; i < GP; ++i) {
                 const int pc = lt + i * SR_LT;
                 const int v = pc >> 2, q8 = pc & 3;
-                const int vx = bx * SR_BX + (v >> 6), vy = by * SR_BY + ((v >> 3) & 7), vz = bz * SR_BZ + (v & 7);
+                const int vx = bx * SR::BX + (v >> 6), vy = by * SR::BY + ((v >> 3) & 7), vz = bz * SR::BZ + (v & 7);
                 gr[i][0] = gr[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (vx < gv.E[0] && vy < gv.E[1] && vz < gv.E[2]) {
-                    const int64_t vox = (int64_t)bb * gv.batch + vx * gv.s[0] + vy * gv.s[1] + vz * gv.s[2];
+                    const int64_t vox = wgrad_voxel(gv, bb, vx, vy, vz);
                     const float4* src = reinterpret_cast<const float4*>(dy + vox * Cout + co0 + q8 * 8);
                     gr[i][0] = src[0];
                     gr[i][1] = src[1];
                 }
             }
             unsigned char* sX = smem + set * SR_SET;
-            unsigned char* sG = sX + 2 * SR_XBYTES;
+            unsigned char* sG = sX + 2 * SR::XBYTES;
 #pragma unroll
             for (int i = 0; i < XP; ++i) {
                 const int pc = lt + i * SR_LT;
-                if (pc < SR_NHALO * 4) {
+                if (pc < SR::NHALO * 4) {
                     uint4 hi, lo;
-                    sr_split8(xr[i][0], xr[i][1], hi, lo);
+                    split8(xr[i][0], xr[i][1], hi, lo);
                     *reinterpret_cast<uint4*>(sX + pc * 16) = hi;
-                    *reinterpret_cast<uint4*>(sX + SR_XBYTES + pc * 16) = lo;
+                    *reinterpret_cast<uint4*>(sX + SR::XBYTES + pc * 16) = lo;
                 }
             }
 #pragma unroll
             for (int i = 0; i < GP; ++i) {
                 const int pc = lt + i * SR_LT;
                 uint4 hi, lo;
-                sr_split8(gr[i][0], gr[i][1], hi, lo);
+                split8(gr[i][0], gr[i][1], hi, lo);
                 *reinterpret_cast<uint4*>(sG + pc * 16) = hi;
-                *reinterpret_cast<uint4*>(sG + SR_GBYTES + pc * 16) = lo;
+                *reinterpret_cast<uint4*>(sG + SR::GPLANE + pc * 16) = lo;
             }
         };
         int brick = split, it = 0;
         if (brick < nbricks) stage(brick, 0);
         for (; brick < nbricks; brick += nsplit, ++it) {
-            sr_barrier();  // brick `it` is staged, the computing waves are done with brick it - 1
+            vmem_lds_barrier();  // brick `it` is staged, the computing waves are done with brick it - 1
             if (brick + nsplit < nbricks) stage(brick + nsplit, (it + 1) & 1);
         }
         return;
@@ -176,17 +121,12 @@ conv3_wgrad_split_ring_kernel(const float* __restrict__ x1, int C1, const float*
     const int cnt = wave < 3 ? 4 : 3;
     const bool bias_slot = wave == 7;
 
-    // fragment lane geometry (tdx_conv3_wgrad_mfma.hip): a K step is 16 voxels; lane group g of 16 lanes reads voxel rows
-    // 8 kh + q and + 4, columns 16 (g & 1) + 4 p .. + 3
-    const int g = lane >> 4, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
-    const int col_off = (16 * (g & 1) + 4 * p) * 2;
-    const int kh = g >> 1;
+    const WgradLane L = wgrad_lane(lane);  // fragment lane geometry
+    const int q = L.q, kh = L.kh, col_off = L.col_off;
     int a_off[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        const int tap = min(first + t, 26);
-        const int ex = tap / 9 - 1, ey = (tap / 3) % 3 - 1, ez = tap % 3 - 1;
-        a_off[t] = ((SR_HY + kh + 1) * SR_HZ + (q + 1) + (ex * SR_HY + ey) * SR_HZ + ez) * 64 + col_off;
+        a_off[t] = wgrad_x_frag_row<SR>(L, SR::tap_offset(min(first + t, 26))) * 64 + col_off;
     }
     const int b_row = (8 * kh + q) * 64 + col_off;
 
@@ -205,19 +145,19 @@ conv3_wgrad_split_ring_kernel(const float* __restrict__ x1, int C1, const float*
         constexpr bool FOURTH = decltype(fourth_c)::value;
         int it = 0;
         for (int brick = split; brick < nbricks; brick += nsplit, ++it) {
-            sr_barrier();
+            vmem_lds_barrier();
             const unsigned char* bX = smem + (it & 1) * SR_SET;
-            const unsigned char* bG = bX + 2 * SR_XBYTES + b_row;
-            auto step_off = [&](int s) { return ((s >> 2) * SR_HY + 2 * (s & 3)) * SR_HZ * 64; };
+            const unsigned char* bG = bX + 2 * SR::XBYTES + b_row;
+            auto step_off = [&](int s) { return wgrad_x_step_offset<SR>(s); };
             auto read_a = [&](int s, int t, bf16x8& h, bf16x8& l) {
                 const unsigned char* ap = bX + a_off[t] + step_off(s);
-                h = sr_tr_frag(ap, ap + 4 * 64);
-                l = sr_tr_frag(ap + SR_XBYTES, ap + SR_XBYTES + 4 * 64);
+                h = tr_frag(ap, ap + 4 * 64);
+                l = tr_frag(ap + SR::XBYTES, ap + SR::XBYTES + 4 * 64);
             };
             auto read_b = [&](int s, bf16x8& h, bf16x8& l) {
                 const unsigned char* bp = bG + s * (16 * 64);
-                h = sr_tr_frag(bp, bp + 4 * 64);
-                l = sr_tr_frag(bp + SR_GBYTES, bp + SR_GBYTES + 4 * 64);
+                h = tr_frag(bp, bp + 4 * 64);
+                l = tr_frag(bp + SR::GPLANE, bp + SR::GPLANE + 4 * 64);
             };
             bf16x8 Ah[4], Al[4], Bh[2], Bl[2];
 #pragma unroll
@@ -258,7 +198,7 @@ conv3_wgrad_split_ring_kernel(const float* __restrict__ x1, int C1, const float*
     for (int i = 0; i < 4; ++i) {
         const int ltap = first + i;
         if (i < cnt) {
-            const int tap = (ltap / 9) * gv.ws[0] + ((ltap / 3) % 3) * gv.ws[1] + (ltap % 3) * gv.ws[2];
+            const int tap = wgrad_global_tap(gv, ltap);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int ci = ci0 + (e & 3) + 8 * (e >> 2) + 4 * hh;
@@ -282,8 +222,8 @@ int conv3_wgrad_split_ring_launch(const Conv3WgradCall& c) {
     if (!conv3_wgrad_mfma_split_supported(c.C1, c.C2, Cout)) return TDX_ESHAPE;
     const int Cin = c.C1 + c.C2;
     // local axes: brick 2 x 8 x 8; the short axis goes where it leaves the fewest bricks
-    WgradSplitRingView g;
-    const int nbricks = conv3_wgrad_view(g, c, SR_BX, SR_BY, SR_BZ);
+    WgradView g;
+    const int nbricks = conv3_wgrad_view(g, c, SR::BX, SR::BY, SR::BZ);
     const int n_ci = (Cin + 31) / 32, n_co = Cout / 32;
     const int ntiles = n_ci * n_co;
     const int cus = tdx_persistent_cus();

@@ -17,12 +17,7 @@
 // with (o + pad - t dil) divisible by s along every axis.  Workgroups therefore own voxels of ONE residue class o mod s, the
 // divisibility test is uniform per workgroup and the dead taps (7 of 8 at stride 2) are skipped, not masked.
 #include "tdx_common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+#include "tdx_mfma.h"
 
 struct ConvGM {
     int B;
@@ -337,13 +332,6 @@ int convg_mfma_apply_epilogue(const void* in, const float* w, const float* bias,
 // Partial tiles are merged with fp32 atomics; dW / dbias must be zero on entry.
 #define CGW_PLANE (CGM_ROWS * 64)  // one [256 voxels][32 channels] bf16 plane
 
-__device__ __forceinline__ bf16x8 cgm_tr_frag(const unsigned char* lo, const unsigned char* hi) {
-    s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lo));
-    s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(hi));
-    s16x8 rr = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, rr);
-}
-
 __global__ void __launch_bounds__(256, 2)
 convg_wgrad_mfma_kernel(const bf16* __restrict__ in, const bf16* __restrict__ dy, float* __restrict__ dw, float* __restrict__ dbias,
                         ConvGM g, int nsplit, int n_ci_tiles) {
@@ -416,9 +404,9 @@ convg_wgrad_mfma_kernel(const bf16* __restrict__ in, const bf16* __restrict__ dy
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
                 const unsigned char* ap = sX + m * CGW_PLANE + row * 64 + col_off;
-                af[m] = cgm_tr_frag(ap, ap + 4 * 64);
+                af[m] = tr_frag(ap, ap + 4 * 64);
                 const unsigned char* bp = sG + m * CGW_PLANE + row * 64 + col_off;
-                bfv[m] = cgm_tr_frag(bp, bp + 4 * 64);
+                bfv[m] = tr_frag(bp, bp + 4 * 64);
             }
 #pragma unroll
             for (int m = 0; m < 2; ++m)

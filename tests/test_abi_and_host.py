@@ -549,3 +549,29 @@ def test_conv3_routing_is_pinned(monkeypatch):
     finally:
         lib.tdx_set_scratch(None, 0)
         L._ACTIVE = None  # a later GPU test in this process binds its real arena again
+
+
+def test_kernel_asm_diff_splits_assembly_per_kernel():
+    """tools/kernel_asm_diff.py: body (label .. .size) and descriptor per .amdhsa_kernel name, __hip_cuid_ normalised,
+    --rename applied to the old side's mangled names.  Synthetic assembly: the tool itself needs hipcc, not a GPU."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("kernel_asm_diff", ROOT / "tools" / "kernel_asm_diff.py")
+    kad = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kad)
+
+    def asm(view, cuid, extra=""):
+        k = f"_Z1kPf{len(view)}{view}i"
+        return (f"\t.globl\t{k}\n{k}:\n\ts_load_dword s0, s[4:5], 0x0\n{extra}\ts_endpgm\n.Lfunc_end0:\n\t.size\t{k}, .Lfunc_end0-{k}\n"
+                f"\t.amdhsa_kernel {k}\n\t\t.amdhsa_next_free_vgpr 4\n\t.end_amdhsa_kernel\n"
+                f"\t.globl\t__hip_cuid_{cuid}\n__hip_cuid_{cuid}:\n")
+
+    old = kad.kernels(asm("WgradViewS", "0123abcd"), [("10WgradViewS", "9WgradView")])
+    new = kad.kernels(asm("WgradView", "89ef4567"), [])
+    assert list(old) == list(new) == ["_Z1kPf9WgradViewi"]
+    assert old == new
+    body, desc = new["_Z1kPf9WgradViewi"]
+    assert body.startswith("_Z1kPf9WgradViewi:\n") and body.rstrip().endswith(".Lfunc_end0-_Z1kPf9WgradViewi")
+    assert ".amdhsa_next_free_vgpr 4" in desc and "hip_cuid" not in body
+    assert kad.kernels(asm("WgradView", "89ef4567", "\ts_nop 0\n"), []) != new
+    assert list(kad.kernels(asm("WgradViewS", "0123abcd"), [])) == ["_Z1kPf10WgradViewSi"]  # unrenamed: lost + added

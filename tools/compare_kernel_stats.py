@@ -3,7 +3,7 @@
     python tools/compare_kernel_stats.py A.csv B.csv --steps 6 --scale-a 485000 --scale-b 589824 --labels real bench
 --scale-*: work units (voxels, or batch) of each run: the last columns give B's time per unit over A's and, with
 --fit Ba Bb (batch sizes), the batch-independent part f of a two-point fit t = f + s B."""
-import argparse, csv
+import argparse, csv, re
 
 ap = argparse.ArgumentParser()
 ap.add_argument("a"); ap.add_argument("b")
@@ -15,8 +15,14 @@ ap.add_argument("--top", type=int, default=60)
 a = ap.parse_args()
 
 
+# kernels pair up by their full name, which spells out parameter types: the four per-kernel copies of the weight-gradient
+# view struct became one WgradView (csrc/tdx_conv3_wgrad.h), so traces from before that read as traces from after it
+OLD_VIEWS = re.compile(r"\bWgrad(ViewS|ViewF|RingView|SplitRingView)\b")
+
+
 def load(f):
-    return {r["Name"]: (int(r["Calls"]) / a.steps, float(r["TotalDurationNs"]) / 1e6 / a.steps) for r in csv.DictReader(open(f))}
+    return {OLD_VIEWS.sub("WgradView", r["Name"]): (int(r["Calls"]) / a.steps, float(r["TotalDurationNs"]) / 1e6 / a.steps)
+            for r in csv.DictReader(open(f))}
 
 
 A, B = load(a.a), load(a.b)
