@@ -54,6 +54,143 @@ def _grid(x: torch.Tensor):
     return x.shape[0], x.shape[1], x.shape[2], x.shape[3], x.shape[4]
 
 
+# --------------------------------------------------------------------------- launches
+#
+# One function per kernel entry that has more than one user: it owns the entry's argument list, the allocation of its
+# outputs, its workspace (size query, plain or TDX_WS_CLEAN, tag) and its figures for the timers, and returns the
+# outputs.  Tensors arrive contiguous; sizes, the dtype code and the stream arrive as plain values, because the hot
+# nodes launch a dozen kernels on the same ones and reading them off a tensor again costs the host a microsecond each.
+# A workspace that several launches of one node share is made once by the node (`_gn_ws`, `_conv3_bwd_data_ws`,
+# `_conv3_wgrad_ws`) and passed in as `ws`.
+
+
+def _to_nvc(x, dtype):
+    B, Cc, X, Y, Z = x.shape
+    y = torch.empty((B, X, Y, Z, Cc), dtype=dtype, device=x.device)
+    L.call("tdx_ncv_to_nvc", L.ptr(x), L.ptr(y), B, Cc, X * Y * Z, L.dtype_code(x.dtype), L.dtype_code(dtype), L.stream())
+    return y
+
+
+def _to_ncv(x, dtype):
+    B, X, Y, Z, Cc = x.shape
+    y = torch.empty((B, Cc, X, Y, Z), dtype=dtype, device=x.device)
+    L.call("tdx_nvc_to_ncv", L.ptr(x), L.ptr(y), B, Cc, X * Y * Z, L.dtype_code(x.dtype), L.dtype_code(dtype), L.stream())
+    return y
+
+
+def _gn_ws(B, Cc, dev, clean=False):
+    """Workspace of the GroupNorm statistics: `clean` for the entries that take TDX_WS_CLEAN (the conv epilogues)."""
+    nbytes = L.query("tdx_gn_workspace_bytes", B, Cc)
+    return _clean_ws(nbytes, dev) if clean else _ws(nbytes, dev)
+
+
+def _conv3_fwd(x1, C1, x2, C2, wf, bias, grid, Cout, code, impl, st, gn=None, ws=None, real=None, timed=True):
+    """y = conv3([x1 | x2]) on grid = (B, X, Y, Z) from the packed forward operand `wf`; gn = (groups, eps): (y, GroupNorm
+    statistics of y).  `real`: input channels that carry data (the composed first conv runs on zero-padded raw
+    channels; the timers' figures count the algorithmic channels only)."""
+    B, X, Y, Z = grid
+    y = x1.new_empty((B, X, Y, Z, Cout))
+    work = 54.0 * (real or (C1 + C2)) * Cout * B * X * Y * Z if timed else 0.0
+    meta = (lambda: L.conv3_fwd_meta(C1, C2, Cout, B, X, Y, Z, x1.dtype, real)) if timed else None  # queried under a timer only
+    if gn is None:
+        L.call("tdx_conv3_fwd", L.ptr(x1), C1, L.ptr(x2), C2, L.ptr(wf), L.ptr(bias), L.ptr(y), B, X, Y, Z, Cout, code, impl, st,
+               work=work, meta=meta)
+        return y
+    groups, eps = gn
+    stats = x1.new_empty((B, groups, 2), dtype=torch.float32)
+    if ws is None:
+        ws = _gn_ws(B, Cout, x1.device, clean=True)
+    L.call("tdx_conv3_fwd_gn", L.ptr(x1), C1, L.ptr(x2), C2, L.ptr(wf), L.ptr(bias), L.ptr(y), L.ptr(stats), groups, float(eps),
+           L.ptr(ws), B, X, Y, Z, Cout, code, impl | WS_CLEAN, st, work=work, meta=meta)
+    return y, stats
+
+
+def _conv3_bwd_data_ws(grid, Cin, code, impl, dev):
+    return _ws(L.query("tdx_conv3_bwd_data_workspace_bytes", *grid, Cin, code, impl), dev)
+
+
+def _conv3_bwd_data(gy, wb, x1, C1, x2, C2, grid, Cout, code, impl, st, ws=None, add=None, real=None):
+    """(gx1, gx2): the data gradient of conv3([x1 | x2]) from the packed backward operand `wb`, shaped like x1 and x2
+    (which are not read); `add` is added to gx1 in the kernel's epilogue (tdx_conv3_bwd_data_add)."""
+    B, X, Y, Z = grid
+    gx1, gx2 = torch.empty_like(x1), None if x2 is None else torch.empty_like(x2)
+    if ws is None:
+        ws = _conv3_bwd_data_ws(grid, C1 + C2, code, impl, gy.device)
+    work = 54.0 * (real or (C1 + C2)) * Cout * B * X * Y * Z
+    if add is None:
+        L.call("tdx_conv3_bwd_data", L.ptr(gy), L.ptr(wb), L.ptr(gx1), C1, L.ptr(gx2), C2, 0, B, X, Y, Z, Cout, code, impl,
+               L.ptr(ws), st, work=work)
+    else:
+        L.call("tdx_conv3_bwd_data_add", L.ptr(gy), L.ptr(wb), L.ptr(gx1), C1, L.ptr(gx2), C2, L.ptr(add), None, B, X, Y, Z,
+               Cout, code, impl, L.ptr(ws), st, work=work)
+    return gx1, gx2
+
+
+def _conv3_wgrad_out(wshape, has_bias, dev):
+    return (torch.empty(wshape, dtype=torch.float32, device=dev),
+            torch.empty(wshape[0], dtype=torch.float32, device=dev) if has_bias else None)
+
+
+def _conv3_wgrad_ws(Cin, Cout, impl, dev):
+    # one workspace per (Cin, Cout): the accumulator / slab layout inside depends on both
+    return _clean_ws(L.query("tdx_conv3_bwd_weight_workspace_bytes", Cin, Cout, impl), dev, ("w3", Cin, Cout))
+
+
+def _conv3_wgrad(x1, C1, x2, C2, gy, gw, gb, grid, Cout, code, impl, ws, st, real=None):
+    """gw, gb (None: no bias) = weight and bias gradient of conv3([x1 | x2]).  The launch alone: a fused block runs it on
+    the side stream (`_WgradSide.run`; `st` is then that stream), and the outputs (`_conv3_wgrad_out`) and the workspace
+    (`_conv3_wgrad_ws`) must come from the launching stream's allocator pool, so the node makes them before it switches."""
+    B, X, Y, Z = grid
+    L.call("tdx_conv3_bwd_weight", L.ptr(x1), C1, L.ptr(x2), C2, L.ptr(gy), L.ptr(gw), L.ptr(gb), B, X, Y, Z, Cout, code,
+           impl | WS_CLEAN, L.ptr(ws), st, work=54.0 * (real or (C1 + C2)) * Cout * B * X * Y * Z)
+
+
+def _conv1_fwd(x1, C1, x2, C2, w, ldw, col, bias, add, lead, rows, Cout, code, st):
+    """y = [x1 | x2] @ W (+ bias) (+ add) over the leading dimensions `lead` (`rows` voxels); W = the (C1 + C2, Cout) block that starts at
+    column `col` of the row-major f32 matrix `w` with rows of `ldw`: all of a transposed weight ([Cin][Cout], `_conv1_wt`)
+    in a forward, columns [col, col + Cout) of a (Cout', Cin') weight in the data gradient of a 1x1 conv."""
+    y = x1.new_empty((*lead, Cout))
+    L.call("tdx_conv1_fwd", L.ptr(x1), C1, L.ptr(x2), C2, L.ptr(w) + 4 * col, ldw, L.ptr(bias), L.ptr(add), L.ptr(y), rows, Cout,
+           code, st)
+    return y
+
+
+def _gn_apply(x, stats, gamma, beta, scale, shift, res, B, V, Cc, groups, act, code, st):
+    """y = [silu]( GN(x; stats) * (1 + scale) + shift ) + res; scale / shift (B, C) f32, and res, may be None."""
+    y = torch.empty_like(x)
+    L.call("tdx_gn_apply", L.ptr(x), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(scale), L.ptr(shift), L.ptr(res), L.ptr(y),
+           B, V, Cc, groups, act, code, st)
+    return y
+
+
+def _gn_bwd(x, gy, stats, gamma, beta, scale, shift, dscale, dshift, B, V, Cc, groups, act, code, st, ws=None):
+    """(gx, dgamma, dbeta) of `_gn_apply`; dscale / dshift are written too where scale / shift were given (the caller
+    allocates them: two tensors for gn_film_silu, the halves of one (2, B, C) tensor for a fused block)."""
+    gx, dgamma, dbeta = torch.empty_like(x), stats.new_empty(Cc), stats.new_empty(Cc)
+    if ws is None:
+        ws = _gn_ws(B, Cc, x.device)
+    L.call("tdx_gn_bwd", L.ptr(x), L.ptr(gy), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(scale), L.ptr(shift), L.ptr(gx),
+           L.ptr(dgamma), L.ptr(dbeta), L.ptr(dscale), L.ptr(dshift), B, V, Cc, groups, act, code, L.ptr(ws), st)
+    return gx, dgamma, dbeta
+
+
+def _resize_fwd(x, size):
+    """(x resampled to grid `size`, the geometry that `_resize_bwd` takes)."""
+    B, Xi, Yi, Zi, Cc = _grid(x)
+    Xo, Yo, Zo = (int(s) for s in size)
+    y = torch.empty((B, Xo, Yo, Zo, Cc), dtype=x.dtype, device=x.device)
+    L.call("tdx_resize_fwd", L.ptr(x), L.ptr(y), B, Xi, Yi, Zi, Xo, Yo, Zo, Cc, L.dtype_code(x.dtype), L.stream())
+    return y, (B, Xi, Yi, Zi, Xo, Yo, Zo, Cc)
+
+
+def _resize_bwd(gy, add, geom):
+    """The adjoint of `_resize_fwd` (+ add, a gradient that arrives at the resize's input by another path)."""
+    B, Xi, Yi, Zi, Xo, Yo, Zo, Cc = geom
+    gx = torch.empty((B, Xi, Yi, Zi, Cc), dtype=gy.dtype, device=gy.device)
+    L.call("tdx_resize_bwd", L.ptr(gy), L.ptr(add), L.ptr(gx), B, Xi, Yi, Zi, Xo, Yo, Zo, Cc, L.dtype_code(gy.dtype), L.stream())
+    return gx
+
+
 # --------------------------------------------------------------------------- layout
 
 
@@ -62,21 +199,13 @@ class _ToNVC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, dtype):
-        B, Cc, X, Y, Z = x.shape
-        x = x.contiguous()
-        y = torch.empty((B, X, Y, Z, Cc), dtype=dtype, device=x.device)
-        L.call("tdx_ncv_to_nvc", L.ptr(x), L.ptr(y), B, Cc, X * Y * Z, L.dtype_code(x.dtype), L.dtype_code(dtype), L.stream())
         ctx.in_dtype = x.dtype
-        return y
+        return _to_nvc(x.contiguous(), dtype)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        B, X, Y, Z, Cc = gy.shape
-        gy = gy.contiguous()
-        gx = torch.empty((B, Cc, X, Y, Z), dtype=ctx.in_dtype, device=gy.device)
-        L.call("tdx_nvc_to_ncv", L.ptr(gy), L.ptr(gx), B, Cc, X * Y * Z, L.dtype_code(gy.dtype), L.dtype_code(ctx.in_dtype), L.stream())
-        return gx, None
+        return _to_ncv(gy.contiguous(), ctx.in_dtype), None
 
 
 class _ToNCV(torch.autograd.Function):
@@ -84,21 +213,13 @@ class _ToNCV(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, dtype):
-        B, X, Y, Z, Cc = x.shape
-        x = x.contiguous()
-        y = torch.empty((B, Cc, X, Y, Z), dtype=dtype, device=x.device)
-        L.call("tdx_nvc_to_ncv", L.ptr(x), L.ptr(y), B, Cc, X * Y * Z, L.dtype_code(x.dtype), L.dtype_code(dtype), L.stream())
         ctx.in_dtype = x.dtype
-        return y
+        return _to_ncv(x.contiguous(), dtype)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        B, Cc, X, Y, Z = gy.shape
-        gy = gy.contiguous()
-        gx = torch.empty((B, X, Y, Z, Cc), dtype=ctx.in_dtype, device=gy.device)
-        L.call("tdx_ncv_to_nvc", L.ptr(gy), L.ptr(gx), B, Cc, X * Y * Z, L.dtype_code(gy.dtype), L.dtype_code(ctx.in_dtype), L.stream())
-        return gx, None
+        return _to_nvc(gy.contiguous(), ctx.in_dtype), None
 
 
 def to_nvc(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
@@ -243,12 +364,24 @@ def decode_fused_supported(C: int, w) -> bool:
 _pack_cache: dict = {}
 
 
-def _packed_conv3(weight: torch.Tensor, dtype: torch.dtype):
-    code = L.pack_code(dtype)
-    key = (id(weight), dtype, code)
+def _cached(key, weight):
+    """(a, b) stored under `key` for this very parameter -- same object, version and address -- or None."""
     hit = _pack_cache.get(key)
     if hit is not None and hit[0]() is weight and hit[1] == weight._version and hit[2] == weight.data_ptr():
         return hit[3], hit[4]
+    return None
+
+
+def _cache_store(key, weight, a, b=None):
+    _pack_cache[key] = (weakref.ref(weight), weight._version, weight.data_ptr(), a, b)
+
+
+def _packed_conv3(weight: torch.Tensor, dtype: torch.dtype):
+    code = L.pack_code(dtype)
+    key = (id(weight), dtype, code)
+    hit = _cached(key, weight)
+    if hit is not None:
+        return hit
     Cout, Cin = weight.shape[0], weight.shape[1]
     w = weight.detach().contiguous()
     wf = torch.empty(27 * Cin * Cout, dtype=dtype, device=w.device)
@@ -256,7 +389,7 @@ def _packed_conv3(weight: torch.Tensor, dtype: torch.dtype):
     L.call("tdx_conv3_pack_weight", L.ptr(w), L.ptr(wf), L.ptr(wb), Cin, Cout, code, L.stream())
     if len(_pack_cache) > 4096:
         _pack_cache.clear()
-    _pack_cache[key] = (weakref.ref(weight), weight._version, weight.data_ptr(), wf, wb)
+    _cache_store(key, weight, wf, wb)
     return wf, wb
 
 
@@ -265,20 +398,15 @@ def _packed_conv3_cin_slice(weight: torch.Tensor, lo: int, hi: int, dtype: torch
     _packed_conv3 (keyed on the full parameter's version)."""
     code = L.pack_code(dtype)
     key = (id(weight), dtype, lo, hi, code)
-    hit = _pack_cache.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version and hit[2] == weight.data_ptr():
-        return hit[3]
+    hit = _cached(key, weight)
+    if hit is not None:
+        return hit[0]
     Cout, Cin = weight.shape[0], hi - lo
     w = weight.detach()[:, lo:hi].contiguous()
     wf = torch.empty(27 * Cin * Cout, dtype=dtype, device=w.device)
     L.call("tdx_conv3_pack_weight", L.ptr(w), L.ptr(wf), None, Cin, Cout, code, L.stream())
-    _pack_cache[key] = (weakref.ref(weight), weight._version, weight.data_ptr(), wf, None)
+    _cache_store(key, weight, wf)
     return wf
-
-
-def _cache_fresh(key, weight) -> bool:
-    hit = _pack_cache.get(key)
-    return hit is not None and hit[0]() is weight and hit[1] == weight._version and hit[2] == weight.data_ptr()
 
 
 class PackPlan:
@@ -311,16 +439,18 @@ class PackPlan:
                 and all(a is b for a, b in zip(ws, self.w3 + self.w1)) and all(w.data_ptr() == p for w, p in zip(ws, self.ptrs)))
 
     def refresh(self) -> None:
+        # stale = the plan's OWN buffers are behind the weight (`seen`), whatever the shared cache holds: a new plan's first
+        # refresh always launches and moves the cache entries onto its buffers (a captured step must contain that launch)
         if self.w3 and any(w._version != v for w, v in zip(self.w3, self.seen3)):
             L.call("tdx_conv3_pack_weights", self.tab3, len(self.w3), self.code, L.stream())
             for i, (w, (wf, wb)) in enumerate(zip(self.w3, self.ops3)):
                 self.seen3[i] = w._version
-                _pack_cache[(id(w), self.dtype, self.code)] = (weakref.ref(w), w._version, w.data_ptr(), wf, wb)
+                _cache_store((id(w), self.dtype, self.code), w, wf, wb)  # _packed_conv3's key
         if self.w1 and any(w._version != v for w, v in zip(self.w1, self.seen1)):
             L.call("tdx_transpose_many", self.tab1, len(self.w1), L.stream())
             for i, (w, wt) in enumerate(zip(self.w1, self.ops1)):
                 self.seen1[i] = w._version
-                _pack_cache[(id(w), "wt")] = (weakref.ref(w), w._version, w.data_ptr(), wt, None)
+                _cache_store((id(w), "wt"), w, wt)  # _conv1_wt's key
 
 
 def prefetch_weights(conv3_weights, conv1_weights, dtype: torch.dtype, plan: "PackPlan | None" = None) -> "PackPlan | None":
@@ -350,10 +480,8 @@ def conv3_shared_tail(e, weight, n_lead: int):
     B, X, Y, Z, Ce = _grid(e)
     assert B == 1 and Ce == Cin - n_lead
     wf = _packed_conv3_cin_slice(weight, n_lead, Cin, e.dtype)
-    y = torch.empty((1, X, Y, Z, weight.shape[0]), dtype=e.dtype, device=e.device)
-    L.call("tdx_conv3_fwd", L.ptr(e.contiguous()), Ce, None, 0, L.ptr(wf), None, L.ptr(y), 1, X, Y, Z, weight.shape[0],
-           L.dtype_code(e.dtype), L.conv_impl(), L.stream())
-    return y
+    return _conv3_fwd(e.contiguous(), Ce, None, 0, wf, None, (1, X, Y, Z), weight.shape[0], L.dtype_code(e.dtype), L.conv_impl(),
+                      L.stream(), timed=False)  # (once per sampling run: not in the timers' conv figures)
 
 
 class _Conv3(torch.autograd.Function):
@@ -365,26 +493,16 @@ class _Conv3(torch.autograd.Function):
         assert weight.shape[1] == C1 + C2 and tuple(weight.shape[2:]) == (3, 3, 3)
         x1 = x1.contiguous()
         x2 = None if x2 is None else x2.contiguous()
-        dt = x1.dtype
-        wf, wb = _packed_conv3(weight, dt)
-        y = torch.empty((B, X, Y, Z, Cout), dtype=dt, device=x1.device)
-        flops = 54.0 * (C1 + C2) * Cout * B * X * Y * Z
+        wf, wb = _packed_conv3(weight, x1.dtype)
         ctx.save_for_backward(x1, x2, wb)
         ctx.has_bias = bias is not None
         ctx.wshape = tuple(weight.shape)
         impl = ctx.impl = L.conv_impl()  # the backward runs outside the model's conv_impl_scope: it reuses this
+        out = _conv3_fwd(x1, C1, x2, C2, wf, bias, (B, X, Y, Z), Cout, L.dtype_code(x1.dtype), impl, L.stream(),
+                         gn=(gn_groups, gn_eps) if gn_groups else None)
         if gn_groups:
-            stats = torch.empty((B, gn_groups, 2), dtype=torch.float32, device=x1.device)
-            ws = _clean_ws(L.query("tdx_gn_workspace_bytes", B, Cout), x1.device)
-            L.call("tdx_conv3_fwd_gn", L.ptr(x1), C1, L.ptr(x2), C2, L.ptr(wf), L.ptr(bias), L.ptr(y), L.ptr(stats),
-                   gn_groups, float(gn_eps), L.ptr(ws), B, X, Y, Z, Cout, L.dtype_code(dt), impl | WS_CLEAN,
-                   L.stream(), work=flops, meta=lambda: L.conv3_fwd_meta(C1, C2, Cout, B, X, Y, Z, dt))
-            ctx.mark_non_differentiable(stats)
-            return y, stats
-        L.call("tdx_conv3_fwd", L.ptr(x1), C1, L.ptr(x2), C2, L.ptr(wf), L.ptr(bias), L.ptr(y), B, X, Y, Z, Cout,
-               L.dtype_code(dt), impl, L.stream(), work=flops,
-               meta=lambda: L.conv3_fwd_meta(C1, C2, Cout, B, X, Y, Z, dt))
-        return y
+            ctx.mark_non_differentiable(out[1])
+        return out
 
     @staticmethod
     @once_differentiable
@@ -394,21 +512,13 @@ class _Conv3(torch.autograd.Function):
         C2 = 0 if x2 is None else x2.shape[-1]
         Cout, Cin = ctx.wshape[0], ctx.wshape[1]
         gy = gy.contiguous()
-        dt, dev = gy.dtype, gy.device
-        code, impl, st = L.dtype_code(dt), ctx.impl, L.stream()
+        grid, code, impl, st, dev = (B, X, Y, Z), L.dtype_code(gy.dtype), ctx.impl, L.stream(), gy.device
         gx1 = gx2 = gw = gb = None
         if ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[1]):
-            gx1 = torch.empty_like(x1)
-            gx2 = None if x2 is None else torch.empty_like(x2)
-            ws = _ws(L.query("tdx_conv3_bwd_data_workspace_bytes", B, X, Y, Z, Cin, code, impl), dev)
-            L.call("tdx_conv3_bwd_data", L.ptr(gy), L.ptr(wb), L.ptr(gx1), C1, L.ptr(gx2), C2, 0, B, X, Y, Z, Cout,
-                   code, impl, L.ptr(ws), st, work=54.0 * Cin * Cout * B * X * Y * Z)
+            gx1, gx2 = _conv3_bwd_data(gy, wb, x1, C1, x2, C2, grid, Cout, code, impl, st)
         if ctx.needs_input_grad[2]:
-            gw = torch.empty(ctx.wshape, dtype=torch.float32, device=dev)
-            gb = torch.empty(Cout, dtype=torch.float32, device=dev) if ctx.has_bias else None
-            ws = _clean_ws(L.query("tdx_conv3_bwd_weight_workspace_bytes", Cin, Cout, impl), dev, ("w3", Cin, Cout))
-            L.call("tdx_conv3_bwd_weight", L.ptr(x1), C1, L.ptr(x2), C2, L.ptr(gy), L.ptr(gw), L.ptr(gb), B, X, Y, Z,
-                   Cout, code, impl | WS_CLEAN, L.ptr(ws), st, work=54.0 * Cin * Cout * B * X * Y * Z)
+            gw, gb = _conv3_wgrad_out(ctx.wshape, ctx.has_bias, dev)
+            _conv3_wgrad(x1, C1, x2, C2, gy, gw, gb, grid, Cout, code, impl, _conv3_wgrad_ws(Cin, Cout, impl, dev), st)
         return gx1, gx2, gw, gb, None, None
 
 
@@ -430,11 +540,11 @@ def _conv1_wt(weight: torch.Tensor) -> torch.Tensor:
     """[Cin][Cout] f32 copy of a 1x1 conv weight (the layout tdx_conv1_fwd reads), cached until the
     parameter changes (Tensor._version) instead of being re-transposed on every call."""
     key = (id(weight), "wt")
-    hit = _pack_cache.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version and hit[2] == weight.data_ptr():
-        return hit[3]
+    hit = _cached(key, weight)
+    if hit is not None:
+        return hit[0]
     wt = weight.detach().reshape(weight.shape[0], -1).t().contiguous()
-    _pack_cache[key] = (weakref.ref(weight), weight._version, weight.data_ptr(), wt, None)
+    _cache_store(key, weight, wt)
     return wt
 
 
@@ -463,11 +573,9 @@ class _Conv1(torch.autograd.Function):
         x1 = x1.contiguous()
         x2 = None if x2 is None else x2.contiguous()
         add = None if add is None else add.contiguous()
-        rows = x1.numel() // C1
-        wt = _conv1_wt(weight)  # [Cin][Cout]
-        y = torch.empty(x1.shape[:-1] + (Cout,), dtype=x1.dtype, device=x1.device)
-        L.call("tdx_conv1_fwd", L.ptr(x1), C1, L.ptr(x2), C2, L.ptr(wt), Cout, L.ptr(bias), L.ptr(add), L.ptr(y), rows,
-               Cout, L.dtype_code(x1.dtype), L.stream())
+        lead = tuple(x1.shape[:-1])
+        y = _conv1_fwd(x1, C1, x2, C2, _conv1_wt(weight), Cout, 0, bias, add, lead, x1.numel() // C1, Cout,
+                       L.dtype_code(x1.dtype), L.stream())
         ctx.save_for_backward(x1, x2, w2.contiguous())
         ctx.has_bias = bias is not None
         ctx.has_add = add is not None
@@ -482,15 +590,13 @@ class _Conv1(torch.autograd.Function):
         C2 = 0 if x2 is None else x2.shape[-1]
         Cout, Cin = w2.shape
         gy = gy.contiguous()
-        rows = gy.numel() // Cout
-        code, st, dev = L.dtype_code(gy.dtype), L.stream(), gy.device
+        lead, rows = tuple(gy.shape[:-1]), gy.numel() // Cout
+        code, st = L.dtype_code(gy.dtype), L.stream()
         gx1 = gx2 = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx1 = torch.empty_like(x1)
-            L.call("tdx_conv1_fwd", L.ptr(gy), Cout, None, 0, w2.data_ptr(), Cin, None, None, L.ptr(gx1), rows, C1, code, st)
-        if x2 is not None and ctx.needs_input_grad[1]:
-            gx2 = torch.empty_like(x2)
-            L.call("tdx_conv1_fwd", L.ptr(gy), Cout, None, 0, w2.data_ptr() + 4 * C1, Cin, None, None, L.ptr(gx2), rows, C2, code, st)
+        if ctx.needs_input_grad[0]:  # gy @ w2[:, :C1]
+            gx1 = _conv1_fwd(gy, Cout, None, 0, w2, Cin, 0, None, None, lead, rows, C1, code, st)
+        if x2 is not None and ctx.needs_input_grad[1]:  # gy @ w2[:, C1:]
+            gx2 = _conv1_fwd(gy, Cout, None, 0, w2, Cin, C1, None, None, lead, rows, C2, code, st)
         if ctx.needs_input_grad[2]:
             gw, gb = _conv1_weight_grad(x1, C1, x2, C2, gy, Cout, ctx.has_bias, rows, code, st)
             gw = gw.view(ctx.wshape)
@@ -512,18 +618,15 @@ class _GnFilmSilu(torch.autograd.Function):
         V = X * Y * Z
         x = x.contiguous()
         res = None if res is None else res.contiguous()
-        dev, code, st = x.device, L.dtype_code(x.dtype), L.stream()
+        code, st = L.dtype_code(x.dtype), L.stream()
         gamma, beta = gamma.detach().contiguous(), beta.detach().contiguous()
         if scale is not None:
             scale = scale.detach().reshape(B, Cc).float().contiguous()
             shift = shift.detach().reshape(B, Cc).float().contiguous()
         if stats is None:
-            stats = torch.empty((B, groups, 2), dtype=torch.float32, device=dev)
-            ws = _ws(L.query("tdx_gn_workspace_bytes", B, Cc), dev)
-            L.call("tdx_gn_stats", L.ptr(x), L.ptr(stats), B, V, Cc, groups, float(eps), code, L.ptr(ws), st)
-        y = torch.empty_like(x)
-        L.call("tdx_gn_apply", L.ptr(x), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(scale), L.ptr(shift), L.ptr(res),
-               L.ptr(y), B, V, Cc, groups, int(act), code, st)
+            stats = torch.empty((B, groups, 2), dtype=torch.float32, device=x.device)
+            L.call("tdx_gn_stats", L.ptr(x), L.ptr(stats), B, V, Cc, groups, float(eps), code, L.ptr(_gn_ws(B, Cc, x.device)), st)
+        y = _gn_apply(x, stats, gamma, beta, scale, shift, res, B, V, Cc, groups, int(act), code, st)
         ctx.save_for_backward(x, stats, gamma, beta, scale, shift)
         ctx.cfg = (groups, int(act), res is not None)
         return y
@@ -534,20 +637,12 @@ class _GnFilmSilu(torch.autograd.Function):
         x, stats, gamma, beta, scale, shift = ctx.saved_tensors
         groups, act, has_res = ctx.cfg
         B, X, Y, Z, Cc = _grid(x)
-        V = X * Y * Z
         gy = gy.contiguous()
-        dev, code, st = x.device, L.dtype_code(x.dtype), L.stream()
-        gx = torch.empty_like(x)
-        dgamma = torch.empty(Cc, dtype=torch.float32, device=dev)
-        dbeta = torch.empty(Cc, dtype=torch.float32, device=dev)
         dscale = dshift = None
         if scale is not None:
-            dscale = torch.empty((B, Cc), dtype=torch.float32, device=dev)
-            dshift = torch.empty((B, Cc), dtype=torch.float32, device=dev)
-        ws = _ws(L.query("tdx_gn_workspace_bytes", B, Cc), dev)
-        L.call("tdx_gn_bwd", L.ptr(x), L.ptr(gy), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(scale), L.ptr(shift),
-               L.ptr(gx), L.ptr(dgamma), L.ptr(dbeta), L.ptr(dscale), L.ptr(dshift), B, V, Cc, groups, act, code,
-               L.ptr(ws), st)
+            dscale, dshift = torch.empty_like(scale), torch.empty_like(shift)
+        gx, dgamma, dbeta = _gn_bwd(x, gy, stats, gamma, beta, scale, shift, dscale, dshift, B, X * Y * Z, Cc, groups, act,
+                                    L.dtype_code(x.dtype), L.stream())
         return gx, dgamma, dbeta, dscale, dshift, (gy if has_res else None), None, None, None, None
 
 
@@ -563,22 +658,13 @@ def gn_film_silu(x, gamma, beta, groups, scale=None, shift=None, res=None, act=T
 class _Resize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, size):
-        B, Xi, Yi, Zi, Cc = _grid(x)
-        Xo, Yo, Zo = (int(s) for s in size)
-        x = x.contiguous()
-        y = torch.empty((B, Xo, Yo, Zo, Cc), dtype=x.dtype, device=x.device)
-        L.call("tdx_resize_fwd", L.ptr(x), L.ptr(y), B, Xi, Yi, Zi, Xo, Yo, Zo, Cc, L.dtype_code(x.dtype), L.stream())
-        ctx.geom = (B, Xi, Yi, Zi, Xo, Yo, Zo, Cc)
+        y, ctx.geom = _resize_fwd(x.contiguous(), size)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        B, Xi, Yi, Zi, Xo, Yo, Zo, Cc = ctx.geom
-        gy = gy.contiguous()
-        gx = torch.empty((B, Xi, Yi, Zi, Cc), dtype=gy.dtype, device=gy.device)
-        L.call("tdx_resize_bwd", L.ptr(gy), None, L.ptr(gx), B, Xi, Yi, Zi, Xo, Yo, Zo, Cc, L.dtype_code(gy.dtype), L.stream())
-        return gx, None
+        return _resize_bwd(gy.contiguous(), None, ctx.geom), None
 
 
 def resize(x, size):
@@ -593,27 +679,17 @@ class _SkipAndResize(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, size):
-        B, Xi, Yi, Zi, Cc = _grid(x)
-        Xo, Yo, Zo = (int(s) for s in size)
         x = x.contiguous()
-        y = torch.empty((B, Xo, Yo, Zo, Cc), dtype=x.dtype, device=x.device)
-        L.call("tdx_resize_fwd", L.ptr(x), L.ptr(y), B, Xi, Yi, Zi, Xo, Yo, Zo, Cc, L.dtype_code(x.dtype), L.stream())
-        ctx.geom = (B, Xi, Yi, Zi, Xo, Yo, Zo, Cc)
+        y, ctx.geom = _resize_fwd(x, size)
         ctx.set_materialize_grads(False)  # an unused output arrives as None, not as a zero tensor
         return x.view_as(x), y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_skip, gy):
-        B, Xi, Yi, Zi, Xo, Yo, Zo, Cc = ctx.geom
         if gy is None:
             return g_skip, None
-        gy = gy.contiguous()
-        add = None if g_skip is None else g_skip.contiguous()
-        gx = torch.empty((B, Xi, Yi, Zi, Cc), dtype=gy.dtype, device=gy.device)
-        L.call("tdx_resize_bwd", L.ptr(gy), L.ptr(add), L.ptr(gx), B, Xi, Yi, Zi, Xo, Yo, Zo, Cc, L.dtype_code(gy.dtype),
-               L.stream())
-        return gx, None
+        return _resize_bwd(gy.contiguous(), None if g_skip is None else g_skip.contiguous(), ctx.geom), None
 
 
 def skip_and_resize(x, size):
@@ -920,7 +996,7 @@ class _ResnetBlock(torch.autograd.Function):
         C2 = 0 if x2 is None else x2.shape[-1]
         Cin, Cout = C1 + C2, w1.shape[0]
         if xc is not None:
-            assert x2 is None and wr is None and partial is None and xc.shape[:4] == x1.shape[:4]
+            assert x2 is None and wr is None and partial is None and xc.shape[:4] == x1.shape[:4] and xc.dtype == x1.dtype
             xc = xc.contiguous()
         if enc is not None:
             # enc: operands of the encoders whose output x1 stands for (encode_deferred); x1 itself is never read
@@ -938,19 +1014,9 @@ class _ResnetBlock(torch.autograd.Function):
         g1, be1, g2, be2 = f32c(g1), f32c(be1), f32c(g2), f32c(be2)
         film = f32c(film.reshape(2, B, Cout))  # (scale | shift) of film_projections: dense (B, Cout) halves, no copies
         scale, shift = film[0], film[1]
-        gws = _clean_ws(L.query("tdx_gn_workspace_bytes", B, Cout), dev)
+        grid, gn, gws = (B, X, Y, Z), (groups, eps), _gn_ws(B, Cout, dev, clean=True)  # one statistics workspace for both convs
 
-        def conv_gn(xa, Ca, xb, Cb, wf, bias, real=None):
-            # `real`: channels that carry data (the composed first conv runs on zero-padded raw channels; the
-            # timers' work figure counts the algorithmic channels only)
-            y = torch.empty((B, X, Y, Z, Cout), dtype=dt, device=dev)
-            stats = torch.empty((B, groups, 2), dtype=torch.float32, device=dev)
-            L.call("tdx_conv3_fwd_gn", L.ptr(xa), Ca, L.ptr(xb), Cb, L.ptr(wf), L.ptr(bias), L.ptr(y), L.ptr(stats), groups,
-                   float(eps), L.ptr(gws), B, X, Y, Z, Cout, code, impl | WS_CLEAN, st,
-                   work=54.0 * (real or (Ca + Cb)) * Cout * B * V,
-                   meta=lambda: L.conv3_fwd_meta(Ca, Cb, Cout, B, X, Y, Z, dt, real))
-            return y, stats
-
+        # ---- h1 = conv3(w1) + statistics; a1 = silu(GN(h1) * (1 + scale) + shift); h2 = conv3(a1; w2) + statistics
         if partial is not None:
             # inference only: conv1 over the leading n_lead channels of x1, continued from the
             # precomputed convolution of the batch-shared tail (tdx_conv3_fwd_partial)
@@ -962,15 +1028,14 @@ class _ResnetBlock(torch.autograd.Function):
                    L.ptr(b1), L.ptr(init), 1, L.ptr(h1), L.ptr(st1), groups, float(eps), L.ptr(gws), B, X, Y, Z, Cout, code,
                    impl | WS_CLEAN, st, work=54.0 * n_lead * Cout * B * V)
         elif xc is not None:
-            h1, st1 = conv_gn(xc, Cc, None, 0, wf1, b1, real=xc_real)
+            h1, st1 = _conv3_fwd(xc, Cc, None, 0, wf1, b1, grid, Cout, code, impl, st, gn, gws, real=xc_real)
         else:
-            h1, st1 = conv_gn(x1, C1, x2, C2, wf1, b1)
-        a1 = torch.empty_like(h1)
-        L.call("tdx_gn_apply", L.ptr(h1), L.ptr(st1), L.ptr(g1), L.ptr(be1), L.ptr(scale), L.ptr(shift), None, L.ptr(a1),
-               B, V, Cout, groups, 1, code, st)
-        h2, st2 = conv_gn(a1, Cout, None, 0, wf2, b2)
+            h1, st1 = _conv3_fwd(x1, C1, x2, C2, wf1, b1, grid, Cout, code, impl, st, gn, gws)
+        a1 = _gn_apply(h1, st1, g1, be1, scale, shift, None, B, V, Cout, groups, 1, code, st)
+        h2, st2 = _conv3_fwd(a1, Cout, None, 0, wf2, b2, grid, Cout, code, impl, st, gn, gws)
+
+        # ---- y = silu(GN(h2)) + skip
         wr2 = None
-        fused_tail = False
         if dec is not None:
             # inference only: the block output goes straight through the model's 1x1 decoder (tdx_gn_apply_decode) and is
             # never written; returns the decoded (B, F, X, Y, Z) f32 tensor instead of the block output
@@ -984,29 +1049,24 @@ class _ResnetBlock(torch.autograd.Function):
                    L.ptr(wd.detach().reshape(F, Cout).float().contiguous()), L.ptr(bd.detach().float().contiguous()), L.ptr(out),
                    B, V, Cout, groups, F, code, st)
             return out
-        y = torch.empty_like(h1)
-        if enc is not None:
+        if enc is not None:  # skip = the encoders' output, evaluated in the kernel
             xr, Fx, wx2, bx2, cr, Fc, wc2, bc2, D = enc
+            y = torch.empty_like(h1)
             L.call("tdx_gn_apply_encoded", L.ptr(h2), L.ptr(st2), L.ptr(g2), L.ptr(be2), L.ptr(xr), Fx, L.ptr(wx2), L.ptr(bx2),
                    L.ptr(cr), Fc, L.ptr(wc2), L.ptr(bc2), L.ptr(y), B, V, D, groups, code, st)
-            fused_tail = True
-        elif wr is None:
+        elif wr is None:  # skip = x1
             assert x2 is None and Cin == Cout
-            res = x1
-        else:
+            y = _gn_apply(h2, st2, g2, be2, None, None, x1, B, V, Cout, groups, 1, code, st)
+        else:  # skip = conv1x1([x1|x2]; wr)
             wr2 = wr.detach().reshape(Cout, Cin).contiguous()
             if FUSE_SKIP_TAIL and dt in L.H16_DTYPES and C1 % 32 == 0 and C2 % 32 == 0 and Cout % 32 == 0:
-                # y = silu(GN(h2)) + conv1x1([x1|x2]) in one pass: the skip tensor is never written or re-read
+                # in one pass: the skip tensor is never written or re-read
+                y = torch.empty_like(h1)
                 L.call("tdx_conv1_fwd_gn", L.ptr(x1), C1, L.ptr(x2), C2, L.ptr(_conv1_wt(wr)), Cout, L.ptr(br), L.ptr(h2),
                        L.ptr(st2), L.ptr(g2), L.ptr(be2), groups, L.ptr(y), B, V, Cout, code, st)
-                fused_tail = True
             else:
-                res = torch.empty_like(h1)
-                L.call("tdx_conv1_fwd", L.ptr(x1), C1, L.ptr(x2), C2, L.ptr(_conv1_wt(wr)), Cout, L.ptr(br), None,
-                       L.ptr(res), B * V, Cout, code, st)
-        if not fused_tail:
-            L.call("tdx_gn_apply", L.ptr(h2), L.ptr(st2), L.ptr(g2), L.ptr(be2), None, None, L.ptr(res), L.ptr(y), B, V, Cout,
-                   groups, 1, code, st)
+                res = _conv1_fwd(x1, C1, x2, C2, _conv1_wt(wr), Cout, 0, br, None, grid, B * V, Cout, code, st)
+                y = _gn_apply(h2, st2, g2, be2, None, None, res, B, V, Cout, groups, 1, code, st)
         ctx.save_for_backward(x1, x2, h1, st1, a1, h2, st2, film, g1, be1, g2, be2, wb1, wb2, wr2, xc)
         ctx.cfg = (groups, tuple(w1.shape), tuple(w2.shape), None if wr is None else tuple(wr.shape),
                    b1 is not None, b2 is not None, br is not None)
@@ -1032,70 +1092,48 @@ class _ResnetBlock(torch.autograd.Function):
         C2 = 0 if x2 is None else x2.shape[-1]
         Cin, Cout = C1 + C2, w1s[0]
         Cc = w1s[1]  # input channels of block1's conv (= Cin unless the conv has its own input xc)
-        V = X * Y * Z
+        grid, V = (B, X, Y, Z), X * Y * Z
         gy = gy.contiguous()
-        dev, dt = gy.device, gy.dtype
-        code, impl, st = L.dtype_code(dt), ctx.impl, L.stream()
-        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        gws = _ws(L.query("tdx_gn_workspace_bytes", B, Cout), dev)
-        flops = lambda ci: 54.0 * ci * Cout * B * V
+        dev, code, impl, st = gy.device, L.dtype_code(gy.dtype), ctx.impl, L.stream()
+        gws = _gn_ws(B, Cout, dev)  # shared by both GroupNorm backwards
 
-        # ---- block2: GroupNorm + SiLU (+ residual: its gradient is gy itself)
-        dh2, dg2, dbe2 = torch.empty_like(h2), f32(Cout), f32(Cout)
-        L.call("tdx_gn_bwd", L.ptr(h2), L.ptr(gy), L.ptr(st2), L.ptr(g2), L.ptr(be2), None, None, L.ptr(dh2), L.ptr(dg2),
-               L.ptr(dbe2), None, None, B, V, Cout, groups, 1, code, L.ptr(gws), st)
-        dw2, db2 = f32(*w2s), (f32(Cout) if hb2 else None)
-        # one workspace per (Cin, Cout): the accumulator / slab layout inside depends on both
-        wws2 = _clean_ws(L.query("tdx_conv3_bwd_weight_workspace_bytes", Cout, Cout, impl), dev, ("w3", Cout, Cout))
-        wws1 = _clean_ws(L.query("tdx_conv3_bwd_weight_workspace_bytes", Cc, Cout, impl), dev, ("w3", Cc, Cout))
-        side.run(lambda: L.call("tdx_conv3_bwd_weight", L.ptr(a1), Cout, None, 0, L.ptr(dh2), L.ptr(dw2), L.ptr(db2), B, X, Y, Z,
-                                Cout, code, impl | WS_CLEAN, L.ptr(wws2), L.stream(), work=flops(Cout)), a1, dh2, dw2, db2)
-        da1 = torch.empty_like(a1)
-        dws = _ws(L.query("tdx_conv3_bwd_data_workspace_bytes", B, X, Y, Z, max(Cin, Cout, Cc), code, impl), dev)
-        L.call("tdx_conv3_bwd_data", L.ptr(dh2), L.ptr(wb2), L.ptr(da1), Cout, None, 0, 0, B, X, Y, Z, Cout, code, impl,
-               L.ptr(dws), st, work=flops(Cout))
+        # ---- block2: GroupNorm + SiLU (+ residual: its gradient is gy itself), then conv2's two gradients
+        dh2, dg2, dbe2 = _gn_bwd(h2, gy, st2, g2, be2, None, None, None, None, B, V, Cout, groups, 1, code, st, gws)
+        # the weight gradients run on the side stream: outputs and workspaces are allocated here, on the launching stream
+        dw2, db2 = _conv3_wgrad_out(w2s, hb2, dev)
+        wws2, wws1 = _conv3_wgrad_ws(Cout, Cout, impl, dev), _conv3_wgrad_ws(Cc, Cout, impl, dev)
+        side.run(lambda: _conv3_wgrad(a1, Cout, None, 0, dh2, dw2, db2, grid, Cout, code, impl, wws2, L.stream()), a1, dh2, dw2, db2)
+        dws = _conv3_bwd_data_ws(grid, max(Cin, Cout, Cc), code, impl, dev)  # for all data gradients of the block
+        da1, _ = _conv3_bwd_data(dh2, wb2, a1, Cout, None, 0, grid, Cout, code, impl, st, dws)
         del dh2
-        # ---- block1: GroupNorm + FiLM + SiLU
-        dh1, dg1, dbe1, dfilm = torch.empty_like(h1), f32(Cout), f32(Cout), f32(2, B, Cout)
-        dscale, dshift = dfilm[0], dfilm[1]
-        L.call("tdx_gn_bwd", L.ptr(h1), L.ptr(da1), L.ptr(st1), L.ptr(g1), L.ptr(be1), L.ptr(scale), L.ptr(shift), L.ptr(dh1),
-               L.ptr(dg1), L.ptr(dbe1), L.ptr(dscale), L.ptr(dshift), B, V, Cout, groups, 1, code, L.ptr(gws), st)
+        # ---- block1: GroupNorm + FiLM + SiLU, then conv1's weight gradient
+        dfilm = torch.empty((2, B, Cout), dtype=torch.float32, device=dev)
+        dh1, dg1, dbe1 = _gn_bwd(h1, da1, st1, g1, be1, scale, shift, dfilm[0], dfilm[1], B, V, Cout, groups, 1, code, st, gws)
         del da1
-        dw1, db1 = f32(*w1s), (f32(Cout) if hb1 else None)
+        dw1, db1 = _conv3_wgrad_out(w1s, hb1, dev)
         if xc is not None:
             # block1's conv has its own input: weight gradient w.r.t. that input; the block input x1 only
             # feeds the identity skip, so its gradient is gy; the data gradient of the conv is needed only
             # if xc itself requires one (e.g. a learned cell-type embedding behind the raw conditioning)
-            side.run(lambda: L.call("tdx_conv3_bwd_weight", L.ptr(xc), Cc, None, 0, L.ptr(dh1), L.ptr(dw1), L.ptr(db1), B, X, Y, Z,
-                                    Cout, code, impl | WS_CLEAN, L.ptr(wws1), L.stream(), work=flops(ctx.xc_real or Cc)),
+            real = ctx.xc_real
+            side.run(lambda: _conv3_wgrad(xc, Cc, None, 0, dh1, dw1, db1, grid, Cout, code, impl, wws1, L.stream(), real),
                      xc, dh1, dw1, db1)
             dxc = None
             if ctx.needs_input_grad[16]:
-                dxc = torch.empty_like(xc)
-                L.call("tdx_conv3_bwd_data", L.ptr(dh1), L.ptr(wb1), L.ptr(dxc), Cc, None, 0, 0, B, X, Y, Z, Cout, code, impl,
-                       L.ptr(dws), st, work=flops(ctx.xc_real or Cc))
+                dxc, _ = _conv3_bwd_data(dh1, wb1, xc, Cc, None, 0, grid, Cout, code, impl, st, dws, real=real)
             side.join()
             return (gy, None, dfilm, dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2, None, None, None, None, None, dxc, None, None,
                     None)
-        side.run(lambda: L.call("tdx_conv3_bwd_weight", L.ptr(x1), C1, L.ptr(x2), C2, L.ptr(dh1), L.ptr(dw1), L.ptr(db1), B, X, Y, Z,
-                                Cout, code, impl | WS_CLEAN, L.ptr(wws1), L.stream(), work=flops(Cin)), x1, x2, dh1, dw1, db1)
+        side.run(lambda: _conv3_wgrad(x1, C1, x2, C2, dh1, dw1, db1, grid, Cout, code, impl, wws1, L.stream()),
+                 x1, x2, dh1, dw1, db1)
         # ---- input gradient = conv1 data gradient + residual-path gradient
-        gx1 = torch.empty_like(x1)
-        gx2 = None if x2 is None else torch.empty_like(x2)
         dwr = dbr = None
-        if wr2 is None:  # identity skip: add gy inside the data-gradient epilogue
-            L.call("tdx_conv3_bwd_data_add", L.ptr(dh1), L.ptr(wb1), L.ptr(gx1), C1, None, 0, L.ptr(gy), None, B, X, Y, Z, Cout,
-                   code, impl, L.ptr(dws), st, work=flops(Cin))
-        else:
-            t1 = torch.empty_like(x1)
-            t2 = None if x2 is None else torch.empty_like(x2)
-            L.call("tdx_conv3_bwd_data", L.ptr(dh1), L.ptr(wb1), L.ptr(t1), C1, L.ptr(t2), C2, 0, B, X, Y, Z, Cout, code, impl,
-                   L.ptr(dws), st, work=flops(Cin))
-            # 1x1 skip: dx = gy @ wr (+ t) -- the add rides in the 1x1 kernel's epilogue
-            L.call("tdx_conv1_fwd", L.ptr(gy), Cout, None, 0, wr2.data_ptr(), Cin, None, L.ptr(t1), L.ptr(gx1), B * V, C1, code, st)
-            if x2 is not None:
-                L.call("tdx_conv1_fwd", L.ptr(gy), Cout, None, 0, wr2.data_ptr() + 4 * C1, Cin, None, L.ptr(t2), L.ptr(gx2),
-                       B * V, C2, code, st)
+        if wr2 is None:  # identity skip: gy is added inside the data-gradient epilogue
+            gx1, gx2 = _conv3_bwd_data(dh1, wb1, x1, C1, None, 0, grid, Cout, code, impl, st, dws, add=gy)
+        else:  # 1x1 skip: dx = gy @ wr + t -- the add rides in the 1x1 kernel's epilogue
+            t1, t2 = _conv3_bwd_data(dh1, wb1, x1, C1, x2, C2, grid, Cout, code, impl, st, dws)
+            gx1 = _conv1_fwd(gy, Cout, None, 0, wr2, Cin, 0, None, t1, grid, B * V, C1, code, st)
+            gx2 = None if x2 is None else _conv1_fwd(gy, Cout, None, 0, wr2, Cin, C1, None, t2, grid, B * V, C2, code, st)
             dwr, dbr = _conv1_weight_grad(x1, C1, x2, C2, gy, Cout, hbr, B * V, code, st)
             dwr = dwr.view(wrs)
         side.join()

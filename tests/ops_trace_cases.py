@@ -1,0 +1,278 @@
+"""What `turbdiff_amd.ops` sends across the C ABI, recorded on the CPU: the recorder and the cases shared by
+tests/test_ops_call_trace.py and tests/golden/make_golden_ops_trace.py.
+
+`recording(ops)` replaces `L.call`, `L.query`, `L.ptr` and `L.stream`, so nothing is launched and no library is needed;
+the operators then run forward and backward on small CPU tensors and every call and query is written down:
+
+    {"call": name, "args": [...], "work": w, "meta": {...} or null}      {"query": name, "args": [...], "ret": n}
+
+An argument whose ctypes type (`_lib.SIGNATURES`) is a pointer is written as null, "stream", a list of structs (job
+tables) or `[label, byte offset]`.  The label names the allocation the address lies in: `t<k> <dtype> <shape>`, k = order
+of first appearance in the case's calls, dtype / shape those of the tensor first seen at it.  Addresses that ops.py
+computes itself (`w2.data_ptr() + 4 * C1`) resolve the same way: `Tensor.data_ptr` is wrapped while recording, so every
+tensor whose address was taken is known -- and kept alive, so that no two labels can share an address.
+"""
+
+import contextlib
+import ctypes as C
+import json
+import os
+
+import torch
+
+B, GRID, GROUPS = 2, (4, 3, 5), 8
+STREAM = 0x57AEA  # what the recorder's L.stream returns
+
+
+class Recorder:
+    def __init__(self, signatures):
+        self.sig = signatures
+        self.trace = []
+        self.spans = {}  # allocation base address -> (bytes, first tensor seen in it)
+        self.exact = {}  # address -> (dtype, shape) of the last tensor whose data_ptr() it was
+        self.labels = {}  # allocation base address -> label
+
+    def saw(self, t, p):
+        st = t.untyped_storage()
+        self.spans.setdefault(st.data_ptr(), (st.nbytes(), t))
+        self.exact[p] = (t.dtype, tuple(t.shape))
+
+    def pointer(self, p):
+        if p is None:
+            return None
+        if p == STREAM:
+            return "stream"
+        if isinstance(p, C.Array):
+            return [{f: (self.pointer(getattr(s, f)) if ty is C.c_void_p else getattr(s, f)) for f, ty in s._fields_} for s in p]
+        for base, (nbytes, first) in self.spans.items():
+            if base <= p < base + max(nbytes, 1):
+                if base not in self.labels:
+                    dtype, shape = self.exact.get(p, (first.dtype, tuple(first.shape)))
+                    self.labels[base] = f"t{len(self.labels)} {str(dtype)[6:]} {list(shape)}"
+                return [self.labels[base], p - base]
+        raise AssertionError(f"pointer argument {p:#x} belongs to no tensor whose address was taken")
+
+    def args(self, name, args):
+        types = self.sig[name][1]
+        assert len(args) == len(types), f"{name}: {len(args)} arguments for {len(types)} parameters"
+        return [self.pointer(a) if ty is C.c_void_p else a for a, ty in zip(args, types)]
+
+    def query(self, name, *args):
+        ret = 1 if not name.endswith("_bytes") else 256 + 16 * sum(a for a in args if isinstance(a, int))
+        self.trace.append({"query": name, "args": self.args(name, args), "ret": ret})
+        return ret
+
+    def call(self, name, *args, work=0.0, meta=None):
+        assert meta is None or callable(meta), "meta= stays lazy: a zero-argument callable"
+        meta = meta() if meta is not None else None  # its library query is recorded in front of the call
+        self.trace.append({"call": name, "args": self.args(name, args), "work": float(work), "meta": meta})
+
+    @staticmethod
+    def ptr(t):
+        if t is None:
+            return None
+        if not t.is_contiguous():
+            raise RuntimeError("tdx kernels need contiguous tensors")
+        return t.data_ptr()
+
+
+@contextlib.contextmanager
+def recording(ops):
+    """The recorder, attached to `ops` and its `_lib`; default switches (side stream off: it needs a device)."""
+    L = ops.L
+    rec = Recorder(L.SIGNATURES)
+    real_data_ptr = torch.Tensor.data_ptr
+
+    def data_ptr(t):
+        p = real_data_ptr(t)
+        rec.saw(t, p)
+        return p
+
+    saved = {(m, k): getattr(m, k) for m, ks in ((L, ("call", "query", "ptr", "stream", "_conv_impl_override")),
+                                                 (ops, ("WGRAD_STREAM", "WS_CLEAN", "FUSE_SKIP_TAIL"))) for k in ks}
+    had_own = "data_ptr" in torch.Tensor.__dict__
+    env = os.environ.pop("TDX_CONV_IMPL", None)
+    ops._pack_cache.clear()
+    ops._CLEAN.clear()
+    try:
+        L.call, L.query, L.ptr, L.stream, L._conv_impl_override = rec.call, rec.query, rec.ptr, lambda device_index=None: STREAM, None
+        ops.WGRAD_STREAM, ops.WS_CLEAN, ops.FUSE_SKIP_TAIL = False, L.WS_CLEAN, True
+        torch.Tensor.data_ptr = data_ptr
+        yield rec
+    finally:
+        if had_own:
+            torch.Tensor.data_ptr = real_data_ptr
+        else:
+            del torch.Tensor.data_ptr
+        for (m, k), v in saved.items():
+            setattr(m, k, v)
+        if env is not None:
+            os.environ["TDX_CONV_IMPL"] = env
+        ops._pack_cache.clear()
+        ops._CLEAN.clear()
+
+
+# --------------------------------------------------------------------------- tensors
+
+
+def act(c, dtype, grad=True, b=B, grid=GRID):
+    return torch.zeros((b, *grid, c), dtype=dtype).requires_grad_(grad)
+
+
+def par(*shape, grad=True):
+    return torch.zeros(shape, dtype=torch.float32).requires_grad_(grad)
+
+
+def back(*outs):
+    torch.autograd.backward(list(outs), [torch.zeros_like(o) for o in outs])
+
+
+class _DeviceParameter(torch.Tensor):
+    """A CPU tensor that says it is on the device: PackPlan accepts device parameters only."""
+
+    is_cuda = True
+
+
+def block_args(cin, cout, skip, cconv=None, grad=True):
+    conv1 = (par(cout, cconv or cin, 3, 3, 3, grad=grad), par(cout, grad=grad))
+    conv2 = (par(cout, cout, 3, 3, 3, grad=grad), par(cout, grad=grad))
+    norm1, norm2 = (par(cout, grad=grad), par(cout, grad=grad)), (par(cout, grad=grad), par(cout, grad=grad))
+    return conv1, norm1, conv2, norm2, ((par(cout, cin, 1, 1, 1, grad=grad), par(cout, grad=grad)) if skip else None)
+
+
+def block(ops, dtype, c1, c2, cout, skip, film=True, grad=True, x_grad=True, **kw):
+    x1 = kw.pop("x1", None)
+    if x1 is None:
+        x1 = act(c1, dtype, grad and x_grad)
+    x2 = act(c2, dtype, grad and x_grad) if c2 else None
+    conv1, norm1, conv2, norm2, skip_wb = block_args(c1 + c2, cout, skip, kw.pop("cconv", None), grad)
+    if film:
+        y = ops.resnet_block(x1, x2, None, None, conv1, norm1, conv2, norm2, skip_wb, GROUPS, film=par(2, B, cout, grad=grad), **kw)
+    else:
+        y = ops.resnet_block(x1, x2, par(B, cout, grad=grad), par(B, cout, 1, 1, 1, grad=grad), conv1, norm1, conv2, norm2,
+                             skip_wb, GROUPS, eps=1e-6, **kw)
+    if grad:
+        back(y)
+
+
+# --------------------------------------------------------------------------- cases
+
+bf16, f32 = torch.bfloat16, torch.float32
+
+
+def _block_unfused_tail(ops):
+    ops.FUSE_SKIP_TAIL = False
+    block(ops, bf16, 32, 32, 64, True)
+
+
+def _block_split_scope(ops):
+    # the forward runs inside a model's conv_impl_scope, the backward outside: ctx.impl carries the choice over
+    x1, x2 = act(32, f32), act(32, f32)
+    conv1, norm1, conv2, norm2, skip_wb = block_args(64, 32, True)
+    with ops.L.conv_impl_scope("split"):
+        y = ops.resnet_block(x1, x2, None, None, conv1, norm1, conv2, norm2, skip_wb, GROUPS, film=par(2, B, 32))
+    back(y)
+
+
+def _block_encoded(ops):
+    X, Y, Z = GRID
+    enc = ops.encode_deferred(torch.zeros(B, 4, X, Y, Z), torch.zeros(4, X, Y, Z), par(32, 4, 1, 1, 1), par(32),
+                              par(32, 4, 1, 1, 1), par(32), bf16)
+    block(ops, bf16, 64, 0, 64, False, x1=enc.standin, cconv=32, conv1_input=act(32, bf16, False), conv1_real_channels=8,
+          skip_encoded=enc)
+
+
+def _block_partial(ops):
+    with torch.no_grad():
+        x1 = act(64, bf16, False)
+        conv1, norm1, conv2, norm2, _ = block_args(64, 64, False, grad=False)
+        init = ops.conv3_shared_tail(act(32, bf16, False, b=1), conv1[0], 32)
+        ops.resnet_block(x1, None, None, None, conv1, norm1, conv2, norm2, None, GROUPS, partial=(32, init), film=par(2, B, 64, grad=False))
+
+
+def _block_decode(ops):
+    with torch.no_grad():
+        block(ops, bf16, 64, 0, 64, False, grad=False, decode_wb=(par(4, 64, 1, 1, 1, grad=False), par(4, grad=False)))
+
+
+def _conv3(ops, dtype, c2, bias, x_grad=True, w_grad=True):
+    x2 = act(32, dtype, x_grad) if c2 else None
+    back(ops.conv3(act(32, dtype, x_grad), par(64, 32 + c2, 3, 3, 3, grad=w_grad), par(64, grad=w_grad) if bias else None, x2=x2))
+
+
+def _conv3_gn_stats(ops):
+    y, stats = ops.conv3_gn_stats(act(32, bf16), par(64, 64, 3, 3, 3), par(64), GROUPS, eps=1e-6, x2=act(32, bf16))
+    back(ops.gn_film_silu(y, par(64), par(64), GROUPS, stats=stats))
+
+
+def _conv1(ops, dtype, c2, add, x2_grad=True):
+    x2 = act(64, dtype, x2_grad) if c2 else None
+    back(ops.conv1(act(32, dtype), par(64, 32 + c2, 1, 1, 1), par(64), x2=x2, add=act(64, dtype) if add else None))
+
+
+def _gn(ops, dtype, film, res, act_):
+    scale, shift = (par(B, 32), par(B, 32)) if film else (None, None)
+    back(ops.gn_film_silu(act(32, dtype), par(32), par(32), GROUPS, scale, shift, act(32, dtype) if res else None, act=act_))
+
+
+def _skip_and_resize(ops, use_resized):
+    skip, y = ops.skip_and_resize(act(32, bf16), (2, 2, 3))
+    back(skip, y) if use_resized else back(skip)
+
+
+def _layout(ops):
+    X, Y, Z = GRID
+    back(ops.to_nvc(torch.zeros(B, 32, X, Y, Z, requires_grad=True), bf16))
+    back(ops.to_ncv(act(32, bf16)))
+
+
+def _prefetch(ops):
+    dev = lambda *shape: torch.Tensor._make_subclass(_DeviceParameter, torch.zeros(shape), True)
+    w3, w1 = [dev(64, 32, 3, 3, 3), dev(32, 64, 3, 3, 3)], [dev(64, 32, 1, 1, 1)]
+    plan = ops.prefetch_weights(w3, w1, bf16)
+    assert ops.prefetch_weights(w3, w1, bf16, plan) is plan  # nothing changed: no launch
+    with torch.no_grad():
+        ops.conv3(ops.conv3(act(32, bf16, False), w3[0]), w3[1])
+        ops.conv1(act(32, bf16, False), w1[0])
+
+
+CASES = {
+    "block_two_inputs_bf16_fused_tail": lambda ops: block(ops, bf16, 32, 32, 64, True),
+    "block_two_inputs_f32_scale_shift": lambda ops: block(ops, f32, 32, 32, 64, True, film=False),
+    "block_two_inputs_bf16_unfused_tail": _block_unfused_tail,
+    "block_two_inputs_f32_split_scope": _block_split_scope,
+    "block_one_input_projected_skip_f32": lambda ops: block(ops, f32, 32, 0, 64, True),
+    "block_identity_skip_bf16": lambda ops: block(ops, bf16, 64, 0, 64, False),
+    "block_identity_skip_f32_scale_shift": lambda ops: block(ops, f32, 64, 0, 64, False, film=False),
+    "block_conv1_input": lambda ops: block(ops, bf16, 64, 0, 64, False, cconv=32, conv1_input=act(32, bf16, False)),
+    "block_conv1_input_with_grad": lambda ops: block(ops, bf16, 64, 0, 64, False, cconv=32, conv1_input=act(32, bf16)),
+    "block_conv1_input_real_channels": lambda ops: block(ops, f32, 64, 0, 64, False, cconv=32, conv1_input=act(32, f32),
+                                                         conv1_real_channels=8),
+    "block_skip_encoded": _block_encoded,
+    "block_partial_nograd": _block_partial,
+    "block_decode_nograd": _block_decode,
+    "conv3_bf16": lambda ops: _conv3(ops, bf16, 0, False),
+    "conv3_x2_bias_f32": lambda ops: _conv3(ops, f32, 32, True),
+    "conv3_weight_grad_only": lambda ops: _conv3(ops, bf16, 32, True, x_grad=False),
+    "conv3_data_grad_only": lambda ops: _conv3(ops, bf16, 0, True, w_grad=False),
+    "conv3_gn_stats": _conv3_gn_stats,
+    "conv3_shared_tail": lambda ops: ops.conv3_shared_tail(act(32, bf16, False, b=1), par(64, 64, 3, 3, 3, grad=False), 32),
+    "conv1_bf16": lambda ops: _conv1(ops, bf16, 0, False),
+    "conv1_x2_add_f32": lambda ops: _conv1(ops, f32, 64, True),
+    "conv1_x2_without_grad": lambda ops: _conv1(ops, bf16, 64, False, x2_grad=False),
+    "gn_film_silu_plain": lambda ops: _gn(ops, bf16, False, False, True),
+    "gn_film_silu_film_res_f32": lambda ops: _gn(ops, f32, True, True, True),
+    "gn_film_silu_film_noact": lambda ops: _gn(ops, bf16, True, False, False),
+    "resize": lambda ops: back(ops.resize(act(32, bf16), (7, 5, 9))),
+    "skip_and_resize": lambda ops: _skip_and_resize(ops, True),
+    "skip_and_resize_resized_unused": lambda ops: _skip_and_resize(ops, False),
+    "to_nvc_to_ncv": _layout,
+    "prefetch_then_convs": _prefetch,
+}
+
+
+def record(ops, name):
+    """The trace of one case as plain JSON values."""
+    with recording(ops) as rec:
+        CASES[name](ops)
+    return json.loads(json.dumps(rec.trace))

@@ -17,12 +17,49 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(tdx_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_prototypes():
+    """{name: (return type, [argument types])} of include/tdx.h, every type reduced to its class: "ptr" (any pointer;
+    `const char*` as a return type stays itself), int, int64_t, uint64_t (= size_t on this ABI), uint32_t, float, double."""
+    text = (ROOT / "include" / "tdx.h").read_text()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+
+    def cls(decl, name=True):
+        decl = decl.strip()
+        if "*" in decl:
+            return "ptr"
+        words = [w for w in decl.split() if w != "const"]
+        words = words[:-1] if name and len(words) > 1 else words  # drop the parameter's name
+        return {"size_t": "uint64_t"}.get(" ".join(words), " ".join(words))
+
+    protos = {}
+    for ret, name, args in re.findall(r"^\s*([A-Za-z_][\w \t]*?[\w*])\s*\b(tdx_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        ret = ret.strip()
+        args = [] if args.strip() in ("", "void") else [cls(a) for a in args.split(",")]
+        protos[name] = ("const char*" if re.fullmatch(r"const\s+char\s*\*", ret) else cls(ret, name=False), args)
+    return protos
+
+
 def test_header_symbols_are_bound_and_exported():
+    import ctypes as C
+
     from turbdiff_amd import _lib
 
     syms = declared_symbols()
     assert len(syms) >= 25
     assert sorted(_lib.SIGNATURES) == syms, "ctypes table and include/tdx.h disagree"
+    # ... and argument by argument: a ctypes table that names every symbol can still pass an int where the header takes
+    # an int64_t.  c_size_t and c_uint64 are one ctypes class on this ABI, so size_t counts as uint64_t.
+    assert C.c_size_t is C.c_uint64
+    kinds = {C.c_void_p: "ptr", C.c_int: "int", C.c_int64: "int64_t", C.c_uint64: "uint64_t", C.c_uint32: "uint32_t",
+             C.c_float: "float", C.c_double: "double", C.c_char_p: "const char*"}
+    protos = declared_prototypes()
+    assert sorted(protos) == syms, "a prototype of include/tdx.h was not parsed"
+    for name, (ret, args) in protos.items():
+        res, argtypes = _lib.SIGNATURES[name]
+        assert ret in ("int", "uint64_t", "int64_t", "const char*"), f"{name}: return type {ret}"
+        assert kinds[res] == ret, f"{name}: returns {ret}, bound as {kinds[res]}"
+        assert [kinds[a] for a in argtypes] == args, f"{name}: header {args}, bound as {[kinds[a] for a in argtypes]}"
     lib = _lib.load()  # raises if the .so is missing: run __graft_entry__.build() first
     for s in syms:
         assert hasattr(lib, s), f"{s} not exported by libtdx_hip.so"

@@ -1,4 +1,4 @@
-"""Does any kernel of the training step read memory nobody wrote?  Every torch.empty / empty_like of the step is filled with NaN
+"""Does any kernel of the training step read memory nobody wrote?  Every torch.empty / empty_like / Tensor.new_empty of the step is filled with NaN
 (byte workspaces with 0xFF) before use; an uninitialised read shows up as a non-finite loss or gradient.  Two eager steps of the
 two-level golden model (f32) or of the benchmark model at 96x32x24 in a given mode.  Round 6: clean in every mode.
 GPU box: python tools/uninit_read_probe.py [f32 | full bf16 | full fp16 | full f32s]"""
@@ -15,6 +15,8 @@ def nan_fill(t):
     return t
 torch.empty = lambda *a, **k: nan_fill(_empty(*a, **k))
 torch.empty_like = lambda *a, **k: nan_fill(_empty_like(*a, **k))
+_new_empty = torch.Tensor.new_empty  # the launch helpers of ops.py allocate outputs next to an input this way
+torch.Tensor.new_empty = lambda self, *a, **k: nan_fill(_new_empty(self, *a, **k))
 import test_parallel_gpu as T
 dev = torch.device("cuda:0")
 mode = sys.argv[1] if len(sys.argv) > 1 else "f32"
