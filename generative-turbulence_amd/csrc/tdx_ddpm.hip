@@ -476,6 +476,143 @@ extern "C" int tdx_p_sample_step_rng(const float* x_t, const float* eps, const f
     return tdx_launch_status();
 }
 
+// ------------------------------------------------------------------ DDIM step over a timestep subsequence ---
+// Generalized DDIM update (Song et al. 2021, eq. 12) from tau_k to tau_{k-1}; tab = 6 rows of S floats (schedules.
+// DDIM_PACKED_ORDER), column k.  x0 is formed as model_predictions forms it (BC cells keep x_t without noise_bcs, then the
+// clip); where that changed it, eps is re-derived from it (predict_noise_from_start) so that x0 and the direction term
+// describe the same point.  BC cells under noise_bcs are re-noised at the level of the state PRODUCED, tau_{k-1} (sp =
+// sqrt(abar), sbp = sqrt(1 - abar) there): the ancestral loop re-noises them at level t for x_{t-1}, one level off, an
+// offset a subsequence cannot keep.  Step k = 0 writes the mean and fixes the BC cells.
+struct DdimCoef {
+    float recip, recipm1, sp, dir, sigma, sbp;
+    bool last;
+};
+__device__ __forceinline__ DdimCoef ddim_coef(const float* __restrict__ tab, int S, int64_t k) {
+    DdimCoef c;
+    c.recip = tab[k]; c.recipm1 = tab[S + k]; c.sp = tab[2 * S + k];
+    c.dir = tab[3 * S + k]; c.sigma = tab[4 * S + k]; c.sbp = tab[5 * S + k];
+    c.last = (k == 0);
+    return c;
+}
+// one element; both kernels below go through it.  Every multiply-add is spelled as an fmaf: left to the compiler, the
+// contraction of a * b + c * d came out differently in the scalar and in the 4-wide loop (1 ulp apart), and the two entries
+// are specified to agree bit for bit.  z is read only where sigma != 0 (eta = 0: the interior does not depend on the noise
+// at all, not even through the sign of a zero).
+__device__ __forceinline__ float ddim_update(const DdimCoef& c, float xt, float eps, float z, float z2, float xb,
+                                             bool inside, int noise_bcs, int clip) {
+    const float raw = fmaf(c.recip, xt, -(c.recipm1 * eps));
+    float x0 = raw;
+    if (!noise_bcs && !inside) x0 = xt;
+    if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    const float e = (x0 == raw) ? eps : fmaf(c.recip, xt, -x0) / c.recipm1;
+    float r = fmaf(c.sp, x0, c.dir * e);
+    if (c.last) {
+        if (!inside) r = xb;
+    } else if (inside) {
+        if (c.sigma != 0.0f) r = fmaf(c.sigma, z, r);
+    } else if (noise_bcs) {
+        r = fmaf(c.sp, xb, c.sbp * z2);
+    }
+    return r;
+}
+
+__global__ void __launch_bounds__(256)
+ddim_step_kernel(const float* __restrict__ x_t, const float* __restrict__ eps, const float* __restrict__ z,
+                 const float* __restrict__ z2, const float* __restrict__ x_bcs, const uint8_t* __restrict__ mask,
+                 const float* __restrict__ tab, int S, const int64_t* __restrict__ kp, int noise_bcs, int clip,
+                 float* __restrict__ out, int64_t V) {
+    const int64_t k = *kp;
+    if (k < 0 || k >= S) return;  // a finished trajectory: no column to read
+    const DdimCoef c = ddim_coef(tab, S, k);
+    // a NULL noise tensor reads as "no noise" rather than being dereferenced (the host cannot see k or sigma)
+    const bool use_z = !c.last && c.sigma != 0.0f && z, use_z2 = !c.last && noise_bcs && z2;
+    const int64_t base = (int64_t)blockIdx.y * V;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += stride) {
+        const bool inside = mask[i] != 0;
+        const float zz = (use_z && inside) ? z[base + i] : 0.f;
+        const float zb = (use_z2 && !inside) ? z2[base + i] : 0.f;
+        out[base + i] = ddim_update(c, x_t[base + i], eps[base + i], zz, zb, x_bcs[base + i], inside, noise_bcs, clip);
+    }
+}
+
+extern "C" int tdx_ddim_step(const float* x_t, const float* eps, const float* z, const float* z2, const float* x_bcs,
+                             const uint8_t* mask, const float* tab, int S, const int64_t* k, const int64_t* tau,
+                             const int64_t* t, int noise_bcs, int clip, float* out, int B, int F, int64_t V,
+                             void* stream) {
+    TDX_CHECK_ARG(x_t && eps && x_bcs && mask && tab && k && tau && t && out && S > 0 && B > 0 && F > 0 && V > 0);
+    dim3 grid((unsigned)min((int64_t)128, (V + 255) / 256), B * F);
+    hipLaunchKernelGGL(ddim_step_kernel, grid, dim3(256), 0, as_stream(stream), x_t, eps, z, z2, x_bcs, mask, tab, S, k,
+                       noise_bcs, clip, out, V);
+    return tdx_launch_status();
+}
+
+// The same update with z and z2 drawn where they are consumed, laid out and counted exactly as
+// p_sample_step_rng_kernel does (z: counter off + i, z2: off + n4 + i), so a run is bit-identical to
+// tdx_randn_batched(z); [tdx_randn_batched(z2);] tdx_ddim_step(...).  The Philox rounds for z are skipped when sigma == 0
+// (eta = 0) as they are when no lane of the quad is inside; the offset still advances as if they had been drawn.
+__global__ void __launch_bounds__(256)
+ddim_step_rng_kernel(const float* __restrict__ x_t, const float* __restrict__ eps, const float* __restrict__ x_bcs,
+                     const uint8_t* __restrict__ mask, const float* __restrict__ tab, int S,
+                     const int64_t* __restrict__ kp, int noise_bcs, int clip, float* __restrict__ out, int64_t V,
+                     int64_t n4, uint64_t seed, const uint64_t* __restrict__ sids, const uint64_t* __restrict__ offp) {
+    const int64_t k = *kp;
+    if (k < 0 || k >= S) return;  // a finished trajectory: no column to read
+    const uint64_t off = *offp, sid = sids[blockIdx.y];
+    const DdimCoef c = ddim_coef(tab, S, k);
+    const bool use_z = !c.last && c.sigma != 0.0f, use_z2 = !c.last && noise_bcs;
+    const int64_t base4 = (int64_t)blockIdx.y * n4;
+    const int64_t v4 = V >> 2;
+    const float4* xt4 = reinterpret_cast<const float4*>(x_t) + base4;
+    const float4* e4 = reinterpret_cast<const float4*>(eps) + base4;
+    const float4* xb4 = reinterpret_cast<const float4*>(x_bcs) + base4;
+    const uchar4* m4 = reinterpret_cast<const uchar4*>(mask);
+    float4* o4 = reinterpret_cast<float4*>(out) + base4;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const float4 xv = xt4[i], ev = e4[i];
+        const uchar4 mv = m4[i % v4];
+        const bool in[4] = {mv.x != 0, mv.y != 0, mv.z != 0, mv.w != 0};
+        const bool any_in = in[0] | in[1] | in[2] | in[3], any_out = !(in[0] & in[1] & in[2] & in[3]);
+        const float xt[4] = {xv.x, xv.y, xv.z, xv.w}, ee[4] = {ev.x, ev.y, ev.z, ev.w};
+        float xb[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f}, z2[4] = {0.f, 0.f, 0.f, 0.f};
+        if (any_out && (c.last || noise_bcs)) {
+            const float4 bv = xb4[i];
+            xb[0] = bv.x; xb[1] = bv.y; xb[2] = bv.z; xb[3] = bv.w;
+        }
+        if (use_z && any_in) philox_normal4(off + (uint64_t)i, sid, seed, z);
+        if (use_z2 && any_out) philox_normal4(off + (uint64_t)n4 + (uint64_t)i, sid, seed, z2);
+        float r[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[j] = ddim_update(c, xt[j], ee[j], z[j], z2[j], xb[j], in[j], noise_bcs, clip);
+        o4[i] = make_float4(r[0], r[1], r[2], r[3]);
+    }
+}
+// offset += by; k -= 1; t = tau[k] while a step is left: the scalar updates that close a DDIM step, in one launch
+__global__ void advance_ddim_step(uint64_t* offp, uint64_t by, int64_t* kp, const int64_t* __restrict__ tau, int S,
+                                  int64_t* tp) {
+    *offp += by;
+    const int64_t k = *kp - 1;
+    *kp = k;
+    if (k >= 0 && k < S) *tp = tau[k];
+}
+
+extern "C" int tdx_ddim_step_rng(const float* x_t, const float* eps, const float* x_bcs, const uint8_t* mask,
+                                 const float* tab, int S, int64_t* k, const int64_t* tau, int64_t* t, int noise_bcs,
+                                 int clip, float* out, int B, int F, int64_t V, uint64_t seed,
+                                 const uint64_t* stream_ids, uint64_t* offset_dev, void* stream) {
+    TDX_CHECK_ARG(x_t && eps && x_bcs && mask && tab && k && tau && t && out && stream_ids && offset_dev);
+    TDX_CHECK_ARG(S > 0 && B > 0 && F > 0 && V > 0 && (V & 3) == 0);
+    TDX_CHECK_ARG(((uintptr_t)x_t | (uintptr_t)eps | (uintptr_t)x_bcs | (uintptr_t)out) % 16 == 0 && (uintptr_t)mask % 4 == 0);
+    const int64_t n4 = (int64_t)F * V / 4;
+    dim3 grid((unsigned)min((int64_t)256, (n4 + 255) / 256), B);
+    hipLaunchKernelGGL(ddim_step_rng_kernel, grid, dim3(256), 0, as_stream(stream), x_t, eps, x_bcs, mask, tab, S,
+                       (const int64_t*)k, noise_bcs, clip, out, V, n4, seed, stream_ids, (const uint64_t*)offset_dev);
+    hipLaunchKernelGGL(advance_ddim_step, dim3(1), dim3(1), 0, as_stream(stream), offset_dev,
+                       (uint64_t)(noise_bcs ? 2 * n4 : n4), k, tau, S, t);
+    return tdx_launch_status();
+}
+
 extern "C" int tdx_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, uint64_t* offset_dev, void* stream) {
     TDX_CHECK_ARG(out && offset_dev && n > 0);
     const int64_t n4 = (n + 3) >> 2;

@@ -609,6 +609,7 @@ class GaussianDiffusion(nn.Module):
         self.elbo_weight = elbo_weight
         self.detach_elbo_mean = detach_elbo_mean
         self.num_timesteps = timesteps
+        self.beta_schedule = beta_schedule  # the DDIM coefficient tables are built from it per subsequence
         self.loss_type = loss_type
         if loss_type not in ("l1", "l2"):
             raise ValueError(f"invalid loss type {loss_type}")
@@ -699,8 +700,12 @@ class GaussianDiffusion(nn.Module):
 
     @torch.no_grad()
     def p_sample_loop(self, x_bcs, C, cell_idx, pbar=False, start_from: int | None = None, noise_fn=None, seed=None,
-                      trajectory_ids=None):
-        """Ancestral sampling (reference ddpm.py:767-816).
+                      trajectory_ids=None, sampling_timesteps: int | None = None, eta: float = 0.0):
+        """Ancestral sampling (reference ddpm.py:767-816), or with `sampling_timesteps = S` the generalized DDIM sampler
+        (Song et al. 2021) over S of the training timesteps, `schedules.ddim_timesteps`: eta = 0 deterministic given
+        x_T, eta = 1 the posterior variance of the sub-sampled chain (NOT the fixed-large variance of the ancestral loop, so
+        S = T, eta = 1 is not expected to reproduce it).  Same routes, same noise order (z is consumed at eta = 0 too, and
+        ignored); ValueError with learned variances, S outside [1, start_from or T] or eta outside [0, 1].
 
         Default (`noise_fn is None`): the hipGraph-captured reverse step of `sampling.GraphSampler`, replayed T times --
         this is what `DiffusionTrainer.sample`, `tools/eval_ckpt.py` and a `dropin` user get.  Noise comes from the
@@ -712,18 +717,24 @@ class GaussianDiffusion(nn.Module):
         input shape and pointed at the new batch / geometry by copies (`GraphSampler.rebind`); a weight update re-captures.
         With `noise_fn(like)` -- injected noise in the reference's drawing order (x_T; then per step t > 0: z, and z' if
         noise_bcs), the golden tests -- or TDX_GRAPH_SAMPLER=0 the loop runs eagerly, one launch sequence per step."""
+        if sampling_timesteps is not None:
+            from ..sampling import check_ddim_arguments
+
+            check_ddim_arguments(self, sampling_timesteps, eta, start_from)
         if self.learned_variances:
             return self._general_sample(x_bcs, C, cell_idx, pbar, start_from, noise_fn)
         if noise_fn is None and GRAPH_SAMPLER and x_bcs.is_cuda and hasattr(self.model, "encode_local"):
-            return self._graph_sample(x_bcs, C, cell_idx, pbar, start_from, seed, trajectory_ids)
+            return self._graph_sample(x_bcs, C, cell_idx, pbar, start_from, seed, trajectory_ids, sampling_timesteps, eta)
+        if sampling_timesteps is not None:
+            return self._eager_ddim_sample(x_bcs, C, cell_idx, pbar, start_from, noise_fn, int(sampling_timesteps), float(eta))
         return self._eager_sample(x_bcs, C, cell_idx, pbar, start_from, noise_fn)
 
-    def _graph_sample(self, x_bcs, C, cell_idx, pbar, start_from, seed, trajectory_ids):
+    def _graph_sample(self, x_bcs, C, cell_idx, pbar, start_from, seed, trajectory_ids, sampling_timesteps=None, eta=0.0):
         from ..sampling import GraphSampler
 
         nonce = int(torch.randint(0, 2**31 - 1, (1,)).item()) if seed is None else int(seed) % (2**31 - 1)
         x_bcs = x_bcs.contiguous().float()
-        sig = GraphSampler.signature_of(self, x_bcs, C)
+        sig = GraphSampler.signature_of(self, x_bcs, C, sampling_timesteps, eta)
         cache = self.graph_samplers()
         gs = cache.get(sig)
         if gs is None:
@@ -731,7 +742,7 @@ class GaussianDiffusion(nn.Module):
             # captured sampler each; all of them capture on ONE stream, hence share one scratch arena
             shared = next(iter(cache.values()))._capture_stream if cache else None
             gs = cache[sig] = GraphSampler(self, x_bcs, C, cell_idx, seed=0, trajectory_ids=trajectory_ids, nonce=nonce,
-                                           capture_stream=shared)
+                                           capture_stream=shared, sampling_timesteps=sampling_timesteps, eta=eta)
             while len(cache) > MAX_GRAPH_SAMPLERS:
                 cache.popitem(last=False)
         else:
@@ -806,6 +817,39 @@ class GaussianDiffusion(nn.Module):
             z2 = randn(x_bcs) if (t > 0 and self.noise_bcs) else None
             x_t = ops.p_sample_step(x_t, eps, z, z2, x_bcs, mask, self.step_tables, self.num_timesteps, ts[t : t + 1],
                                     self.noise_bcs, self.clip_denoised)
+        return x_t
+
+    def _eager_ddim_sample(self, x_bcs, C, cell_idx, pbar, start_from, noise_fn, S, eta):
+        """The DDIM loop, one launch sequence per step over `ops.ddim_step`; noise in the ancestral order (x_T; then per
+        step k > 0: z, and z' if noise_bcs)."""
+        randn = noise_fn if noise_fn is not None else torch.randn_like
+        x_bcs = x_bcs.contiguous().float()
+        B = x_bcs.shape[0]
+        dev = x_bcs.device
+        mask, _ = self.domain_mask(cell_idx, x_bcs[0, 0].numel())
+        taus = schedules.ddim_timesteps(self.num_timesteps, S, start_from)
+        tab = schedules.ddim_tables(self.beta_schedule, self.num_timesteps, taus, eta).to(dev)
+        tau = torch.tensor(taus, dtype=torch.long, device=dev)
+        ks = torch.arange(S, dtype=torch.long, device=dev)
+        if start_from is None:
+            x_t = randn(x_bcs)
+        else:
+            x_t = ops.q_sample(x_bcs, randn(x_bcs), self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, tau[-1:])
+        if not self.noise_bcs:
+            x_t = self._outside_keep(mask, x_t, x_bcs)
+        enc = self.model.encode_local(C) if hasattr(self.model, "encode_local") else None
+        kw = {"encoded_local": enc} if enc is not None else {}
+        steps = reversed(range(S))
+        if pbar:
+            from tqdm.auto import tqdm
+
+            steps = tqdm(steps, desc="sampling loop time step", total=S, position=1)
+        for k in steps:
+            eps = self.model(x_t, tau[k].expand(B), C, **kw)
+            z = randn(x_t) if k > 0 else None
+            z2 = randn(x_bcs) if (k > 0 and self.noise_bcs) else None
+            x_t = ops.ddim_step(x_t, eps, z, z2, x_bcs, mask, tab, ks[k : k + 1], tau, tau[k : k + 1], self.noise_bcs,
+                                self.clip_denoised)
         return x_t
 
     def p_losses(self, x_start, t, C, metadata, variables, noise=None):

@@ -782,6 +782,38 @@ def p_sample_step_rng(x_t, eps, x_bcs, mask, sched, T, t_dev, noise_bcs, clip, s
     return out
 
 
+def ddim_step(x_t, eps, z, z2, x_bcs, mask, tab, k_dev, tau_dev, t_dev, noise_bcs, clip, out=None):
+    """One generalized DDIM update from tau[k] to tau[k-1]; tab = schedules.ddim_tables(...) on the device ([6, S]),
+    k_dev / t_dev device int64 scalars, tau_dev the device int64 subsequence.  z / z2 may be None where unused."""
+    B, F = x_t.shape[:2]
+    V = x_t[0, 0].numel()
+    if out is None:
+        out = torch.empty_like(x_t)
+    L.call("tdx_ddim_step", L.ptr(x_t), L.ptr(eps), L.ptr(z), L.ptr(z2), L.ptr(x_bcs), L.ptr(mask), L.ptr(tab),
+           _ddim_steps(tab, tau_dev), L.ptr(k_dev), L.ptr(tau_dev), L.ptr(t_dev), int(noise_bcs), int(clip), L.ptr(out), B, F, V, L.stream())
+    return out
+
+
+def ddim_step_rng(x_t, eps, x_bcs, mask, tab, k_dev, tau_dev, t_dev, noise_bcs, clip, seed, stream_ids, offset_dev, out=None):
+    """The DDIM step with z (and z2) drawn in the kernel (layouts: p_sample_step_rng_supported); on the device it then
+    advances offset_dev, decrements k_dev and sets t_dev = tau[k] while a step is left."""
+    B, F = x_t.shape[:2]
+    V = x_t[0, 0].numel()
+    if out is None:
+        out = torch.empty_like(x_t)
+    L.call("tdx_ddim_step_rng", L.ptr(x_t), L.ptr(eps), L.ptr(x_bcs), L.ptr(mask), L.ptr(tab), _ddim_steps(tab, tau_dev), L.ptr(k_dev),
+           L.ptr(tau_dev), L.ptr(t_dev), int(noise_bcs), int(clip), L.ptr(out), B, F, V, seed, L.ptr(stream_ids),
+           L.ptr(offset_dev), L.stream())
+    return out
+
+
+def _ddim_steps(tab, tau_dev) -> int:
+    """S of a [6, S] float32 coefficient table and its int64 subsequence (the kernels index both by the device-side k)."""
+    if tab.dtype != torch.float32 or tab.ndim != 2 or tab.shape[0] != 6 or tau_dev.dtype != torch.int64 or tau_dev.numel() != tab.shape[1]:
+        raise ValueError(f"DDIM step: table {tuple(tab.shape)} {tab.dtype} and tau {tuple(tau_dev.shape)} {tau_dev.dtype} do not fit")
+    return tab.shape[1]
+
+
 class _MaskedLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, eps_hat, noise, mask, n_cells, l1):

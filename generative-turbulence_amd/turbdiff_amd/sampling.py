@@ -10,6 +10,11 @@ so a replay needs no new arguments.
 
 Noise comes from a counter-based generator keyed by (seed, trajectory id, offset): results do
 not depend on how trajectories are sharded over GPUs.
+
+With `sampling_timesteps = S` the same captured step walks an increasing subsequence tau of S training timesteps with
+the generalized DDIM update of Song et al. 2021 (`tdx_ddim_step_rng`; eta = 0 deterministic, eta = 1 the posterior
+variance of the sub-sampled chain) instead of the T ancestral ones: the step index k, tau and the [6, S] coefficient
+table live in device memory next to t, so a replay still needs no new arguments.
 """
 
 from __future__ import annotations
@@ -18,13 +23,23 @@ from __future__ import annotations
 import torch
 
 from . import _lib as L
-from . import ops
+from . import ops, schedules
 
 # module constants (tests flip them; they were environment A/B switches while the two routes were being compared):
 # FUSED_STEP_NOISE = False: draw z / z2 into tensors with tdx_randn_batched and run tdx_p_sample_step on them (same values);
 # COND_TABLE = False: the time MLP runs every reverse step instead of one look-up in a per-timestep table
 FUSED_STEP_NOISE = True
 COND_TABLE = True
+
+
+def check_ddim_arguments(diffusion, sampling_timesteps, eta, start_from=None):
+    """ValueError for what the DDIM sampler does not cover: learned variances (the per-voxel variance has no DDIM
+    counterpart here), a step count outside [1, L], eta outside [0, 1]."""
+    if getattr(diffusion, "learned_variances", False):
+        raise ValueError("sampling_timesteps needs fixed variances: learned_variances=True has no DDIM counterpart here")
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError(f"eta = {eta} outside [0, 1]")
+    schedules.ddim_timesteps(diffusion.num_timesteps, sampling_timesteps, start_from)
 
 
 class GraphSampler:
@@ -34,8 +49,12 @@ class GraphSampler:
     p_sample_loop` keeps one sampler per input shape and re-uses its graph from call to call."""
 
     def __init__(self, diffusion, x_bcs, C, cell_idx, seed: int = 0, trajectory_ids=None, use_graph: bool = True, nonce: int = 0,
-                 capture_stream=None):
+                 capture_stream=None, sampling_timesteps: int | None = None, eta: float = 0.0):
         self.d = diffusion
+        self.sampling_timesteps = None if sampling_timesteps is None else int(sampling_timesteps)
+        self.eta = float(eta)
+        if self.sampling_timesteps is not None:
+            check_ddim_arguments(diffusion, self.sampling_timesteps, self.eta)
         self.x_bcs = x_bcs.detach().float().contiguous().clone()
         self.C = {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in C.items()} if isinstance(C, dict) else C
         B = self.x_bcs.shape[0]
@@ -51,6 +70,13 @@ class GraphSampler:
         self.stream_ids = torch.tensor(self._sids(ids, nonce), dtype=torch.int64, device=dev)
         self.offset = torch.zeros(1, dtype=torch.int64, device=dev)
         self.t = torch.zeros(1, dtype=torch.int64, device=dev)
+        # DDIM: step index k into the subsequence tau and the [6, S] coefficient table, all on the device (the shapes are
+        # fixed by S, so `reset(start_from)` refills them under a captured graph)
+        S = self.sampling_timesteps
+        self.k = None if S is None else torch.zeros(1, dtype=torch.int64, device=dev)
+        self.tau = None if S is None else torch.zeros(S, dtype=torch.int64, device=dev)
+        self.ddim_table = None if S is None else torch.zeros(len(schedules.DDIM_PACKED_ORDER), S, dtype=torch.float32, device=dev)
+        self._taus = None  # host copy of what self.tau / self.ddim_table hold
         self.x_t = torch.empty_like(self.x_bcs)
         # noise drawn inside the update kernel (tdx_p_sample_step_rng) unless the layout rules that out; only then do the
         # two noise tensors exist at all
@@ -74,17 +100,18 @@ class GraphSampler:
         return [(int(nonce) << 32) | int(i) for i in ids]
 
     @staticmethod
-    def signature_of(diffusion, x_bcs, C):
+    def signature_of(diffusion, x_bcs, C, sampling_timesteps=None, eta=0.0):
         """What must match for `rebind`: shapes / dtypes of everything the captured step reads, and the switches the
-        captured step was built under."""
+        captured step was built under (the last two entries: the DDIM subsequence length, None = ancestral, and eta)."""
         c = tuple(sorted((str(k), tuple(v.shape), str(v.dtype)) for k, v in C.items() if torch.is_tensor(v))) \
             if isinstance(C, dict) else None
         m = diffusion.model
         return (tuple(x_bcs.shape), str(x_bcs.device), c, getattr(m, "compute_dtype", None), getattr(m, "conv_impl", None),
-                L.conv_impl(), diffusion.noise_bcs, diffusion.clip_denoised, diffusion.num_timesteps)
+                L.conv_impl(), diffusion.noise_bcs, diffusion.clip_denoised, diffusion.num_timesteps,
+                None if sampling_timesteps is None else int(sampling_timesteps), float(eta))
 
     def signature(self):
-        return self.signature_of(self.d, self.x_bcs, self.C)
+        return self.signature_of(self.d, self.x_bcs, self.C, self.sampling_timesteps, self.eta)
 
     @torch.no_grad()
     def rebind(self, x_bcs, C, cell_idx, nonce=None, trajectory_ids=None):
@@ -149,18 +176,30 @@ class GraphSampler:
 
     @torch.no_grad()
     def reset(self, start_from: int | None = None):
-        """x_T ~ N(0, I) (or q_sample(x_bcs, start_from - 1)); t <- T - 1; RNG offset <- 0."""
+        """x_T ~ N(0, I) (or q_sample(x_bcs, start_from - 1)); t <- T - 1; RNG offset <- 0.  DDIM: tau and the table are
+        refilled when `start_from` changes them; k <- S - 1, t <- tau[S - 1]."""
         d = self.d
         self.offset.zero_()
         T = d.num_timesteps if start_from is None else start_from
-        self.t.fill_(T - 1)
+        if self.sampling_timesteps is None:
+            self.t.fill_(T - 1)
+            steps = T
+        else:
+            steps = self.sampling_timesteps
+            taus = schedules.ddim_timesteps(d.num_timesteps, steps, start_from)
+            if taus != self._taus:
+                self.tau.copy_(torch.tensor(taus, dtype=torch.int64))
+                self.ddim_table.copy_(schedules.ddim_tables(d.beta_schedule, d.num_timesteps, taus, self.eta))
+                self._taus = taus
+            self.k.fill_(steps - 1)
+            self.t.fill_(taus[-1])
         self._randn(self.x_t)
         if start_from is not None:
             tt = torch.full((1,), start_from - 1, dtype=torch.int64, device=self.dev)
             self.x_t.copy_(ops.q_sample(self.x_bcs, self.x_t, d.sqrt_alphas_cumprod, d.sqrt_one_minus_alphas_cumprod, tt))
         if not d.noise_bcs:
             self.x_t.copy_(torch.where(self.mask.view(self.x_t.shape[-3:]).bool(), self.x_t, self.x_bcs))
-        self.steps_left = T
+        self.steps_left = steps
 
     # ---- one reverse step (graph body)
     def _step(self):
@@ -170,6 +209,8 @@ class GraphSampler:
             # all trajectories are at the same t: one row of the table instead of the time MLP (~12 launches per step)
             kw["cond"] = self.c_table.index_select(0, self.t).expand(self.B, -1)
         eps = d.model(self.x_t, self.t.expand(self.B), self.C, **kw)
+        if self.sampling_timesteps is not None:
+            return self._ddim_update(eps)
         if self.fused_noise:
             # same draws, same counters, bit-identical x_{t-1}; also advances the offset and decrements t
             ops.p_sample_step_rng(self.x_t, eps, self.x_bcs, self.mask, d.step_tables, d.num_timesteps, self.t,
@@ -182,13 +223,28 @@ class GraphSampler:
                           d.num_timesteps, self.t, d.noise_bcs, d.clip_denoised, out=self.x_t)
         self.t.sub_(1)
 
+    def _ddim_update(self, eps):
+        """x_{tau_k} -> x_{tau_{k-1}}, then k -= 1 and t = tau[k] on the device."""
+        d = self.d
+        if self.fused_noise:
+            ops.ddim_step_rng(self.x_t, eps, self.x_bcs, self.mask, self.ddim_table, self.k, self.tau, self.t, d.noise_bcs,
+                              d.clip_denoised, self.seed, self.stream_ids, self.offset, out=self.x_t)
+            return
+        self._randn(self.z)
+        if d.noise_bcs:
+            self._randn(self.z2)
+        ops.ddim_step(self.x_t, eps, self.z, self.z2 if d.noise_bcs else None, self.x_bcs, self.mask, self.ddim_table,
+                      self.k, self.tau, self.t, d.noise_bcs, d.clip_denoised, out=self.x_t)
+        self.k.sub_(1)
+        self.t.copy_(self.tau.index_select(0, self.k.clamp(min=0)))  # after the last step: stays tau[0]
+
     @torch.no_grad()
     def _capture(self):
         # warm up on the sampler's own side stream (packs weights, sizes the allocator, creates that stream's scratch
         # arena), then capture on the same stream: the conv kernels' arena is bound per stream (_lib.ensure_scratch), so
         # nothing is allocated inside the capture and the replayed graph never shares an arena with eager work on another
         # stream.  Re-captures (after a weight update) re-use the stream -- and with it the arena.
-        state = (self.x_t.clone(), self.t.clone(), self.offset.clone())
+        state = (self.x_t.clone(), self.t.clone(), self.offset.clone(), None if self.k is None else self.k.clone())
         if self._capture_stream is None:
             self._capture_stream = torch.cuda.Stream(device=self.dev)
         s = self._capture_stream
@@ -205,6 +261,8 @@ class GraphSampler:
         with torch.cuda.graph(self.graph, stream=s, capture_error_mode="thread_local"):
             self._step()
         self.x_t.copy_(state[0]); self.t.copy_(state[1]); self.offset.copy_(state[2])
+        if self.k is not None:
+            self.k.copy_(state[3])
         # The graph has the addresses of the packed weight operands (ops._pack_cache) baked in.  Keep those
         # buffers alive for as long as the graph lives, and remember the parameter versions they were packed
         # from: a weight update (optimiser step, load_state_dict) makes replay() re-capture instead of running on

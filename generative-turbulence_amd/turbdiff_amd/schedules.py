@@ -100,6 +100,58 @@ def pack_step_tables(tab: dict[str, torch.Tensor]) -> torch.Tensor:
     return torch.stack([tab[k] for k in PACKED_ORDER]).contiguous()
 
 
+# order of the 6 rows of the packed [6, S] array consumed by tdx_ddim_step (column k = step k of the subsequence);
+# a = abar[tau_k], p = abar[tau_{k-1}] (1 at k = 0), sigma as in Song et al. 2021, eq. 16
+DDIM_PACKED_ORDER = (
+    "sqrt_recip_a",      # rsqrt(a)
+    "sqrt_recipm1_a",    # sqrt(1 / a - 1)
+    "sqrt_p",            # sqrt(p)
+    "dir",               # sqrt(max(1 - p - sigma^2, 0))
+    "sigma",             # eta sqrt((1 - p) / (1 - a)) sqrt(max(1 - a / p, 0))
+    "sqrt_one_minus_p",  # sqrt(1 - p)
+)
+
+
+def ddim_timesteps(T: int, steps: int, start_from: int | None = None) -> list[int]:
+    """The increasing subsequence tau of the training timesteps a `steps`-step DDIM sampler visits (in reverse): evenly
+    spread over 0 .. L - 1 with both ends included, L = T or `start_from`.  Integer arithmetic (round half up), so the
+    same on every host."""
+    L = int(T) if start_from is None else int(start_from)
+    S = int(steps)
+    if not 1 <= L <= int(T):
+        raise ValueError(f"start_from = {start_from} outside [1, {T}]")
+    if not 1 <= S <= L:
+        raise ValueError(f"sampling_timesteps = {steps} outside [1, {L}]")
+    if S == 1:
+        return [L - 1]
+    return [(k * (L - 1) + (S - 1) // 2) // (S - 1) for k in range(S)]
+
+
+def ddim_tables(beta_schedule: str, T: int, taus, eta: float, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """[6, S] coefficients of the generalized DDIM step over the subsequence `taus` (rows: DDIM_PACKED_ORDER), evaluated
+    in float64 and rounded once.  eta = 0: deterministic; eta = 1: the posterior variance of the sub-sampled chain."""
+    eta = float(eta)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"eta = {eta} outside [0, 1]")
+    taus = [int(t) for t in taus]
+    if not taus or taus[0] < 0 or taus[-1] >= T or any(b <= a for a, b in zip(taus, taus[1:])):
+        raise ValueError(f"taus must be a strictly increasing subsequence of 0 .. {T - 1}")
+    abar = torch.cumprod(1.0 - betas_for(beta_schedule, T).to(torch.float64), dim=0)
+    a = abar[torch.tensor(taus, dtype=torch.int64)]
+    p = torch.nn.functional.pad(a[:-1], (1, 0), value=1.0)
+    # the clamps: 1 - a / p and 1 - p - sigma^2 are 0 in exact arithmetic where float64 can land an ulp below it (k = 0)
+    sigma = eta * torch.sqrt((1.0 - p) / (1.0 - a)) * torch.sqrt(torch.clamp(1.0 - a / p, min=0.0))
+    rows = {
+        "sqrt_recip_a": torch.rsqrt(a),
+        "sqrt_recipm1_a": torch.sqrt(1.0 / a - 1),
+        "sqrt_p": torch.sqrt(p),
+        "dir": torch.sqrt(torch.clamp(1.0 - p - sigma * sigma, min=0.0)),
+        "sigma": sigma,
+        "sqrt_one_minus_p": torch.sqrt(1.0 - p),
+    }
+    return torch.stack([rows[k] for k in DDIM_PACKED_ORDER]).to(dtype).contiguous()
+
+
 def nyquist_embedding_tables(dim: int, timesteps: int) -> tuple[torch.Tensor, torch.Tensor]:
     """(scale, bias) of the time embedding sin(bias + scale t)  (ddpm.py:122-148)."""
     assert dim % 2 == 0

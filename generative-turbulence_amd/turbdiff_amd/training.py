@@ -158,6 +158,10 @@ class DiffusionTrainer(nn.Module):
         # fp16 training: initial loss scale (a power of two), or None = chosen from the first batch so that the seed of the
         # backward pass, 2 (eps_hat - eps) / (B F n_cells), lands near 2^-3 (initial_loss_scale)
         self.loss_scale = None
+        # sampling: None = the full ancestral chain; S = DDIM over S of the training timesteps with `sampling_eta`
+        # (GaussianDiffusion.p_sample_loop); what sample / sample_cells / validation_step / measure_sample_time use
+        self.sampling_timesteps = None
+        self.sampling_eta = 0.0
         self._opt = self._sched = None
         self.ddp = None  # set to a parallel.BucketedDataParallel(self) for multi-GPU training
         self.stats = None
@@ -252,23 +256,27 @@ class DiffusionTrainer(nn.Module):
         return loss
 
     @torch.no_grad()
-    def sample(self, batch, start_from=None, noise_fn=None):
-        """diffusion.py:152-158: dense denormalised samples (B, F, X, Y, Z)."""
-        x = self._sample_normalized(batch, start_from, noise_fn)
+    def sample(self, batch, start_from=None, noise_fn=None, sampling_timesteps=None, eta=None):
+        """diffusion.py:152-158: dense denormalised samples (B, F, X, Y, Z).  `sampling_timesteps` / `eta`, when given, stand in for
+        the trainer's `sampling_timesteps` / `sampling_eta` for this call."""
+        x = self._sample_normalized(batch, start_from, noise_fn, sampling_timesteps, eta)
         if self._is_openfoam_batch(batch):
             return self.normalization.denormalize_grid(x, batch.stats)
         return self.denormalize_grid(x, batch.mean, batch.std)
 
     @torch.no_grad()
-    def sample_cells(self, batch, start_from=None, noise_fn=None):
+    def sample_cells(self, batch, start_from=None, noise_fn=None, sampling_timesteps=None, eta=None):
         """The samples as ``SampleStore.add_samples`` stores them (metrics.py:52-58): per variable the
         denormalised in-domain values, channels-last (B, n_cells, dims) -- one fused egress kernel."""
-        x = self._sample_normalized(batch, start_from, noise_fn)
+        x = self._sample_normalized(batch, start_from, noise_fn, sampling_timesteps, eta)
         return self.normalization.denormalized_cells(x, batch.data.metadata, batch.stats)
 
-    def _sample_normalized(self, batch, start_from, noise_fn):
+    def _sample_normalized(self, batch, start_from, noise_fn, sampling_timesteps=None, eta=None):
         x, C = self._model_input(batch)
+        steps = self.sampling_timesteps if sampling_timesteps is None else sampling_timesteps
         kw = {}
+        if steps is not None:
+            kw.update(sampling_timesteps=steps, eta=self.sampling_eta if eta is None else eta)
         if noise_fn is None and not self.model.learned_variances:
             # identically seeded ranks draw the same per-call nonce: the trajectory ids keep their noise streams apart
             # (rank r samples trajectories r B ... r B + B - 1 of the global set, whatever the sharding)

@@ -341,6 +341,34 @@ int tdx_p_sample_step_rng(const float* x_t, const float* eps, const float* x_bcs
                           int T, int64_t* t, int noise_bcs, int clip, float* out, int B, int F, int64_t V, uint64_t seed,
                           const uint64_t* stream_ids, uint64_t* offset_dev, void* stream);
 
+/* One generalized DDIM step (Song et al. 2021, eq. 12) over an increasing subsequence tau[0..S-1] of the training
+ * timesteps, from tau[k] to tau[k-1]; not in the reference.  tab = 6 consecutive f32 rows of length S, column k:
+ *   recip = rsqrt(a), recipm1 = sqrt(1/a - 1), sp = sqrt(p), dir = sqrt(1 - p - sigma^2), sigma, sbp = sqrt(1 - p)
+ * with a = abar[tau[k]], p = abar[tau[k-1]] (1 at k = 0), sigma = eta sqrt((1-p)/(1-a)) sqrt(1 - a/p).  Per element:
+ *   raw = recip x_t - recipm1 eps
+ *   x0  = raw;  [!noise_bcs: x0 = x_t outside mask];  [clip +-1]                (as tdx_p_sample_step forms it)
+ *   e   = x0 == raw ? eps : (recip x_t - x0) / recipm1                           (predict_noise_from_start)
+ *   r   = sp x0 + dir e
+ *   k == 0:  out = r, then out = x_bcs outside the mask
+ *   k  > 0:  inside the mask out = r + sigma z (z is not read where sigma == 0);
+ *            noise_bcs: outside the mask out = sp x_bcs + sbp z2
+ * i.e. boundary cells are re-noised at the level of the state PRODUCED, tau[k-1].  (The ancestral step re-noises them at
+ * level t for x_{t-1}, one level off; a subsequence cannot keep that offset.)
+ * k and t are device int64 scalars, tau a device int64 array of length S; the update reads column k only (t == tau[k] is
+ * what the model ran at).  k outside [0, S) writes nothing.  z, z2 may be NULL when unused (NULL reads as no noise). */
+int tdx_ddim_step(const float* x_t, const float* eps, const float* z, const float* z2, const float* x_bcs,
+                  const uint8_t* mask, const float* tab, int S, const int64_t* k, const int64_t* tau, const int64_t* t,
+                  int noise_bcs, int clip, float* out, int B, int F, int64_t V, void* stream);
+
+/* The same DDIM step with its noise drawn inside the kernel (needs V % 4 == 0 and 16-byte aligned tensors): bit-identical
+ * to tdx_randn_batched(z, ...); [tdx_randn_batched(z2, ...) if noise_bcs;] tdx_ddim_step(...) with the same seed, stream
+ * ids and offset (z: counter offset + i, z2: offset + F V / 4 + i, as tdx_p_sample_step_rng).  Afterwards, on the device:
+ * *offset_dev += (noise_bcs ? 2 : 1) * F V / 4 whatever eta is (the draws for z are skipped at sigma == 0, their counters
+ * are not re-used); *k -= 1; if (*k >= 0) *t = tau[*k]. */
+int tdx_ddim_step_rng(const float* x_t, const float* eps, const float* x_bcs, const uint8_t* mask, const float* tab, int S,
+                      int64_t* k, const int64_t* tau, int64_t* t, int noise_bcs, int clip, float* out, int B, int F,
+                      int64_t V, uint64_t seed, const uint64_t* stream_ids, uint64_t* offset_dev, void* stream);
+
 /* Masked loss (ddpm.py:845-852): loss = mean_b mean_{f, cells} err(eps_hat, noise),
  * err = squared (l1 = 0) or absolute (l1 = 1) error.  n_cells = number of mask ones.
  * Writes loss[0] and, if grad != NULL, d loss / d eps_hat (zero outside the mask). */

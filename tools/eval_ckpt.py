@@ -15,7 +15,8 @@ Differences, all on the I/O side (no h5py / POT in this image): validation cases
 paper table reports; ``--sample-metrics`` adds the reference's own ``SampleMetricsCollection`` metrics without the
 expensive one (``tke-front``, ``tke-middle``, ``tke-back``, ``tke``, ``max-mean-tke-pos``, as the reference's
 eval_ckpt.py computes them with ``expensive_metrics=False``), ``--expensive-metrics`` also ``wasserstein`` (exact W2 by
-the batched device auction).  Their side files (``regions.npz``, ``max-mean-tke.npy``, ``mean-flow.h5``) come from an
+the batched device auction).  ``--sampling-steps N [--eta E]`` draws the samples with the DDIM sampler over N of the training
+timesteps instead of the full ancestral chain (what that does to the metrics has not been measured).  Their side files (``regions.npz``, ``max-mean-tke.npy``, ``mean-flow.h5``) come from an
 optional ``side`` entry of the ``--cases`` blob, ``{case_name: {file name: value}}``; ``--synthetic`` cases bring their
 own (channel-aligned region blocks, a nominal max-mean-TKE position).
 """
@@ -127,8 +128,10 @@ def sample_metrics(store, cases, stats, device, *, side=None, expensive=False, p
 
 
 def evaluate(ckpt: dict, cases, stats, device, *, overrides=(), seed=2883413570083077179, samples_path=None,
-             eval_batch_size=None, val_samples=2, discard_first_seconds=0.0, start_from=None, compute_mode=None):
-    """The body of eval_ckpt.py:43-76.  Returns (store, metrics dict, task)."""
+             eval_batch_size=None, val_samples=2, discard_first_seconds=0.0, start_from=None, compute_mode=None,
+             sampling_steps=None, eta=0.0):
+    """The body of eval_ckpt.py:43-76.  Returns (store, metrics dict, task).  `sampling_steps`: sample with the DDIM
+    sampler over that many of the training timesteps (and `eta`) instead of the full ancestral chain."""
     from turbdiff_amd.data.ofles import InMemoryRepository, OpenFOAMDataset, OpenFOAMEvaluationSampler
     from turbdiff_amd.data.staging import DeviceStager
     from turbdiff_amd.models.metrics import LogTKESpectrumL2Distance, SampleStore
@@ -141,6 +144,7 @@ def evaluate(ckpt: dict, cases, stats, device, *, overrides=(), seed=28834135700
     task = DiffusionTrainer.from_config(config, max_train_steps=1, compute_mode=compute_mode)
     task.load_state_dict(ckpt["state_dict"], strict=True)
     task = task.to(device).eval()
+    task.sampling_timesteps, task.sampling_eta = sampling_steps, eta
 
     dataset = OpenFOAMDataset(InMemoryRepository(cases), stats, discard_first_seconds)
     bs = eval_batch_size or int(config["model"].get("eval_batch_size", 8))
@@ -186,6 +190,9 @@ def main():
     ap.add_argument("--cases", help="torch.save'd {'cases': [...], 'stats': OpenFOAMStats.stats} of the validation cases")
     ap.add_argument("--synthetic", type=int, default=0, help="evaluate on N synthetic cases instead")
     ap.add_argument("--start-from", type=int, default=None, help="start the reverse process at this step (smoke runs)")
+    ap.add_argument("--sampling-steps", type=int, default=None,
+                    help="DDIM sampling over this many of the training timesteps instead of the full ancestral chain")
+    ap.add_argument("--eta", type=float, default=0.0, help="with --sampling-steps: 0 = deterministic DDIM ... 1 = posterior variance")
     ap.add_argument("--compute-mode", default=None, choices=[None, "f32", "f32s", "bf16", "fp16"])
     ap.add_argument("--sample-metrics", action="store_true", help="also print the reference's cheap sample metrics")
     ap.add_argument("--expensive-metrics", action="store_true", help="with --sample-metrics, also the Wasserstein metric")
@@ -209,7 +216,8 @@ def main():
         cases, stats = synthetic_cases(max(args.synthetic, 1))
     device = torch.device(args.device)
     store, metrics, _ = evaluate(ckpt, cases, stats, device, overrides=args.overrides, seed=args.seed,
-                                 samples_path=samples_path, start_from=args.start_from, compute_mode=args.compute_mode)
+                                 samples_path=samples_path, start_from=args.start_from, compute_mode=args.compute_mode,
+                                 sampling_steps=args.sampling_steps, eta=args.eta)
     if args.sample_metrics or args.expensive_metrics:
         metrics.update(sample_metrics(store, cases, stats, device, side=side, expensive=args.expensive_metrics))
     for key in sorted(metrics):

@@ -5,6 +5,9 @@ one hipGraph-captured reverse step per replay (no collective inside the loop).
   python tools/sample_bench.py --trajectories 8 --timesteps 1000            # 1 GPU
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/sample_bench.py --trajectories 64
 
+  python tools/sample_bench.py --trajectories 8 --sampling-steps 50 --eta 0  # DDIM over 50 of the 1000 timesteps; the
+                                                                            # ancestral sampler is timed in the same process
+
 Prints one JSON line (rank 0): whole-job samples/s = trajectories / max-over-ranks wall time."""
 import argparse, json, sys, time
 from pathlib import Path
@@ -20,6 +23,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--trajectories", type=int, default=8)
 ap.add_argument("--timesteps", type=int, default=1000)
 ap.add_argument("--steps", type=int, default=0, help="time only this many reverse steps and extrapolate (0 = full loop)")
+ap.add_argument("--sampling-steps", type=int, default=None,
+                help="DDIM sampling over this many of the training timesteps; the ancestral loop is timed first, as `ancestral`")
+ap.add_argument("--eta", type=float, default=0.0, help="with --sampling-steps: 0 = deterministic DDIM ... 1 = posterior variance")
 ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "f32", "f32s"])
 ap.add_argument("--no-graph", action="store_true")
 a = ap.parse_args()
@@ -33,23 +39,43 @@ diff = bench.build_model(dev, bench.MODE_DTYPE[a.dtype], timesteps=a.timesteps)
 ids = list(parallel.shard_trajectories(a.trajectories, rank, world))
 x, c, cell_idx = bench.synthetic_inputs(len(ids), dev)
 C = {Conditioning.Type.CELL_TYPE: c}
-s = GraphSampler(diff, x, C, cell_idx, seed=0, trajectory_ids=ids, use_graph=not a.no_graph)
-s.run_steps(2); s.reset()          # warm-up incl. graph capture
-torch.cuda.synchronize()
-if world > 1: torch.distributed.barrier()
-t0 = time.perf_counter()
-n = a.steps if a.steps > 0 else a.timesteps
-s.run_steps(n)
-torch.cuda.synchronize()
-dt = time.perf_counter() - t0
-if world > 1:
-    t = torch.tensor([dt], device=dev, dtype=torch.float64)
-    torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX); dt = t.item()
+
+
+def measure(total, **kw):
+    """(seconds for the timed steps, timed steps, sampler) of a sampler whose full loop has `total` reverse steps"""
+    s = GraphSampler(diff, x, C, cell_idx, seed=0, trajectory_ids=ids, use_graph=not a.no_graph, **kw)
+    s.run_steps(2); s.reset()          # warm-up incl. graph capture
+    torch.cuda.synchronize()
+    if world > 1: torch.distributed.barrier()
+    t0 = time.perf_counter()
+    n = min(a.steps, total) if a.steps > 0 else total
+    s.run_steps(n)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([dt], device=dev, dtype=torch.float64)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX); dt = t.item()
+    return dt, n, s
+
+
+def record(dt, n, total):
+    return {"timed_steps": n, "extrapolated": n != total, "ms_per_reverse_step": 1e3 * dt / n, "seconds_per_batch": dt * total / n}
+
+
+total = a.timesteps if a.sampling_steps is None else a.sampling_steps
+extra = {}
+if a.sampling_steps is not None:
+    dt, n, s = measure(a.timesteps)
+    extra = {"sampling_steps": a.sampling_steps, "eta": a.eta, "ancestral": record(dt, n, a.timesteps)}
+    del s
+    dt, n, s = measure(total, sampling_timesteps=a.sampling_steps, eta=a.eta)
+else:
+    dt, n, s = measure(total)
 if rank == 0:
-    full = dt * a.timesteps / n
+    full = dt * total / n
     print(json.dumps({"metric": "DDPM samples/sec (192x64x48x4)", "value": a.trajectories / full, "unit": "samples/s",
                       "n_gpus": world, "trajectories": a.trajectories, "per_gpu": len(ids), "timesteps": a.timesteps,
-                      "timed_steps": n, "extrapolated": n != a.timesteps, "ms_per_reverse_step": 1e3 * dt / n,
-                      "dtype": a.dtype, "hipgraph": not a.no_graph, "finite": bool(torch.isfinite(s.x_t).all())}))
+                      **record(dt, n, total), "dtype": a.dtype, "hipgraph": not a.no_graph,
+                      "finite": bool(torch.isfinite(s.x_t).all()), **extra}))
 if world > 1:
     torch.distributed.barrier(); torch.distributed.destroy_process_group()
