@@ -327,6 +327,171 @@ extern "C" int tdx_masked_loss_dyn(const float* eps_hat, const float* noise, con
     return masked_loss_launch(eps_hat, noise, mask, 0, n_cells_dev, l1, loss, grad, B, F, V, workspace, stream);
 }
 
+// ------------------------------------------------------------------ simple + ELBO loss (learned variances) ---
+// The loss of the learned-variance model (ddpm.py:853-870) in one pass over out = [eps_hat | w] (B, 2F, V): the masked
+// simple loss on eps_hat plus elbo_weight times the variational bound term -- KL(q(x_{t-1} | x_t, x_0) || p) for samples
+// at t > 0, the negative log-likelihood (evaluated at x_t, as the reference does) for samples at t == 0 -- with
+// log_var = lb + sigmoid(w) (plv - lb) per element, and its gradient with respect to all 2F planes.  One block row per
+// (b, f) plane, so the sample's t and its table entries are block-uniform scalars.
+struct ElboCoef {
+    double recip, recipm1, c1, c2, lb, plv, dl, epl;  // dl = plv - lb, epl = exp(plv)
+    bool first;                                       // t == 0: likelihood term
+};
+__device__ __forceinline__ ElboCoef elbo_coef(const float* __restrict__ sched, const float* __restrict__ plv, int T, int64_t t) {
+    ElboCoef c;
+    c.recip = sched[t]; c.recipm1 = sched[T + t]; c.c1 = sched[2 * T + t]; c.c2 = sched[3 * T + t];
+    c.lb = sched[4 * T + t]; c.plv = plv[t]; c.dl = c.plv - c.lb; c.epl = exp(c.plv);
+    c.first = (t == 0);
+    return c;
+}
+// sigmoid of the variance weight for the reverse step (float; the loss below evaluates its own in double)
+__device__ __forceinline__ float lv_sigmoid(float w) { return 1.0f / (1.0f + expf(-w)); }
+
+// one in-domain element: adds its two loss terms to (simple, elbo) and returns the gradients of
+// gscale * (simple + elbo_weight * elbo) with respect to eps_hat and w.
+// The ELBO term is evaluated in DOUBLE from the float inputs.  Its summands reach |log_var| + (diff^2) exp(-log_var) --
+// tens at t == 0, where exp(-log_var) ~ 1e3 -- while their mean is O(1) and the total subtracts it from the simple term:
+// in float the per-element roundings of log_var alone (|log_var| 2^-24 ~ 4e-7) left the mean 2e-7 off and the total
+// several ulps off where the two terms cancel.  Two double exponentials per element; the pass moves 28 B per element.  The simple term's gradient is the float expression of masked_loss_kernel, bit for bit.
+__device__ __forceinline__ void elbo_elem(const ElboCoef& c, float eps, float w, float noise, float xs, float xt, int l1,
+                                          int clip, int detach_mean, float gscale, double escale, double& simple, double& elbo,
+                                          float& g_eps, float& g_w) {
+    const float d = eps - noise;
+    const double dd = (double)eps - (double)noise;
+    if (l1) { simple += fabs(dd); g_eps = (d > 0.f) ? gscale : ((d < 0.f) ? -gscale : 0.f); }
+    else { simple += dd * dd; g_eps = 2.0f * d * gscale; }
+    const double s = 1.0 / (1.0 + exp(-(double)w));
+    const double lv = c.lb + s * c.dl;
+    const double raw = c.recip * xt - c.recipm1 * eps;
+    const double x0 = clip ? fmin(fmax(raw, -1.0), 1.0) : raw;
+    const bool pass = (x0 == raw);  // torch.clamp: the gradient passes for -1 <= x0 <= 1
+    // t > 0: true_mean - mean = c1 (x_start - x0), the c2 x_t of both means cancels; t == 0: x_t - mean
+    const double diff = c.first ? xt - (c.c1 * x0 + c.c2 * xt) : c.c1 * (xs - x0);
+    const double inv = exp(-lv);
+    const double q = diff * diff * inv;
+    const double a = c.first ? 0.0 : c.epl * inv;                       // exp(plv - log_var)
+    const double cst = c.first ? 1.8378770664093453 : -c.plv - 1.0;     // log(2 pi)
+    elbo += 0.5 * (lv + cst + a + q);
+    g_w = (float)(escale * (0.5 * (1.0 - a - q)) * (c.dl * s * (1.0 - s)));
+    // d term / d mean = -diff inv in both branches; d mean / d eps_hat = -c1 recipm1 where the clip left x0 alone
+    if (!detach_mean && pass) g_eps = (float)((double)g_eps + escale * (diff * inv * (c.c1 * c.recipm1)));
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+elbo_loss_kernel(const float* __restrict__ out, const float* __restrict__ noise, const float* __restrict__ x_start,
+                 const float* __restrict__ x_t, const uint8_t* __restrict__ mask, const int64_t* __restrict__ t,
+                 const float* __restrict__ sched, const float* __restrict__ plv, int T, int l1, int clip, int detach_mean,
+                 double elbo_weight, double* __restrict__ acc, float* __restrict__ grad, double inv_n, int F, int64_t V,
+                 const int64_t* __restrict__ n_cells_dev, double samples, double quant) {
+    if (n_cells_dev) inv_n = 1.0 / (samples * (double)*n_cells_dev);
+    const float gscale = (float)inv_n;  // as masked_loss_kernel
+    const double escale = elbo_weight * inv_n;
+    const int plane = blockIdx.y, b = plane / F, f = plane - b * F;
+    const ElboCoef c = elbo_coef(sched, plv, T, t[b]);
+    const int64_t base = (int64_t)plane * V;                      // noise, x_start, x_t
+    const int64_t ebase = ((int64_t)b * 2 * F + f) * V, wbase = ebase + (int64_t)F * V;  // out, grad
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    double ssum = 0.0, esum = 0.0;
+    if (VEC) {
+        const int64_t V4 = V >> 2;
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V4; i += stride) {
+            const float4 e4 = *reinterpret_cast<const float4*>(out + ebase + 4 * i);
+            const float4 w4 = *reinterpret_cast<const float4*>(out + wbase + 4 * i);
+            const float4 n4 = *reinterpret_cast<const float4*>(noise + base + 4 * i);
+            const float4 s4 = *reinterpret_cast<const float4*>(x_start + base + 4 * i);
+            const float4 x4 = *reinterpret_cast<const float4*>(x_t + base + 4 * i);
+            const unsigned m = *reinterpret_cast<const unsigned*>(mask + 4 * i);
+            const float e[4] = {e4.x, e4.y, e4.z, e4.w}, w[4] = {w4.x, w4.y, w4.z, w4.w}, n[4] = {n4.x, n4.y, n4.z, n4.w};
+            const float xs[4] = {s4.x, s4.y, s4.z, s4.w}, xt[4] = {x4.x, x4.y, x4.z, x4.w};
+            float ge[4] = {0.f, 0.f, 0.f, 0.f}, gw[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if ((m >> (8 * k)) & 0xffu)
+                    elbo_elem(c, e[k], w[k], n[k], xs[k], xt[k], l1, clip, detach_mean, gscale, escale, ssum, esum, ge[k], gw[k]);
+            if (grad) {
+                *reinterpret_cast<float4*>(grad + ebase + 4 * i) = make_float4(ge[0], ge[1], ge[2], ge[3]);
+                *reinterpret_cast<float4*>(grad + wbase + 4 * i) = make_float4(gw[0], gw[1], gw[2], gw[3]);
+            }
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += stride) {
+            float ge = 0.f, gw = 0.f;
+            if (mask[i])
+                elbo_elem(c, out[ebase + i], out[wbase + i], noise[base + i], x_start[base + i], x_t[base + i], l1, clip,
+                          detach_mean, gscale, escale, ssum, esum, ge, gw);
+            if (grad) { grad[ebase + i] = ge; grad[wbase + i] = gw; }
+        }
+    }
+    __shared__ double part[2][4];
+    const double ws = wave_sum(ssum), we = wave_sum(esum);
+    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = ws; part[1][threadIdx.x >> 6] = we; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        double s = part[threadIdx.x][0] + part[threadIdx.x][1] + part[threadIdx.x][2] + part[threadIdx.x][3];
+        if (quant != 0.0) s = rint(s * quant) / quant;  // TDX_DETERMINISTIC: exact (order-independent) f64 sums, as masked_loss_kernel
+        atomicAdd(acc + threadIdx.x, s);
+    }
+}
+// loss = {total, simple, elbo}: both terms are means over the same B F n_cells elements
+__global__ void elbo_loss_finish(const double* acc, float* loss, double inv, const int64_t* n_cells_dev, double samples,
+                                 double elbo_weight) {
+    if (n_cells_dev) inv = 1.0 / (samples * (double)*n_cells_dev);
+    const double simple = acc[0] * inv, elbo = acc[1] * inv;
+    loss[0] = (float)(simple + elbo_weight * elbo);
+    loss[1] = (float)simple;
+    loss[2] = (float)elbo;
+}
+
+extern "C" size_t tdx_elbo_loss_workspace_bytes(void) { return 16; }
+static int elbo_loss_launch(const float* out, const float* noise, const float* x_start, const float* x_t, const uint8_t* mask,
+                            int64_t n_cells, const int64_t* n_cells_dev, const int64_t* t, const float* sched,
+                            const float* plv, int T, int l1, int clip, int detach_mean, double elbo_weight, float* loss,
+                            float* grad, int B, int F, int64_t V, void* workspace, void* stream) {
+    int err = tdx_zero_async(workspace, 16, as_stream(stream));
+    if (err != TDX_OK) return err;
+    const double samples = (double)B * F;
+    const double inv = n_cells_dev ? 0.0 : 1.0 / (samples * (double)n_cells);
+    const double quant = tdx_deterministic() ? 1048576.0 : 0.0;  // block partials on a 2^-20 grid, as masked_loss_launch
+    const bool vec = (V % 4) == 0 && (((uintptr_t)out | (uintptr_t)noise | (uintptr_t)x_start | (uintptr_t)x_t | (uintptr_t)grad) % 16) == 0 &&
+                     ((uintptr_t)mask % 4) == 0;
+    if (vec) {
+        dim3 grid((unsigned)min((int64_t)128, (V / 4 + 255) / 256), B * F);
+        hipLaunchKernelGGL(elbo_loss_kernel<true>, grid, dim3(256), 0, as_stream(stream), out, noise, x_start, x_t, mask, t,
+                           sched, plv, T, l1, clip, detach_mean, elbo_weight, (double*)workspace, grad, inv, F, V,
+                           n_cells_dev, samples, quant);
+    } else {
+        dim3 grid((unsigned)min((int64_t)64, (V + 255) / 256), B * F);
+        hipLaunchKernelGGL(elbo_loss_kernel<false>, grid, dim3(256), 0, as_stream(stream), out, noise, x_start, x_t, mask, t,
+                           sched, plv, T, l1, clip, detach_mean, elbo_weight, (double*)workspace, grad, inv, F, V,
+                           n_cells_dev, samples, quant);
+    }
+    hipLaunchKernelGGL(elbo_loss_finish, dim3(1), dim3(1), 0, as_stream(stream), (const double*)workspace, loss, inv,
+                       n_cells_dev, samples, elbo_weight);
+    return tdx_launch_status();
+}
+
+extern "C" int tdx_elbo_loss(const float* out, const float* noise, const float* x_start, const float* x_t,
+                             const uint8_t* mask, int64_t n_cells, const int64_t* t, const float* sched,
+                             const float* posterior_log_var, int T, int l1, int clip, int detach_mean, double elbo_weight,
+                             float* loss, float* grad, int B, int F, int64_t V, void* workspace, void* stream) {
+    TDX_CHECK_ARG(out && noise && x_start && x_t && mask && t && sched && posterior_log_var && loss && workspace);
+    TDX_CHECK_ARG(n_cells > 0 && T > 0 && B > 0 && F > 0 && V > 0);
+    return elbo_loss_launch(out, noise, x_start, x_t, mask, n_cells, nullptr, t, sched, posterior_log_var, T, l1, clip,
+                            detach_mean, elbo_weight, loss, grad, B, F, V, workspace, stream);
+}
+// n_cells read from device memory when the kernels run, as tdx_masked_loss_dyn: the captured training step
+extern "C" int tdx_elbo_loss_dyn(const float* out, const float* noise, const float* x_start, const float* x_t,
+                                 const uint8_t* mask, const int64_t* n_cells_dev, const int64_t* t, const float* sched,
+                                 const float* posterior_log_var, int T, int l1, int clip, int detach_mean,
+                                 double elbo_weight, float* loss, float* grad, int B, int F, int64_t V, void* workspace,
+                                 void* stream) {
+    TDX_CHECK_ARG(out && noise && x_start && x_t && mask && t && sched && posterior_log_var && loss && workspace);
+    TDX_CHECK_ARG(n_cells_dev && T > 0 && B > 0 && F > 0 && V > 0);
+    return elbo_loss_launch(out, noise, x_start, x_t, mask, 0, n_cells_dev, t, sched, posterior_log_var, T, l1, clip,
+                            detach_mean, elbo_weight, loss, grad, B, F, V, workspace, stream);
+}
+
 // ------------------------------------------------------------------ Philox N(0,1) --------
 __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
     const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
@@ -471,6 +636,141 @@ extern "C" int tdx_p_sample_step_rng(const float* x_t, const float* eps, const f
     dim3 grid((unsigned)min((int64_t)256, (n4 + 255) / 256), B);
     hipLaunchKernelGGL(p_sample_step_rng_kernel, grid, dim3(256), 0, as_stream(stream), x_t, eps, x_bcs, mask, sched, T,
                        (const int64_t*)t, noise_bcs, clip, out, V, n4, seed, stream_ids, (const uint64_t*)offset_dev);
+    hipLaunchKernelGGL(advance_step, dim3(1), dim3(1), 0, as_stream(stream), offset_dev,
+                       (uint64_t)(noise_bcs ? 2 * n4 : n4), t);
+    return tdx_launch_status();
+}
+
+// ------------------------------------------------------------------ reverse step, learned variances ---
+// p_sample_step_kernel for the model that also predicts its variance (ddpm.py:732-741): `mo` is the decoder's output
+// (B, 2F, V) = [eps_hat | w], and the noise inside the domain is scaled per element by sigma = exp(log_var / 2),
+// log_var = lb + sigmoid(w) (plv - lb), lb = log_betas[t], plv = posterior_log_var[t], instead of by exp(lb / 2).
+struct LvStepCoef {
+    float recip, recipm1, c1, c2, lb, dl, sa, sb;  // dl = plv - lb
+    bool last;
+};
+__device__ __forceinline__ LvStepCoef lv_step_coef(const float* __restrict__ sched, const float* __restrict__ plv, int T, int64_t t) {
+    LvStepCoef c;
+    c.recip = sched[t]; c.recipm1 = sched[T + t]; c.c1 = sched[2 * T + t]; c.c2 = sched[3 * T + t];
+    c.lb = sched[4 * T + t]; c.dl = plv[t] - c.lb;
+    c.sa = sched[5 * T + t]; c.sb = sched[6 * T + t];
+    c.last = (t == 0);
+    return c;
+}
+// one element; both kernels below go through it, every multiply-add spelled as an fmaf for the reason given at
+// ddim_update (the two entries are specified to agree bit for bit).  w and z are read only where they are used.
+__device__ __forceinline__ float lv_step_update(const LvStepCoef& c, float xt, float eps, float w, float z, float z2, float xb,
+                                                bool inside, int noise_bcs, int clip) {
+    float x0 = fmaf(c.recip, xt, -(c.recipm1 * eps));
+    if (!noise_bcs && !inside) x0 = xt;
+    if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    float r = fmaf(c.c1, x0, c.c2 * xt);
+    if (c.last) {
+        if (!inside) r = xb;
+    } else if (inside) {
+        const float sigma = expf(0.5f * fmaf(lv_sigmoid(w), c.dl, c.lb));
+        r = fmaf(sigma, z, r);
+    } else if (noise_bcs) {
+        r = fmaf(c.sa, xb, c.sb * z2);
+    }
+    return r;
+}
+
+__global__ void __launch_bounds__(256)
+p_sample_step_lv_kernel(const float* __restrict__ x_t, const float* __restrict__ mo, const float* __restrict__ z,
+                        const float* __restrict__ z2, const float* __restrict__ x_bcs, const uint8_t* __restrict__ mask,
+                        const float* __restrict__ sched, const float* __restrict__ plv, int T, const int64_t* __restrict__ tp,
+                        int noise_bcs, int clip, float* __restrict__ out, int F, int64_t V) {
+    const int64_t t = *tp;
+    if (t < 0 || t >= T) return;  // a finished trajectory: no column to read
+    const LvStepCoef c = lv_step_coef(sched, plv, T, t);
+    // a NULL noise tensor reads as "no noise" rather than being dereferenced (the host cannot see t)
+    const bool use_z = !c.last && z, use_z2 = !c.last && noise_bcs && z2;
+    const int plane = blockIdx.y, b = plane / F, f = plane - b * F;
+    const int64_t base = (int64_t)plane * V;
+    const int64_t ebase = ((int64_t)b * 2 * F + f) * V, wbase = ebase + (int64_t)F * V;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += stride) {
+        const bool inside = mask[i] != 0;
+        const bool noisy = use_z && inside;
+        const float zz = noisy ? z[base + i] : 0.f, ww = noisy ? mo[wbase + i] : 0.f;
+        const float zb = (use_z2 && !inside) ? z2[base + i] : 0.f;
+        out[base + i] = lv_step_update(c, x_t[base + i], mo[ebase + i], ww, zz, zb, x_bcs[base + i], inside, noise_bcs, clip);
+    }
+}
+
+extern "C" int tdx_p_sample_step_lv(const float* x_t, const float* model_out, const float* z, const float* z2,
+                                    const float* x_bcs, const uint8_t* mask, const float* sched,
+                                    const float* posterior_log_var, int T, const int64_t* t, int noise_bcs, int clip,
+                                    float* out, int B, int F, int64_t V, void* stream) {
+    TDX_CHECK_ARG(x_t && model_out && x_bcs && mask && sched && posterior_log_var && t && out);
+    TDX_CHECK_ARG(T > 0 && B > 0 && F > 0 && V > 0);
+    dim3 grid((unsigned)min((int64_t)128, (V + 255) / 256), B * F);
+    hipLaunchKernelGGL(p_sample_step_lv_kernel, grid, dim3(256), 0, as_stream(stream), x_t, model_out, z, z2, x_bcs, mask,
+                       sched, posterior_log_var, T, t, noise_bcs, clip, out, F, V);
+    return tdx_launch_status();
+}
+
+// The same update with z and z2 drawn where they are consumed, laid out, counted and skipped exactly as
+// p_sample_step_rng_kernel does (z: counter off + i, z2: off + n4 + i, n4 = F V / 4 over the F STATE planes), so a run is
+// bit-identical to tdx_randn_batched(z); [tdx_randn_batched(z2);] tdx_p_sample_step_lv(...).
+__global__ void __launch_bounds__(256)
+p_sample_step_lv_rng_kernel(const float* __restrict__ x_t, const float* __restrict__ mo, const float* __restrict__ x_bcs,
+                            const uint8_t* __restrict__ mask, const float* __restrict__ sched,
+                            const float* __restrict__ plv, int T, const int64_t* __restrict__ tp, int noise_bcs, int clip,
+                            float* __restrict__ out, int64_t V, int64_t n4, uint64_t seed,
+                            const uint64_t* __restrict__ sids, const uint64_t* __restrict__ offp) {
+    const int64_t t = *tp;
+    if (t < 0 || t >= T) return;  // a finished trajectory: no column to read
+    const uint64_t off = *offp, sid = sids[blockIdx.y];
+    const LvStepCoef c = lv_step_coef(sched, plv, T, t);
+    const int64_t base4 = (int64_t)blockIdx.y * n4;
+    const int64_t v4 = V >> 2;
+    const float4* xt4 = reinterpret_cast<const float4*>(x_t) + base4;
+    const float4* e4 = reinterpret_cast<const float4*>(mo) + 2 * base4;  // sample b: F planes of eps_hat, then F of w
+    const float4* w4 = e4 + n4;
+    const float4* xb4 = reinterpret_cast<const float4*>(x_bcs) + base4;
+    const uchar4* m4 = reinterpret_cast<const uchar4*>(mask);
+    float4* o4 = reinterpret_cast<float4*>(out) + base4;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const float4 xv = xt4[i], ev = e4[i];
+        const uchar4 mv = m4[i % v4];
+        const bool in[4] = {mv.x != 0, mv.y != 0, mv.z != 0, mv.w != 0};
+        const bool any_in = in[0] | in[1] | in[2] | in[3], any_out = !(in[0] & in[1] & in[2] & in[3]);
+        const float xt[4] = {xv.x, xv.y, xv.z, xv.w}, ee[4] = {ev.x, ev.y, ev.z, ev.w};
+        float xb[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f}, z2[4] = {0.f, 0.f, 0.f, 0.f}, w[4] = {0.f, 0.f, 0.f, 0.f};
+        if (any_out && (c.last || noise_bcs)) {
+            const float4 bv = xb4[i];
+            xb[0] = bv.x; xb[1] = bv.y; xb[2] = bv.z; xb[3] = bv.w;
+        }
+        if (!c.last) {
+            if (any_in) {
+                const float4 wv = w4[i];
+                w[0] = wv.x; w[1] = wv.y; w[2] = wv.z; w[3] = wv.w;
+                philox_normal4(off + (uint64_t)i, sid, seed, z);
+            }
+            if (noise_bcs && any_out) philox_normal4(off + (uint64_t)n4 + (uint64_t)i, sid, seed, z2);
+        }
+        float r[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = lv_step_update(c, xt[k], ee[k], w[k], z[k], z2[k], xb[k], in[k], noise_bcs, clip);
+        o4[i] = make_float4(r[0], r[1], r[2], r[3]);
+    }
+}
+
+extern "C" int tdx_p_sample_step_lv_rng(const float* x_t, const float* model_out, const float* x_bcs, const uint8_t* mask,
+                                        const float* sched, const float* posterior_log_var, int T, int64_t* t,
+                                        int noise_bcs, int clip, float* out, int B, int F, int64_t V, uint64_t seed,
+                                        const uint64_t* stream_ids, uint64_t* offset_dev, void* stream) {
+    TDX_CHECK_ARG(x_t && model_out && x_bcs && mask && sched && posterior_log_var && t && out && stream_ids && offset_dev);
+    TDX_CHECK_ARG(T > 0 && B > 0 && F > 0 && V > 0 && (V & 3) == 0);
+    TDX_CHECK_ARG(((uintptr_t)x_t | (uintptr_t)model_out | (uintptr_t)x_bcs | (uintptr_t)out) % 16 == 0 && (uintptr_t)mask % 4 == 0);
+    const int64_t n4 = (int64_t)F * V / 4;
+    dim3 grid((unsigned)min((int64_t)256, (n4 + 255) / 256), B);
+    hipLaunchKernelGGL(p_sample_step_lv_rng_kernel, grid, dim3(256), 0, as_stream(stream), x_t, model_out, x_bcs, mask, sched,
+                       posterior_log_var, T, (const int64_t*)t, noise_bcs, clip, out, V, n4, seed, stream_ids,
+                       (const uint64_t*)offset_dev);
     hipLaunchKernelGGL(advance_step, dim3(1), dim3(1), 0, as_stream(stream), offset_dev,
                        (uint64_t)(noise_bcs ? 2 * n4 : n4), t);
     return tdx_launch_status();

@@ -594,8 +594,13 @@ class GaussianDiffusion(nn.Module):
     (reference ddpm.py:620-882).
 
     The q_sample / loss / reverse-step arithmetic runs in fused HIP kernels over a dense
-    in-domain mask built once per ``cell_idx`` tensor; the learned-variance + ELBO branch
-    (off in the shipped configuration) is evaluated with torch ops on the same tensors.
+    in-domain mask built once per ``cell_idx`` tensor.  That includes the learned-variance
+    model (off in the shipped configuration): its simple + ELBO loss and gradient are one kernel
+    (``ops.elbo_loss``), its reverse step with the per-voxel variance another
+    (``ops.p_sample_step_lv[_rng]``), so it trains in the captured step and samples through the
+    captured sampler like the fixed-variance model.  The torch formulation of the ELBO branch is
+    kept as ``_p_losses_elbo_torch`` (the yardstick of the tests), the eager torch loop as
+    ``_general_sample`` (``noise_fn=`` / TDX_GRAPH_SAMPLER=0).
     """
 
     def __init__(self, model, *, timesteps: int = 1000, loss_type: str = "l2", beta_schedule: str = "sigmoid",
@@ -706,6 +711,9 @@ class GaussianDiffusion(nn.Module):
         x_T, eta = 1 the posterior variance of the sub-sampled chain (NOT the fixed-large variance of the ancestral loop, so
         S = T, eta = 1 is not expected to reproduce it).  Same routes, same noise order (z is consumed at eta = 0 too, and
         ignored); ValueError with learned variances, S outside [1, start_from or T] or eta outside [0, 1].
+        With learned variances the ancestral loop scales the noise per voxel (ddpm.py:732-741), on the same routes: the
+        default call draws its noise from the counter-based generator below, not from `torch.randn_like` (which only
+        TDX_GRAPH_SAMPLER=0 still uses), and takes `seed` / `trajectory_ids` like the fixed-variance model.
 
         Default (`noise_fn is None`): the hipGraph-captured reverse step of `sampling.GraphSampler`, replayed T times --
         this is what `DiffusionTrainer.sample`, `tools/eval_ckpt.py` and a `dropin` user get.  Noise comes from the
@@ -721,10 +729,10 @@ class GaussianDiffusion(nn.Module):
             from ..sampling import check_ddim_arguments
 
             check_ddim_arguments(self, sampling_timesteps, eta, start_from)
-        if self.learned_variances:
-            return self._general_sample(x_bcs, C, cell_idx, pbar, start_from, noise_fn)
         if noise_fn is None and GRAPH_SAMPLER and x_bcs.is_cuda and hasattr(self.model, "encode_local"):
             return self._graph_sample(x_bcs, C, cell_idx, pbar, start_from, seed, trajectory_ids, sampling_timesteps, eta)
+        if self.learned_variances:
+            return self._general_sample(x_bcs, C, cell_idx, pbar, start_from, noise_fn)
         if sampling_timesteps is not None:
             return self._eager_ddim_sample(x_bcs, C, cell_idx, pbar, start_from, noise_fn, int(sampling_timesteps), float(eta))
         return self._eager_sample(x_bcs, C, cell_idx, pbar, start_from, noise_fn)
@@ -752,10 +760,10 @@ class GaussianDiffusion(nn.Module):
         return gs.sample(start_from, pbar=pbar)
 
     def _general_sample(self, x_bcs, C, cell_idx, pbar, start_from, noise_fn):
-        """The reference's loop step by step over `p_sample` (ddpm.py:767-816) for what the fused update kernel does not
-        cover: learned variances, where `log_var` is the per-voxel lerp between log beta_t and the posterior log-variance
-        (ddpm.py:732-741).  The unmodified reference cannot finish this loop -- ddpm.py:805 hands the 5-D std to
-        `broadcast_right`, which asks for reshape(-1, -1, -1, -1, -1) (utils.py:11, RuntimeError; recorded in
+        """The reference's loop step by step over `p_sample` (ddpm.py:767-816) for learned variances, where `log_var` is the
+        per-voxel lerp between log beta_t and the posterior log-variance (ddpm.py:732-741): the eager route behind
+        `noise_fn=` and TDX_GRAPH_SAMPLER=0, and what the captured sampler's `tdx_p_sample_step_lv_rng` is tested against.
+        The unmodified reference cannot finish this loop -- ddpm.py:805 hands the 5-D std to `broadcast_right`, which asks for reshape(-1, -1, -1, -1, -1) (utils.py:11, RuntimeError; recorded in
         tests/golden/options.npz) -- so this is the arithmetic the loop spells out, with the std used as it is: the
         U-Net forward runs on the HIP kernels, the elementwise rest on torch ops over the same tensors."""
         randn = noise_fn if noise_fn is not None else torch.randn_like
@@ -860,7 +868,6 @@ class GaussianDiffusion(nn.Module):
             # (uint8 [V] mask, int64 device scalar n_cells) in buffers the caller owns: training.GraphedTrainingStep
             # replays one captured step for every geometry of a grid size by copying into them
             mask, n_cells = dm
-            assert not (self.learned_variances and self.elbo_weight is not None), "the ELBO term gathers by cell_idx"
         else:
             mask, n_cells = self.domain_mask(cell_idx, x_start[0, 0].numel())
         if noise is None:
@@ -871,16 +878,39 @@ class GaussianDiffusion(nn.Module):
             out = self.model(x_t, t, C)
             pred_noise = out.chunk(2, dim=1)[0].contiguous() if self.learned_variances else out
             return ops.masked_loss(pred_noise, noise, mask, n_cells, l1=self.loss_type == "l1"), t
-        # learned variances + ELBO term (reference ddpm.py:853-870), torch ops
-        pred = self.model_predictions(x_t, t, C, cell_idx, clip_x_start=self.clip_denoised)
-        loss = ops.masked_loss(pred.noise.contiguous(), noise, mask, n_cells, l1=self.loss_type == "l1")
-        true_mean, true_log_var = self.q_posterior(x_start, x_t, t)
-        model_mean = pred.mean.detach() if self.detach_elbo_mean else pred.mean
+        # learned variances + ELBO term (reference ddpm.py:853-870): one kernel for both terms and their gradient
+        out = self.model(x_t, t, C)
+        loss = ops.elbo_loss(out, noise, x_start, x_t, mask, n_cells, t, self.step_tables, self.posterior_log_var,
+                             l1=self.loss_type == "l1", clip=self.clip_denoised, detach_mean=self.detach_elbo_mean,
+                             elbo_weight=self.elbo_weight)
+        return loss, t
+
+    def _p_losses_elbo_torch(self, out, x_start, x_t, t, noise, mask, n_cells, cell_idx, parts=False):
+        """The loss of the learned-variance + ELBO branch from the model output `out`, spelled with torch ops as the
+        reference does (ddpm.py:853-870; the simple term by `ops.masked_loss` on a GPU): what `ops.elbo_loss` replaced on
+        the route `p_losses` takes.  Kept as the yardstick of that kernel -- any dtype, any device.  parts=True: (total, simple,
+        elbo) instead of the total."""
+        pred_noise, vw = out.chunk(2, dim=1)
+        log_var = torch.lerp(broadcast_right(self.log_betas[t], vw), broadcast_right(self.posterior_log_var[t], vw),
+                             torch.sigmoid(vw))
+        x0 = self.predict_start_from_noise(x_t, t, pred_noise)
+        if not self.noise_bcs:
+            x0 = self._outside_keep(mask, x0, x_t)
+        if self.clip_denoised:
+            x0 = torch.clamp(x0, min=-1.0, max=1.0)
+        mean, _ = self.q_posterior(x0, x_t, t)
         sel = lambda v: v.flatten(-3)[..., cell_idx]
-        kl = sel(normal_kl(true_mean, true_log_var, model_mean, pred.log_var))
-        ll = sel(normal_log_lk(x_t, model_mean, pred.log_var))
-        elbo = torch.where(t == 0, -batch_mean(ll), batch_mean(kl))
-        return loss + self.elbo_weight * elbo.mean(), t
+        if out.is_cuda and out.dtype == torch.float32:
+            loss = ops.masked_loss(pred_noise.contiguous(), noise, mask, n_cells, l1=self.loss_type == "l1")
+        else:
+            loss = batch_mean(self.loss_fn(sel(pred_noise), sel(noise), reduction="none")).mean()
+        true_mean, true_log_var = self.q_posterior(x_start, x_t, t)
+        model_mean = mean.detach() if self.detach_elbo_mean else mean
+        kl = sel(normal_kl(true_mean, true_log_var, model_mean, log_var))
+        ll = sel(normal_log_lk(x_t, model_mean, log_var))
+        elbo = torch.where(t == 0, -batch_mean(ll), batch_mean(kl)).mean()
+        total = loss + self.elbo_weight * elbo
+        return (total, loss, elbo) if parts else total
 
     def forward(self, x, *args, **kwargs):
         t = torch.randint(0, self.num_timesteps, (x.shape[0],), device=x.device, dtype=torch.long)

@@ -10,6 +10,7 @@ the reference's shapes and float32 (so state_dicts round-trip). 
     resize           F.interpolate(trilinear, align_corners=True)         ddpm.py:359-369
     attention        F.scaled_dot_product_attention                       attention.py:9-15
     q_sample / p_sample_step / masked_loss                                ddpm.py:745-852
+    p_sample_step_lv / elbo_loss (learned variances)                      ddpm.py:732-741,853-870
 
 There is no CPU implementation: tensors must live on the GPU.
 """
@@ -782,6 +783,39 @@ def p_sample_step_rng(x_t, eps, x_bcs, mask, sched, T, t_dev, noise_bcs, clip, s
     return out
 
 
+def _lv_step_shapes(x_t, model_out):
+    B, F = x_t.shape[:2]
+    if (model_out.dtype != torch.float32 or not model_out.is_contiguous() or model_out.shape[0] != B
+            or model_out.shape[1] != 2 * F or model_out.shape[2:] != x_t.shape[2:]):
+        raise ValueError(f"learned-variance step: model output {tuple(model_out.shape)} {model_out.dtype} is not the contiguous "
+                         f"float32 [eps_hat | w] of a state {tuple(x_t.shape)}")
+    return B, F, x_t[0, 0].numel()
+
+
+def p_sample_step_lv(x_t, model_out, z, z2, x_bcs, mask, sched, posterior_log_var, T, t_dev, noise_bcs, clip, out=None):
+    """The fused reverse update of a model with learned variances: model_out = (B, 2F, X, Y, Z) = [eps_hat | w], the noise
+    inside the domain scaled per voxel by exp(log_var / 2), log_var = log beta_t + sigmoid(w) (posterior_log_var_t - log beta_t)."""
+    B, F, V = _lv_step_shapes(x_t, model_out)
+    if out is None:
+        out = torch.empty_like(x_t)
+    L.call("tdx_p_sample_step_lv", L.ptr(x_t), L.ptr(model_out), L.ptr(z), L.ptr(z2), L.ptr(x_bcs), L.ptr(mask), L.ptr(sched),
+           L.ptr(posterior_log_var), T, L.ptr(t_dev), int(noise_bcs), int(clip), L.ptr(out), B, F, V, L.stream())
+    return out
+
+
+def p_sample_step_lv_rng(x_t, model_out, x_bcs, mask, sched, posterior_log_var, T, t_dev, noise_bcs, clip, seed, stream_ids,
+                         offset_dev, out=None):
+    """p_sample_step_lv with z (and z2) drawn in the kernel (layouts: p_sample_step_rng_supported); advances offset_dev and
+    decrements t_dev on the device."""
+    B, F, V = _lv_step_shapes(x_t, model_out)
+    if out is None:
+        out = torch.empty_like(x_t)
+    L.call("tdx_p_sample_step_lv_rng", L.ptr(x_t), L.ptr(model_out), L.ptr(x_bcs), L.ptr(mask), L.ptr(sched),
+           L.ptr(posterior_log_var), T, L.ptr(t_dev), int(noise_bcs), int(clip), L.ptr(out), B, F, V, seed, L.ptr(stream_ids),
+           L.ptr(offset_dev), L.stream())
+    return out
+
+
 def ddim_step(x_t, eps, z, z2, x_bcs, mask, tab, k_dev, tau_dev, t_dev, noise_bcs, clip, out=None):
     """One generalized DDIM update from tau[k] to tau[k-1]; tab = schedules.ddim_tables(...) on the device ([6, S]),
     k_dev / t_dev device int64 scalars, tau_dev the device int64 subsequence.  z / z2 may be None where unused."""
@@ -847,6 +881,56 @@ def masked_loss(eps_hat, noise, mask, n_cells, l1=False):
         assert n_cells.dtype == torch.int64 and n_cells.numel() == 1 and n_cells.is_cuda
         return _MaskedLoss.apply(eps_hat, noise, mask, n_cells, l1)
     return _MaskedLoss.apply(eps_hat, noise, mask, int(n_cells), l1)
+
+
+class _ElboLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out, noise, x_start, x_t, mask, n_cells, t, sched, plv, l1, clip, detach_mean, elbo_weight):
+        B, F = x_t.shape[:2]
+        V = x_t[0, 0].numel()
+        out, noise, x_start, x_t = out.contiguous(), noise.contiguous(), x_start.contiguous(), x_t.contiguous()
+        loss = torch.empty(3, dtype=torch.float32, device=out.device)
+        grad = torch.empty_like(out) if ctx.needs_input_grad[0] else None
+        ws = _ws(L.query("tdx_elbo_loss_workspace_bytes"), out.device)
+        dyn = torch.is_tensor(n_cells)  # device int64 scalar, read when the kernels run (captured training step)
+        L.call("tdx_elbo_loss_dyn" if dyn else "tdx_elbo_loss", L.ptr(out), L.ptr(noise), L.ptr(x_start), L.ptr(x_t), L.ptr(mask),
+               L.ptr(n_cells) if dyn else n_cells, L.ptr(t), L.ptr(sched), L.ptr(plv), sched.shape[1], int(l1), int(clip),
+               int(detach_mean), float(elbo_weight), L.ptr(loss), L.ptr(grad), B, F, V, L.ptr(ws), L.stream())
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        parts = loss[1:]  # (simple, elbo): reported, not differentiated
+        ctx.mark_non_differentiable(parts)
+        return loss[0], parts
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _):
+        (grad,) = ctx.saved_tensors
+        return (grad * g,) + (None,) * 12
+
+
+def elbo_loss(out, noise, x_start, x_t, mask, n_cells, t, step_tables, posterior_log_var, l1=False, clip=False,
+              detach_mean=True, elbo_weight=1.0, parts=False):
+    """simple loss + elbo_weight * ELBO term of the learned-variance model (ddpm.py:853-870) in one pass, with its gradient
+    with respect to `out` = the model's (B, 2F, X, Y, Z) output [eps_hat | w].  noise, x_start, x_t: (B, F, X, Y, Z) float32;
+    t: (B,) int64; step_tables / posterior_log_var: the diffusion's packed [7, T] tables and its [T] table; n_cells as for
+    masked_loss.  parts=True also returns the float32 pair (simple, elbo), detached."""
+    B, F = x_t.shape[:2]
+    if (out.dtype != torch.float32 or out.shape[0] != B or out.shape[1] != 2 * F or out.shape[2:] != x_t.shape[2:]
+            or noise.shape != x_t.shape or x_start.shape != x_t.shape):
+        raise ValueError(f"elbo_loss: model output {tuple(out.shape)} {out.dtype} against a state {tuple(x_t.shape)}")
+    T = posterior_log_var.numel()
+    if step_tables.dtype != torch.float32 or tuple(step_tables.shape) != (7, T) or posterior_log_var.dtype != torch.float32:
+        raise ValueError(f"elbo_loss: tables {tuple(step_tables.shape)} / {tuple(posterior_log_var.shape)} do not fit")
+    t = t.to(torch.int64).contiguous()
+    assert t.numel() == B
+    if torch.is_tensor(n_cells):
+        assert n_cells.dtype == torch.int64 and n_cells.numel() == 1 and n_cells.is_cuda
+    else:
+        n_cells = int(n_cells)
+    total, both = _ElboLoss.apply(out, noise, x_start, x_t, mask, n_cells, t, step_tables.contiguous(),
+                                  posterior_log_var.contiguous(), l1, clip, detach_mean, elbo_weight)
+    return (total, both) if parts else total
 
 
 def randn_philox(out: torch.Tensor, seed: int, stream_id: int, offset_dev: torch.Tensor):

@@ -15,6 +15,9 @@ With `sampling_timesteps = S` the same captured step walks an increasing subsequ
 the generalized DDIM update of Song et al. 2021 (`tdx_ddim_step_rng`; eta = 0 deterministic, eta = 1 the posterior
 variance of the sub-sampled chain) instead of the T ancestral ones: the step index k, tau and the [6, S] coefficient
 table live in device memory next to t, so a replay still needs no new arguments.
+
+A model with learned variances (`diffusion.learned_variances`, Nichol & Dhariwal 2021) runs the same captured ancestral
+step with `tdx_p_sample_step_lv_rng` as its update: the decoder emits [eps_hat | w] and the noise is scaled per voxel.
 """
 
 from __future__ import annotations
@@ -102,13 +105,17 @@ class GraphSampler:
     @staticmethod
     def signature_of(diffusion, x_bcs, C, sampling_timesteps=None, eta=0.0):
         """What must match for `rebind`: shapes / dtypes of everything the captured step reads, and the switches the
-        captured step was built under (the last two entries: the DDIM subsequence length, None = ancestral, and eta)."""
+        captured step was built under.  The last two entries name the update the step applies: None = the ancestral step
+        with fixed variances, "learned-variances" = the ancestral step with the per-voxel variance (read with getattr:
+        stand-ins for a diffusion need not carry the attribute), an int = the DDIM subsequence length (which excludes
+        learned variances, `check_ddim_arguments`); and eta."""
         c = tuple(sorted((str(k), tuple(v.shape), str(v.dtype)) for k, v in C.items() if torch.is_tensor(v))) \
             if isinstance(C, dict) else None
         m = diffusion.model
         return (tuple(x_bcs.shape), str(x_bcs.device), c, getattr(m, "compute_dtype", None), getattr(m, "conv_impl", None),
                 L.conv_impl(), diffusion.noise_bcs, diffusion.clip_denoised, diffusion.num_timesteps,
-                None if sampling_timesteps is None else int(sampling_timesteps), float(eta))
+                int(sampling_timesteps) if sampling_timesteps is not None
+                else ("learned-variances" if getattr(diffusion, "learned_variances", False) else None), float(eta))
 
     def signature(self):
         return self.signature_of(self.d, self.x_bcs, self.C, self.sampling_timesteps, self.eta)
@@ -211,6 +218,8 @@ class GraphSampler:
         eps = d.model(self.x_t, self.t.expand(self.B), self.C, **kw)
         if self.sampling_timesteps is not None:
             return self._ddim_update(eps)
+        if getattr(d, "learned_variances", False):
+            return self._lv_update(eps)
         if self.fused_noise:
             # same draws, same counters, bit-identical x_{t-1}; also advances the offset and decrements t
             ops.p_sample_step_rng(self.x_t, eps, self.x_bcs, self.mask, d.step_tables, d.num_timesteps, self.t,
@@ -221,6 +230,20 @@ class GraphSampler:
             self._randn(self.z2)
         ops.p_sample_step(self.x_t, eps, self.z, self.z2 if d.noise_bcs else None, self.x_bcs, self.mask, d.step_tables,
                           d.num_timesteps, self.t, d.noise_bcs, d.clip_denoised, out=self.x_t)
+        self.t.sub_(1)
+
+    def _lv_update(self, out):
+        """The ancestral step of a model with learned variances: `out` = [eps_hat | w], the noise scaled per voxel."""
+        d = self.d
+        if self.fused_noise:
+            ops.p_sample_step_lv_rng(self.x_t, out, self.x_bcs, self.mask, d.step_tables, d.posterior_log_var, d.num_timesteps,
+                                     self.t, d.noise_bcs, d.clip_denoised, self.seed, self.stream_ids, self.offset, out=self.x_t)
+            return
+        self._randn(self.z)
+        if d.noise_bcs:
+            self._randn(self.z2)
+        ops.p_sample_step_lv(self.x_t, out, self.z, self.z2 if d.noise_bcs else None, self.x_bcs, self.mask, d.step_tables,
+                             d.posterior_log_var, d.num_timesteps, self.t, d.noise_bcs, d.clip_denoised, out=self.x_t)
         self.t.sub_(1)
 
     def _ddim_update(self, eps):

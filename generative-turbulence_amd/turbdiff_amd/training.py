@@ -277,7 +277,7 @@ class DiffusionTrainer(nn.Module):
         kw = {}
         if steps is not None:
             kw.update(sampling_timesteps=steps, eta=self.sampling_eta if eta is None else eta)
-        if noise_fn is None and not self.model.learned_variances:
+        if noise_fn is None:
             # identically seeded ranks draw the same per-call nonce: the trajectory ids keep their noise streams apart
             # (rank r samples trajectories r B ... r B + B - 1 of the global set, whatever the sharding)
             kw["trajectory_ids"] = self._global_trajectory_ids(x.shape[0])
@@ -386,7 +386,8 @@ class GraphedTrainingStep:
     """`DiffusionTrainer.training_step` + `backward()` as one hipGraph per input signature (shapes, arithmetic mode).
 
     Everything the captured step reads lives in buffers this object owns: the normalised input x, the conditioning
-    tensors, the in-domain mask and the number of in-domain cells (a device scalar: `tdx_masked_loss_dyn`), so batches
+    tensors, the in-domain mask and the number of in-domain cells (a device scalar: `tdx_masked_loss_dyn`, or
+    `tdx_elbo_loss_dyn` for a model with learned variances and an ELBO weight), so batches
     of ANY geometry of the same grid size replay the same graph after four small copies.  What stays eager around the
     replay: `_model_input` (fused ingress kernels, cell-type embedding) before it, and after it the short chain from the
     conditioning tensors' gradients back into whatever produced them (the learned cell-type table), then clip +
@@ -426,7 +427,10 @@ class GraphedTrainingStep:
                 # what else the capture bakes in: parameter storage and which of them take gradients, the loss
                 # configuration, whether the backward runs on a scaled loss
                 tuple((id(p), p.data_ptr(), bool(p.requires_grad)) for p in self.tr.parameters()),
-                self.tr.model.loss_type, bool(self.tr.model.noise_bcs), getattr(self.tr._opt, "loss_scale", None) is not None)
+                self.tr.model.loss_type, bool(self.tr.model.noise_bcs), getattr(self.tr._opt, "loss_scale", None) is not None,
+                # the learned-variance loss: which kernel the capture holds, and its launch arguments
+                bool(getattr(self.tr.model, "learned_variances", False)), getattr(self.tr.model, "elbo_weight", None),
+                bool(getattr(self.tr.model, "detach_elbo_mean", True)), bool(getattr(self.tr.model, "clip_denoised", False)))
 
     def __call__(self, batch):
         tr = self.tr

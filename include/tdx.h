@@ -341,6 +341,28 @@ int tdx_p_sample_step_rng(const float* x_t, const float* eps, const float* x_bcs
                           int T, int64_t* t, int noise_bcs, int clip, float* out, int B, int F, int64_t V, uint64_t seed,
                           const uint64_t* stream_ids, uint64_t* offset_dev, void* stream);
 
+/* The reverse step of a model with learned variances (ddpm.py:732-741 in front of the loop body above): model_out is the
+ * decoder's contiguous (B, 2F, V) output, eps_hat = model_out[:, :F], w = model_out[:, F:] (the reference's chunk(2, dim=1)).
+ * tdx_p_sample_step with eps = eps_hat and, inside the mask at t > 0, per element
+ *   log_var = log_betas[t] + sigmoid(w) (posterior_log_var[t] - log_betas[t]),   out = mean + exp(log_var / 2) z
+ * instead of the scalar exp(log_betas[t] / 2).  x0, the !noise_bcs keep, the clip, the mean, the t == 0 branch, the
+ * re-noising of BC cells at level t under noise_bcs and the final BC fix are those of tdx_p_sample_step.  sched = the same
+ * 7 tables; posterior_log_var = one more f32 table of length T.  Any V, any alignment.  t outside [0, T) writes nothing.
+ * z, z2 may be NULL when unused (NULL reads as no noise). */
+int tdx_p_sample_step_lv(const float* x_t, const float* model_out, const float* z, const float* z2, const float* x_bcs,
+                         const uint8_t* mask, const float* sched, const float* posterior_log_var, int T, const int64_t* t,
+                         int noise_bcs, int clip, float* out, int B, int F, int64_t V, void* stream);
+
+/* The same step with its noise drawn inside the kernel (needs V % 4 == 0 and 16-byte aligned tensors): bit-identical to
+ * tdx_randn_batched(z, ...); [tdx_randn_batched(z2, ...) if noise_bcs;] tdx_p_sample_step_lv(...) with the same seed, stream
+ * ids and offset.  Counters as tdx_p_sample_step_rng: z at offset + i, z2 at offset + n4 + i with n4 = F V / 4 counted over
+ * the F planes of the STATE, not the 2F of model_out; drawn under the same conditions.  Afterwards, on the device,
+ * *offset_dev += (noise_bcs ? 2 : 1) * n4 and *t -= 1. */
+int tdx_p_sample_step_lv_rng(const float* x_t, const float* model_out, const float* x_bcs, const uint8_t* mask,
+                             const float* sched, const float* posterior_log_var, int T, int64_t* t, int noise_bcs, int clip,
+                             float* out, int B, int F, int64_t V, uint64_t seed, const uint64_t* stream_ids,
+                             uint64_t* offset_dev, void* stream);
+
 /* One generalized DDIM step (Song et al. 2021, eq. 12) over an increasing subsequence tau[0..S-1] of the training
  * timesteps, from tau[k] to tau[k-1]; not in the reference.  tab = 6 consecutive f32 rows of length S, column k:
  *   recip = rsqrt(a), recipm1 = sqrt(1/a - 1), sp = sqrt(p), dir = sqrt(1 - p - sigma^2), sigma, sbp = sqrt(1 - p)
@@ -380,6 +402,35 @@ int tdx_masked_loss(const float* eps_hat, const float* noise, const uint8_t* mas
 int tdx_masked_loss_dyn(const float* eps_hat, const float* noise, const unsigned char* mask, const int64_t* n_cells_dev,
                         int l1, float* loss, float* grad, int B, int F, int64_t V, void* workspace, void* stream);
 size_t tdx_masked_loss_workspace_bytes(void);
+
+/* Simple loss + ELBO term of the learned-variance model (ddpm.py:853-870) and its gradient, one pass + a finish launch.
+ * out = model output (B, 2F, V) = [eps_hat | w]; noise, x_start, x_t (B, F, V); mask [V]; t [B] int64 (sample b uses t[b]);
+ * sched = the 7 tables of tdx_p_sample_step, posterior_log_var one more of length T.  Only cells with mask != 0
+ * contribute.  Per contributing element, lb = log_betas[t], plv = posterior_log_var[t]:
+ *   simple:   d = eps_hat - noise;  |d| (l1) or d^2
+ *   log_var = lb + sigmoid(w) (plv - lb)
+ *   x0   = recip[t] x_t - recipm1[t] eps_hat  [clip: clamped to +-1];   mean = coef1[t] x0 + coef2[t] x_t
+ *   t  > 0:  0.5 (log_var - plv - 1 + exp(plv - log_var) + (true_mean - mean)^2 exp(-log_var)),
+ *            true_mean = coef1[t] x_start + coef2[t] x_t                       (KL of the two posteriors)
+ *   t == 0:  0.5 (log_var + log 2 pi + (x_t - mean)^2 exp(-log_var))           (-log-likelihood, evaluated at x_t)
+ * loss[0..2] = {simple + elbo_weight elbo, simple, elbo}, each term a mean over the B F n_cells contributing elements
+ * (= the reference's mean over b of per-sample means).  If grad != NULL it receives d loss[0] / d out, (B, 2F, V), zero
+ * outside the mask: the simple loss's gradient in the eps_hat planes (0 at d == 0 for l1), the ELBO term's in the w
+ * planes, and -- only when detach_mean == 0 -- the ELBO term's gradient through mean in the eps_hat planes, zero where
+ * the clip was active (it passes for -1 <= x0 <= 1, as torch.clamp's does).  Sums: double partials per block, one
+ * atomicAdd(double) per block and term; under TDX_DETERMINISTIC the partials are quantised as tdx_masked_loss does.
+ * The ELBO term and its gradient are evaluated in double from the float inputs (its summands are tens where their mean is
+ * O(1)); the simple term's gradient is tdx_masked_loss's float expression.  workspace: tdx_elbo_loss_workspace_bytes() bytes. */
+int tdx_elbo_loss(const float* out, const float* noise, const float* x_start, const float* x_t, const uint8_t* mask,
+                  int64_t n_cells, const int64_t* t, const float* sched, const float* posterior_log_var, int T, int l1,
+                  int clip, int detach_mean, double elbo_weight, float* loss, float* grad, int B, int F, int64_t V,
+                  void* workspace, void* stream);
+/* The same with n_cells read from device memory when the kernels run, as tdx_masked_loss_dyn. */
+int tdx_elbo_loss_dyn(const float* out, const float* noise, const float* x_start, const float* x_t, const uint8_t* mask,
+                      const int64_t* n_cells_dev, const int64_t* t, const float* sched, const float* posterior_log_var,
+                      int T, int l1, int clip, int detach_mean, double elbo_weight, float* loss, float* grad, int B, int F,
+                      int64_t V, void* workspace, void* stream);
+size_t tdx_elbo_loss_workspace_bytes(void);
 
 /* ------------------------------------------------------------------ data ingress / egress */
 /* The callers either side of the path.  Samples are the HDF5 files' channels-last

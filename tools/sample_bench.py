@@ -8,6 +8,11 @@ one hipGraph-captured reverse step per replay (no collective inside the loop).
   python tools/sample_bench.py --trajectories 8 --sampling-steps 50 --eta 0  # DDIM over 50 of the 1000 timesteps; the
                                                                             # ancestral sampler is timed in the same process
 
+  python tools/sample_bench.py --trajectories 8 --learned-variances --steps 50
+      # the U-Net with 2F output channels and the per-voxel variance (tdx_p_sample_step_lv_rng); timed in the same process,
+      # alternating: this captured step, the eager torch loop it replaces on the default route (`general_loop`, what
+      # TDX_GRAPH_SAMPLER=0 runs) and the fixed-variance captured step (`fixed_variance`)
+
 Prints one JSON line (rank 0): whole-job samples/s = trajectories / max-over-ranks wall time."""
 import argparse, json, sys, time
 from pathlib import Path
@@ -28,6 +33,8 @@ ap.add_argument("--sampling-steps", type=int, default=None,
 ap.add_argument("--eta", type=float, default=0.0, help="with --sampling-steps: 0 = deterministic DDIM ... 1 = posterior variance")
 ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "f32", "f32s"])
 ap.add_argument("--no-graph", action="store_true")
+ap.add_argument("--learned-variances", action="store_true", help="out_features = 2F, learned_variances=True; see above")
+ap.add_argument("--rounds", type=int, default=3, help="with --learned-variances: how often the three sides are timed in turn")
 a = ap.parse_args()
 if a.dtype == "f32s":  # fp32 tensors, split-precision convs
     import os
@@ -35,16 +42,29 @@ if a.dtype == "f32s":  # fp32 tensors, split-precision convs
 rank, world, local = parallel.init_from_env("nccl")
 torch.cuda.set_device(local)
 dev = torch.device("cuda", local)
-diff = bench.build_model(dev, bench.MODE_DTYPE[a.dtype], timesteps=a.timesteps)
+fixed = bench.build_model(dev, bench.MODE_DTYPE[a.dtype], timesteps=a.timesteps)
+diff = fixed
+if a.learned_variances:
+    from turbdiff_amd.models.ddpm import DenoisingModel, GaussianDiffusion
+    if a.sampling_steps is not None:
+        ap.error("--sampling-steps needs fixed variances")
+    torch.manual_seed(0)
+    net = DenoisingModel(in_features=4, out_features=8, c_local_features=4, c_global_features=0, timesteps=a.timesteps, dim=32,
+                         u_net_levels=4, norm_type="group")
+    diff = GaussianDiffusion(net, timesteps=a.timesteps, beta_schedule="log-snr-linear", loss_type="l2", noise_bcs=True,
+                             learned_variances=True).to(dev)
+    diff.model.set_compute_dtype(bench.MODE_DTYPE[a.dtype])
 ids = list(parallel.shard_trajectories(a.trajectories, rank, world))
 x, c, cell_idx = bench.synthetic_inputs(len(ids), dev)
 C = {Conditioning.Type.CELL_TYPE: c}
 
 
-def measure(total, **kw):
+def measure(total, s=None, model=None, **kw):
     """(seconds for the timed steps, timed steps, sampler) of a sampler whose full loop has `total` reverse steps"""
-    s = GraphSampler(diff, x, C, cell_idx, seed=0, trajectory_ids=ids, use_graph=not a.no_graph, **kw)
-    s.run_steps(2); s.reset()          # warm-up incl. graph capture
+    if s is None:
+        s = GraphSampler(model or diff, x, C, cell_idx, seed=0, trajectory_ids=ids, use_graph=not a.no_graph, **kw)
+        s.run_steps(2)                 # warm-up incl. graph capture
+    s.reset()
     torch.cuda.synchronize()
     if world > 1: torch.distributed.barrier()
     t0 = time.perf_counter()
@@ -62,9 +82,35 @@ def record(dt, n, total):
     return {"timed_steps": n, "extrapolated": n != total, "ms_per_reverse_step": 1e3 * dt / n, "seconds_per_batch": dt * total / n}
 
 
+def measure_general_loop(n):
+    """seconds for n reverse steps of the eager learned-variance loop (GaussianDiffusion._general_sample: one launch
+    sequence and a dozen torch elementwise ops per step, torch.randn_like noise), started at timestep n"""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    diff.p_sample_loop(x, C, cell_idx, start_from=n, noise_fn=torch.randn_like)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
 total = a.timesteps if a.sampling_steps is None else a.sampling_steps
 extra = {}
-if a.sampling_steps is not None:
+if a.learned_variances:
+    n_gen = min(a.steps, total) if a.steps > 0 else total
+    measure_general_loop(2)  # warm-up
+    dt, n, s = measure(total)
+    _, _, sf = measure(total, model=fixed)
+    sides = {"captured": [], "general_loop": [], "fixed_variance": []}
+    for _ in range(a.rounds):
+        dt, n, s = measure(total, s=s)
+        sides["captured"].append(1e3 * dt / n)
+        sides["general_loop"].append(1e3 * measure_general_loop(n_gen) / n_gen)
+        sides["fixed_variance"].append(1e3 * measure(total, s=sf)[0] / n)
+    med = lambda v: sorted(v)[len(v) // 2]
+    extra = {"learned_variances": True, "rounds_ms_per_reverse_step": sides,
+             "general_loop": {"timed_steps": n_gen, "ms_per_reverse_step": med(sides["general_loop"])},
+             "fixed_variance": {"timed_steps": n, "ms_per_reverse_step": med(sides["fixed_variance"])}}
+    dt = 1e-3 * med(sides["captured"]) * n
+elif a.sampling_steps is not None:
     dt, n, s = measure(a.timesteps)
     extra = {"sampling_steps": a.sampling_steps, "eta": a.eta, "ancestral": record(dt, n, a.timesteps)}
     del s

@@ -2,8 +2,11 @@
 """One training step (fwd + bwd + clip + RAdam) of the BASELINE configs[1] U-Net on an arbitrary grid, for profiling:
     python tools/step_bench.py --grid 194 50 50 --mode bf16 --batch 6 --steps 5
 --model cfg1: the 2-level U-Net of BASELINE configs[0] instead (with --grid 48 32 32 --batch 1 its host-bound eager step).
+--learned-variances --elbo-weight W: the same U-Net with 2F output channels and the simple + ELBO loss (ops.elbo_loss);
+--torch-elbo (or TDX_STEP_BENCH_TORCH_ELBO=1, so that tools/ab_step.sh can flip it) evaluates that loss with the torch formulation the
+kernel replaced (GaussianDiffusion._p_losses_elbo_torch), --ab N times both N times in this process, alternating.
 prints ms per step; under `rocprofv3 --kernel-trace --stats` the per-kernel table of exactly these steps."""
-import argparse, sys, time
+import argparse, os, sys, time
 from pathlib import Path
 from types import SimpleNamespace
 
@@ -20,15 +23,54 @@ ap.add_argument("--batch", type=int, default=6)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--model", default="bench", choices=["bench", "cfg1"])
+ap.add_argument("--learned-variances", action="store_true", help="2F output channels, per-voxel variance")
+ap.add_argument("--elbo-weight", type=float, default=None, help="with --learned-variances: weight of the ELBO term (None: simple loss only)")
+ap.add_argument("--torch-elbo", action="store_true", default=os.environ.get("TDX_STEP_BENCH_TORCH_ELBO", "0") not in ("", "0"),
+                help="the ELBO loss by torch ops (the route before ops.elbo_loss) instead of the fused kernel")
+ap.add_argument("--ab", type=int, default=0, help="with --elbo-weight: time fused and torch ELBO alternately, this many times each")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
+
+
+def torch_elbo_p_losses(diff):
+    """p_losses as it ran before the fused loss: q_sample, model, then GaussianDiffusion._p_losses_elbo_torch"""
+    from turbdiff_amd import ops
+
+    def p_losses(x_start, t, C, metadata, variables, noise=None):
+        x_start = x_start.contiguous().float()
+        mask, n_cells = diff.domain_mask(metadata.cell_idx, x_start[0, 0].numel())
+        noise = torch.randn_like(x_start) if noise is None else noise
+        x_t = ops.q_sample(x_start, noise, diff.sqrt_alphas_cumprod, diff.sqrt_one_minus_alphas_cumprod, t, mask=mask,
+                           keep_bcs=not diff.noise_bcs)
+        return diff._p_losses_elbo_torch(diff.model(x_t, t, C), x_start, x_t, t, noise, mask, n_cells, metadata.cell_idx), t
+
+    return p_losses
+
+
 if a.model == "cfg1":
     from turbdiff_amd.models.ddpm import GaussianDiffusion
     diff = GaussianDiffusion(bench.new_cfg1_denoiser(), timesteps=10, beta_schedule="log-snr-linear", loss_type="l2", noise_bcs=True).to(dev)
+elif a.learned_variances:
+    from turbdiff_amd.models.ddpm import DenoisingModel, GaussianDiffusion
+    torch.manual_seed(0)
+    net = DenoisingModel(in_features=4, out_features=8, c_local_features=4, c_global_features=0, timesteps=500, dim=32,
+                         u_net_levels=4, norm_type="group")
+    diff = GaussianDiffusion(net, timesteps=500, beta_schedule="log-snr-linear", loss_type="l2", noise_bcs=True,
+                             learned_variances=True, elbo_weight=a.elbo_weight).to(dev)
 else:
     diff = bench.build_model(dev)
 x, c, idx = bench.synthetic_inputs(a.batch, dev, tuple(a.grid))
 C, md = {Conditioning.Type.CELL_TYPE: c}, SimpleNamespace(cell_idx=idx)
-ms = bench.timed_train_steps(diff, x, C, md, a.mode, a.steps, a.warmup)
 v = a.grid[0] * a.grid[1] * a.grid[2]
+if a.learned_variances and a.elbo_weight is not None and (a.torch_elbo or a.ab):
+    fused = diff.p_losses
+    for i in range(max(a.ab, 1)):
+        for name, fn in (("fused-elbo", fused), ("torch-elbo", torch_elbo_p_losses(diff))):
+            if name == "fused-elbo" and not a.ab:
+                continue
+            diff.p_losses = fn  # (an instance attribute: GaussianDiffusion.forward calls self.p_losses)
+            ms = bench.timed_train_steps(diff, x, C, md, a.mode, a.steps, a.warmup)
+            print(f"{name}: grid {a.grid} B {a.batch} {a.mode}: {ms:.3f} ms/step = {a.batch * v / ms / 1e3:.1f} M voxels/s")
+    sys.exit(0)
+ms = bench.timed_train_steps(diff, x, C, md, a.mode, a.steps, a.warmup)
 print(f"grid {a.grid} B {a.batch} {a.mode}: {ms:.3f} ms/step = {a.batch * v / ms / 1e3:.1f} M voxels/s")
