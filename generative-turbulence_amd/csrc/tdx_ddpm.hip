@@ -162,53 +162,41 @@ extern "C" int tdx_q_sample(const float* x0, const float* noise, const float* sq
     return tdx_launch_status();
 }
 
-// ------------------------------------------------------------------ fused reverse step ---
-__global__ void __launch_bounds__(256)
-p_sample_step_kernel(const float* __restrict__ x_t, const float* __restrict__ eps, const float* __restrict__ z,
-                     const float* __restrict__ z2, const float* __restrict__ x_bcs, const uint8_t* __restrict__ mask,
-                     const float* __restrict__ sched, int T, const int64_t* __restrict__ tp, int noise_bcs, int clip,
-                     float* __restrict__ out, int64_t V) {
-    const int64_t t = *tp;
-    const float recip = sched[t], recipm1 = sched[T + t], c1 = sched[2 * T + t], c2 = sched[3 * T + t];
-    const float sigma = __expf(sched[4 * T + t] * 0.5f);
-    const float sa = sched[5 * T + t], sb = sched[6 * T + t];
-    const bool last = (t == 0);
-    const int64_t base = (int64_t)blockIdx.y * V;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += stride) {
-        const bool inside = mask[i] != 0;
-        const float xt = x_t[base + i];
-        float x0h = recip * xt - recipm1 * eps[base + i];
-        if (!noise_bcs && !inside) x0h = xt;
-        if (clip) x0h = fminf(fmaxf(x0h, -1.0f), 1.0f);
-        float r = c1 * x0h + c2 * xt;
-        if (last) {
-            if (!inside) r = x_bcs[base + i];
-        } else {
-            if (noise_bcs) {
-                if (inside) r += sigma * z[base + i];
-                else r = sa * x_bcs[base + i] + sb * z2[base + i];
-            } else {
-                if (inside) r += sigma * z[base + i];
-            }
-        }
-        out[base + i] = r;
-    }
-}
-
-extern "C" int tdx_p_sample_step(const float* x_t, const float* eps, const float* z, const float* z2,
-                                 const float* x_bcs, const uint8_t* mask, const float* sched, int T, const int64_t* t,
-                                 int noise_bcs, int clip, float* out, int B, int F, int64_t V, void* stream) {
-    TDX_CHECK_ARG(x_t && eps && x_bcs && mask && sched && t && out && T > 0 && B > 0 && F > 0 && V > 0);
-    dim3 grid((unsigned)min((int64_t)128, (V + 255) / 256), B * F);
-    hipLaunchKernelGGL(p_sample_step_kernel, grid, dim3(256), 0, as_stream(stream), x_t, eps, z, z2, x_bcs, mask, sched,
-                       T, t, noise_bcs, clip, out, V);
-    return tdx_launch_status();
-}
-
 // ------------------------------------------------------------------ masked loss ----------
 // pass 1: per-block partial sums in double -> atomicAdd(double) into workspace[0]
 // pass 2: scale -> loss.   grad written in pass 1.
+
+// The tail of the loss kernels: N per-thread sums -> wave sums -> block sums through LDS -> thread k adds sum k to acc[k].
+// quant != 0 (TDX_DETERMINISTIC) puts the block sums on a grid where f64 additions are exact, hence order-independent
+// (see gn_stats_launch).
+template <int N>
+__device__ __forceinline__ void block_sum_atomic(double* __restrict__ acc, const double (&sums)[N], double quant) {
+    __shared__ double part[N][4];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const double ws = wave_sum(sums[k]);
+        if ((threadIdx.x & 63) == 0) part[k][threadIdx.x >> 6] = ws;
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        double t = part[threadIdx.x][0] + part[threadIdx.x][1] + part[threadIdx.x][2] + part[threadIdx.x][3];
+        if (quant != 0.0) t = rint(t * quant) / quant;
+        atomicAdd(acc + threadIdx.x, t);
+    }
+}
+// one in-domain element of the simple loss, d = eps_hat - noise: the gradient of gscale * term.  Both masked-loss kernels
+// and elbo_elem take it from here, so their gradients agree bit for bit.
+__device__ __forceinline__ float simple_loss_grad(float d, int l1, float gscale) {
+    if (l1) return (d > 0.f) ? gscale : ((d < 0.f) ? -gscale : 0.f);
+    return 2.0f * d * gscale;
+}
+// the same, and adds the element's term to the float sum of the masked-loss kernels
+__device__ __forceinline__ float simple_loss_elem(float d, int l1, float gscale, float* sum) {
+    if (l1) *sum += fabsf(d);
+    else *sum += d * d;
+    return simple_loss_grad(d, l1, gscale);
+}
+
 __global__ void __launch_bounds__(256)
 masked_loss_kernel(const float* __restrict__ e, const float* __restrict__ n, const uint8_t* __restrict__ mask, int l1,
                    double* __restrict__ acc, float* __restrict__ grad, float gscale, int64_t V,
@@ -219,23 +207,11 @@ masked_loss_kernel(const float* __restrict__ e, const float* __restrict__ n, con
     float s = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += stride) {
         const float d = e[base + i] - n[base + i];
-        const bool in = mask[i] != 0;
         float g = 0.f;
-        if (in) {
-            if (l1) { s += fabsf(d); g = (d > 0.f) ? gscale : ((d < 0.f) ? -gscale : 0.f); }
-            else { s += d * d; g = 2.0f * d * gscale; }
-        }
+        if (mask[i] != 0) g = simple_loss_elem(d, l1, gscale, &s);
         if (grad) grad[base + i] = g;
     }
-    __shared__ double part[4];
-    double ws = wave_sum((double)s);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = ws;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = part[0] + part[1] + part[2] + part[3];
-        if (quant != 0.0) t = rint(t * quant) / quant;  // TDX_DETERMINISTIC: exact (order-independent) f64 sums, see gn_stats_launch
-        atomicAdd(acc, t);
-    }
+    block_sum_atomic<1>(acc, {(double)s}, quant);
 }
 // the same pass with 16-B accesses, two independent trips in flight per thread (V % 4 == 0: every sample and feature
 // plane starts on a 16-B boundary).  The scalar kernel above walks 36 dependent-free but ROLLED trips of 4-B loads per
@@ -254,10 +230,7 @@ masked_loss_vec_kernel(const float* __restrict__ e, const float* __restrict__ n,
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             g[k] = 0.f;
-            if ((m >> (8 * k)) & 0xffu) {
-                if (l1) { s += fabsf(d[k]); g[k] = (d[k] > 0.f) ? gscale : ((d[k] < 0.f) ? -gscale : 0.f); }
-                else { s += d[k] * d[k]; g[k] = 2.0f * d[k] * gscale; }
-            }
+            if ((m >> (8 * k)) & 0xffu) g[k] = simple_loss_elem(d[k], l1, gscale, &s);
         }
         if (grad) *reinterpret_cast<float4*>(grad + base + 4 * i) = make_float4(g[0], g[1], g[2], g[3]);
     };
@@ -272,15 +245,7 @@ masked_loss_vec_kernel(const float* __restrict__ e, const float* __restrict__ n,
     for (; i < V4; i += stride)
         one(*reinterpret_cast<const float4*>(e + base + 4 * i), *reinterpret_cast<const float4*>(n + base + 4 * i),
             *reinterpret_cast<const unsigned*>(mask + 4 * i), i);
-    __shared__ double part[4];
-    double ws = wave_sum((double)s);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = ws;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = part[0] + part[1] + part[2] + part[3];
-        if (quant != 0.0) t = rint(t * quant) / quant;  // TDX_DETERMINISTIC: exact (order-independent) f64 sums, see gn_stats_launch
-        atomicAdd(acc, t);
-    }
+    block_sum_atomic<1>(acc, {(double)s}, quant);
 }
 __global__ void masked_loss_finish(const double* acc, float* loss, double inv, const int64_t* n_cells_dev, double samples) {
     if (n_cells_dev) inv = 1.0 / (samples * (double)*n_cells_dev);
@@ -352,14 +317,15 @@ __device__ __forceinline__ float lv_sigmoid(float w) { return 1.0f / (1.0f + exp
 // The ELBO term is evaluated in DOUBLE from the float inputs.  Its summands reach |log_var| + (diff^2) exp(-log_var) --
 // tens at t == 0, where exp(-log_var) ~ 1e3 -- while their mean is O(1) and the total subtracts it from the simple term:
 // in float the per-element roundings of log_var alone (|log_var| 2^-24 ~ 4e-7) left the mean 2e-7 off and the total
-// several ulps off where the two terms cancel.  Two double exponentials per element; the pass moves 28 B per element.  The simple term's gradient is the float expression of masked_loss_kernel, bit for bit.
+// several ulps off where the two terms cancel.  Two double exponentials per element; the pass moves 28 B per element.
+// The simple term's gradient is the one masked_loss_kernel writes (simple_loss_grad); its sum is kept in double here.
 __device__ __forceinline__ void elbo_elem(const ElboCoef& c, float eps, float w, float noise, float xs, float xt, int l1,
                                           int clip, int detach_mean, float gscale, double escale, double& simple, double& elbo,
                                           float& g_eps, float& g_w) {
-    const float d = eps - noise;
     const double dd = (double)eps - (double)noise;
-    if (l1) { simple += fabs(dd); g_eps = (d > 0.f) ? gscale : ((d < 0.f) ? -gscale : 0.f); }
-    else { simple += dd * dd; g_eps = 2.0f * d * gscale; }
+    g_eps = simple_loss_grad(eps - noise, l1, gscale);
+    if (l1) simple += fabs(dd);
+    else simple += dd * dd;
     const double s = 1.0 / (1.0 + exp(-(double)w));
     const double lv = c.lb + s * c.dl;
     const double raw = c.recip * xt - c.recipm1 * eps;
@@ -423,15 +389,7 @@ elbo_loss_kernel(const float* __restrict__ out, const float* __restrict__ noise,
             if (grad) { grad[ebase + i] = ge; grad[wbase + i] = gw; }
         }
     }
-    __shared__ double part[2][4];
-    const double ws = wave_sum(ssum), we = wave_sum(esum);
-    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = ws; part[1][threadIdx.x >> 6] = we; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        double s = part[threadIdx.x][0] + part[threadIdx.x][1] + part[threadIdx.x][2] + part[threadIdx.x][3];
-        if (quant != 0.0) s = rint(s * quant) / quant;  // TDX_DETERMINISTIC: exact (order-independent) f64 sums, as masked_loss_kernel
-        atomicAdd(acc + threadIdx.x, s);
-    }
+    block_sum_atomic<2>(acc, {ssum, esum}, quant);
 }
 // loss = {total, simple, elbo}: both terms are means over the same B F n_cells elements
 __global__ void elbo_loss_finish(const double* acc, float* loss, double inv, const int64_t* n_cells_dev, double samples,
@@ -521,9 +479,8 @@ __device__ __forceinline__ void philox_normal4(uint64_t ctr, uint64_t sid, uint6
     }
 }
 
-__global__ void __launch_bounds__(256) randn_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t sid,
-                                                    const uint64_t* __restrict__ offp) {
-    const uint64_t off = *offp;
+// n draws of stream `sid` from counter `off` on, four per counter, by the lanes of one grid row
+__device__ __forceinline__ void philox_fill(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t sid, uint64_t off) {
     const int64_t n4 = (n + 3) >> 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
@@ -534,23 +491,16 @@ __global__ void __launch_bounds__(256) randn_kernel(float* __restrict__ out, int
             if (4 * i + k < n) out[4 * i + k] = r[k];
     }
 }
+__global__ void __launch_bounds__(256) randn_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t sid,
+                                                    const uint64_t* __restrict__ offp) {
+    philox_fill(out, n, seed, sid, *offp);
+}
 __global__ void advance_offset(uint64_t* offp, uint64_t by) { *offp += by; }
 
 __global__ void __launch_bounds__(256) randn_batched_kernel(float* __restrict__ out, int64_t n, uint64_t seed,
                                                             const uint64_t* __restrict__ sids,
                                                             const uint64_t* __restrict__ offp) {
-    const uint64_t off = *offp;
-    const uint64_t sid = sids[blockIdx.y];
-    float* o = out + (int64_t)blockIdx.y * n;
-    const int64_t n4 = (n + 3) >> 2;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        float r[4];
-        philox_normal4(off + (uint64_t)i, sid, seed, r);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (4 * i + k < n) o[4 * i + k] = r[k];
-    }
+    philox_fill(out + (int64_t)blockIdx.y * n, n, seed, sids[blockIdx.y], *offp);
 }
 
 extern "C" int tdx_randn_batched(float* out, int B, int64_t n, uint64_t seed, const uint64_t* stream_ids,
@@ -563,172 +513,195 @@ extern "C" int tdx_randn_batched(float* out, int B, int64_t n, uint64_t seed, co
     return tdx_launch_status();
 }
 
-// ------------------------------------------------------------------ reverse step, noise drawn in the kernel ---
-// The same update as p_sample_step_kernel with z and z2 generated where they are consumed: lane i of sample b draws the
-// four normals randn_batched_kernel would have written to z[b][4i..4i+3] (counter off + i) and to z2 (counter
-// off + n4 + i), so a run is bit-identical to tdx_randn_batched(z); tdx_randn_batched(z2); tdx_p_sample_step(...).
-// Saves two 4-byte writes and two reads per value; the Philox rounds are a few microseconds of VALU per launch.
-__global__ void __launch_bounds__(256)
-p_sample_step_rng_kernel(const float* __restrict__ x_t, const float* __restrict__ eps, const float* __restrict__ x_bcs,
-                         const uint8_t* __restrict__ mask, const float* __restrict__ sched, int T,
-                         const int64_t* __restrict__ tp, int noise_bcs, int clip, float* __restrict__ out, int64_t V,
-                         int64_t n4, uint64_t seed, const uint64_t* __restrict__ sids,
-                         const uint64_t* __restrict__ offp) {
-    const int64_t t = *tp;
-    const uint64_t off = *offp, sid = sids[blockIdx.y];
-    const float recip = sched[t], recipm1 = sched[T + t], c1 = sched[2 * T + t], c2 = sched[3 * T + t];
-    const float sigma = __expf(sched[4 * T + t] * 0.5f);
-    const float sa = sched[5 * T + t], sb = sched[6 * T + t];
-    const bool last = (t == 0);
-    const int64_t base4 = (int64_t)blockIdx.y * n4;
-    const int64_t v4 = V >> 2;
-    const float4* xt4 = reinterpret_cast<const float4*>(x_t) + base4;
-    const float4* e4 = reinterpret_cast<const float4*>(eps) + base4;
-    const float4* xb4 = reinterpret_cast<const float4*>(x_bcs) + base4;
-    const uchar4* m4 = reinterpret_cast<const uchar4*>(mask);
-    float4* o4 = reinterpret_cast<float4*>(out) + base4;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const float4 xv = xt4[i], ev = e4[i];
-        const uchar4 mv = m4[i % v4];
-        const bool in[4] = {mv.x != 0, mv.y != 0, mv.z != 0, mv.w != 0};
-        const bool any_in = in[0] | in[1] | in[2] | in[3], any_out = !(in[0] & in[1] & in[2] & in[3]);
-        const float xt[4] = {xv.x, xv.y, xv.z, xv.w}, ee[4] = {ev.x, ev.y, ev.z, ev.w};
-        float xb[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f}, z2[4] = {0.f, 0.f, 0.f, 0.f};
-        if (any_out && (last || noise_bcs)) {
-            const float4 bv = xb4[i];
-            xb[0] = bv.x; xb[1] = bv.y; xb[2] = bv.z; xb[3] = bv.w;
-        }
-        if (!last) {
-            if (any_in) philox_normal4(off + (uint64_t)i, sid, seed, z);
-            if (noise_bcs && any_out) philox_normal4(off + (uint64_t)n4 + (uint64_t)i, sid, seed, z2);
-        }
-        float r[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float x0h = recip * xt[k] - recipm1 * ee[k];
-            if (!noise_bcs && !in[k]) x0h = xt[k];
-            if (clip) x0h = fminf(fmaxf(x0h, -1.0f), 1.0f);
-            float v = c1 * x0h + c2 * xt[k];
-            if (last) {
-                if (!in[k]) v = xb[k];
-            } else if (in[k]) {
-                v += sigma * z[k];
-            } else if (noise_bcs) {
-                v = sa * xb[k] + sb * z2[k];
-            }
-            r[k] = v;
-        }
-        o4[i] = make_float4(r[0], r[1], r[2], r[3]);
+// ------------------------------------------------------------------ reverse step: three rules over two skeletons ---
+// One launch takes the state from one timestep of its sequence to the one before.  A RULE says which tables a step reads
+// and what it does to one element:
+//   Coef          the step's coefficients (block-uniform scalars); `last` = the step that writes the mean and fixes the BC cells
+//   valid(i)      is i a column of the tables?  A finished trajectory has none: the skeletons then write nothing
+//   load(i)       column i
+//   draws_z(c)    does the interior consume z at this step?
+//   update(...)   one element; w, z, z2 and xb arrive as 0 where the step does not use them
+//   reads_w       eps is the decoder's [eps_hat | w], 2F planes per sample, and w feeds the update
+// The two SKELETONS own everything else -- indexing, the mask, which operands are read, where the noise comes from -- so the
+// tensor-noise and the in-kernel-noise entry of a rule agree bit for bit by construction of `update`: the DDIM and the
+// learned-variance rule spell every multiply-add as an fmaf because, left to the compiler, the contraction of a * b + c * d
+// came out differently in the scalar and in the 4-wide loop (1 ulp apart).
+
+// ddpm.py:745-752 + 797-811: x0h from eps, the posterior mean, sigma = exp(log_betas[t] / 2) for the interior, BC cells
+// re-noised at level t under noise_bcs.  sched = the 7 tables of include/tdx.h.  The two kernels this rule replaced wrote
+// plain a * b - c * d and a * b + c * d; the fmafs below are the contractions the compiler chose for them (read off their
+// ISA: the mean fuses c2 x_t, NOT c1 x0h as LvRule does), and tests/golden/reverse_step_bits.json pins the bits.  Left
+// unspelled, the scalar skeleton contracted sa xb + sb z2 the other way round and came out 1 ulp off.  Fast exp for sigma.
+struct AncestralRule {
+    const float* sched;
+    int T;
+    static constexpr bool reads_w = false;
+    struct Coef {
+        float recip, recipm1, c1, c2, sigma, sa, sb;
+        bool last;
+    };
+    __device__ __forceinline__ bool valid(int64_t t) const { return t >= 0 && t < T; }
+    __device__ __forceinline__ Coef load(int64_t t) const {
+        Coef c;
+        c.recip = sched[t]; c.recipm1 = sched[T + t]; c.c1 = sched[2 * T + t]; c.c2 = sched[3 * T + t];
+        c.sigma = __expf(sched[4 * T + t] * 0.5f);
+        c.sa = sched[5 * T + t]; c.sb = sched[6 * T + t];
+        c.last = (t == 0);
+        return c;
     }
-}
-// offset += by; t -= 1: the two scalar updates that close a reverse step, in one launch
-__global__ void advance_step(uint64_t* offp, uint64_t by, int64_t* tp) { *offp += by; *tp -= 1; }
-
-extern "C" int tdx_p_sample_step_rng(const float* x_t, const float* eps, const float* x_bcs, const uint8_t* mask,
-                                     const float* sched, int T, int64_t* t, int noise_bcs, int clip, float* out, int B,
-                                     int F, int64_t V, uint64_t seed, const uint64_t* stream_ids, uint64_t* offset_dev,
-                                     void* stream) {
-    TDX_CHECK_ARG(x_t && eps && x_bcs && mask && sched && t && out && stream_ids && offset_dev);
-    TDX_CHECK_ARG(T > 0 && B > 0 && F > 0 && V > 0 && (V & 3) == 0);
-    TDX_CHECK_ARG(((uintptr_t)x_t | (uintptr_t)eps | (uintptr_t)x_bcs | (uintptr_t)out) % 16 == 0 && (uintptr_t)mask % 4 == 0);
-    const int64_t n4 = (int64_t)F * V / 4;
-    dim3 grid((unsigned)min((int64_t)256, (n4 + 255) / 256), B);
-    hipLaunchKernelGGL(p_sample_step_rng_kernel, grid, dim3(256), 0, as_stream(stream), x_t, eps, x_bcs, mask, sched, T,
-                       (const int64_t*)t, noise_bcs, clip, out, V, n4, seed, stream_ids, (const uint64_t*)offset_dev);
-    hipLaunchKernelGGL(advance_step, dim3(1), dim3(1), 0, as_stream(stream), offset_dev,
-                       (uint64_t)(noise_bcs ? 2 * n4 : n4), t);
-    return tdx_launch_status();
-}
-
-// ------------------------------------------------------------------ reverse step, learned variances ---
-// p_sample_step_kernel for the model that also predicts its variance (ddpm.py:732-741): `mo` is the decoder's output
-// (B, 2F, V) = [eps_hat | w], and the noise inside the domain is scaled per element by sigma = exp(log_var / 2),
-// log_var = lb + sigmoid(w) (plv - lb), lb = log_betas[t], plv = posterior_log_var[t], instead of by exp(lb / 2).
-struct LvStepCoef {
-    float recip, recipm1, c1, c2, lb, dl, sa, sb;  // dl = plv - lb
-    bool last;
+    static __device__ __forceinline__ bool draws_z(const Coef& c) { return !c.last; }
+    static __device__ __forceinline__ float update(const Coef& c, float xt, float eps, float, float z, float z2, float xb,
+                                                   bool inside, int noise_bcs, int clip) {
+        float x0h = fmaf(c.recip, xt, -(c.recipm1 * eps));
+        if (!noise_bcs && !inside) x0h = xt;
+        if (clip) x0h = fminf(fmaxf(x0h, -1.0f), 1.0f);
+        float r = fmaf(c.c2, xt, c.c1 * x0h);
+        if (c.last) {
+            if (!inside) r = xb;
+        } else if (inside) {
+            r = fmaf(c.sigma, z, r);
+        } else if (noise_bcs) {
+            r = fmaf(c.sa, xb, c.sb * z2);
+        }
+        return r;
+    }
 };
-__device__ __forceinline__ LvStepCoef lv_step_coef(const float* __restrict__ sched, const float* __restrict__ plv, int T, int64_t t) {
-    LvStepCoef c;
-    c.recip = sched[t]; c.recipm1 = sched[T + t]; c.c1 = sched[2 * T + t]; c.c2 = sched[3 * T + t];
-    c.lb = sched[4 * T + t]; c.dl = plv[t] - c.lb;
-    c.sa = sched[5 * T + t]; c.sb = sched[6 * T + t];
-    c.last = (t == 0);
-    return c;
-}
-// one element; both kernels below go through it, every multiply-add spelled as an fmaf for the reason given at
-// ddim_update (the two entries are specified to agree bit for bit).  w and z are read only where they are used.
-__device__ __forceinline__ float lv_step_update(const LvStepCoef& c, float xt, float eps, float w, float z, float z2, float xb,
-                                                bool inside, int noise_bcs, int clip) {
-    float x0 = fmaf(c.recip, xt, -(c.recipm1 * eps));
-    if (!noise_bcs && !inside) x0 = xt;
-    if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    float r = fmaf(c.c1, x0, c.c2 * xt);
-    if (c.last) {
-        if (!inside) r = xb;
-    } else if (inside) {
-        const float sigma = expf(0.5f * fmaf(lv_sigmoid(w), c.dl, c.lb));
-        r = fmaf(sigma, z, r);
-    } else if (noise_bcs) {
-        r = fmaf(c.sa, xb, c.sb * z2);
-    }
-    return r;
-}
 
+// The ancestral step of the model that also predicts its variance (ddpm.py:732-741): the noise inside the domain is
+// scaled per element by sigma = exp(log_var / 2), log_var = lb + sigmoid(w) (plv - lb), lb = log_betas[t], plv =
+// posterior_log_var[t], instead of by exp(lb / 2).
+struct LvRule {
+    const float *sched, *plv;
+    int T;
+    static constexpr bool reads_w = true;
+    struct Coef {
+        float recip, recipm1, c1, c2, lb, dl, sa, sb;  // dl = plv - lb
+        bool last;
+    };
+    __device__ __forceinline__ bool valid(int64_t t) const { return t >= 0 && t < T; }
+    __device__ __forceinline__ Coef load(int64_t t) const {
+        Coef c;
+        c.recip = sched[t]; c.recipm1 = sched[T + t]; c.c1 = sched[2 * T + t]; c.c2 = sched[3 * T + t];
+        c.lb = sched[4 * T + t]; c.dl = plv[t] - c.lb;
+        c.sa = sched[5 * T + t]; c.sb = sched[6 * T + t];
+        c.last = (t == 0);
+        return c;
+    }
+    static __device__ __forceinline__ bool draws_z(const Coef& c) { return !c.last; }
+    static __device__ __forceinline__ float update(const Coef& c, float xt, float eps, float w, float z, float z2, float xb,
+                                                   bool inside, int noise_bcs, int clip) {
+        float x0 = fmaf(c.recip, xt, -(c.recipm1 * eps));
+        if (!noise_bcs && !inside) x0 = xt;
+        if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        float r = fmaf(c.c1, x0, c.c2 * xt);
+        if (c.last) {
+            if (!inside) r = xb;
+        } else if (inside) {
+            const float sigma = expf(0.5f * fmaf(lv_sigmoid(w), c.dl, c.lb));
+            r = fmaf(sigma, z, r);
+        } else if (noise_bcs) {
+            r = fmaf(c.sa, xb, c.sb * z2);
+        }
+        return r;
+    }
+};
+
+// Generalized DDIM update (Song et al. 2021, eq. 12) from tau_k to tau_{k-1}; tab = 6 rows of S floats (schedules.
+// DDIM_PACKED_ORDER), column k.  x0 is formed as model_predictions forms it (BC cells keep x_t without noise_bcs, then the
+// clip); where that changed it, eps is re-derived from it (predict_noise_from_start) so that x0 and the direction term
+// describe the same point.  BC cells under noise_bcs are re-noised at the level of the state PRODUCED, tau_{k-1} (sp =
+// sqrt(abar), sbp = sqrt(1 - abar) there): the ancestral loop re-noises them at level t for x_{t-1}, one level off, an
+// offset a subsequence cannot keep.  Step k = 0 writes the mean and fixes the BC cells.  z is consumed only where
+// sigma != 0 (eta = 0: the interior does not depend on the noise at all, not even through the sign of a zero); the Philox
+// rounds for it are then skipped, the offset still advances as if they had been drawn.
+struct DdimRule {
+    const float* tab;
+    int S;
+    static constexpr bool reads_w = false;
+    struct Coef {
+        float recip, recipm1, sp, dir, sigma, sbp;
+        bool last;
+    };
+    __device__ __forceinline__ bool valid(int64_t k) const { return k >= 0 && k < S; }
+    __device__ __forceinline__ Coef load(int64_t k) const {
+        Coef c;
+        c.recip = tab[k]; c.recipm1 = tab[S + k]; c.sp = tab[2 * S + k];
+        c.dir = tab[3 * S + k]; c.sigma = tab[4 * S + k]; c.sbp = tab[5 * S + k];
+        c.last = (k == 0);
+        return c;
+    }
+    static __device__ __forceinline__ bool draws_z(const Coef& c) { return !c.last && c.sigma != 0.0f; }
+    static __device__ __forceinline__ float update(const Coef& c, float xt, float eps, float, float z, float z2, float xb,
+                                                   bool inside, int noise_bcs, int clip) {
+        const float raw = fmaf(c.recip, xt, -(c.recipm1 * eps));
+        float x0 = raw;
+        if (!noise_bcs && !inside) x0 = xt;
+        if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        const float e = (x0 == raw) ? eps : fmaf(c.recip, xt, -x0) / c.recipm1;
+        float r = fmaf(c.sp, x0, c.dir * e);
+        if (c.last) {
+            if (!inside) r = xb;
+        } else if (inside) {
+            if (c.sigma != 0.0f) r = fmaf(c.sigma, z, r);
+        } else if (noise_bcs) {
+            r = fmaf(c.sp, xb, c.sbp * z2);
+        }
+        return r;
+    }
+};
+
+// Skeleton 1: z and z2 are tensors.  One block row per (b, f) plane, one element per lane and trip.  A NULL noise tensor
+// reads as "no noise" rather than being dereferenced (the host cannot see the step index); x_bcs, z, z2 and w are read
+// only where the step uses them.
+template <typename Rule>
 __global__ void __launch_bounds__(256)
-p_sample_step_lv_kernel(const float* __restrict__ x_t, const float* __restrict__ mo, const float* __restrict__ z,
-                        const float* __restrict__ z2, const float* __restrict__ x_bcs, const uint8_t* __restrict__ mask,
-                        const float* __restrict__ sched, const float* __restrict__ plv, int T, const int64_t* __restrict__ tp,
-                        int noise_bcs, int clip, float* __restrict__ out, int F, int64_t V) {
-    const int64_t t = *tp;
-    if (t < 0 || t >= T) return;  // a finished trajectory: no column to read
-    const LvStepCoef c = lv_step_coef(sched, plv, T, t);
-    // a NULL noise tensor reads as "no noise" rather than being dereferenced (the host cannot see t)
-    const bool use_z = !c.last && z, use_z2 = !c.last && noise_bcs && z2;
-    const int plane = blockIdx.y, b = plane / F, f = plane - b * F;
+reverse_step_kernel(Rule rule, const float* __restrict__ x_t, const float* __restrict__ eps, const float* __restrict__ z,
+                    const float* __restrict__ z2, const float* __restrict__ x_bcs, const uint8_t* __restrict__ mask,
+                    const int64_t* __restrict__ ip, int noise_bcs, int clip, float* __restrict__ out, int F, int64_t V) {
+    const int64_t idx = *ip;
+    if (!rule.valid(idx)) return;  // a finished trajectory: no column to read
+    const typename Rule::Coef c = rule.load(idx);
+    const bool use_z = Rule::draws_z(c) && z, use_z2 = !c.last && noise_bcs && z2, use_xb = c.last || noise_bcs;
+    const int plane = blockIdx.y;
     const int64_t base = (int64_t)plane * V;
-    const int64_t ebase = ((int64_t)b * 2 * F + f) * V, wbase = ebase + (int64_t)F * V;
+    int64_t ebase = base, wbase = 0;
+    if (Rule::reads_w) {  // sample b: F planes of eps_hat, then F of w
+        const int b = plane / F, f = plane - b * F;
+        ebase = ((int64_t)b * 2 * F + f) * V;
+        wbase = ebase + (int64_t)F * V;
+    }
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += stride) {
         const bool inside = mask[i] != 0;
         const bool noisy = use_z && inside;
-        const float zz = noisy ? z[base + i] : 0.f, ww = noisy ? mo[wbase + i] : 0.f;
+        const float zz = noisy ? z[base + i] : 0.f, ww = (Rule::reads_w && noisy) ? eps[wbase + i] : 0.f;
         const float zb = (use_z2 && !inside) ? z2[base + i] : 0.f;
-        out[base + i] = lv_step_update(c, x_t[base + i], mo[ebase + i], ww, zz, zb, x_bcs[base + i], inside, noise_bcs, clip);
+        const float xb = (use_xb && !inside) ? x_bcs[base + i] : 0.f;
+        out[base + i] = Rule::update(c, x_t[base + i], eps[ebase + i], ww, zz, zb, xb, inside, noise_bcs, clip);
     }
 }
 
-extern "C" int tdx_p_sample_step_lv(const float* x_t, const float* model_out, const float* z, const float* z2,
-                                    const float* x_bcs, const uint8_t* mask, const float* sched,
-                                    const float* posterior_log_var, int T, const int64_t* t, int noise_bcs, int clip,
-                                    float* out, int B, int F, int64_t V, void* stream) {
-    TDX_CHECK_ARG(x_t && model_out && x_bcs && mask && sched && posterior_log_var && t && out);
-    TDX_CHECK_ARG(T > 0 && B > 0 && F > 0 && V > 0);
-    dim3 grid((unsigned)min((int64_t)128, (V + 255) / 256), B * F);
-    hipLaunchKernelGGL(p_sample_step_lv_kernel, grid, dim3(256), 0, as_stream(stream), x_t, model_out, z, z2, x_bcs, mask,
-                       sched, posterior_log_var, T, t, noise_bcs, clip, out, F, V);
-    return tdx_launch_status();
-}
-
-// The same update with z and z2 drawn where they are consumed, laid out, counted and skipped exactly as
-// p_sample_step_rng_kernel does (z: counter off + i, z2: off + n4 + i, n4 = F V / 4 over the F STATE planes), so a run is
-// bit-identical to tdx_randn_batched(z); [tdx_randn_batched(z2);] tdx_p_sample_step_lv(...).
+// Skeleton 2: z and z2 are generated where they are consumed.  One block row per sample, four elements per lane and trip:
+// lane i of sample b draws the four normals randn_batched_kernel would have written to z[b][4i..4i+3] (counter off + i)
+// and to z2 (counter off + n4 + i, n4 = F V / 4 over the F planes of the STATE), so a run is bit-identical to
+// tdx_randn_batched(z); [tdx_randn_batched(z2);] <the rule's tensor-noise entry>.  Saves two 4-byte writes and two reads
+// per value; the Philox rounds are a few microseconds of VALU per launch, and are skipped for a quad that has no use for them.
+template <typename Rule>
 __global__ void __launch_bounds__(256)
-p_sample_step_lv_rng_kernel(const float* __restrict__ x_t, const float* __restrict__ mo, const float* __restrict__ x_bcs,
-                            const uint8_t* __restrict__ mask, const float* __restrict__ sched,
-                            const float* __restrict__ plv, int T, const int64_t* __restrict__ tp, int noise_bcs, int clip,
-                            float* __restrict__ out, int64_t V, int64_t n4, uint64_t seed,
-                            const uint64_t* __restrict__ sids, const uint64_t* __restrict__ offp) {
-    const int64_t t = *tp;
-    if (t < 0 || t >= T) return;  // a finished trajectory: no column to read
+reverse_step_rng_kernel(Rule rule, const float* __restrict__ x_t, const float* __restrict__ eps,
+                        const float* __restrict__ x_bcs, const uint8_t* __restrict__ mask, const int64_t* __restrict__ ip,
+                        int noise_bcs, int clip, float* __restrict__ out, int64_t V, int64_t n4, uint64_t seed,
+                        const uint64_t* __restrict__ sids, const uint64_t* __restrict__ offp) {
+    const int64_t idx = *ip;
+    if (!rule.valid(idx)) return;  // a finished trajectory: no column to read
     const uint64_t off = *offp, sid = sids[blockIdx.y];
-    const LvStepCoef c = lv_step_coef(sched, plv, T, t);
+    const typename Rule::Coef c = rule.load(idx);
+    const bool use_z = Rule::draws_z(c), use_z2 = !c.last && noise_bcs, use_xb = c.last || noise_bcs;
     const int64_t base4 = (int64_t)blockIdx.y * n4;
     const int64_t v4 = V >> 2;
     const float4* xt4 = reinterpret_cast<const float4*>(x_t) + base4;
-    const float4* e4 = reinterpret_cast<const float4*>(mo) + 2 * base4;  // sample b: F planes of eps_hat, then F of w
-    const float4* w4 = e4 + n4;
+    const float4* e4 = reinterpret_cast<const float4*>(eps) + (Rule::reads_w ? 2 : 1) * base4;
+    const float4* w4 = e4 + n4;  // reads_w: sample b holds F planes of eps_hat, then F of w
     const float4* xb4 = reinterpret_cast<const float4*>(x_bcs) + base4;
     const uchar4* m4 = reinterpret_cast<const uchar4*>(mask);
     float4* o4 = reinterpret_cast<float4*>(out) + base4;
@@ -740,127 +713,38 @@ p_sample_step_lv_rng_kernel(const float* __restrict__ x_t, const float* __restri
         const bool any_in = in[0] | in[1] | in[2] | in[3], any_out = !(in[0] & in[1] & in[2] & in[3]);
         const float xt[4] = {xv.x, xv.y, xv.z, xv.w}, ee[4] = {ev.x, ev.y, ev.z, ev.w};
         float xb[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f}, z2[4] = {0.f, 0.f, 0.f, 0.f}, w[4] = {0.f, 0.f, 0.f, 0.f};
-        if (any_out && (c.last || noise_bcs)) {
+        if (use_xb && any_out) {
             const float4 bv = xb4[i];
             xb[0] = bv.x; xb[1] = bv.y; xb[2] = bv.z; xb[3] = bv.w;
         }
-        if (!c.last) {
-            if (any_in) {
+        if (use_z && any_in) {
+            if (Rule::reads_w) {
                 const float4 wv = w4[i];
                 w[0] = wv.x; w[1] = wv.y; w[2] = wv.z; w[3] = wv.w;
-                philox_normal4(off + (uint64_t)i, sid, seed, z);
             }
-            if (noise_bcs && any_out) philox_normal4(off + (uint64_t)n4 + (uint64_t)i, sid, seed, z2);
+            philox_normal4(off + (uint64_t)i, sid, seed, z);
         }
+        if (use_z2 && any_out) philox_normal4(off + (uint64_t)n4 + (uint64_t)i, sid, seed, z2);
         float r[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) r[k] = lv_step_update(c, xt[k], ee[k], w[k], z[k], z2[k], xb[k], in[k], noise_bcs, clip);
+        for (int k = 0; k < 4; ++k) r[k] = Rule::update(c, xt[k], ee[k], w[k], z[k], z2[k], xb[k], in[k], noise_bcs, clip);
         o4[i] = make_float4(r[0], r[1], r[2], r[3]);
     }
 }
-
-extern "C" int tdx_p_sample_step_lv_rng(const float* x_t, const float* model_out, const float* x_bcs, const uint8_t* mask,
-                                        const float* sched, const float* posterior_log_var, int T, int64_t* t,
-                                        int noise_bcs, int clip, float* out, int B, int F, int64_t V, uint64_t seed,
-                                        const uint64_t* stream_ids, uint64_t* offset_dev, void* stream) {
-    TDX_CHECK_ARG(x_t && model_out && x_bcs && mask && sched && posterior_log_var && t && out && stream_ids && offset_dev);
-    TDX_CHECK_ARG(T > 0 && B > 0 && F > 0 && V > 0 && (V & 3) == 0);
-    TDX_CHECK_ARG(((uintptr_t)x_t | (uintptr_t)model_out | (uintptr_t)x_bcs | (uintptr_t)out) % 16 == 0 && (uintptr_t)mask % 4 == 0);
-    const int64_t n4 = (int64_t)F * V / 4;
-    dim3 grid((unsigned)min((int64_t)256, (n4 + 255) / 256), B);
-    hipLaunchKernelGGL(p_sample_step_lv_rng_kernel, grid, dim3(256), 0, as_stream(stream), x_t, model_out, x_bcs, mask, sched,
-                       posterior_log_var, T, (const int64_t*)t, noise_bcs, clip, out, V, n4, seed, stream_ids,
-                       (const uint64_t*)offset_dev);
-    hipLaunchKernelGGL(advance_step, dim3(1), dim3(1), 0, as_stream(stream), offset_dev,
-                       (uint64_t)(noise_bcs ? 2 * n4 : n4), t);
-    return tdx_launch_status();
-}
-
-// ------------------------------------------------------------------ DDIM step over a timestep subsequence ---
-// Generalized DDIM update (Song et al. 2021, eq. 12) from tau_k to tau_{k-1}; tab = 6 rows of S floats (schedules.
-// DDIM_PACKED_ORDER), column k.  x0 is formed as model_predictions forms it (BC cells keep x_t without noise_bcs, then the
-// clip); where that changed it, eps is re-derived from it (predict_noise_from_start) so that x0 and the direction term
-// describe the same point.  BC cells under noise_bcs are re-noised at the level of the state PRODUCED, tau_{k-1} (sp =
-// sqrt(abar), sbp = sqrt(1 - abar) there): the ancestral loop re-noises them at level t for x_{t-1}, one level off, an
-// offset a subsequence cannot keep.  Step k = 0 writes the mean and fixes the BC cells.
-struct DdimCoef {
-    float recip, recipm1, sp, dir, sigma, sbp;
-    bool last;
-};
-__device__ __forceinline__ DdimCoef ddim_coef(const float* __restrict__ tab, int S, int64_t k) {
-    DdimCoef c;
-    c.recip = tab[k]; c.recipm1 = tab[S + k]; c.sp = tab[2 * S + k];
-    c.dir = tab[3 * S + k]; c.sigma = tab[4 * S + k]; c.sbp = tab[5 * S + k];
-    c.last = (k == 0);
-    return c;
-}
-// one element; both kernels below go through it.  Every multiply-add is spelled as an fmaf: left to the compiler, the
-// contraction of a * b + c * d came out differently in the scalar and in the 4-wide loop (1 ulp apart), and the two entries
-// are specified to agree bit for bit.  z is read only where sigma != 0 (eta = 0: the interior does not depend on the noise
-// at all, not even through the sign of a zero).
-__device__ __forceinline__ float ddim_update(const DdimCoef& c, float xt, float eps, float z, float z2, float xb,
-                                             bool inside, int noise_bcs, int clip) {
-    const float raw = fmaf(c.recip, xt, -(c.recipm1 * eps));
-    float x0 = raw;
-    if (!noise_bcs && !inside) x0 = xt;
-    if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    const float e = (x0 == raw) ? eps : fmaf(c.recip, xt, -x0) / c.recipm1;
-    float r = fmaf(c.sp, x0, c.dir * e);
-    if (c.last) {
-        if (!inside) r = xb;
-    } else if (inside) {
-        if (c.sigma != 0.0f) r = fmaf(c.sigma, z, r);
-    } else if (noise_bcs) {
-        r = fmaf(c.sp, xb, c.sbp * z2);
-    }
-    return r;
-}
-
-__global__ void __launch_bounds__(256)
-ddim_step_kernel(const float* __restrict__ x_t, const float* __restrict__ eps, const float* __restrict__ z,
-                 const float* __restrict__ z2, const float* __restrict__ x_bcs, const uint8_t* __restrict__ mask,
-                 const float* __restrict__ tab, int S, const int64_t* __restrict__ kp, int noise_bcs, int clip,
-                 float* __restrict__ out, int64_t V) {
-    const int64_t k = *kp;
-    if (k < 0 || k >= S) return;  // a finished trajectory: no column to read
-    const DdimCoef c = ddim_coef(tab, S, k);
-    // a NULL noise tensor reads as "no noise" rather than being dereferenced (the host cannot see k or sigma)
-    const bool use_z = !c.last && c.sigma != 0.0f && z, use_z2 = !c.last && noise_bcs && z2;
-    const int64_t base = (int64_t)blockIdx.y * V;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += stride) {
-        const bool inside = mask[i] != 0;
-        const float zz = (use_z && inside) ? z[base + i] : 0.f;
-        const float zb = (use_z2 && !inside) ? z2[base + i] : 0.f;
-        out[base + i] = ddim_update(c, x_t[base + i], eps[base + i], zz, zb, x_bcs[base + i], inside, noise_bcs, clip);
-    }
-}
-
-extern "C" int tdx_ddim_step(const float* x_t, const float* eps, const float* z, const float* z2, const float* x_bcs,
-                             const uint8_t* mask, const float* tab, int S, const int64_t* k, const int64_t* tau,
-                             const int64_t* t, int noise_bcs, int clip, float* out, int B, int F, int64_t V,
-                             void* stream) {
-    TDX_CHECK_ARG(x_t && eps && x_bcs && mask && tab && k && tau && t && out && S > 0 && B > 0 && F > 0 && V > 0);
-    dim3 grid((unsigned)min((int64_t)128, (V + 255) / 256), B * F);
-    hipLaunchKernelGGL(ddim_step_kernel, grid, dim3(256), 0, as_stream(stream), x_t, eps, z, z2, x_bcs, mask, tab, S, k,
-                       noise_bcs, clip, out, V);
-    return tdx_launch_status();
-}
-
-// The same update with z and z2 drawn where they are consumed, laid out and counted exactly as
-// p_sample_step_rng_kernel does (z: counter off + i, z2: off + n4 + i), so a run is bit-identical to
-// tdx_randn_batched(z); [tdx_randn_batched(z2);] tdx_ddim_step(...).  The Philox rounds for z are skipped when sigma == 0
-// (eta = 0) as they are when no lane of the quad is inside; the offset still advances as if they had been drawn.
+// Skeleton 2 for DdimRule, written out as it stood before the skeletons: reverse_step_rng_kernel<DdimRule> averaged 56.6 us
+// at 8 x 4 x 192 x 64 x 48 against 55.6 / 56.2 us for this form, 0.15 us over what the comparison allows
+// (profiles/r19_reverse_step_rules.txt, item 6).  Same loop without the w plane; coefficients and update are the rule's.
 __global__ void __launch_bounds__(256)
 ddim_step_rng_kernel(const float* __restrict__ x_t, const float* __restrict__ eps, const float* __restrict__ x_bcs,
                      const uint8_t* __restrict__ mask, const float* __restrict__ tab, int S,
                      const int64_t* __restrict__ kp, int noise_bcs, int clip, float* __restrict__ out, int64_t V,
                      int64_t n4, uint64_t seed, const uint64_t* __restrict__ sids, const uint64_t* __restrict__ offp) {
     const int64_t k = *kp;
-    if (k < 0 || k >= S) return;  // a finished trajectory: no column to read
+    const DdimRule rule{tab, S};
+    if (!rule.valid(k)) return;  // a finished trajectory: no column to read
     const uint64_t off = *offp, sid = sids[blockIdx.y];
-    const DdimCoef c = ddim_coef(tab, S, k);
-    const bool use_z = !c.last && c.sigma != 0.0f, use_z2 = !c.last && noise_bcs;
+    const DdimRule::Coef c = rule.load(k);
+    const bool use_z = DdimRule::draws_z(c), use_z2 = !c.last && noise_bcs;
     const int64_t base4 = (int64_t)blockIdx.y * n4;
     const int64_t v4 = V >> 2;
     const float4* xt4 = reinterpret_cast<const float4*>(x_t) + base4;
@@ -884,10 +768,12 @@ ddim_step_rng_kernel(const float* __restrict__ x_t, const float* __restrict__ ep
         if (use_z2 && any_out) philox_normal4(off + (uint64_t)n4 + (uint64_t)i, sid, seed, z2);
         float r[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) r[j] = ddim_update(c, xt[j], ee[j], z[j], z2[j], xb[j], in[j], noise_bcs, clip);
+        for (int j = 0; j < 4; ++j) r[j] = DdimRule::update(c, xt[j], ee[j], 0.f, z[j], z2[j], xb[j], in[j], noise_bcs, clip);
         o4[i] = make_float4(r[0], r[1], r[2], r[3]);
     }
 }
+// offset += by; t -= 1: the two scalar updates that close a reverse step, in one launch
+__global__ void advance_step(uint64_t* offp, uint64_t by, int64_t* tp) { *offp += by; *tp -= 1; }
 // offset += by; k -= 1; t = tau[k] while a step is left: the scalar updates that close a DDIM step, in one launch
 __global__ void advance_ddim_step(uint64_t* offp, uint64_t by, int64_t* kp, const int64_t* __restrict__ tau, int S,
                                   int64_t* tp) {
@@ -897,20 +783,90 @@ __global__ void advance_ddim_step(uint64_t* offp, uint64_t by, int64_t* kp, cons
     if (k >= 0 && k < S) *tp = tau[k];
 }
 
+// the launch of each skeleton: the checks every rule shares, and the grid.  `idx` is the rule's device-side step index.
+template <typename Rule>
+static int reverse_step_launch(const Rule& rule, const float* x_t, const float* eps, const float* z, const float* z2,
+                               const float* x_bcs, const uint8_t* mask, const int64_t* idx, int noise_bcs, int clip,
+                               float* out, int B, int F, int64_t V, void* stream) {
+    TDX_CHECK_ARG(x_t && eps && x_bcs && mask && idx && out && B > 0 && F > 0 && V > 0);
+    dim3 grid((unsigned)min((int64_t)128, (V + 255) / 256), B * F);
+    hipLaunchKernelGGL((reverse_step_kernel<Rule>), grid, dim3(256), 0, as_stream(stream), rule, x_t, eps, z, z2, x_bcs, mask,
+                       idx, noise_bcs, clip, out, F, V);
+    return tdx_launch_status();
+}
+// ... then `advance(by)` launches the rule's scalar updates, by = the counters the step has consumed
+template <typename Rule, typename Advance>
+static int reverse_step_rng_launch(const Rule& rule, const float* x_t, const float* eps, const float* x_bcs,
+                                   const uint8_t* mask, const int64_t* idx, int noise_bcs, int clip, float* out, int B, int F,
+                                   int64_t V, uint64_t seed, const uint64_t* stream_ids, const uint64_t* offset_dev,
+                                   void* stream, Advance advance) {
+    TDX_CHECK_ARG(x_t && eps && x_bcs && mask && idx && out && stream_ids && offset_dev);
+    TDX_CHECK_ARG(B > 0 && F > 0 && V > 0 && (V & 3) == 0);
+    TDX_CHECK_ARG(((uintptr_t)x_t | (uintptr_t)eps | (uintptr_t)x_bcs | (uintptr_t)out) % 16 == 0 && (uintptr_t)mask % 4 == 0);
+    const int64_t n4 = (int64_t)F * V / 4;
+    dim3 grid((unsigned)min((int64_t)256, (n4 + 255) / 256), B);
+    if constexpr (std::is_same_v<Rule, DdimRule>)  // written out, see ddim_step_rng_kernel
+        hipLaunchKernelGGL(ddim_step_rng_kernel, grid, dim3(256), 0, as_stream(stream), x_t, eps, x_bcs, mask, rule.tab, rule.S,
+                           idx, noise_bcs, clip, out, V, n4, seed, stream_ids, offset_dev);
+    else
+        hipLaunchKernelGGL((reverse_step_rng_kernel<Rule>), grid, dim3(256), 0, as_stream(stream), rule, x_t, eps, x_bcs, mask,
+                           idx, noise_bcs, clip, out, V, n4, seed, stream_ids, offset_dev);
+    advance((uint64_t)(noise_bcs ? 2 * n4 : n4));
+    return tdx_launch_status();
+}
+
+extern "C" int tdx_p_sample_step(const float* x_t, const float* eps, const float* z, const float* z2,
+                                 const float* x_bcs, const uint8_t* mask, const float* sched, int T, const int64_t* t,
+                                 int noise_bcs, int clip, float* out, int B, int F, int64_t V, void* stream) {
+    TDX_CHECK_ARG(sched && T > 0);
+    return reverse_step_launch(AncestralRule{sched, T}, x_t, eps, z, z2, x_bcs, mask, t, noise_bcs, clip, out, B, F, V, stream);
+}
+extern "C" int tdx_p_sample_step_rng(const float* x_t, const float* eps, const float* x_bcs, const uint8_t* mask,
+                                     const float* sched, int T, int64_t* t, int noise_bcs, int clip, float* out, int B,
+                                     int F, int64_t V, uint64_t seed, const uint64_t* stream_ids, uint64_t* offset_dev,
+                                     void* stream) {
+    TDX_CHECK_ARG(sched && T > 0);
+    return reverse_step_rng_launch(AncestralRule{sched, T}, x_t, eps, x_bcs, mask, t, noise_bcs, clip, out, B, F, V, seed,
+                                   stream_ids, offset_dev, stream, [&](uint64_t by) {
+        hipLaunchKernelGGL(advance_step, dim3(1), dim3(1), 0, as_stream(stream), offset_dev, by, t);
+    });
+}
+
+extern "C" int tdx_p_sample_step_lv(const float* x_t, const float* model_out, const float* z, const float* z2,
+                                    const float* x_bcs, const uint8_t* mask, const float* sched,
+                                    const float* posterior_log_var, int T, const int64_t* t, int noise_bcs, int clip,
+                                    float* out, int B, int F, int64_t V, void* stream) {
+    TDX_CHECK_ARG(sched && posterior_log_var && T > 0);
+    return reverse_step_launch(LvRule{sched, posterior_log_var, T}, x_t, model_out, z, z2, x_bcs, mask, t, noise_bcs, clip,
+                               out, B, F, V, stream);
+}
+extern "C" int tdx_p_sample_step_lv_rng(const float* x_t, const float* model_out, const float* x_bcs, const uint8_t* mask,
+                                        const float* sched, const float* posterior_log_var, int T, int64_t* t,
+                                        int noise_bcs, int clip, float* out, int B, int F, int64_t V, uint64_t seed,
+                                        const uint64_t* stream_ids, uint64_t* offset_dev, void* stream) {
+    TDX_CHECK_ARG(sched && posterior_log_var && T > 0);
+    return reverse_step_rng_launch(LvRule{sched, posterior_log_var, T}, x_t, model_out, x_bcs, mask, t, noise_bcs, clip, out,
+                                   B, F, V, seed, stream_ids, offset_dev, stream, [&](uint64_t by) {
+        hipLaunchKernelGGL(advance_step, dim3(1), dim3(1), 0, as_stream(stream), offset_dev, by, t);
+    });
+}
+
+extern "C" int tdx_ddim_step(const float* x_t, const float* eps, const float* z, const float* z2, const float* x_bcs,
+                             const uint8_t* mask, const float* tab, int S, const int64_t* k, const int64_t* tau,
+                             const int64_t* t, int noise_bcs, int clip, float* out, int B, int F, int64_t V,
+                             void* stream) {
+    TDX_CHECK_ARG(tab && S > 0 && tau && t);
+    return reverse_step_launch(DdimRule{tab, S}, x_t, eps, z, z2, x_bcs, mask, k, noise_bcs, clip, out, B, F, V, stream);
+}
 extern "C" int tdx_ddim_step_rng(const float* x_t, const float* eps, const float* x_bcs, const uint8_t* mask,
                                  const float* tab, int S, int64_t* k, const int64_t* tau, int64_t* t, int noise_bcs,
                                  int clip, float* out, int B, int F, int64_t V, uint64_t seed,
                                  const uint64_t* stream_ids, uint64_t* offset_dev, void* stream) {
-    TDX_CHECK_ARG(x_t && eps && x_bcs && mask && tab && k && tau && t && out && stream_ids && offset_dev);
-    TDX_CHECK_ARG(S > 0 && B > 0 && F > 0 && V > 0 && (V & 3) == 0);
-    TDX_CHECK_ARG(((uintptr_t)x_t | (uintptr_t)eps | (uintptr_t)x_bcs | (uintptr_t)out) % 16 == 0 && (uintptr_t)mask % 4 == 0);
-    const int64_t n4 = (int64_t)F * V / 4;
-    dim3 grid((unsigned)min((int64_t)256, (n4 + 255) / 256), B);
-    hipLaunchKernelGGL(ddim_step_rng_kernel, grid, dim3(256), 0, as_stream(stream), x_t, eps, x_bcs, mask, tab, S,
-                       (const int64_t*)k, noise_bcs, clip, out, V, n4, seed, stream_ids, (const uint64_t*)offset_dev);
-    hipLaunchKernelGGL(advance_ddim_step, dim3(1), dim3(1), 0, as_stream(stream), offset_dev,
-                       (uint64_t)(noise_bcs ? 2 * n4 : n4), k, tau, S, t);
-    return tdx_launch_status();
+    TDX_CHECK_ARG(tab && S > 0 && tau && t);
+    return reverse_step_rng_launch(DdimRule{tab, S}, x_t, eps, x_bcs, mask, k, noise_bcs, clip, out, B, F, V, seed, stream_ids,
+                                   offset_dev, stream, [&](uint64_t by) {
+        hipLaunchKernelGGL(advance_ddim_step, dim3(1), dim3(1), 0, as_stream(stream), offset_dev, by, k, tau, S, t);
+    });
 }
 
 extern "C" int tdx_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, uint64_t* offset_dev, void* stream) {

@@ -796,69 +796,51 @@ class GaussianDiffusion(nn.Module):
                 x_t = torch.where(inside, x_t, self.q_sample(x_bcs, times(t), randn(x_bcs)))
         return torch.where(inside, x_t, x_bcs)
 
-    def _eager_sample(self, x_bcs, C, cell_idx, pbar, start_from, noise_fn):
+    def _eager_loop(self, x_bcs, C, cell_idx, pbar, start_from, noise_fn, times, step):
+        """The eager reverse loop, one launch sequence per step, over the timesteps `times` (int64 on the device,
+        increasing, visited from the last): noise in the reference's drawing order (x_T; then per step i > 0: z, and z' if
+        noise_bcs); `step(x_t, eps, z, z2, x_bcs, mask, i)` is the update of step i."""
         randn = noise_fn if noise_fn is not None else torch.randn_like
         x_bcs = x_bcs.contiguous().float()
-        B, Fd = x_bcs.shape[:2]
-        V = x_bcs[0, 0].numel()
-        dev = x_bcs.device
-        mask, _ = self.domain_mask(cell_idx, V)
-        ts = torch.arange(self.num_timesteps, dtype=torch.long, device=dev)
+        B = x_bcs.shape[0]
+        mask, _ = self.domain_mask(cell_idx, x_bcs[0, 0].numel())
         if start_from is None:
-            x_t, T = randn(x_bcs), self.num_timesteps
+            x_t = randn(x_bcs)
         else:
-            x_t = ops.q_sample(x_bcs, randn(x_bcs), self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod,
-                               ts[start_from - 1 : start_from])
-            T = start_from
+            x_t = ops.q_sample(x_bcs, randn(x_bcs), self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, times[-1:])
         if not self.noise_bcs:
             x_t = self._outside_keep(mask, x_t, x_bcs)
         enc = self.model.encode_local(C) if hasattr(self.model, "encode_local") else None
         kw = {"encoded_local": enc} if enc is not None else {}
-        steps = reversed(range(T))
+        n = times.numel()
+        steps = reversed(range(n))
         if pbar:
             from tqdm.auto import tqdm
 
-            steps = tqdm(steps, desc="sampling loop time step", total=T, position=1)
-        for t in steps:
-            eps = self.model(x_t, ts[t].expand(B), C, **kw)
-            z = randn(x_t) if t > 0 else None
-            z2 = randn(x_bcs) if (t > 0 and self.noise_bcs) else None
-            x_t = ops.p_sample_step(x_t, eps, z, z2, x_bcs, mask, self.step_tables, self.num_timesteps, ts[t : t + 1],
-                                    self.noise_bcs, self.clip_denoised)
+            steps = tqdm(steps, desc="sampling loop time step", total=n, position=1)
+        for i in steps:
+            eps = self.model(x_t, times[i].expand(B), C, **kw)
+            z = randn(x_t) if i > 0 else None
+            z2 = randn(x_bcs) if (i > 0 and self.noise_bcs) else None
+            x_t = step(x_t, eps, z, z2, x_bcs, mask, i)
         return x_t
 
+    def _eager_sample(self, x_bcs, C, cell_idx, pbar, start_from, noise_fn):
+        ts = torch.arange(self.num_timesteps if start_from is None else start_from, dtype=torch.long, device=x_bcs.device)
+        step = lambda x_t, eps, z, z2, xb, mask, t: ops.p_sample_step(
+            x_t, eps, z, z2, xb, mask, self.step_tables, self.num_timesteps, ts[t : t + 1], self.noise_bcs, self.clip_denoised)
+        return self._eager_loop(x_bcs, C, cell_idx, pbar, start_from, noise_fn, ts, step)
+
     def _eager_ddim_sample(self, x_bcs, C, cell_idx, pbar, start_from, noise_fn, S, eta):
-        """The DDIM loop, one launch sequence per step over `ops.ddim_step`; noise in the ancestral order (x_T; then per
-        step k > 0: z, and z' if noise_bcs)."""
-        randn = noise_fn if noise_fn is not None else torch.randn_like
-        x_bcs = x_bcs.contiguous().float()
-        B = x_bcs.shape[0]
+        """The DDIM loop over `ops.ddim_step`; noise in the ancestral order."""
         dev = x_bcs.device
-        mask, _ = self.domain_mask(cell_idx, x_bcs[0, 0].numel())
         taus = schedules.ddim_timesteps(self.num_timesteps, S, start_from)
         tab = schedules.ddim_tables(self.beta_schedule, self.num_timesteps, taus, eta).to(dev)
         tau = torch.tensor(taus, dtype=torch.long, device=dev)
         ks = torch.arange(S, dtype=torch.long, device=dev)
-        if start_from is None:
-            x_t = randn(x_bcs)
-        else:
-            x_t = ops.q_sample(x_bcs, randn(x_bcs), self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, tau[-1:])
-        if not self.noise_bcs:
-            x_t = self._outside_keep(mask, x_t, x_bcs)
-        enc = self.model.encode_local(C) if hasattr(self.model, "encode_local") else None
-        kw = {"encoded_local": enc} if enc is not None else {}
-        steps = reversed(range(S))
-        if pbar:
-            from tqdm.auto import tqdm
-
-            steps = tqdm(steps, desc="sampling loop time step", total=S, position=1)
-        for k in steps:
-            eps = self.model(x_t, tau[k].expand(B), C, **kw)
-            z = randn(x_t) if k > 0 else None
-            z2 = randn(x_bcs) if (k > 0 and self.noise_bcs) else None
-            x_t = ops.ddim_step(x_t, eps, z, z2, x_bcs, mask, tab, ks[k : k + 1], tau, tau[k : k + 1], self.noise_bcs,
-                                self.clip_denoised)
-        return x_t
+        step = lambda x_t, eps, z, z2, xb, mask, k: ops.ddim_step(
+            x_t, eps, z, z2, xb, mask, tab, ks[k : k + 1], tau, tau[k : k + 1], self.noise_bcs, self.clip_denoised)
+        return self._eager_loop(x_bcs, C, cell_idx, pbar, start_from, noise_fn, tau, step)
 
     def p_losses(self, x_start, t, C, metadata, variables, noise=None):
         x_start = x_start.contiguous().float()

@@ -757,15 +757,23 @@ def q_sample(x0, noise, sqrt_ac, sqrt_1mac, t, mask=None, keep_bcs=False):
     return out
 
 
-def p_sample_step(x_t, eps, z, z2, x_bcs, mask, sched, T, t_dev, noise_bcs, clip, out=None):
-    """One fused reverse-diffusion update; t_dev is a device int64 scalar tensor."""
+def _reverse_step(entry, lead, noise_bcs, clip, out, rng=()):
+    """What the six reverse-step entries share: B, F, V of the state, `out` made unless given (it may be x_t), and the
+    argument list -- `lead` (the entry's operands from the state x_t to its step index; tensors go as pointers), noise_bcs,
+    clip, out, B, F, V, then `rng` = (seed, stream_ids, offset_dev) for the entries that draw their noise, and the stream."""
+    x_t = lead[0]
     B, F = x_t.shape[:2]
     V = x_t[0, 0].numel()
     if out is None:
         out = torch.empty_like(x_t)
-    L.call("tdx_p_sample_step", L.ptr(x_t), L.ptr(eps), L.ptr(z), L.ptr(z2), L.ptr(x_bcs), L.ptr(mask), L.ptr(sched), T,
-           L.ptr(t_dev), int(noise_bcs), int(clip), L.ptr(out), B, F, V, L.stream())
+    args = (*lead, int(noise_bcs), int(clip), out, B, F, V, *rng)
+    L.call(entry, *(L.ptr(a) if a is None or torch.is_tensor(a) else a for a in args), L.stream())
     return out
+
+
+def p_sample_step(x_t, eps, z, z2, x_bcs, mask, sched, T, t_dev, noise_bcs, clip, out=None):
+    """One fused reverse-diffusion update; t_dev is a device int64 scalar tensor."""
+    return _reverse_step("tdx_p_sample_step", (x_t, eps, z, z2, x_bcs, mask, sched, T, t_dev), noise_bcs, clip, out)
 
 
 def p_sample_step_rng_supported(x_t) -> bool:
@@ -774,71 +782,48 @@ def p_sample_step_rng_supported(x_t) -> bool:
 
 def p_sample_step_rng(x_t, eps, x_bcs, mask, sched, T, t_dev, noise_bcs, clip, seed, stream_ids, offset_dev, out=None):
     """The reverse step with z (and z2) drawn in the kernel; advances offset_dev and decrements t_dev on the device."""
-    B, F = x_t.shape[:2]
-    V = x_t[0, 0].numel()
-    if out is None:
-        out = torch.empty_like(x_t)
-    L.call("tdx_p_sample_step_rng", L.ptr(x_t), L.ptr(eps), L.ptr(x_bcs), L.ptr(mask), L.ptr(sched), T, L.ptr(t_dev),
-           int(noise_bcs), int(clip), L.ptr(out), B, F, V, seed, L.ptr(stream_ids), L.ptr(offset_dev), L.stream())
-    return out
+    return _reverse_step("tdx_p_sample_step_rng", (x_t, eps, x_bcs, mask, sched, T, t_dev), noise_bcs, clip, out,
+                         (seed, stream_ids, offset_dev))
 
 
-def _lv_step_shapes(x_t, model_out):
+def _check_lv_output(x_t, model_out):
     B, F = x_t.shape[:2]
     if (model_out.dtype != torch.float32 or not model_out.is_contiguous() or model_out.shape[0] != B
             or model_out.shape[1] != 2 * F or model_out.shape[2:] != x_t.shape[2:]):
         raise ValueError(f"learned-variance step: model output {tuple(model_out.shape)} {model_out.dtype} is not the contiguous "
                          f"float32 [eps_hat | w] of a state {tuple(x_t.shape)}")
-    return B, F, x_t[0, 0].numel()
 
 
 def p_sample_step_lv(x_t, model_out, z, z2, x_bcs, mask, sched, posterior_log_var, T, t_dev, noise_bcs, clip, out=None):
     """The fused reverse update of a model with learned variances: model_out = (B, 2F, X, Y, Z) = [eps_hat | w], the noise
     inside the domain scaled per voxel by exp(log_var / 2), log_var = log beta_t + sigmoid(w) (posterior_log_var_t - log beta_t)."""
-    B, F, V = _lv_step_shapes(x_t, model_out)
-    if out is None:
-        out = torch.empty_like(x_t)
-    L.call("tdx_p_sample_step_lv", L.ptr(x_t), L.ptr(model_out), L.ptr(z), L.ptr(z2), L.ptr(x_bcs), L.ptr(mask), L.ptr(sched),
-           L.ptr(posterior_log_var), T, L.ptr(t_dev), int(noise_bcs), int(clip), L.ptr(out), B, F, V, L.stream())
-    return out
+    _check_lv_output(x_t, model_out)
+    return _reverse_step("tdx_p_sample_step_lv", (x_t, model_out, z, z2, x_bcs, mask, sched, posterior_log_var, T, t_dev),
+                         noise_bcs, clip, out)
 
 
 def p_sample_step_lv_rng(x_t, model_out, x_bcs, mask, sched, posterior_log_var, T, t_dev, noise_bcs, clip, seed, stream_ids,
                          offset_dev, out=None):
     """p_sample_step_lv with z (and z2) drawn in the kernel (layouts: p_sample_step_rng_supported); advances offset_dev and
     decrements t_dev on the device."""
-    B, F, V = _lv_step_shapes(x_t, model_out)
-    if out is None:
-        out = torch.empty_like(x_t)
-    L.call("tdx_p_sample_step_lv_rng", L.ptr(x_t), L.ptr(model_out), L.ptr(x_bcs), L.ptr(mask), L.ptr(sched),
-           L.ptr(posterior_log_var), T, L.ptr(t_dev), int(noise_bcs), int(clip), L.ptr(out), B, F, V, seed, L.ptr(stream_ids),
-           L.ptr(offset_dev), L.stream())
-    return out
+    _check_lv_output(x_t, model_out)
+    return _reverse_step("tdx_p_sample_step_lv_rng", (x_t, model_out, x_bcs, mask, sched, posterior_log_var, T, t_dev),
+                         noise_bcs, clip, out, (seed, stream_ids, offset_dev))
 
 
 def ddim_step(x_t, eps, z, z2, x_bcs, mask, tab, k_dev, tau_dev, t_dev, noise_bcs, clip, out=None):
     """One generalized DDIM update from tau[k] to tau[k-1]; tab = schedules.ddim_tables(...) on the device ([6, S]),
     k_dev / t_dev device int64 scalars, tau_dev the device int64 subsequence.  z / z2 may be None where unused."""
-    B, F = x_t.shape[:2]
-    V = x_t[0, 0].numel()
-    if out is None:
-        out = torch.empty_like(x_t)
-    L.call("tdx_ddim_step", L.ptr(x_t), L.ptr(eps), L.ptr(z), L.ptr(z2), L.ptr(x_bcs), L.ptr(mask), L.ptr(tab),
-           _ddim_steps(tab, tau_dev), L.ptr(k_dev), L.ptr(tau_dev), L.ptr(t_dev), int(noise_bcs), int(clip), L.ptr(out), B, F, V, L.stream())
-    return out
+    S = _ddim_steps(tab, tau_dev)
+    return _reverse_step("tdx_ddim_step", (x_t, eps, z, z2, x_bcs, mask, tab, S, k_dev, tau_dev, t_dev), noise_bcs, clip, out)
 
 
 def ddim_step_rng(x_t, eps, x_bcs, mask, tab, k_dev, tau_dev, t_dev, noise_bcs, clip, seed, stream_ids, offset_dev, out=None):
     """The DDIM step with z (and z2) drawn in the kernel (layouts: p_sample_step_rng_supported); on the device it then
     advances offset_dev, decrements k_dev and sets t_dev = tau[k] while a step is left."""
-    B, F = x_t.shape[:2]
-    V = x_t[0, 0].numel()
-    if out is None:
-        out = torch.empty_like(x_t)
-    L.call("tdx_ddim_step_rng", L.ptr(x_t), L.ptr(eps), L.ptr(x_bcs), L.ptr(mask), L.ptr(tab), _ddim_steps(tab, tau_dev), L.ptr(k_dev),
-           L.ptr(tau_dev), L.ptr(t_dev), int(noise_bcs), int(clip), L.ptr(out), B, F, V, seed, L.ptr(stream_ids),
-           L.ptr(offset_dev), L.stream())
-    return out
+    S = _ddim_steps(tab, tau_dev)
+    return _reverse_step("tdx_ddim_step_rng", (x_t, eps, x_bcs, mask, tab, S, k_dev, tau_dev, t_dev), noise_bcs, clip, out,
+                         (seed, stream_ids, offset_dev))
 
 
 def _ddim_steps(tab, tau_dev) -> int:

@@ -22,6 +22,7 @@ step with `tdx_p_sample_step_lv_rng` as its update: the decoder emits [eps_hat |
 
 from __future__ import annotations
 
+import gc
 
 import torch
 
@@ -43,6 +44,26 @@ def check_ddim_arguments(diffusion, sampling_timesteps, eta, start_from=None):
     if not 0.0 <= float(eta) <= 1.0:
         raise ValueError(f"eta = {eta} outside [0, 1]")
     schedules.ddim_timesteps(diffusion.num_timesteps, sampling_timesteps, start_from)
+
+
+# ---- the update rules of a GraphSampler `s`: (ops entry that draws its noise, ops entry on noise tensors, the operands
+# between the mask and noise_bcs, the scalar advance the second entry leaves to its caller).  Plain functions of the sampler:
+# stored on it they close over nothing, so they add no reference cycle that would keep its captured graph and pool alive.
+def _advance_t(s):
+    s.t.sub_(1)
+
+
+def _advance_ddim(s):
+    s.k.sub_(1)
+    s.t.copy_(s.tau.index_select(0, s.k.clamp(min=0)))  # after the last step: stays tau[0]
+
+
+# x_t -> x_{t-1}, then t -= 1; with learned variances the same on the model's output [eps_hat | w], the noise scaled per voxel
+_ANCESTRAL = (ops.p_sample_step_rng, ops.p_sample_step, lambda s: (s.d.step_tables, s.d.num_timesteps, s.t), _advance_t)
+_LEARNED_VARIANCES = (ops.p_sample_step_lv_rng, ops.p_sample_step_lv,
+                      lambda s: (s.d.step_tables, s.d.posterior_log_var, s.d.num_timesteps, s.t), _advance_t)
+# x_{tau_k} -> x_{tau_{k-1}}, then k -= 1 and t = tau[k] on the device
+_DDIM = (ops.ddim_step_rng, ops.ddim_step, lambda s: (s.ddim_table, s.k, s.tau, s.t), _advance_ddim)
 
 
 class GraphSampler:
@@ -94,6 +115,8 @@ class GraphSampler:
             self.enc = diffusion.model.encode_local(self.C)
         self.c_table = None  # (T, c_dim) conditioning vectors per timestep (DenoisingModel.conditioning_table) or None
         self._table_versions = None
+        rule = _DDIM if S is not None else (_LEARNED_VARIANCES if getattr(diffusion, "learned_variances", False) else _ANCESTRAL)
+        self._fused, self._plain, self._operands, self._advance = rule  # the update, chosen once
         self._refresh_tables()
         self.reset()
 
@@ -215,51 +238,18 @@ class GraphSampler:
         if self.c_table is not None:
             # all trajectories are at the same t: one row of the table instead of the time MLP (~12 launches per step)
             kw["cond"] = self.c_table.index_select(0, self.t).expand(self.B, -1)
-        eps = d.model(self.x_t, self.t.expand(self.B), self.C, **kw)
-        if self.sampling_timesteps is not None:
-            return self._ddim_update(eps)
-        if getattr(d, "learned_variances", False):
-            return self._lv_update(eps)
+        out = d.model(self.x_t, self.t.expand(self.B), self.C, **kw)
         if self.fused_noise:
-            # same draws, same counters, bit-identical x_{t-1}; also advances the offset and decrements t
-            ops.p_sample_step_rng(self.x_t, eps, self.x_bcs, self.mask, d.step_tables, d.num_timesteps, self.t,
-                                  d.noise_bcs, d.clip_denoised, self.seed, self.stream_ids, self.offset, out=self.x_t)
+            # same draws, same counters, bit-identical x_{t-1}; also advances the offset and the step scalars
+            self._fused(self.x_t, out, self.x_bcs, self.mask, *self._operands(self), d.noise_bcs, d.clip_denoised, self.seed,
+                        self.stream_ids, self.offset, out=self.x_t)
             return
         self._randn(self.z)
         if d.noise_bcs:
             self._randn(self.z2)
-        ops.p_sample_step(self.x_t, eps, self.z, self.z2 if d.noise_bcs else None, self.x_bcs, self.mask, d.step_tables,
-                          d.num_timesteps, self.t, d.noise_bcs, d.clip_denoised, out=self.x_t)
-        self.t.sub_(1)
-
-    def _lv_update(self, out):
-        """The ancestral step of a model with learned variances: `out` = [eps_hat | w], the noise scaled per voxel."""
-        d = self.d
-        if self.fused_noise:
-            ops.p_sample_step_lv_rng(self.x_t, out, self.x_bcs, self.mask, d.step_tables, d.posterior_log_var, d.num_timesteps,
-                                     self.t, d.noise_bcs, d.clip_denoised, self.seed, self.stream_ids, self.offset, out=self.x_t)
-            return
-        self._randn(self.z)
-        if d.noise_bcs:
-            self._randn(self.z2)
-        ops.p_sample_step_lv(self.x_t, out, self.z, self.z2 if d.noise_bcs else None, self.x_bcs, self.mask, d.step_tables,
-                             d.posterior_log_var, d.num_timesteps, self.t, d.noise_bcs, d.clip_denoised, out=self.x_t)
-        self.t.sub_(1)
-
-    def _ddim_update(self, eps):
-        """x_{tau_k} -> x_{tau_{k-1}}, then k -= 1 and t = tau[k] on the device."""
-        d = self.d
-        if self.fused_noise:
-            ops.ddim_step_rng(self.x_t, eps, self.x_bcs, self.mask, self.ddim_table, self.k, self.tau, self.t, d.noise_bcs,
-                              d.clip_denoised, self.seed, self.stream_ids, self.offset, out=self.x_t)
-            return
-        self._randn(self.z)
-        if d.noise_bcs:
-            self._randn(self.z2)
-        ops.ddim_step(self.x_t, eps, self.z, self.z2 if d.noise_bcs else None, self.x_bcs, self.mask, self.ddim_table,
-                      self.k, self.tau, self.t, d.noise_bcs, d.clip_denoised, out=self.x_t)
-        self.k.sub_(1)
-        self.t.copy_(self.tau.index_select(0, self.k.clamp(min=0)))  # after the last step: stays tau[0]
+        self._plain(self.x_t, out, self.z, self.z2 if d.noise_bcs else None, self.x_bcs, self.mask, *self._operands(self),
+                    d.noise_bcs, d.clip_denoised, out=self.x_t)
+        self._advance(self)
 
     @torch.no_grad()
     def _capture(self):
@@ -304,7 +294,16 @@ class GraphSampler:
         if self._tables_stale():
             self._refresh_tables()
         if self.use_graph and (self.graph is None or self._stale()):
-            self._capture()
+            # a dead sampler (a dropped diffusion and the samplers in its cache form a cycle) frees its captured graph when the
+            # collector finds it; inside a capture that aborts the process.  Collect before the capture, never during it.
+            gc.collect()
+            was_enabled = gc.isenabled()
+            gc.disable()
+            try:
+                self._capture()
+            finally:
+                if was_enabled:
+                    gc.enable()
         steps = range(n)
         if pbar:
             from tqdm.auto import tqdm

@@ -326,8 +326,8 @@ int tdx_q_sample(const float* x0, const float* noise, const float* sqrt_ac, cons
  *            noise_bcs: outside the mask out = sqrt_ac[t] x_bcs + sqrt_1mac[t] z2
  * sched = 7 consecutive f32 tables of length T:
  *   recip, recipm1, coef1, coef2, log_betas, sqrt_ac, sqrt_1mac.
- * t is a device int64 scalar (graph replay updates it on device). z, z2 may be NULL when
- * unused. */
+ * t is a device int64 scalar (graph replay updates it on device).  t outside [0, T) writes nothing.
+ * z, z2 may be NULL when unused (NULL reads as no noise). */
 int tdx_p_sample_step(const float* x_t, const float* eps, const float* z, const float* z2, const float* x_bcs,
                       const uint8_t* mask, const float* sched, int T, const int64_t* t, int noise_bcs, int clip,
                       float* out, int B, int F, int64_t V, void* stream);
@@ -336,7 +336,8 @@ int tdx_p_sample_step(const float* x_t, const float* eps, const float* z, const 
  * to tdx_randn_batched(z, ...); [tdx_randn_batched(z2, ...) if noise_bcs;] tdx_p_sample_step(...) with the same seed,
  * stream ids and offset -- lane i of trajectory b draws the normals those calls would have written to z[b][4i..4i+3] -- without
  * the two noise tensors ever touching HBM.  Afterwards *offset_dev += (noise_bcs ? 2 : 1) * F V / 4 and *t -= 1 (both on the
- * device, so a captured graph replays the whole ddpm.py:789-813 loop body). */
+ * device, so a captured graph replays the whole ddpm.py:789-813 loop body).  t outside [0, T) writes nothing; the offset and
+ * t still advance. */
 int tdx_p_sample_step_rng(const float* x_t, const float* eps, const float* x_bcs, const uint8_t* mask, const float* sched,
                           int T, int64_t* t, int noise_bcs, int clip, float* out, int B, int F, int64_t V, uint64_t seed,
                           const uint64_t* stream_ids, uint64_t* offset_dev, void* stream);

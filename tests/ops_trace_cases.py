@@ -236,6 +236,85 @@ def _prefetch(ops):
         ops.conv1(act(32, bf16, False), w1[0])
 
 
+# the DDPM arithmetic: (B, F, X, Y, Z) float32 states, F = 4; the decoder output of a learned-variance model has 2 F planes
+def state(f=4, grad=False):
+    return torch.zeros((B, f, *GRID)).requires_grad_(grad)
+
+
+def i64(*shape):
+    return torch.zeros(shape, dtype=torch.int64)
+
+
+def dev_scalar():
+    return torch.Tensor._make_subclass(_DeviceParameter, i64(1), False)
+
+
+def _step_operands():
+    X, Y, Z = GRID
+    return state(), state(), state(), torch.zeros(X * Y * Z, dtype=torch.uint8), torch.zeros(7, 10), i64(1)
+
+
+def _p_sample_step(ops):
+    x, eps, xb, mask, sched, t = _step_operands()
+    ops.p_sample_step(x, eps, state(), state(), xb, mask, sched, 10, t, True, False)
+    ops.p_sample_step(x, eps, state(), None, xb, mask, sched, 10, t, False, True, out=x)
+
+
+def _p_sample_step_rng(ops):
+    x, eps, xb, mask, sched, t = _step_operands()
+    ops.p_sample_step_rng(x, eps, xb, mask, sched, 10, t, True, False, 1234, i64(B), i64(1))
+    ops.p_sample_step_rng(x, eps, xb, mask, sched, 10, t, False, True, (7 << 32) | 5, i64(B), i64(1), out=x)
+
+
+def _p_sample_step_lv(ops):
+    x, _, xb, mask, sched, t = _step_operands()
+    ops.p_sample_step_lv(x, state(8), state(), state(), xb, mask, sched, torch.zeros(10), 10, t, True, False)
+    ops.p_sample_step_lv(x, state(8), state(), None, xb, mask, sched, torch.zeros(10), 10, t, False, True, out=x)
+
+
+def _p_sample_step_lv_rng(ops):
+    x, _, xb, mask, sched, t = _step_operands()
+    ops.p_sample_step_lv_rng(x, state(8), xb, mask, sched, torch.zeros(10), 10, t, True, False, 1234, i64(B), i64(1))
+    ops.p_sample_step_lv_rng(x, state(8), xb, mask, sched, torch.zeros(10), 10, t, False, True, 99, i64(B), i64(1), out=x)
+
+
+def _ddim_step(ops):
+    x, eps, xb, mask, _, t = _step_operands()
+    ops.ddim_step(x, eps, state(), state(), xb, mask, torch.zeros(6, 4), i64(1), i64(4), t, True, False)
+    ops.ddim_step(x, eps, None, None, xb, mask, torch.zeros(6, 4), i64(1), i64(4), t, False, True, out=x)
+
+
+def _ddim_step_rng(ops):
+    x, eps, xb, mask, _, t = _step_operands()
+    ops.ddim_step_rng(x, eps, xb, mask, torch.zeros(6, 4), i64(1), i64(4), t, True, False, 1234, i64(B), i64(1))
+    ops.ddim_step_rng(x, eps, xb, mask, torch.zeros(6, 4), i64(1), i64(4), t, False, True, 99, i64(B), i64(1), out=x)
+
+
+def _q_sample(ops):
+    _, _, _, mask, _, _ = _step_operands()
+    ops.q_sample(state(), state(), torch.zeros(10), torch.zeros(10), i64(B))
+    ops.q_sample(state(), state(), torch.zeros(10), torch.zeros(10), i64(1), mask=mask, keep_bcs=True)
+
+
+def _masked_loss(ops, n_cells):
+    _, _, _, mask, _, _ = _step_operands()
+    back(ops.masked_loss(state(grad=True), state(), mask, n_cells, l1=True))
+    ops.masked_loss(state(), state(), mask, n_cells)  # no gradient asked for
+
+
+def _elbo_loss(ops, n_cells):
+    _, _, _, mask, sched, _ = _step_operands()
+    total, parts = ops.elbo_loss(state(8, grad=True), state(), state(), state(), mask, n_cells, i64(B), sched, torch.zeros(10),
+                                 l1=True, clip=True, detach_mean=False, elbo_weight=0.1, parts=True)
+    back(total)
+    ops.elbo_loss(state(8), state(), state(), state(), mask, n_cells, i64(B), sched, torch.zeros(10))
+
+
+def _randn(ops):
+    ops.randn_philox(torch.zeros(37), 1234, (7 << 32) | 5, i64(1))
+    ops.randn_philox_batched(state(), 1234, i64(B), i64(1))
+
+
 CASES = {
     "block_two_inputs_bf16_fused_tail": lambda ops: block(ops, bf16, 32, 32, 64, True),
     "block_two_inputs_f32_scale_shift": lambda ops: block(ops, f32, 32, 32, 64, True, film=False),
@@ -268,6 +347,18 @@ CASES = {
     "skip_and_resize_resized_unused": lambda ops: _skip_and_resize(ops, False),
     "to_nvc_to_ncv": _layout,
     "prefetch_then_convs": _prefetch,
+    "p_sample_step": _p_sample_step,
+    "p_sample_step_rng": _p_sample_step_rng,
+    "p_sample_step_lv": _p_sample_step_lv,
+    "p_sample_step_lv_rng": _p_sample_step_lv_rng,
+    "ddim_step": _ddim_step,
+    "ddim_step_rng": _ddim_step_rng,
+    "q_sample": _q_sample,
+    "masked_loss_int_n_cells": lambda ops: _masked_loss(ops, 40),
+    "masked_loss_device_n_cells": lambda ops: _masked_loss(ops, dev_scalar()),
+    "elbo_loss_int_n_cells": lambda ops: _elbo_loss(ops, 40),
+    "elbo_loss_device_n_cells": lambda ops: _elbo_loss(ops, dev_scalar()),
+    "randn_philox": _randn,
 }
 
 

@@ -612,3 +612,22 @@ def test_kernel_asm_diff_splits_assembly_per_kernel():
     assert ".amdhsa_next_free_vgpr 4" in desc and "hip_cuid" not in body
     assert kad.kernels(asm("WgradView", "89ef4567", "\ts_nop 0\n"), []) != new
     assert list(kad.kernels(asm("WgradViewS", "0123abcd"), [])) == ["_Z1kPf10WgradViewSi"]  # unrenamed: lost + added
+
+
+def test_kernel_asm_diff_ignores_only_the_function_ordinal_of_local_labels():
+    """tools/kernel_asm_diff.py sets the function's ordinal in its file to 0 in .LBB<f>_<n>, the `; %bb` comments' BB<f>_<n>
+    and .Lfunc_end<f> (a kernel that becomes a template renumbers every function behind it); the block number <n>, and with it
+    where a branch goes, still counts."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("kernel_asm_diff", ROOT / "tools" / "kernel_asm_diff.py")
+    kad = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kad)
+
+    def asm(f, target):
+        return (f"k:\n\ts_cbranch_scc1 .LBB{f}_{target}\n.LBB{f}_1: ; %bb.1, preds =BB{f}_0\n\ts_nop 0\n.LBB{f}_2:\n\ts_endpgm\n"
+                f".Lfunc_end{f}:\n\t.size\tk, .Lfunc_end{f}-k\n\t.amdhsa_kernel k\n\t.end_amdhsa_kernel\n")
+
+    assert kad.kernels(asm(3, 2), []) == kad.kernels(asm(17, 2), [])
+    assert ".LBB0_2" in kad.kernels(asm(17, 2), [])["k"][0] and ".Lfunc_end0-k" in kad.kernels(asm(17, 2), [])["k"][0]
+    assert kad.kernels(asm(3, 2), []) != kad.kernels(asm(3, 1), [])  # another branch target is another kernel

@@ -100,23 +100,39 @@ def test_ddim_step_matches_fp64_restatement(shape, sched, noise_bcs, clip):
 
 
 def test_ddim_step_writes_nothing_for_a_finished_trajectory():
-    """k outside [0, S) has no column in the table: the step must not read one (nor write)."""
-    from turbdiff_amd import ops
+    """An index outside the tables -- k outside [0, S) for the DDIM step, t outside [0, T) for the two ancestral ones -- has
+    no column: no step may read one (nor write), through either entry.  The entry that draws its noise still advances the
+    offset and the index."""
+    from turbdiff_amd import ops, schedules
 
     d = dev()
     shape = (1, 4, 2, 2, 2)
     tab, taus = _tables("logsnr10", 1.0)
     x, e, xb = (rnd(*shape, seed=s).to(d) for s in range(3))
+    mo = rnd(1, 8, 2, 2, 2, seed=3).to(d)
     mask = torch.ones(8, dtype=torch.uint8, device=d)
-    tau_d, t_d = torch.tensor(taus, device=d), torch.tensor([0], device=d)
+    tab_d, tau_d, t_d = tab.to(d), torch.tensor(taus, device=d), torch.tensor([0], device=d)
+    tables = schedules.diffusion_tables("log-snr-linear", 10)
+    sched, plv = schedules.pack_step_tables(tables).to(d), tables["posterior_log_var"].to(d)
     sids, off = torch.tensor([3], dtype=torch.int64, device=d), torch.zeros(1, dtype=torch.int64, device=d)
-    for k in (-1, 4):
-        out = torch.full(shape, 7.0, device=d)
-        ops.ddim_step(x, e, x, x, xb, mask, tab.to(d), torch.tensor([k], device=d), tau_d, t_d, True, False, out=out)
-        assert torch.equal(out, torch.full(shape, 7.0, device=d))
-        k_d = torch.tensor([k], device=d)
-        ops.ddim_step_rng(x, e, xb, mask, tab.to(d), k_d, tau_d, t_d, True, False, 1, sids, off, out=out)
-        assert torch.equal(out, torch.full(shape, 7.0, device=d)) and int(k_d) == k - 1
+    rng = (1, sids, off)
+    rules = {  # number of columns, the entry on noise tensors, the entry that draws its noise
+        "ddim": (4, lambda i, out: ops.ddim_step(x, e, x, x, xb, mask, tab_d, i, tau_d, t_d, True, False, out=out),
+                 lambda i, out: ops.ddim_step_rng(x, e, xb, mask, tab_d, i, tau_d, t_d, True, False, *rng, out=out)),
+        "ancestral": (10, lambda i, out: ops.p_sample_step(x, e, x, x, xb, mask, sched, 10, i, True, False, out=out),
+                      lambda i, out: ops.p_sample_step_rng(x, e, xb, mask, sched, 10, i, True, False, *rng, out=out)),
+        "lv": (10, lambda i, out: ops.p_sample_step_lv(x, mo, x, x, xb, mask, sched, plv, 10, i, True, False, out=out),
+               lambda i, out: ops.p_sample_step_lv_rng(x, mo, xb, mask, sched, plv, 10, i, True, False, *rng, out=out)),
+    }
+    for rule, (n, plain, fused) in rules.items():
+        for k in (-1, n):
+            out = torch.full(shape, 7.0, device=d)
+            plain(torch.tensor([k], device=d), out)
+            assert torch.equal(out, torch.full(shape, 7.0, device=d)), rule
+            k_d, off0 = torch.tensor([k], device=d), int(off)
+            fused(k_d, out)
+            assert torch.equal(out, torch.full(shape, 7.0, device=d)) and int(k_d) == k - 1, rule
+            assert int(off) == off0 + 2 * (4 * 8 // 4), rule  # noise_bcs: 2 F V / 4 counters, drawn or not
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -127,7 +143,7 @@ def _bits(x):
 
 @pytest.mark.parametrize("clip", [False, True])
 @pytest.mark.parametrize("noise_bcs", [True, False])
-@pytest.mark.parametrize("shape", [(3, 4, 6, 5, 4), (1, 4, 2, 2, 1), (2, 4, 40, 33, 28)])
+@pytest.mark.parametrize("shape", [(3, 4, 6, 5, 4), (1, 4, 2, 2, 1), (2, 4, 40, 33, 28), (1, 4, 48, 48, 32)])
 def test_ddim_step_rng_matches_separate_draws_bitwise(shape, noise_bcs, clip):
     """tdx_ddim_step_rng == tdx_randn_batched(z); [tdx_randn_batched(z2);] tdx_ddim_step, bit for bit, out of place and in
     place; afterwards the offset has advanced by (2 if noise_bcs else 1) F V / 4 whatever eta is, k is k - 1 and t is

@@ -322,7 +322,7 @@ def test_p_sample_step(noise_bcs, t):
 @pytest.mark.parametrize("noise_bcs", [True, False])
 @pytest.mark.parametrize("clip", [False, True])
 @pytest.mark.parametrize("t", [0, 1, 7])
-@pytest.mark.parametrize("shape", [(3, 4, 6, 5, 4), (1, 4, 2, 2, 1), (2, 4, 40, 33, 28)])
+@pytest.mark.parametrize("shape", [(3, 4, 6, 5, 4), (1, 4, 2, 2, 1), (2, 4, 40, 33, 28), (1, 4, 48, 48, 32)])
 def test_p_sample_step_rng_matches_separate_draws_bitwise(noise_bcs, clip, t, shape):
     """tdx_p_sample_step_rng == tdx_randn_batched(z); [tdx_randn_batched(z2);] tdx_p_sample_step, bit for bit, and it leaves
     the same RNG offset and t - 1 behind (the contract include/tdx.h states)."""

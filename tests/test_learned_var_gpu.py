@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import assert_grad_close, rel_l2
+from step_inputs import _loss_inputs, _mask_idx, _tables, rnd  # the seeded inputs, shared with reverse_step_cases.py
 
 pytestmark = pytest.mark.gpu
 
@@ -19,25 +20,8 @@ def dev():
     return torch.device("cuda:0")
 
 
-def rnd(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-def _mask_idx(V, seed=0):
-    """two thirds of the cells, scattered: about a third of every quad is outside the domain"""
-    g = torch.Generator().manual_seed(seed)
-    return torch.sort(torch.randperm(V, generator=g)[: (2 * V) // 3]).values
-
-
 def _bits(x):
     return x.contiguous().view(torch.int32)
-
-
-def _tables(name, T):
-    from turbdiff_amd import schedules
-
-    tab = schedules.diffusion_tables(name, T)
-    return tab, schedules.pack_step_tables(tab)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -110,7 +94,7 @@ def test_lv_step_matches_fp64_restatement(shape, noise_bcs, clip):
 # 2. noise drawn in the kernel == separate draws, bit for bit
 @pytest.mark.parametrize("clip", [False, True])
 @pytest.mark.parametrize("noise_bcs", [True, False])
-@pytest.mark.parametrize("shape", [(3, 4, 6, 5, 4), (1, 4, 2, 2, 1), (2, 4, 40, 33, 28)])
+@pytest.mark.parametrize("shape", [(3, 4, 6, 5, 4), (1, 4, 2, 2, 1), (2, 4, 40, 33, 28), (1, 4, 48, 48, 32)])
 def test_lv_step_rng_matches_separate_draws_bitwise(shape, noise_bcs, clip):
     """tdx_p_sample_step_lv_rng == tdx_randn_batched(z); [tdx_randn_batched(z2);] tdx_p_sample_step_lv, bit for bit, out of
     place and in place; afterwards the offset has advanced by (2 if noise_bcs else 1) F V / 4 (F = the state's planes) and t
@@ -179,21 +163,6 @@ def _diffusion(l1, clip, detach_mean, ew=0.1, T=10):
 
     return GaussianDiffusion(torch.nn.Identity(), timesteps=T, beta_schedule="log-snr-linear", loss_type="l1" if l1 else "l2",
                              noise_bcs=True, clip_denoised=clip, learned_variances=True, elbo_weight=ew, detach_elbo_mean=detach_mean)
-
-
-def _loss_inputs(shape, t, clip, tab):
-    """x_start, noise ~ N(0, 1); eps_hat = noise + 0.3 N(0, 1); w ~ N(0, 1); x_t = q_sample in float32.  With the clip x_start
-    is scaled by 1.2: at t = 0 / 1 (recipm1 < 0.1) x0 ~ x_start then leaves [-1, 1] for 40 % of the elements, at the noisy
-    steps for 80-99 %, between 40 % and 70 % over a launch."""
-    B, F = shape[:2]
-    x_start, noise, e, w = (rnd(*shape, seed=s) for s in (11, 12, 13, 14))
-    if clip:
-        x_start = 1.2 * x_start
-    eps_hat = noise + 0.3 * e
-    out = torch.cat([eps_hat, w], dim=1).contiguous()
-    col = lambda name: tab[name][t].view(B, 1, 1, 1, 1)
-    x_t = col("sqrt_alphas_cumprod") * x_start + col("sqrt_one_minus_alphas_cumprod") * noise
-    return out, noise, x_start, x_t
 
 
 def _ulp32(v: float) -> float:

@@ -5,7 +5,8 @@
 
 Every tdx_*.hip of both directories is compiled with the Makefile's CXXFLAGS plus `--cuda-device-only -S`.  Per kernel
 (.amdhsa_kernel name) two pieces of text are compared: the body, from the kernel's label to its .size line, and the
-descriptor, .amdhsa_kernel ... .end_amdhsa_kernel.  __hip_cuid_<hex> is normalised; --rename replaces substrings of the
+descriptor, .amdhsa_kernel ... .end_amdhsa_kernel.  __hip_cuid_<hex> and the function ordinal in local labels (set to 0) are
+normalised; --rename replaces substrings of the
 old tree's mangled names (a renamed parameter type) before the comparison.  Exit status 0 only if every kernel is
 identical and none is added or lost.
 """
@@ -37,6 +38,10 @@ def compile_one(hipcc, flags, src, out):
 def kernels(asm_text, renames):
     """{kernel name: (body, descriptor)} of one assembly file."""
     text = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", asm_text)
+    # local labels carry the function's ordinal in its file (.LBB<f>_<n>, BB<f>_<n> in comments, .Lfunc_end<f>): it moves when a kernel in front
+    # of this one is added, lost or turned into a template, and says nothing about this one
+    text = re.sub(r"(\.L|=)BB\d+_(\d+)", r"\1BB0_\2", text)
+    text = re.sub(r"\.Lfunc_end\d+", ".Lfunc_end0", text)
     for old, new in renames:
         text = text.replace(old, new)
     out = {}
