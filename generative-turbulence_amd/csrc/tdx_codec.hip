@@ -10,30 +10,12 @@
 // 8-channel vector lc of voxel r, 16 B per lane on the NDHWC side; the few-channel NCDHW side
 // is read/written as per-plane scalars.  Parameter gradients are reduced per block through LDS
 // and merged with one f32 atomic per value.
-#include "tdx_common.h"
+#include "tdx_codec_elem.h"  // the encoder lane and the decoder dot, shared with the GroupNorm tails
 #include "tdx_conv3.h"  // tdx_deterministic, ordered_sum_launch, the scratch arena
 
 #define CD_THREADS 256
 #define CD_VOX 512  // voxels per block (~4 resident blocks per CU at 192x64x48)
 #define CD_VOX_DEC 2048  // decode: grid already has a batch dimension; fewer blocks -> fewer gradient atomics
-#define CD_MAXF 8
-
-template <int N>
-__device__ __forceinline__ void block_reduce_lanes(float (&s)[N], int L, int lc, int r, int rows, float* __restrict__ out,
-                                                   int out_stride) {
-    // sum s[] over the `rows` threads that share lc; result j of lane-vector lc -> out[lc*out_stride + j]
-    __shared__ float red[CD_THREADS][N + 1];
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < N; ++j) red[tid][j] = (r < rows) ? s[j] : 0.f;
-    __syncthreads();
-    for (int o = tid; o < L * N; o += CD_THREADS) {
-        const int l = o / N, j = o - l * N;
-        float t = 0.f;
-        for (int q = 0; q < rows; ++q) t += red[q * L + l][j];
-        atomicAdd(&out[l * out_stride + j], t);
-    }
-}
 
 // ------------------------------------------------------------------ encode ---------------
 template <typename T, int F>
@@ -45,31 +27,13 @@ encode_fwd_kernel(const float* __restrict__ x, const float* __restrict__ wx, con
     const int L = Dtot >> 3, rows = CD_THREADS / L;
     const int lc = threadIdx.x % L, r = threadIdx.x / L;
     if (r >= rows) return;
-    const bool is_x = lc * 8 < D;
-    const int ch0 = is_x ? lc * 8 : lc * 8 - D;
-    const float* w = is_x ? wx : wc;
-    const float* bias = is_x ? bx : bc;
-    const float* src = is_x ? x + (int64_t)b * F * V : c;
-    float wr[8][F], br[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        br[j] = bias[ch0 + j];
-#pragma unroll
-        for (int k = 0; k < F; ++k) wr[j][k] = w[(ch0 + j) * F + k];
-    }
+    const EncLane<F> enc(lc, b, D, V, x, wx, bx, c, wc, bc);
     const int64_t v0 = (int64_t)blockIdx.x * CD_VOX, v1 = min(V, v0 + CD_VOX);
     for (int64_t v = v0 + r; v < v1; v += rows) {
-        float in[F];
-#pragma unroll
-        for (int k = 0; k < F; ++k) in[k] = src[(int64_t)k * V + v];
+        const auto in = enc.load(V, v);
         Vec8<T> o;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float a = br[j];
-#pragma unroll
-            for (int k = 0; k < F; ++k) a = __builtin_fmaf(wr[j][k], in[k], a);  // explicit: gn_apply_encoded_kernel repeats it
-            o.v[j] = a;
-        }
+        for (int j = 0; j < 8; ++j) o.v[j] = enc.eval(j, in);
         o.store(y + ((int64_t)b * V + v) * Dtot + lc * 8);
     }
 }
@@ -240,13 +204,9 @@ decode_fwd_kernel(const T* __restrict__ h, const float* __restrict__ w, const fl
     const int b = blockIdx.y;
     const int L = D >> 3, rows = CD_THREADS / L;
     const int lc = threadIdx.x % L, r = threadIdx.x / L;
-    float wr[F][8];
-#pragma unroll
-    for (int f = 0; f < F; ++f)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) wr[f][j] = w[f * D + lc * 8 + j];
+    const DecLane<F> dec(lc, D, w, bias);
     const int64_t v0 = (int64_t)blockIdx.x * CD_VOX_DEC, v1 = min(V, v0 + CD_VOX_DEC);
-    for (int64_t vb = v0; vb < v1; vb += rows) {
+    for (int64_t vb = v0; vb < v1; vb += rows) {  // every lane runs every trip: DecLane::dot is a butterfly
         const int64_t v = vb + r;
         const bool ok = r < rows && v < v1;
         Vec8<T> a;
@@ -255,11 +215,8 @@ decode_fwd_kernel(const T* __restrict__ h, const float* __restrict__ w, const fl
         if (ok) a.load(h + ((int64_t)b * V + v) * D + lc * 8);
 #pragma unroll
         for (int f = 0; f < F; ++f) {
-            float t = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) t = __builtin_fmaf(wr[f][j], a.v[j], t);  // explicit: gn_apply_decode_kernel repeats it
-            for (int o = 1; o < L; o <<= 1) t += __shfl_xor(t, o, 64);
-            if (ok && lc == 0) y[((int64_t)b * F + f) * V + v] = t + bias[f];
+            const float t = dec.dot(f, a.v, L);
+            if (ok && lc == 0) y[((int64_t)b * F + f) * V + v] = t;
         }
     }
 }

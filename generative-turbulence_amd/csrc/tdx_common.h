@@ -270,16 +270,18 @@ int tdx_zero2d_async(void* p, size_t pitch_bytes, size_t width_bytes, size_t row
             return TDX_EDTYPE;                         \
     } while (0)
 
-// 16-bit format dispatch for the matrix-core launchers: runs the statement with `constexpr bool HF`
-#define TDX_DISPATCH_H16(f16, ...)          \
+// bool dispatch for launchers: runs the statement with `constexpr bool NAME`
+#define TDX_DISPATCH_BOOL(flag, NAME, ...)  \
     do {                                    \
-        if (f16) {                          \
-            constexpr bool HF = true;       \
+        if (flag) {                         \
+            constexpr bool NAME = true;     \
             __VA_ARGS__;                    \
         } else {                            \
-            constexpr bool HF = false;      \
+            constexpr bool NAME = false;    \
             __VA_ARGS__;                    \
         }                                   \
     } while (0)
+// 16-bit format dispatch for the matrix-core launchers: runs the statement with `constexpr bool HF`
+#define TDX_DISPATCH_H16(f16, ...) TDX_DISPATCH_BOOL(f16, HF, __VA_ARGS__)
 
 static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

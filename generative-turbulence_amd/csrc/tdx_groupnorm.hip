@@ -12,7 +12,7 @@
 //   backward: reduce pass (P = sum dn, Q = sum dn*xhat per channel; per-block partial sums, no
 //             atomics, deterministic) -> finalize -> apply pass
 #define TDX_NT_LOADS 1  // activations are streamed once per pass: nontemporal 16-B loads (+0.4 % step)
-#include "tdx_common.h"
+#include "tdx_codec_elem.h"  // the encoder lane and the decoder dot of the two fused tails
 #include "tdx_conv3.h"
 
 #define GN_THREADS 256
@@ -24,7 +24,7 @@
 template <int NQ>
 // store (TDX_DETERMINISTIC): `acc` is this block's own table -- the partial is stored, not added; gn_stats_merge_kernel adds
 // the blocks' tables in block order
-__device__ __forceinline__ void block_channel_reduce(float (&s)[NQ][8], int L, int lane_c, bool active,
+__device__ __forceinline__ void block_channel_reduce(float (&s)[NQ][8], int L, bool active,
                                                      double* __restrict__ acc, int C, bool store = false) {
     __shared__ float red[GN_THREADS][NQ * 8 + 1];
     const int tid = threadIdx.x;
@@ -43,7 +43,6 @@ __device__ __forceinline__ void block_channel_reduce(float (&s)[NQ][8], int L, i
         if (store) acc[(size_t)c * NQ + q] = t;
         else atomicAdd(&acc[(size_t)c * NQ + q], t);
     }
-    (void)lane_c;
 }
 
 template <typename T>
@@ -83,8 +82,8 @@ gn_stats_kernel(const T* __restrict__ x, double* __restrict__ acc, int64_t V, in
             for (int j = 0; j < 8; ++j) { s[0][j] += a.v[j]; s[1][j] += a.v[j] * a.v[j]; }
         }
     }
-    if (part) block_channel_reduce<2>(s, L, lc, active, part + ((size_t)b * gridDim.x + blockIdx.x) * C * 2, C, true);
-    else block_channel_reduce<2>(s, L, lc, active, acc + (size_t)b * C * 2, C);
+    if (part) block_channel_reduce<2>(s, L, active, part + ((size_t)b * gridDim.x + blockIdx.x) * C * 2, C, true);
+    else block_channel_reduce<2>(s, L, active, acc + (size_t)b * C * 2, C);
 }
 
 // TDX_DETERMINISTIC: acc[b][c][q] = sum over the sample's blocks of part[b][blk][c][q], in block order (f64)
@@ -152,7 +151,7 @@ gn_stats_finalize(double* __restrict__ acc, float* __restrict__ stats, int B, in
 extern "C" size_t tdx_gn_workspace_bytes(int B, int C) {
     const size_t fwd = (size_t)GN_REPLICAS * B * C * 2 * sizeof(double) + (size_t)B * C * 2 * sizeof(float) + 64;
     const size_t bwd = (size_t)B * C * 2 * sizeof(double) + (size_t)B * C * 2 * sizeof(float) +
-                       (size_t)512 * B * C * 2 * sizeof(float) + 64;
+                       (size_t)GN_MAX_BLOCKS * B * C * 2 * sizeof(float) + 64;
     return fwd > bwd ? fwd : bwd;
 }
 
@@ -209,15 +208,17 @@ int gn_stats_launch(const void* x, float* stats, int B, int64_t V, int C, int G,
     return tdx_launch_status();
 }
 
-// per-thread affine coefficients of its 8 channels: n = x*a + c0  (FiLM folded in)
+// per-thread affine coefficients of its 8 channels: n = x*a + c0  (FiLM folded in).  The forward tails use GnCoef; the
+// backward kernels also need the factors: xhat = x*rstd + mr, k = gam*film
 struct GnCoef {
     float a[8], c0[8];
 };
-__device__ __forceinline__ void gn_load_coef(GnCoef& k, float (&mean)[8], float (&rstd)[8], float (&gam)[8],
-                                             float (&film)[8], const float* __restrict__ stats,
-                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                             const float* __restrict__ scale, const float* __restrict__ shift, int b,
-                                             int C, int G, int cbase) {
+struct GnCoefBwd : GnCoef {
+    float rstd[8], gam[8], film[8], mr[8];
+};
+__device__ __forceinline__ void gn_load_coef(GnCoefBwd& k, const float* __restrict__ stats, const float* __restrict__ gamma,
+                                             const float* __restrict__ beta, const float* __restrict__ scale,
+                                             const float* __restrict__ shift, int b, int C, int G, int cbase) {
     const int cpg = C / G;
     // issue every load before the first use (one exposed latency per block instead of one per channel)
     float be[8], sc[8], sh[8];
@@ -227,7 +228,7 @@ __device__ __forceinline__ void gn_load_coef(GnCoef& k, float (&mean)[8], float 
     {
         const float4 g0 = *reinterpret_cast<const float4*>(gamma + cbase), g1 = *reinterpret_cast<const float4*>(gamma + cbase + 4);
         const float4 b0 = *reinterpret_cast<const float4*>(beta + cbase), b1 = *reinterpret_cast<const float4*>(beta + cbase + 4);
-        gam[0] = g0.x; gam[1] = g0.y; gam[2] = g0.z; gam[3] = g0.w; gam[4] = g1.x; gam[5] = g1.y; gam[6] = g1.z; gam[7] = g1.w;
+        k.gam[0] = g0.x; k.gam[1] = g0.y; k.gam[2] = g0.z; k.gam[3] = g0.w; k.gam[4] = g1.x; k.gam[5] = g1.y; k.gam[6] = g1.z; k.gam[7] = g1.w;
         be[0] = b0.x; be[1] = b0.y; be[2] = b0.z; be[3] = b0.w; be[4] = b1.x; be[5] = b1.y; be[6] = b1.z; be[7] = b1.w;
     }
     if (scale) {
@@ -243,12 +244,20 @@ __device__ __forceinline__ void gn_load_coef(GnCoef& k, float (&mean)[8], float 
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        mean[j] = st[j].x;
-        rstd[j] = st[j].y;
-        film[j] = 1.0f + sc[j];
-        k.a[j] = rstd[j] * gam[j] * film[j];
-        k.c0[j] = (be[j] - mean[j] * rstd[j] * gam[j]) * film[j] + sh[j];
+        const float mean = st[j].x;
+        k.rstd[j] = st[j].y;
+        k.film[j] = 1.0f + sc[j];
+        k.mr[j] = -mean * k.rstd[j];
+        k.a[j] = k.rstd[j] * k.gam[j] * k.film[j];
+        k.c0[j] = (be[j] - mean * k.rstd[j] * k.gam[j]) * k.film[j] + sh[j];
     }
+}
+__device__ __forceinline__ void gn_load_coef(GnCoef& k, const float* __restrict__ stats, const float* __restrict__ gamma,
+                                             const float* __restrict__ beta, const float* __restrict__ scale,
+                                             const float* __restrict__ shift, int b, int C, int G, int cbase) {
+    GnCoefBwd full;
+    gn_load_coef(full, stats, gamma, beta, scale, shift, b, C, G, cbase);
+    k = full;
 }
 
 // Streaming skeleton of the apply / backward passes: block (bx, b) walks the voxels of sample b
@@ -266,6 +275,66 @@ static int gn_blocks_per_sample(int B, int64_t V, int C) {
     return want < 1 ? 1 : (int)want;
 }
 
+// Where a thread streams: lane vector lc (channels [8 lc, 8 lc + 8)) of the voxels first, first + stride, ... of sample
+// blockIdx.y; element (v, its channels) of an activation tensor t is t + base + v * C.  Threads with r >= rows are spares
+// (GN_THREADS % L != 0): their `first` belongs to the next block.
+struct GnLane {
+    int lc, r, rows;
+    int64_t base, stride, first;
+};
+__device__ __forceinline__ GnLane gn_lane(int64_t V, int C) {
+    const int L = C >> 3;
+    GnLane p;
+    p.rows = GN_THREADS / L;
+    p.lc = threadIdx.x % L;
+    p.r = threadIdx.x / L;
+    p.base = ((int64_t)blockIdx.y * V) * C + p.lc * 8;
+    p.stride = (int64_t)gridDim.x * p.rows;
+    p.first = (int64_t)blockIdx.x * p.rows + p.r;
+    return p;
+}
+
+// The two loops.  body(a, s, v) gets voxel v of the NIN tensors `in` as a[0..NIN) and s = side(v), a per-voxel load of
+// the kernel's own that is issued with the trip's other loads.  Spare threads do nothing unless ALL_LANES: a body that
+// ends in a cross-lane butterfly sets it, and every lane of a voxel's group then runs the same trips (v is theirs alike).
+template <typename T, int NIN, bool ALL_LANES, typename Side, typename Body>
+__device__ __forceinline__ void gn_stream(const GnLane& p, const T* const* in, int64_t V, int C, Side side, Body body) {
+    if (!ALL_LANES && p.r >= p.rows) return;
+    int64_t v = p.first;
+    // full trips: GN_UNROLL independent loads in flight, no branches between them
+    for (; v + (GN_UNROLL - 1) * p.stride < V; v += p.stride * GN_UNROLL) {
+        Raw8<T> raw[GN_UNROLL][NIN];
+        decltype(side(v)) s[GN_UNROLL];
+#pragma unroll
+        for (int u = 0; u < GN_UNROLL; ++u) {
+#pragma unroll
+            for (int i = 0; i < NIN; ++i) raw[u][i].load(in[i] + p.base + (v + u * p.stride) * C);
+            s[u] = side(v + u * p.stride);
+        }
+        __builtin_amdgcn_sched_barrier(0);  // all loads of the trip are issued before any arithmetic
+#pragma unroll
+        for (int u = 0; u < GN_UNROLL; ++u) {
+            Vec8<T> a[NIN];
+#pragma unroll
+            for (int i = 0; i < NIN; ++i) a[i] = raw[u][i].get();
+            body(a, s[u], v + u * p.stride);
+        }
+    }
+    for (; v < V; v += p.stride) {
+        Vec8<T> a[NIN];
+#pragma unroll
+        for (int i = 0; i < NIN; ++i) a[i].load(in[i] + p.base + v * C);
+        body(a, side(v), v);
+    }
+}
+// without a side load: body(a, v)
+template <typename T, int NIN, bool ALL_LANES = false, typename Body>
+__device__ __forceinline__ void gn_stream(const GnLane& p, const T* const* in, int64_t V, int C, Body body) {
+    struct None {};
+    gn_stream<T, NIN, ALL_LANES>(p, in, V, C, [](int64_t) { return None(); },
+                                 [&](const Vec8<T>(&a)[NIN], None, int64_t v) { body(a, v); });
+}
+
 // silu(n) + r as ONE explicit fma: the three tail kernels (apply / apply_encoded / apply_decode) promise bit-identical
 // results, which must not hinge on the compiler contracting n * sigmoid(n) + r the same way in each
 __device__ __forceinline__ float silu_add(float n, float r) { return __builtin_fmaf(n, sigmoid_f(n), r); }
@@ -275,49 +344,24 @@ __global__ void __launch_bounds__(GN_THREADS)
 gn_apply_kernel(const T* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
                 const float* __restrict__ beta, const float* __restrict__ scale, const float* __restrict__ shift,
                 const T* __restrict__ res, T* __restrict__ y, int64_t V, int C, int G) {
-    const int b = blockIdx.y;
-    const int L = C >> 3;
-    const int rows = GN_THREADS / L;
-    const int tid = threadIdx.x;
-    const int lc = tid % L, r = tid / L;
-    if (r >= rows) return;
+    const GnLane p = gn_lane(V, C);
     GnCoef k;
-    float mean[8], rstd[8], gam[8], film[8];
-    gn_load_coef(k, mean, rstd, gam, film, stats, gamma, beta, scale, shift, b, C, G, lc * 8);
-    const int64_t base = ((int64_t)b * V) * C + lc * 8;
-    const int64_t stride = (int64_t)gridDim.x * rows;
-    auto one = [&](const Vec8<T>& a, const Vec8<T>& rr, int64_t vv) {
+    gn_load_coef(k, stats, gamma, beta, scale, shift, blockIdx.y, C, G, p.lc * 8);
+    const T* const in[2] = {x, res};
+    gn_stream<T, HAS_RES ? 2 : 1>(p, in, V, C, [&](const Vec8<T>(&a)[HAS_RES ? 2 : 1], int64_t v) {
+        const Vec8<T>& rr = a[HAS_RES];  // a[1] where there is one
         Vec8<T> o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float n = __builtin_fmaf(a.v[j], k.a[j], k.c0[j]);
+            const float n = __builtin_fmaf(a[0].v[j], k.a[j], k.c0[j]);
             if (ACT && HAS_RES) o.v[j] = silu_add(n, rr.v[j]);
             else {
                 o.v[j] = ACT ? silu_f(n) : n;
                 if (HAS_RES) o.v[j] += rr.v[j];
             }
         }
-        o.store(y + base + vv * C);
-    };
-    int64_t v = (int64_t)blockIdx.x * rows + r;
-    // full trips: GN_UNROLL independent loads in flight, no branches between them
-    for (; v + (GN_UNROLL - 1) * stride < V; v += stride * GN_UNROLL) {
-        Raw8<T> a[GN_UNROLL], rr[GN_UNROLL];
-#pragma unroll
-        for (int u = 0; u < GN_UNROLL; ++u) {
-            a[u].load(x + base + (v + u * stride) * C);
-            if (HAS_RES) rr[u].load(res + base + (v + u * stride) * C);
-        }
-        __builtin_amdgcn_sched_barrier(0);  // all loads of the trip are issued before any arithmetic
-#pragma unroll
-        for (int u = 0; u < GN_UNROLL; ++u) one(a[u].get(), HAS_RES ? rr[u].get() : Vec8<T>(), v + u * stride);
-    }
-    for (; v < V; v += stride) {
-        Vec8<T> a, rr;
-        a.load(x + base + v * C);
-        if (HAS_RES) rr.load(res + base + v * C);
-        one(a, rr, v);
-    }
+        o.store(y + p.base + v * C);
+    });
 }
 
 extern "C" int tdx_gn_apply(const void* x, const float* stats, const float* gamma, const float* beta,
@@ -327,92 +371,39 @@ extern "C" int tdx_gn_apply(const void* x, const float* stats, const float* gamm
     TDX_CHECK_ARG((scale == nullptr) == (shift == nullptr));
     if (!gn_shape_ok(C, G)) return TDX_ESHAPE;
     dim3 grid(gn_blocks_per_sample(B, V, C), B);
-#define GN_APPLY_GO(R, A)                                                                                              \
-    TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gn_apply_kernel<T, R, A>), grid, dim3(GN_THREADS), 0,                \
-                                                  as_stream(stream), (const T*)x, stats, gamma, beta, scale, shift,    \
-                                                  (const T*)res, (T*)y, V, C, G))
-    if (res) {
-        if (act) GN_APPLY_GO(true, true); else GN_APPLY_GO(true, false);
-    } else {
-        if (act) GN_APPLY_GO(false, true); else GN_APPLY_GO(false, false);
-    }
-#undef GN_APPLY_GO
+    TDX_DISPATCH_BOOL(res != nullptr, R, TDX_DISPATCH_BOOL(act, A, TDX_DISPATCH_DTYPE(dtype,
+        hipLaunchKernelGGL((gn_apply_kernel<T, R, A>), grid, dim3(GN_THREADS), 0, as_stream(stream), (const T*)x, stats, gamma,
+                           beta, scale, shift, (const T*)res, (T*)y, V, C, G))));
     return tdx_launch_status();
 }
 
 // ---- y = silu(GN(x)) + encode(raw): the tail of the U-Net's FIRST block, whose identity skip is the encoder output
 // cat(Wx x_raw + bx, Wc c_raw + bc) (ddpm.py:495-501).  The skip is recomputed here from the 4 + 4 raw f32 planes instead
 // of being written by tdx_encode_fwd and read back: per voxel 2 x (C x 2 B) of HBM traffic become 8 x 4 B.  The skip value
-// is rounded to T before the add, exactly what a stored encoder output would have held, so the result is bit-identical
-// to tdx_encode_fwd + tdx_gn_apply(res = that tensor).
-template <typename T> __device__ __forceinline__ float round_as(float a);
-template <> __device__ __forceinline__ float round_as<float>(float a) { return a; }
-template <> __device__ __forceinline__ float round_as<bf16>(float a) { return __uint_as_float(pack_bf16x2(a, 0.f) << 16); }
-template <> __device__ __forceinline__ float round_as<f16>(float a) { return (float)(_Float16)a; }
-
+// is the encoder's own element (tdx_codec_elem.h) rounded to T before the add, exactly what a stored encoder output would
+// have held, so the result is bit-identical to tdx_encode_fwd + tdx_gn_apply(res = that tensor).
 template <typename T, int F>
 __global__ void __launch_bounds__(GN_THREADS)
 gn_apply_encoded_kernel(const T* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
                         const float* __restrict__ beta, const float* __restrict__ xr, const float* __restrict__ wx,
                         const float* __restrict__ bx, const float* __restrict__ cr, const float* __restrict__ wc,
                         const float* __restrict__ bc, T* __restrict__ y, int64_t V, int C, int D, int G) {
-    const int b = blockIdx.y;
-    const int L = C >> 3;
-    const int rows = GN_THREADS / L;
-    const int tid = threadIdx.x;
-    const int lc = tid % L, r = tid / L;
-    if (r >= rows) return;
+    const GnLane p = gn_lane(V, C);
     GnCoef k;
-    float mean[8], rstd[8], gam[8], film[8];
-    gn_load_coef(k, mean, rstd, gam, film, stats, gamma, beta, nullptr, nullptr, b, C, G, lc * 8);
-    const bool is_x = lc * 8 < D;
-    const int ch0 = is_x ? lc * 8 : lc * 8 - D;
-    const float* w = is_x ? wx : wc;
-    const float* bias = is_x ? bx : bc;
-    const float* src = is_x ? xr + (int64_t)b * F * V : cr;
-    float wr[8][F], br[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        br[j] = bias[ch0 + j];
-#pragma unroll
-        for (int q = 0; q < F; ++q) wr[j][q] = w[(ch0 + j) * F + q];
-    }
-    const int64_t base = ((int64_t)b * V) * C + lc * 8;
-    const int64_t stride = (int64_t)gridDim.x * rows;
-    auto one = [&](const Vec8<T>& a, const float (&in)[F], int64_t vv) {
+    gn_load_coef(k, stats, gamma, beta, nullptr, nullptr, blockIdx.y, C, G, p.lc * 8);
+    const EncLane<F> enc(p.lc, blockIdx.y, D, V, xr, wx, bx, cr, wc, bc);
+    const T* const in[1] = {x};
+    gn_stream<T, 1, false>(p, in, V, C, [&](int64_t v) { return enc.load(V, v); },  // the F raw planes: the trip's side load
+                           [&](const Vec8<T>(&a)[1], const typename EncLane<F>::In& raw, int64_t v) {
         Vec8<T> o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            float e = br[j];
-#pragma unroll
-            for (int q = 0; q < F; ++q) e = __builtin_fmaf(wr[j][q], in[q], e);  // encode_fwd_kernel's chain, bit for bit
-            const float n = __builtin_fmaf(a.v[j], k.a[j], k.c0[j]);
+            const float e = enc.eval(j, raw);
+            const float n = __builtin_fmaf(a[0].v[j], k.a[j], k.c0[j]);
             o.v[j] = silu_add(n, round_as<T>(e));
         }
-        o.store(y + base + vv * C);
-    };
-    int64_t v = (int64_t)blockIdx.x * rows + r;
-    for (; v + (GN_UNROLL - 1) * stride < V; v += stride * GN_UNROLL) {
-        Raw8<T> a[GN_UNROLL];
-        float in[GN_UNROLL][F];
-#pragma unroll
-        for (int u = 0; u < GN_UNROLL; ++u) {
-            a[u].load(x + base + (v + u * stride) * C);
-#pragma unroll
-            for (int q = 0; q < F; ++q) in[u][q] = src[(int64_t)q * V + v + u * stride];
-        }
-        __builtin_amdgcn_sched_barrier(0);  // all loads of the trip are issued before any arithmetic
-#pragma unroll
-        for (int u = 0; u < GN_UNROLL; ++u) one(a[u].get(), in[u], v + u * stride);
-    }
-    for (; v < V; v += stride) {
-        Vec8<T> a;
-        float in[F];
-        a.load(x + base + v * C);
-#pragma unroll
-        for (int q = 0; q < F; ++q) in[q] = src[(int64_t)q * V + v];
-        one(a, in, v);
-    }
+        o.store(y + p.base + v * C);
+    });
 }
 
 extern "C" int tdx_gn_apply_encoded(const void* x, const float* stats, const float* gamma, const float* beta,
@@ -433,66 +424,32 @@ extern "C" int tdx_gn_apply_encoded(const void* x, const float* stats, const flo
 // ---- out = decode(silu(GN(x)) + res): the tail of the model's LAST ResnetBlock (decode[0], ddpm.py:429) followed by the
 // dim -> F 1x1 decoder and the NDHWC -> NCDHW layout change (decode[1], ddpm.py:505), inference only.  The block output
 // (B, V, C) is neither written nor read back: per voxel 2 x (C x 2 B) of HBM traffic disappear.  The block output is
-// rounded to T before the dot product and the dot product is decode_fwd_kernel's explicit FMA chain + the same butterfly,
-// so the result is bit-identical to tdx_gn_apply(res, act = 1) + tdx_decode_fwd.
+// rounded to T before the dot product and the dot product is the decoder's own (tdx_codec_elem.h), so the result is
+// bit-identical to tdx_gn_apply(res, act = 1) + tdx_decode_fwd.
 template <typename T, int F>
 __global__ void __launch_bounds__(GN_THREADS)
 gn_apply_decode_kernel(const T* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
                        const float* __restrict__ beta, const T* __restrict__ res, const float* __restrict__ w,
                        const float* __restrict__ bias, float* __restrict__ out, int64_t V, int C, int G) {
-    const int b = blockIdx.y;
-    const int L = C >> 3;  // a power of two <= 64 (checked by the host): the L lanes of a voxel are adjacent in a wave
-    const int rows = GN_THREADS / L;
-    const int tid = threadIdx.x;
-    const int lc = tid % L, r = tid / L;
+    const GnLane p = gn_lane(V, C);
     GnCoef k;
-    float mean[8], rstd[8], gam[8], film[8];
-    gn_load_coef(k, mean, rstd, gam, film, stats, gamma, beta, nullptr, nullptr, b, C, G, lc * 8);
-    float wr[F][8], bf[F];
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-        bf[f] = bias[f];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) wr[f][j] = w[f * C + lc * 8 + j];
-    }
-    const int64_t base = ((int64_t)b * V) * C + lc * 8;
-    const int64_t stride = (int64_t)gridDim.x * rows;
-    auto one = [&](const Vec8<T>& a, const Vec8<T>& rr, int64_t vv, bool ok) {
+    gn_load_coef(k, stats, gamma, beta, nullptr, nullptr, blockIdx.y, C, G, p.lc * 8);
+    const DecLane<F> dec(p.lc, C, w, bias);
+    const T* const in[2] = {x, res};
+    // ALL_LANES: DecLane::dot is a butterfly over the C / 8 lanes of the voxel
+    gn_stream<T, 2, true>(p, in, V, C, [&](const Vec8<T>(&a)[2], int64_t v) {
         float o[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float n = __builtin_fmaf(a.v[j], k.a[j], k.c0[j]);
-            o[j] = round_as<T>(silu_add(n, rr.v[j]));
+            const float n = __builtin_fmaf(a[0].v[j], k.a[j], k.c0[j]);
+            o[j] = round_as<T>(silu_add(n, a[1].v[j]));
         }
 #pragma unroll
         for (int f = 0; f < F; ++f) {
-            float t = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) t = __builtin_fmaf(wr[f][j], o[j], t);
-            for (int q = 1; q < L; q <<= 1) t += __shfl_xor(t, q, 64);
-            if (ok && lc == 0) out[((int64_t)b * F + f) * V + vv] = t + bf[f];
+            const float t = dec.dot(f, o, C >> 3);
+            if (p.lc == 0) out[((int64_t)blockIdx.y * F + f) * V + v] = t;
         }
-    };
-    // every lane of a wave takes part in the butterflies: the loop bound is uniform per voxel group, and lanes past the
-    // end (or the spare threads when 256 % L != 0 -- not with L a power of two) compute on zeros
-    int64_t v = (int64_t)blockIdx.x * rows + r;
-    for (; v + (GN_UNROLL - 1) * stride < V; v += stride * GN_UNROLL) {
-        Raw8<T> a[GN_UNROLL], rr[GN_UNROLL];
-#pragma unroll
-        for (int u = 0; u < GN_UNROLL; ++u) {
-            a[u].load(x + base + (v + u * stride) * C);
-            rr[u].load(res + base + (v + u * stride) * C);
-        }
-        __builtin_amdgcn_sched_barrier(0);  // all loads of the trip are issued before any arithmetic
-#pragma unroll
-        for (int u = 0; u < GN_UNROLL; ++u) one(a[u].get(), rr[u].get(), v + u * stride, true);
-    }
-    for (; v < V; v += stride) {
-        Vec8<T> a, rr;
-        a.load(x + base + v * C);
-        rr.load(res + base + v * C);
-        one(a, rr, v, true);
-    }
+    });
 }
 
 extern "C" int tdx_gn_apply_decode(const void* x, const float* stats, const float* gamma, const float* beta, const void* res,
@@ -522,63 +479,37 @@ gn_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, const fl
                      const float* __restrict__ shift, float* __restrict__ partial, int64_t V, int C, int G) {
     __shared__ float red[GN_THREADS][17];
     const int b = blockIdx.y;
-    const int L = C >> 3;
-    const int rows = GN_THREADS / L;
     const int tid = threadIdx.x;
-    const int lc = tid % L, r = tid / L;
-    const bool active = r < rows;
-    float s[2][8];
+    const GnLane p = gn_lane(V, C);
+    GnCoefBwd k;
+    gn_load_coef(k, stats, gamma, beta, scale, shift, b, C, G, p.lc * 8);
+    float s[2][8];  // stays zero in a spare thread
 #pragma unroll
     for (int j = 0; j < 8; ++j) s[0][j] = s[1][j] = 0.f;
-    if (active) {
-        GnCoef k;
-        float mean[8], rstd[8], gam[8], film[8], mr[8];
-        gn_load_coef(k, mean, rstd, gam, film, stats, gamma, beta, scale, shift, b, C, G, lc * 8);
+    const T* const in[2] = {x, dy};
+    gn_stream<T, 2>(p, in, V, C, [&](const Vec8<T>(&a)[2], int64_t) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) mr[j] = -mean[j] * rstd[j];
-        const int64_t base = ((int64_t)b * V) * C + lc * 8;
-        const int64_t stride = (int64_t)gridDim.x * rows;
-        auto one = [&](const Vec8<T>& a, const Vec8<T>& g) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float n = __builtin_fmaf(a.v[j], k.a[j], k.c0[j]);
-                const float dn = ACT ? g.v[j] * dsilu_f(n) : g.v[j];
-                const float xh = __builtin_fmaf(a.v[j], rstd[j], mr[j]);
-                s[0][j] += dn;
-                s[1][j] = __builtin_fmaf(dn, xh, s[1][j]);
-            }
-        };
-        int64_t v = (int64_t)blockIdx.x * rows + r;
-        for (; v + (GN_UNROLL - 1) * stride < V; v += stride * GN_UNROLL) {
-            Raw8<T> a[GN_UNROLL], g[GN_UNROLL];
-#pragma unroll
-            for (int u = 0; u < GN_UNROLL; ++u) {
-                a[u].load(x + base + (v + u * stride) * C);
-                g[u].load(dy + base + (v + u * stride) * C);
-            }
-        __builtin_amdgcn_sched_barrier(0);  // all loads of the trip are issued before any arithmetic
-#pragma unroll
-            for (int u = 0; u < GN_UNROLL; ++u) one(a[u].get(), g[u].get());
+        for (int j = 0; j < 8; ++j) {
+            const float n = __builtin_fmaf(a[0].v[j], k.a[j], k.c0[j]);
+            const float dn = ACT ? a[1].v[j] * dsilu_f(n) : a[1].v[j];
+            const float xh = __builtin_fmaf(a[0].v[j], k.rstd[j], k.mr[j]);
+            s[0][j] += dn;
+            s[1][j] = __builtin_fmaf(dn, xh, s[1][j]);
         }
-        for (; v < V; v += stride) {
-            Vec8<T> a, g;
-            a.load(x + base + v * C);
-            g.load(dy + base + v * C);
-            one(a, g);
-        }
-    }
+    });
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         red[tid][j] = s[0][j];
         red[tid][8 + j] = s[1][j];
     }
     __syncthreads();
+    const int L = C >> 3;
     float* out = partial + ((size_t)b * gridDim.x + blockIdx.x) * C * 2;
     for (int o = tid; o < C * 2; o += GN_THREADS) {
         const int c = o >> 1, q = o & 1;
         const int lcc = c >> 3, j = c & 7;
         float t = 0.f;
-        for (int rr = 0; rr < rows; ++rr) t += red[rr * L + lcc][q * 8 + j];
+        for (int rr = 0; rr < p.rows; ++rr) t += red[rr * L + lcc][q * 8 + j];
         out[o] = t;
     }
 }
@@ -661,56 +592,31 @@ gn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ dy, const flo
                     float* __restrict__ dscale, float* __restrict__ dshift) {
     if (blockIdx.x == 0 && blockIdx.y == 0) gn_bwd_params(acc, gamma, beta, scale, dgamma, dbeta, dscale, dshift, gridDim.y, C);
     const int b = blockIdx.y;
-    const int L = C >> 3;
-    const int rows = GN_THREADS / L;
-    const int tid = threadIdx.x;
-    const int lc = tid % L, r = tid / L;
-    if (r >= rows) return;
-    GnCoef k;
-    float mean[8], rstd[8], gam[8], film[8];
-    gn_load_coef(k, mean, rstd, gam, film, stats, gamma, beta, scale, shift, b, C, G, lc * 8);
+    const GnLane p = gn_lane(V, C);
+    GnCoefBwd k;
+    gn_load_coef(k, stats, gamma, beta, scale, shift, b, C, G, p.lc * 8);
     // dx = k1 dn - k2 - xhat k3,  xhat = x rstd + mr
-    float k1[8], k2[8], k3[8], mr[8];
+    float k1[8], k2[8], k3[8];
     const int cpg = C / G;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const int g = (lc * 8 + j) / cpg;
-        k1[j] = rstd[j] * gam[j] * film[j];
-        k2[j] = rstd[j] * gsum[((size_t)b * G + g) * 2];
-        k3[j] = rstd[j] * gsum[((size_t)b * G + g) * 2 + 1];
-        mr[j] = -mean[j] * rstd[j];
+        const int g = (p.lc * 8 + j) / cpg;
+        k1[j] = k.rstd[j] * k.gam[j] * k.film[j];
+        k2[j] = k.rstd[j] * gsum[((size_t)b * G + g) * 2];
+        k3[j] = k.rstd[j] * gsum[((size_t)b * G + g) * 2 + 1];
     }
-    const int64_t base = ((int64_t)b * V) * C + lc * 8;
-    const int64_t stride = (int64_t)gridDim.x * rows;
-    auto one = [&](const Vec8<T>& a, const Vec8<T>& g, int64_t vv) {
+    const T* const in[2] = {x, dy};
+    gn_stream<T, 2>(p, in, V, C, [&](const Vec8<T>(&a)[2], int64_t v) {
         Vec8<T> o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float n = __builtin_fmaf(a.v[j], k.a[j], k.c0[j]);
-            const float dn = ACT ? g.v[j] * dsilu_f(n) : g.v[j];
-            const float xh = __builtin_fmaf(a.v[j], rstd[j], mr[j]);
+            const float n = __builtin_fmaf(a[0].v[j], k.a[j], k.c0[j]);
+            const float dn = ACT ? a[1].v[j] * dsilu_f(n) : a[1].v[j];
+            const float xh = __builtin_fmaf(a[0].v[j], k.rstd[j], k.mr[j]);
             o.v[j] = __builtin_fmaf(k1[j], dn, -__builtin_fmaf(xh, k3[j], k2[j]));
         }
-        o.store(dx + base + vv * C);
-    };
-    int64_t v = (int64_t)blockIdx.x * rows + r;
-    for (; v + (GN_UNROLL - 1) * stride < V; v += stride * GN_UNROLL) {
-        Raw8<T> a[GN_UNROLL], g[GN_UNROLL];
-#pragma unroll
-        for (int u = 0; u < GN_UNROLL; ++u) {
-            a[u].load(x + base + (v + u * stride) * C);
-            g[u].load(dy + base + (v + u * stride) * C);
-        }
-        __builtin_amdgcn_sched_barrier(0);  // all loads of the trip are issued before any arithmetic
-#pragma unroll
-        for (int u = 0; u < GN_UNROLL; ++u) one(a[u].get(), g[u].get(), v + u * stride);
-    }
-    for (; v < V; v += stride) {
-        Vec8<T> a, g;
-        a.load(x + base + v * C);
-        g.load(dy + base + v * C);
-        one(a, g, v);
-    }
+        o.store(dx + p.base + v * C);
+    });
 }
 
 extern "C" int tdx_gn_bwd(const void* x, const void* dy, const float* stats, const float* gamma, const float* beta,
@@ -727,22 +633,12 @@ extern "C" int tdx_gn_bwd(const void* x, const void* dy, const float* stats, con
     float* partial = gsum + (size_t)B * C * 2;             // [B][nblk][C][2]
     dim3 grid(nblk, B);
     hipStream_t st = as_stream(stream);
-    if (act)
-        TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gn_bwd_reduce_kernel<T, true>), grid, dim3(GN_THREADS), 0, st,
-                                                      (const T*)x, (const T*)dy, stats, gamma, beta, scale, shift,
-                                                      partial, V, C, G));
-    else
-        TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gn_bwd_reduce_kernel<T, false>), grid, dim3(GN_THREADS), 0, st,
-                                                      (const T*)x, (const T*)dy, stats, gamma, beta, scale, shift,
-                                                      partial, V, C, G));
+    TDX_DISPATCH_BOOL(act, A, TDX_DISPATCH_DTYPE(dtype,
+        hipLaunchKernelGGL((gn_bwd_reduce_kernel<T, A>), grid, dim3(GN_THREADS), 0, st, (const T*)x, (const T*)dy, stats, gamma,
+                           beta, scale, shift, partial, V, C, G)));
     hipLaunchKernelGGL(gn_bwd_group_kernel, dim3(B * G), dim3(256), 0, st, partial, acc, gamma, scale, gsum, nblk, C, G, V);
-    if (act)
-        TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gn_bwd_apply_kernel<T, true>), grid, dim3(GN_THREADS), 0, st,
-                                                      (const T*)x, (const T*)dy, stats, gamma, beta, scale, shift, gsum,
-                                                      (T*)dx, V, C, G, acc, dgamma, dbeta, dscale, dshift));
-    else
-        TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gn_bwd_apply_kernel<T, false>), grid, dim3(GN_THREADS), 0, st,
-                                                      (const T*)x, (const T*)dy, stats, gamma, beta, scale, shift, gsum,
-                                                      (T*)dx, V, C, G, acc, dgamma, dbeta, dscale, dshift));
+    TDX_DISPATCH_BOOL(act, A, TDX_DISPATCH_DTYPE(dtype,
+        hipLaunchKernelGGL((gn_bwd_apply_kernel<T, A>), grid, dim3(GN_THREADS), 0, st, (const T*)x, (const T*)dy, stats, gamma,
+                           beta, scale, shift, gsum, (T*)dx, V, C, G, acc, dgamma, dbeta, dscale, dshift)));
     return tdx_launch_status();
 }

@@ -1,7 +1,7 @@
 """The bits of the reverse-step, loss and Philox kernels of csrc/tdx_ddpm.hip: the cases shared by
-tests/test_reverse_step_bits.py and tests/golden/make_golden_reverse_step.py.
+tests/test_reverse_step_bits.py and tests/golden/make_golden_bits.py.
 
-`run(ops, group)` launches every case of one group through `turbdiff_amd.ops` on the GPU and returns, per case,
+`run(group)` launches every case of one group through `turbdiff_amd.ops` on the GPU and returns, per case,
 
     {"sha256": digest of the outputs' float32 bytes (the launches of the case, in order),
      "after":  [[offset, t] or [offset, k, t] per launch]      in-kernel-noise entries and the Philox fills,
@@ -12,12 +12,11 @@ Inputs are the CPU generator draws the GPU tests use (`rnd(..., seed=)`, `_mask_
 """
 
 import contextlib
-import hashlib
 import os
 
-import numpy as np
 import torch
 
+from pinned_bits import record as _record, tensor_bytes as _bytes
 from step_inputs import _loss_inputs, _mask_idx, _tables, rnd
 
 T, S = 10, 4  # the log-snr-linear schedule of the step tests; the DDIM subsequence of T
@@ -40,30 +39,7 @@ ELBO_T = ([6, 0], [0, 0], [T - 1, 1])
 RANDN_N = (5, 36960)
 
 GROUPS = [f"{rule}/{entry}" for rule in RULES for entry in ("tensor", "rng")] + ["masked_loss", "elbo_loss", "randn"]
-
-
-def _bytes(t):
-    t = t.detach().cpu().contiguous()
-    assert t.dtype == torch.float32
-    return t.numpy().tobytes()
-
-
-def _record(outs, smallest=False, **more):
-    h = hashlib.sha256()
-    for o in outs:
-        h.update(_bytes(o))
-    rec = {"sha256": h.hexdigest(), **more}
-    if smallest:
-        rec["bits"] = [_bytes(o).hex() for o in outs]
-    return rec
-
-
-def ulps(got_hex, want_hex):
-    """Largest distance between two recorded outputs in units of the last place."""
-    def ordered(s):  # float32 bit patterns on a line: negative values mirrored below zero
-        i = np.frombuffer(bytes.fromhex(s), dtype="<i4").astype(np.int64)
-        return np.where(i < 0, -(2**31) - i, i)
-    return int(np.abs(ordered(got_hex) - ordered(want_hex)).max())
+FIXTURE = "reverse_step_bits.json"
 
 
 @contextlib.contextmanager
@@ -177,8 +153,10 @@ def _randn(ops, d):
     return res
 
 
-def run(ops, group):
-    """The records of one group of GROUPS, from the library `ops` is bound to."""
+def run(group):
+    """The records of one group of GROUPS, from the library `turbdiff_amd.ops` is bound to."""
+    from turbdiff_amd import ops
+
     d = torch.device("cuda:0")
     if "/" in group:
         return _steps(ops, *group.split("/"), d)

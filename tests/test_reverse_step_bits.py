@@ -1,6 +1,6 @@
 """The reverse-step, loss and Philox kernels of csrc/tdx_ddpm.hip compute the bits they computed before they were
 rewritten over shared skeletons: every case of tests/reverse_step_cases.py must reproduce the digest in
-tests/golden/reverse_step_bits.json, which tests/golden/make_golden_reverse_step.py recorded on the MI355X from the
+tests/golden/reverse_step_bits.json, which tests/golden/make_golden_bits.py recorded on the MI355X from the
 library of the commit BEFORE that change.  For the smallest shape the fixture holds the outputs themselves, so a mismatch
 there is reported in units of the last place."""
 
@@ -10,8 +10,9 @@ import pytest
 
 import reverse_step_cases as cases
 from conftest import GOLDEN
+from pinned_bits import assert_pinned
 
-EXPECTED = json.loads((GOLDEN / "reverse_step_bits.json").read_text())
+EXPECTED = json.loads((GOLDEN / cases.FIXTURE).read_text())
 
 
 def test_fixture_and_cases_agree():
@@ -21,12 +22,4 @@ def test_fixture_and_cases_agree():
 @pytest.mark.gpu
 @pytest.mark.parametrize("group", cases.GROUPS)
 def test_bits_are_pinned(group):
-    from turbdiff_amd import ops
-
-    got, want = cases.run(ops, group), EXPECTED[group]
-    assert sorted(got) == sorted(want)
-    for name, w in want.items():
-        g = got[name]
-        for i, (gb, wb) in enumerate(zip(g.get("bits", ()), w.get("bits", ()))):
-            assert gb == wb, f"{group} {name}: launch {i} is {cases.ulps(gb, wb)} ulp off"
-        assert g == w, f"{group} {name}: {[k for k in w if g.get(k) != w[k]]} differ"
+    assert_pinned(cases.run(group), EXPECTED[group], group)
