@@ -40,19 +40,24 @@ def blocks_per_sample(B, C, V):
     return max(1, min(-(-2048 // B), -(-V // (rows * UNROLL)), MAX_BLOCKS))
 
 
-def lane_paths(B, C, V):
-    """(blocks, stride, spare threads, {(ran a full trip, ran the tail loop)} over the lanes that have a voxel)."""
-    L = C // 8
-    rows = THREADS // L
-    blocks = blocks_per_sample(B, C, V)
-    stride = blocks * rows
+def stream_paths(stride, V):
+    """{(ran a full trip, ran the tail loop)} over the lanes that have one of V voxels, walked with `stride`, UNROLL per trip."""
     paths = set()
     for v in range(min(stride, V)):  # a lane's first voxel
         trips = 0
         while v + (UNROLL - 1) * stride < V:
             v, trips = v + UNROLL * stride, trips + 1
         paths.add((trips > 0, v < V))
-    return blocks, stride, THREADS - rows * L, paths
+    return paths
+
+
+def lane_paths(B, C, V):
+    """(blocks, stride, spare threads, {(ran a full trip, ran the tail loop)} over the lanes that have a voxel)."""
+    L = C // 8
+    rows = THREADS // L
+    blocks = blocks_per_sample(B, C, V)
+    stride = blocks * rows
+    return blocks, stride, THREADS - rows * L, stream_paths(stride, V)
 
 
 def _name(*shape, dtype, **flags):

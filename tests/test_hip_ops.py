@@ -176,7 +176,9 @@ def test_conv1_fwd_bwd(dtype, case):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("case", [(2, 16, 8, 7, 5, 6, True, True), (1, 64, 8, 9, 4, 3, False, True), (2, 32, 32, 5, 5, 5, True, False),
-                                  (1, 512, 8, 12, 4, 3, True, True), (2, 24, 1, 6, 5, 4, False, False)])
+                                  (1, 512, 8, 12, 4, 3, True, True), (2, 24, 1, 6, 5, 4, False, False),
+                                  # V = 12000 / 9000: 94 and 512 streaming blocks per sample (gn_bwd_group_kernel's slots past the first)
+                                  (1, 64, 8, 30, 20, 20, True, True), (1, 512, 8, 25, 20, 18, True, False)])
 def test_gn_film_silu(dtype, case):
     from turbdiff_amd import ops
 
@@ -529,15 +531,41 @@ def test_encode_decode_fused(dtype, with_c, D):
 
 
 @pytest.mark.parametrize("case", [(2, 64, 0, 64, 9, 10, 7, 8), (1, 32, 32, 32, 8, 8, 8, 8), (2, 16, 0, 96, 5, 4, 3, 1), (1, 8, 0, 16, 6, 5, 4, 8)])
-@pytest.mark.parametrize("dtype,impl", [(torch.float32, "auto"), (torch.float32, "split"), (torch.bfloat16, "auto")])
-def test_conv3_with_fused_gn_statistics(case, dtype, impl, monkeypatch):
+@pytest.mark.parametrize("dtype,impl,exact", [
+    pytest.param(dt, impl, exact, id=f"dtype{i}-{impl}" + ("-exact" if exact else ""))
+    for exact in (False, True) for i, dt, impl in ((0, torch.float32, "auto"), (1, torch.float32, "split"), (2, torch.bfloat16, "auto"))])
+def test_conv3_with_fused_gn_statistics(case, dtype, impl, exact, monkeypatch):
     """tdx_conv3_fwd_gn: statistics accumulated in the conv epilogue == the streaming
-    statistics pass over the stored conv output (ragged bricks included)."""
+    statistics pass over the stored conv output (ragged bricks included).
+
+    exact: x and w in {-1, 0, 1} with at most 8 taps per output channel, an integer bias in [-2, 2]: |y| <= 10 is an integer,
+    exact in bf16 and in every partial sum, so y must EQUAL the float64 convolution and the statistics (32 replicas of f64
+    atomics, gn_stats_finalize with R = 32) are exact sums: 1 ulp of float32 from the float64 statistics of y, the rounding of
+    the final cast (tests/gn_reference.py).  A voxel of a ragged brick counted twice or not at all moves them by far more."""
     from turbdiff_amd import ops
 
     B, C1, C2, Cout, X, Y, Z, G = case
     d = dev()
     monkeypatch.setenv("TDX_CONV_IMPL", impl)
+    if exact:
+        import gn_reference as R
+
+        gen = torch.Generator().manual_seed(8)
+        ints = lambda lo, hi, *shape: torch.randint(lo, hi + 1, shape, generator=gen).float()
+        x1c, x2c = ints(-1, 1, B, X, Y, Z, C1), ints(-1, 1, B, X, Y, Z, C2) if C2 else None
+        taps = 27 * (C1 + C2)
+        wc = torch.zeros(Cout, taps)
+        for o in range(Cout):
+            wc[o, torch.randperm(taps, generator=gen)[:8]] = ints(0, 1, 8) * 2 - 1
+        wc, bc = wc.reshape(Cout, C1 + C2, 3, 3, 3), ints(-2, 2, Cout)
+        xin = ncv(x1c if x2c is None else torch.cat((x1c, x2c), dim=-1)).double()
+        y64 = nvc(F.conv3d(F.pad(xin, (1,) * 6, mode="replicate"), wc.double(), bc.double()))
+        assert y64.abs().max() <= 10 and torch.equal(y64, y64.round())  # the precondition: integers that bf16 holds
+        y, stats = ops.conv3_gn_stats(x1c.to(d).to(dtype), wc.to(d), bc.to(d), G, 1e-5, x2=None if x2c is None else x2c.to(d).to(dtype))
+        assert torch.equal(y.double().cpu(), y64)
+        want = R.stats(y64.reshape(B, -1, Cout), G, R.f32(1e-5)).float()
+        assert int(R.ulp_distance(stats.cpu(), want).max()) <= 1
+        return
     x1 = rnd(B, X, Y, Z, C1, seed=1).to(d).to(dtype)
     x2 = rnd(B, X, Y, Z, C2, seed=2).to(d).to(dtype) if C2 else None
     w = rnd(Cout, C1 + C2, 3, 3, 3, seed=3, scale=0.05).to(d)
