@@ -1262,8 +1262,9 @@ def test_stage_scaled_mixed_list_of_250_items():
                                        (512, (6, 4, 3), (3, 3, 3))])
 def test_resize_odd_channel_counts_and_large_factors(C, src, dst):
     """tdx_resize_fwd/bwd on the tile mappings the U-Net grids do not reach: C / 8 not a power of two,
-    up-sampling by up to 10x along an axis (up to 12 contributing outputs per input in the adjoint),
-    wide channels (1-voxel passes), down-sampling."""
+    up-sampling by up to 10x along an axis (z spans of 15 and 28 outputs per input: both up-sampling cases take the generic
+    adjoint, not resize_bwd_kernel<T, 12> -- tests/resize_cases.py has the routes), wide channels (4-voxel passes),
+    down-sampling."""
     from turbdiff_amd import ops
 
     torch.manual_seed(0)
