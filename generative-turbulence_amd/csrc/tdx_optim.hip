@@ -1,7 +1,9 @@
 // Fused tail of a training step: global gradient-norm clipping (the reference trains with
 // gradient_clip_val = 0.1, config/train.yaml:30-31) + the RAdam update (diffusion.py:210-218,
 // torch.optim.RAdam defaults) over ALL parameter tensors in three launches, instead of ~40
-// multi-tensor launches + ~70 fills of the stock foreach implementation.
+// multi-tensor launches + ~70 fills of the stock foreach implementation.  The same three launches serve
+// Adam / AdamW (diffusion.py's other two `optimizer` keys; the regression baselines' torch.optim.Adam,
+// dilresnet.py:158-173): one update skeleton, a rule struct per optimiser.
 //
 // The tensors stay separate allocations (the state_dict keeps the reference's keys); the kernels
 // walk a device table of {param, grad, exp_avg, exp_avg_sq} pointers.  Work is cut into chunks of
@@ -68,27 +70,57 @@ opt_norm_finalize_kernel(const float* __restrict__ partial, int nchunks, float m
     }
 }
 
-struct RAdamArgs {
-    float lr, beta1, beta2, eps;
-    float inv_bc1;   // 1 / (1 - beta1^t)
-    float sqrt_bc2;  // sqrt(1 - beta2^t)
-    float rect;      // variance rectification term, or < 0 while rho_t <= 5 (plain momentum step)
+// ---- the update: ONE skeleton over a rule struct ------------------------------------------------------------------------
+// A rule is `struct Args` (the step's scalars, computed by the host in double and passed by value) and
+// `elem(p, g, m, v, args)`: the update of one element, g already multiplied by the clip / unscale factor.  Everything else --
+// the chunk walk, the alignment test with its scalar fallback, the clip factor, the skip flag, WRITE_GRAD -- is the skeleton's.
+
+// torch.optim.radam._single_tensor_radam
+struct RAdamRule {
+    struct Args {
+        float lr, beta1, beta2, eps;
+        float inv_bc1;   // 1 / (1 - beta1^t)
+        float sqrt_bc2;  // sqrt(1 - beta2^t)
+        float rect;      // variance rectification term, or < 0 while rho_t <= 5 (plain momentum step)
+    };
+    static __device__ __forceinline__ void elem(float& p, float g, float& m, float& v, const Args& a) {
+        m = m + (g - m) * (1.0f - a.beta1);             // exp_avg.lerp_(grad, 1 - beta1)
+        v = v * a.beta2 + (1.0f - a.beta2) * g * g;     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+        const float mhat = m * a.inv_bc1;
+        float upd = mhat * a.lr;
+        if (a.rect >= 0.f) upd = upd * (a.sqrt_bc2 / (sqrtf(v) + a.eps)) * a.rect;
+        p -= upd;
+    }
 };
 
-__device__ __forceinline__ void radam_elem(float& p, float g, float& m, float& v, const RAdamArgs& a) {
-    m = m + (g - m) * (1.0f - a.beta1);             // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * a.beta2 + (1.0f - a.beta2) * g * g;     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-    const float mhat = m * a.inv_bc1;
-    float upd = mhat * a.lr;
-    if (a.rect >= 0.f) upd = upd * (a.sqrt_bc2 / (sqrtf(v) + a.eps)) * a.rect;
-    p -= upd;
-}
+// torch.optim.adam._single_tensor_adam / _multi_tensor_adam, the non-capturable branch (Adam, and AdamW = decoupled decay).
+// torch holds the hyper-parameters as Python floats and hands each kernel its scalar rounded to fp32 ONCE: so does the host
+// here -- (float)(1 - beta2), not 1.0f - (float)beta2, which is 1.3e-5 off and would sit in exp_avg_sq from the first step.
+struct AdamRule {
+    struct Args {
+        float w1;         // 1 - beta1
+        float beta2, w2;  // beta2, 1 - beta2
+        float step_size;  // lr / (1 - beta1^t)
+        float sqrt_bc2;   // sqrt(1 - beta2^t)
+        float eps;
+        float l2;         // weight_decay of the L2 form (grad += wd * param), or 0
+        float keep;       // 1 - lr * weight_decay of the decoupled form (param *= keep), or 1
+    };
+    static __device__ __forceinline__ void elem(float& p, float g, float& m, float& v, const Args& a) {
+        if (a.keep != 1.0f) p *= a.keep;                // param.mul_(1 - lr * weight_decay)
+        if (a.l2 != 0.f) g += a.l2 * p;                 // grad = grad.add(param, alpha=weight_decay)
+        m = m + (g - m) * a.w1;                         // exp_avg.lerp_(grad, 1 - beta1)
+        v = v * a.beta2 + a.w2 * g * g;                 // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+        const float denom = sqrtf(v) / a.sqrt_bc2 + a.eps;  // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
+        p -= a.step_size * (m / denom);                 // param.addcdiv_(exp_avg, denom, value=-step_size)
+    }
+};
 
-template <bool WRITE_GRAD>
+template <class Rule, bool WRITE_GRAD>
 __global__ void __launch_bounds__(OPT_THREADS)
-opt_radam_kernel(const TdxOptTensor* __restrict__ table, const int* __restrict__ chunk_tensor,
-                 const int64_t* __restrict__ chunk_off, const float* __restrict__ clip, const float* __restrict__ skip,
-                 RAdamArgs a) {
+opt_update_kernel(const TdxOptTensor* __restrict__ table, const int* __restrict__ chunk_tensor,
+                  const int64_t* __restrict__ chunk_off, const float* __restrict__ clip, const float* __restrict__ skip,
+                  typename Rule::Args a) {
     const int c = blockIdx.x;
     const TdxOptTensor t = table[chunk_tensor[c]];
     if (t.grad == nullptr) return;  // parameter without a gradient this step: untouched, as torch does
@@ -107,21 +139,32 @@ opt_radam_kernel(const TdxOptTensor* __restrict__ table, const int* __restrict__
         float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
         float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
         gg.x *= coef; gg.y *= coef; gg.z *= coef; gg.w *= coef;
-        radam_elem(pp.x, gg.x, mm.x, vv.x, a);
-        radam_elem(pp.y, gg.y, mm.y, vv.y, a);
-        radam_elem(pp.z, gg.z, mm.z, vv.z, a);
-        radam_elem(pp.w, gg.w, mm.w, vv.w, a);
+        Rule::elem(pp.x, gg.x, mm.x, vv.x, a);
+        Rule::elem(pp.y, gg.y, mm.y, vv.y, a);
+        Rule::elem(pp.z, gg.z, mm.z, vv.z, a);
+        Rule::elem(pp.w, gg.w, mm.w, vv.w, a);
         reinterpret_cast<float4*>(p)[i] = pp;
         reinterpret_cast<float4*>(m)[i] = mm;
         reinterpret_cast<float4*>(v)[i] = vv;
-        if (WRITE_GRAD) reinterpret_cast<float4*>(g)[i] = gg;
+        if (WRITE_GRAD) reinterpret_cast<float4*>(g)[i] = gg;  // (elem takes g by value: the clipped gradient, before any L2 term)
     }
     for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += OPT_THREADS) {
         float pp = p[i], gg = g[i] * coef, mm = m[i], vv = v[i];
-        radam_elem(pp, gg, mm, vv, a);
+        Rule::elem(pp, gg, mm, vv, a);
         p[i] = pp; m[i] = mm; v[i] = vv;
         if (WRITE_GRAD) g[i] = gg;
     }
+}
+
+template <class Rule>
+static int launch_update(const TdxOptTensor* table, const int* chunk_tensor, const int64_t* chunk_off, int nchunks,
+                         const float* clip, const float* skip, const typename Rule::Args& a, int write_grad, void* stream) {
+    hipStream_t st = as_stream(stream);
+    if (write_grad)
+        hipLaunchKernelGGL((opt_update_kernel<Rule, true>), dim3(nchunks), dim3(OPT_THREADS), 0, st, table, chunk_tensor, chunk_off, clip, skip, a);
+    else
+        hipLaunchKernelGGL((opt_update_kernel<Rule, false>), dim3(nchunks), dim3(OPT_THREADS), 0, st, table, chunk_tensor, chunk_off, clip, skip, a);
+    return tdx_launch_status();
 }
 
 extern "C" int64_t tdx_opt_chunk_elems(void) { return OPT_CHUNK; }
@@ -154,17 +197,12 @@ static int radam_step_impl(const TdxOptTensor* table, const int* chunk_tensor, c
     const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
     const double rho_inf = 2.0 / (1.0 - b2) - 1.0;
     const double rho_t = rho_inf - 2.0 * t * pow(b2, t) / bc2;
-    RAdamArgs a;
+    RAdamRule::Args a;
     a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
     a.inv_bc1 = (float)(1.0 / bc1);
     a.sqrt_bc2 = (float)sqrt(bc2);
     a.rect = rho_t > 5.0 ? (float)sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t)) : -1.0f;
-    hipStream_t st = as_stream(stream);
-    if (write_grad)
-        hipLaunchKernelGGL(opt_radam_kernel<true>, dim3(nchunks), dim3(OPT_THREADS), 0, st, table, chunk_tensor, chunk_off, clip, skip, a);
-    else
-        hipLaunchKernelGGL(opt_radam_kernel<false>, dim3(nchunks), dim3(OPT_THREADS), 0, st, table, chunk_tensor, chunk_off, clip, skip, a);
-    return tdx_launch_status();
+    return launch_update<RAdamRule>(table, chunk_tensor, chunk_off, nchunks, clip, skip, a, write_grad, stream);
 }
 
 extern "C" int tdx_radam_step(const TdxOptTensor* table, const int* chunk_tensor, const int64_t* chunk_off, int nchunks,
@@ -179,6 +217,42 @@ extern "C" int tdx_radam_step_scaled(const TdxOptTensor* table, const int* chunk
     TDX_CHECK_ARG(scaled_norm);
     return radam_step_impl(table, chunk_tensor, chunk_off, nchunks, scaled_norm, scaled_norm + 2, step, lr, beta1, beta2, eps,
                            write_grad, stream);
+}
+
+static int adam_step_impl(const TdxOptTensor* table, const int* chunk_tensor, const int64_t* chunk_off, int nchunks,
+                          const float* clip, const float* skip, int64_t step, double lr, double beta1, double beta2, double eps,
+                          double weight_decay, int decoupled, int write_grad, void* stream) {
+    TDX_CHECK_ARG(table && chunk_tensor && chunk_off && nchunks > 0 && step >= 1);
+    TDX_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && weight_decay >= 0.0);
+    // scalar schedule of torch.optim.adam, in double like the Python floats there; every scalar a torch kernel would
+    // receive is rounded to fp32 once, here
+    const double t = (double)step;
+    const double bc1 = 1.0 - pow(beta1, t), bc2 = 1.0 - pow(beta2, t);
+    AdamRule::Args a;
+    a.w1 = (float)(1.0 - beta1);
+    a.beta2 = (float)beta2;
+    a.w2 = (float)(1.0 - beta2);
+    a.step_size = (float)(lr / bc1);
+    a.sqrt_bc2 = (float)sqrt(bc2);
+    a.eps = (float)eps;
+    a.l2 = decoupled ? 0.f : (float)weight_decay;
+    a.keep = decoupled && weight_decay != 0.0 ? (float)(1.0 - lr * weight_decay) : 1.0f;
+    return launch_update<AdamRule>(table, chunk_tensor, chunk_off, nchunks, clip, skip, a, write_grad, stream);
+}
+
+extern "C" int tdx_adam_step(const TdxOptTensor* table, const int* chunk_tensor, const int64_t* chunk_off, int nchunks,
+                             const float* clip, int64_t step, double lr, double beta1, double beta2, double eps,
+                             double weight_decay, int decoupled, int write_grad, void* stream) {
+    return adam_step_impl(table, chunk_tensor, chunk_off, nchunks, clip, nullptr, step, lr, beta1, beta2, eps, weight_decay,
+                          decoupled, write_grad, stream);
+}
+
+extern "C" int tdx_adam_step_scaled(const TdxOptTensor* table, const int* chunk_tensor, const int64_t* chunk_off, int nchunks,
+                                    const float* scaled_norm, int64_t step, double lr, double beta1, double beta2, double eps,
+                                    double weight_decay, int decoupled, int write_grad, void* stream) {
+    TDX_CHECK_ARG(scaled_norm);
+    return adam_step_impl(table, chunk_tensor, chunk_off, nchunks, scaled_norm, scaled_norm + 2, step, lr, beta1, beta2, eps,
+                          weight_decay, decoupled, write_grad, stream);
 }
 
 // ---- gradient staging of the data-parallel step ---------------------------------------------------------------------------

@@ -109,6 +109,8 @@ SIGNATURES = {
     "tdx_stage_scaled": (_i, [_vp, _i, _f, _vp]),
     "tdx_grad_norm_scaled": (_i, [_vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp]),
     "tdx_radam_step_scaled": (_i, [_vp, _vp, _vp, _i, _vp, _i64, _f, _f, _f, _f, _i, _vp]),
+    "tdx_adam_step": (_i, [_vp, _vp, _vp, _i, _vp, _i64] + [C.c_double] * 5 + [_i, _i, _vp]),
+    "tdx_adam_step_scaled": (_i, [_vp, _vp, _vp, _i, _vp, _i64] + [C.c_double] * 5 + [_i, _i, _vp]),
 }
 
 FILM_MAX_LAYERS = 32  # TDX_FILM_MAX_LAYERS

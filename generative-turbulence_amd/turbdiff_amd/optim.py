@@ -1,4 +1,4 @@
-"""Fused tail of the training step: global-norm gradient clipping + RAdam in three kernel launches.
+"""Fused tail of the training step: global-norm gradient clipping + RAdam / Adam / AdamW in three kernel launches.
 
 The reference trains with ``torch.optim.RAdam(lr)`` (models/diffusion.py:210-218) under Lightning's
 ``gradient_clip_val: 0.1`` (config/train.yaml:30-31), i.e. ``clip_grad_norm_`` followed by
@@ -7,8 +7,14 @@ The reference trains with ``torch.optim.RAdam(lr)`` (models/diffusion.py:210-218
 ``ClipRAdam`` does the same arithmetic (torch.optim.radam._single_tensor_radam, same scalar schedule,
 fp32 state) through ``tdx_grad_norm`` / ``tdx_radam_step`` (csrc/tdx_optim.hip).
 
-It is a ``torch.optim.Optimizer``: ``param_groups[i]["lr"]`` is honoured every step (LR schedulers
-work), and the per-parameter state uses torch's RAdam keys (``step``, ``exp_avg``, ``exp_avg_sq``) with
+``ClipAdam`` and ``ClipAdamW`` are the same machinery around ``tdx_adam_step`` (torch/optim/adam.py, the non-capturable
+branch; AdamW is Adam with ``decoupled_weight_decay=True``, as in torch): the reference's other two ``optimizer`` keys
+(diffusion.py:210-218) and the regression baselines' ``torch.optim.Adam(lr)`` (dilresnet.py:158-173, tfnet.py:428-430).
+Everything but the update rule lives in ``_ClipOptimizer``: chunk tables, the rotating pinned pointer table, per-parameter
+step counts, loss scaling, ``state_dict`` interchange with the torch class of the same rule, version bumps.
+
+Each is a ``torch.optim.Optimizer``: ``param_groups[i]["lr"]`` is honoured every step (LR schedulers
+work; ``weight_decay`` too), and the per-parameter state uses torch's keys (``step``, ``exp_avg``, ``exp_avg_sq``) with
 per-parameter step counts (parameters at different counts are updated in one launch per count), so
 optimizer state_dicts move between the two implementations (``state_dict()`` settles the step counts first and carries
 the loss-scaling state under a top-level key of its own, ``loss_scaling``, which torch's ``load_state_dict`` ignores).
@@ -16,11 +22,11 @@ the loss-scaling state under a top-level key of its own, ``loss_scaling``, which
 Loss scaling (fp16 training, ``loss_scale=``): the backward pass runs on ``scale_loss(loss) = S * loss`` (S a power of two) so
 that fp16 activation gradients stay representable; the stored fp32 parameter gradients are then S times the true ones.
 ``tdx_grad_norm_scaled`` reports the true norm, folds 1 / S into the clip factor and raises a device flag when the norm is
-not finite, on which ``tdx_radam_step_scaled`` leaves parameters and moments untouched.  The host never waits for that flag:
-it reads the flag of step k - 2 at the END of step k (an asynchronous copy into pinned memory behind an event that has long fired),
+not finite, on which ``tdx_radam_step_scaled`` / ``tdx_adam_step_scaled`` leave parameters and moments untouched.  The host
+never waits for that flag: it reads the flag of step k - 2 at the END of step k (an asynchronous copy into pinned memory behind an event that has long fired),
 halves S and takes the skipped step out of the step counters then; after ``scale_growth_interval`` clean steps S doubles.
 The lag is a constant two steps, so data-parallel ranks (which see identical all-reduced gradients) change S in lockstep.
-Its price: the one or two steps that follow an overflow run RAdam's bias corrections with a step count that still includes
+Its price: the one or two steps that follow an overflow run the bias corrections with a step count that still includes
 the skipped step(s) (``sync_flags=True`` waits for every step's own flag instead, as ``torch.cuda.amp.GradScaler`` does).
 """
 
@@ -32,15 +38,18 @@ import torch
 from . import _lib as L
 
 
-class ClipRAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, max_norm: float | None = None,
-                 write_clipped_grads: bool = False, loss_scale: float | None = None, scale_growth_interval: int = 2000,
-                 min_loss_scale: float = 1.0, max_loss_scale: float = 2.0**24, sync_flags: bool = False):
+class _ClipOptimizer(torch.optim.Optimizer):
+    """Everything of the fused tail that does not depend on the update rule.  A subclass passes its ``defaults`` and
+    implements ``_update`` (the launch of its rule's kernel over one set of chunks at one step count)."""
+
+    def __init__(self, params, defaults, max_norm, write_clipped_grads, loss_scale, scale_growth_interval, min_loss_scale,
+                 max_loss_scale, sync_flags):
+        lr, betas = defaults["lr"], defaults["betas"]
         if not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr}")
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"Invalid betas: {betas}")
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0.0))
+        super().__init__(params, defaults)
         self.max_norm = max_norm
         self.write_clipped_grads = write_clipped_grads
         self._plans = {}
@@ -94,8 +103,8 @@ class ClipRAdam(torch.optim.Optimizer):
         """torch's layout (``state`` with ``step`` / ``exp_avg`` / ``exp_avg_sq`` per parameter, ``param_groups``), settled first:
         the step counts saved are those of the steps that happened, also within the two-step lag behind an overflow.  The
         loss-scaling state travels under a third top-level key, ``loss_scaling``, which ``torch.optim.Optimizer.load_state_dict``
-        does not read: the same dictionary loads into ``torch.optim.RAdam``.  Like ``settle()``, this waits for the
-        outstanding flags, so a run that checkpoints continues from settled counters -- as the run resumed from the checkpoint does."""
+        does not read: the same dictionary loads into the torch class of the same rule (``torch.optim.RAdam`` / ``Adam`` /
+        ``AdamW``).  Like ``settle()``, this waits for the outstanding flags, so a run that checkpoints continues from settled counters -- as the run resumed from the checkpoint does."""
         self.settle()
         sd = super().state_dict()
         # (the live step counters are views into one tensor that step() increments in place: hand out copies)
@@ -107,7 +116,7 @@ class ClipRAdam(torch.optim.Optimizer):
         return sd
 
     def load_state_dict(self, state_dict):
-        """A ``state_dict()`` of this class or of ``torch.optim.RAdam``.  With loss scaling on, ``loss_scaling`` (if the dictionary
+        """A ``state_dict()`` of this class or of its torch counterpart.  With loss scaling on, ``loss_scaling`` (if the dictionary
         has it) restores the scale, the clean-step count towards its next doubling, the skipped-step count and the step index;
         a dictionary without it (torch's) leaves them as they are.  Flags of steps taken before the call are dropped: they
         belong to the state that is being replaced."""
@@ -133,7 +142,7 @@ class ClipRAdam(torch.optim.Optimizer):
         dev = params[0].device
         for p in params:
             if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev or not p.is_cuda:
-                raise TypeError("ClipRAdam needs contiguous float32 parameters on one GPU")
+                raise TypeError(f"{type(self).__name__} needs contiguous float32 parameters on one GPU")
             st = self.state[p]
             if len(st) == 0:
                 st["step"] = torch.tensor(0.0, dtype=torch.float32)
@@ -176,7 +185,7 @@ class ClipRAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        """clip (if ``max_norm``) + RAdam.  Returns the loss of ``closure`` if given; the total gradient
+        """clip (if ``max_norm``) + the update.  Returns the loss of ``closure`` if given; the total gradient
         norm of the last step stays on the device in ``self.last_grad_norm`` (no host sync)."""
         loss = None
         if closure is not None:
@@ -258,10 +267,9 @@ class ClipRAdam(torch.optim.Optimizer):
                        plan["nchunks"], float(self.max_norm), L.ptr(plan["partial"]), L.ptr(plan["norm"]), stream)
                 clip = plan["norm"]
                 self.last_grad_norm = plan["norm"][0]
-            b1, b2 = group["betas"]
-            # RAdam's bias corrections depend on the step count, which torch keeps per parameter: parameters that
+            # the bias corrections depend on the step count, which torch keeps per parameter: parameters that
             # received gradients on different numbers of steps (conditional branches, a state_dict loaded from
-            # torch.optim.RAdam) are updated in one launch per distinct count, over that count's chunks only
+            # the torch class) are updated in one launch per distinct count, over that count's chunks only
             by_step = {}
             counts = steps.tolist()
             if live_all and counts.count(counts[0]) == len(counts):
@@ -274,9 +282,7 @@ class ClipRAdam(torch.optim.Optimizer):
                     ct, co, n = plan["chunk_tensor"], plan["chunk_off"], plan["nchunks"]
                 else:
                     ct, co, n = self._chunks_of(plan, tuple(members))
-                L.call("tdx_radam_step_scaled" if scaled else "tdx_radam_step", L.ptr(plan["table"]), L.ptr(ct), L.ptr(co), n,
-                       L.ptr(clip), step_count, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                       int(self.write_clipped_grads), stream)
+                self._update(scaled, L.ptr(plan["table"]), L.ptr(ct), L.ptr(co), n, L.ptr(clip), step_count, group, stream)
             # the kernels wrote through raw pointers: tell autograd (and the packed-weight caches keyed
             # on Tensor._version, ops._packed_conv3) that the parameters changed
             torch.autograd.graph.increment_version([p for p in plan["params"] if p.grad is not None])
@@ -285,3 +291,53 @@ class ClipRAdam(torch.optim.Optimizer):
             # steps <= k - 2 are long on the host (a constant lag: data-parallel ranks change the scale in lockstep)
             self._settle_flags(self._step_index + 1 if self.sync_flags else self._step_index - 1, wait=True)
         return loss
+
+    def _update(self, scaled, table, chunk_tensor, chunk_off, nchunks, clip, step_count, group, stream):
+        """Launch the rule's kernel: step number `step_count` over the given chunks, hyper-parameters read from `group`."""
+        raise NotImplementedError
+
+
+class ClipRAdam(_ClipOptimizer):
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, max_norm: float | None = None,
+                 write_clipped_grads: bool = False, loss_scale: float | None = None, scale_growth_interval: int = 2000,
+                 min_loss_scale: float = 1.0, max_loss_scale: float = 2.0**24, sync_flags: bool = False):
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0.0), max_norm, write_clipped_grads,
+                         loss_scale, scale_growth_interval, min_loss_scale, max_loss_scale, sync_flags)
+
+    def _update(self, scaled, table, chunk_tensor, chunk_off, nchunks, clip, step_count, group, stream):
+        b1, b2 = group["betas"]
+        L.call("tdx_radam_step_scaled" if scaled else "tdx_radam_step", table, chunk_tensor, chunk_off, nchunks, clip,
+               step_count, float(group["lr"]), float(b1), float(b2), float(group["eps"]), int(self.write_clipped_grads), stream)
+
+
+class ClipAdam(_ClipOptimizer):
+    """clip + ``torch.optim.Adam`` (L2 weight decay folded into the gradient; ``decoupled_weight_decay=True``: AdamW's)."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 decoupled_weight_decay: bool = False, max_norm: float | None = None, write_clipped_grads: bool = False,
+                 loss_scale: float | None = None, scale_growth_interval: int = 2000, min_loss_scale: float = 1.0,
+                 max_loss_scale: float = 2.0**24, sync_flags: bool = False, amsgrad: bool = False, maximize: bool = False):
+        if amsgrad or maximize:
+            raise ValueError(f"{type(self).__name__} has no amsgrad / maximize variant")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
+                                      decoupled_weight_decay=bool(decoupled_weight_decay)),
+                         max_norm, write_clipped_grads, loss_scale, scale_growth_interval, min_loss_scale, max_loss_scale, sync_flags)
+
+    def _update(self, scaled, table, chunk_tensor, chunk_off, nchunks, clip, step_count, group, stream):
+        if group.get("amsgrad") or group.get("maximize"):  # (a param_group loaded from a torch state_dict can carry them)
+            raise ValueError(f"{type(self).__name__} has no amsgrad / maximize variant")
+        b1, b2 = group["betas"]
+        L.call("tdx_adam_step_scaled" if scaled else "tdx_adam_step", table, chunk_tensor, chunk_off, nchunks, clip, step_count,
+               float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+               int(bool(group.get("decoupled_weight_decay", False))), int(self.write_clipped_grads), stream)
+
+
+class ClipAdamW(ClipAdam):
+    """clip + ``torch.optim.AdamW``: ``ClipAdam`` with decoupled decay and torch's default of 1e-2."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, **kw):
+        if not kw.pop("decoupled_weight_decay", True):
+            raise ValueError("ClipAdamW is decoupled weight decay; use ClipAdam for the L2 form")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled_weight_decay=True, **kw)

@@ -7,8 +7,9 @@
 * the ``dx_mean`` / ``dx_var`` / ``n_train_batches_tracked`` buffers and the reference's ``state_dict`` keys;
 * ``training_step``: one-step prediction of the normalised increment x1 - x0 (noise-injected x0), MSE against
   ``F.batch_norm`` of the increment over the in-domain cells (batch statistics for the first 1000 training batches);
-* ``configure_optimizers``: Adam + LambdaLR exponential decay to ``min_learning_rate`` over ``max_train_steps``;
-  ``fit_step`` = zero_grad, step, backward, clip, optimiser, schedule;
+* ``configure_optimizers``: Adam + LambdaLR exponential decay to ``min_learning_rate`` over ``max_train_steps`` (on a GPU
+  with ``fused_optimizer``: ``optim.ClipAdam``, clip and update in three launches); ``fit_step`` = zero_grad, step, backward,
+  clip, optimiser, schedule;
 * ``_predict_x`` / ``unroll_samples``: the rollout x <- inside ? x + dx_mean + dx_std model(x) : x.  The conditioning conv
   runs once per batch; in bf16 the decode conv applies the update in its epilogue and the state stays fp32;
 * ``validation_step(batch, stores)``: unroll over the batch's target steps, hand the samples at ``sample_steps`` to
@@ -88,6 +89,7 @@ class DilResNetTrainer(nn.Module):
             raise ValueError(f"compute mode {compute_mode!r} not in {COMPUTE_MODES}")
         self.compute_mode = compute_mode
         self.gradient_clip_val = gradient_clip_val
+        self.fused_optimizer = True  # optim.ClipAdam on GPU; False -> clip_grad_norm_ + torch.optim.Adam
         self._opt = self._sched = None
 
     @staticmethod
@@ -175,7 +177,13 @@ class DilResNetTrainer(nn.Module):
         return math.exp(decay_step * min(step, self.max_train_steps))
 
     def configure_optimizers(self):
-        opt = torch.optim.Adam(self.parameters(), lr=self.learning_rate)
+        params = list(self.parameters())
+        if self.fused_optimizer and params[0].is_cuda:
+            from .optim import ClipAdam  # clip + Adam fused; same arithmetic as the two torch calls
+
+            opt = ClipAdam(params, lr=self.learning_rate, max_norm=self.gradient_clip_val or None)
+        else:
+            opt = torch.optim.Adam(params, lr=self.learning_rate)
         return opt, torch.optim.lr_scheduler.LambdaLR(opt, self.lr_lambda)
 
     def fit_step(self, batch, noise: torch.Tensor | None = None):
@@ -186,7 +194,7 @@ class DilResNetTrainer(nn.Module):
         self._opt.zero_grad(set_to_none=True)
         loss = self.training_step(batch, noise)
         loss.backward()
-        if self.gradient_clip_val:
+        if self.gradient_clip_val and not hasattr(self._opt, "max_norm"):
             torch.nn.utils.clip_grad_norm_(self.parameters(), self.gradient_clip_val)
         self._opt.step()
         self._sched.step()

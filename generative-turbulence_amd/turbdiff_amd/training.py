@@ -66,7 +66,7 @@ def _metric_placeholders():
 # "medium" allow reduced-precision products on fp32 tensors (TF32 / bf16 in stock PyTorch) -> split-precision convs
 # (bf16 hi + lo: 16 significand bits, more than TF32's 10).  16-bit STORAGE is never implied by a reference config;
 # ask for it explicitly: compute_mode="fp16" (IEEE half tensors + fp16 MFMA operands: TF32's 11 significand bits at the
-# bf16 kernels' speed; training runs under a power-of-two loss scale, optim.ClipRAdam) or "bf16" (8 bits, no scale needed).
+# bf16 kernels' speed; training runs under a power-of-two loss scale, the optim.Clip* classes) or "bf16" (8 bits, no scale needed).
 MATMUL_PRECISION_TO_MODE = {"highest": "f32", "high": "f32s", "medium": "f32s"}
 COMPUTE_MODES = ("f32", "f32s", "bf16", "fp16")
 _MODE_DTYPE = {"f32": torch.float32, "f32s": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
@@ -154,7 +154,7 @@ class DiffusionTrainer(nn.Module):
         self.clip_denoised, self.noise_bcs, self.learned_variances = clip_denoised, noise_bcs, learned_variances
         self.elbo_weight, self.detach_elbo_mean, self.actfn = elbo_weight, detach_elbo_mean, actfn
         self.gradient_clip_val = gradient_clip_val
-        self.fused_optimizer = True  # ClipRAdam on GPU; False -> clip_grad_norm_ + torch.optim.RAdam
+        self.fused_optimizer = True  # optim.ClipRAdam / ClipAdam / ClipAdamW on GPU; False -> clip_grad_norm_ + the torch class
         # fp16 training: initial loss scale (a power of two), or None = chosen from the first batch so that the seed of the
         # backward pass, 2 (eps_hat - eps) / (B F n_cells), lands near 2^-3 (initial_loss_scale)
         self.loss_scale = None
@@ -309,11 +309,12 @@ class DiffusionTrainer(nn.Module):
         if klass is None:
             raise RuntimeError(f"Unknown optimizer {self.optimizer}")
         params = list(self.parameters())
-        if self.optimizer == "radam" and self.fused_optimizer and params[0].is_cuda:
-            from .optim import ClipRAdam  # clip + RAdam fused; same arithmetic as the two torch calls
+        if self.fused_optimizer and params[0].is_cuda:
+            from . import optim  # clip + update fused; same arithmetic as the two torch calls
 
-            opt = ClipRAdam(params, lr=self.learning_rate, max_norm=self.gradient_clip_val or None,
-                            loss_scale=self._loss_scale_for_optimizer())
+            fused = {"adam": optim.ClipAdam, "adamw": optim.ClipAdamW, "radam": optim.ClipRAdam}[self.optimizer]
+            opt = fused(params, lr=self.learning_rate, max_norm=self.gradient_clip_val or None,
+                        loss_scale=self._loss_scale_for_optimizer())
         else:
             if self.model.model.compute_dtype == torch.float16:
                 raise RuntimeError("fp16 training needs the loss-scaling optimiser: optimizer='radam' with fused_optimizer on a GPU")

@@ -572,6 +572,26 @@ int tdx_radam_step_scaled(const TdxOptTensor* table, const int* chunk_tensor, co
 int tdx_radam_step(const TdxOptTensor* table, const int* chunk_tensor, const int64_t* chunk_off, int nchunks,
                    const float* clip, int64_t step, float lr, float beta1, float beta2, float eps, int write_grad,
                    void* stream);
+/* One Adam / AdamW step number `step` (1-based) over the same tables: replaces torch.optim.Adam.step / AdamW.step
+ * (`optimizer: adam | adamw` of models/diffusion.py:210-218; torch.optim.Adam(lr) of the regression baselines,
+ * models/dilresnet.py:158-173, models/tfnet.py:428-430) -- per tensor _foreach_lerp_, _foreach_mul_, _foreach_addcmul_,
+ * _foreach_sqrt, _foreach_div_, _foreach_add_, _foreach_addcdiv_ (and _foreach_add / _foreach_mul_ under weight decay) of
+ * torch/optim/adam.py's non-capturable branch, same fp32 arithmetic: with g = grad x clip[1] (clip as for tdx_radam_step),
+ *   decoupled == 0 and weight_decay != 0:  g += weight_decay * p          (Adam's L2 term)
+ *   decoupled != 0 and weight_decay != 0:  p *= 1 - lr * weight_decay     (AdamW)
+ *   m += (g - m) * (1 - beta1);  v = v * beta2 + (1 - beta2) * g * g
+ *   p -= lr / (1 - beta1^step) * (m / (sqrt(v) / sqrt(1 - beta2^step) + eps))
+ * The hyper-parameters are doubles, as torch holds them: each scalar of the schedule is computed in double and rounded to
+ * fp32 once (1 - (float)0.999 is 1.3e-5 away from (float)(1 - 0.999), and Adam divides by sqrt(v) from its first step).
+ * weight_decay >= 0.  write_grad != 0 stores g back BEFORE the L2 term: what clip_grad_norm_ leaves in .grad. */
+int tdx_adam_step(const TdxOptTensor* table, const int* chunk_tensor, const int64_t* chunk_off, int nchunks,
+                  const float* clip, int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                  int decoupled, int write_grad, void* stream);
+/* tdx_adam_step with scaled_norm = the `out` of tdx_grad_norm_scaled (loss-scaled gradients): gradients x scaled_norm[1];
+ * the whole step is a no-op when scaled_norm[2] != 0. */
+int tdx_adam_step_scaled(const TdxOptTensor* table, const int* chunk_tensor, const int64_t* chunk_off, int nchunks,
+                         const float* scaled_norm, int64_t step, double lr, double beta1, double beta2, double eps,
+                         double weight_decay, int decoupled, int write_grad, void* stream);
 
 /* ---- gradient staging of the data-parallel step ---------------------------------------------------
  * Replaces the per-parameter copy of a gradient into its all-reduce bucket that DistributedDataParallel's autograd hooks

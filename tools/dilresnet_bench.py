@@ -11,7 +11,12 @@ alternately in one process after warm-up:
 Prints max-abs / rel-L2 of fused against unfused on the same inputs, then one line per (workload, implementation) with the
 median ms over --reps.  GPU only: exits with an error without one.
 
-    python tools/dilresnet_bench.py [--reps 5] [--steps 30]
+--optimizer: what ends the training steps -- fused (optim.ClipAdam, clip 0.1 + Adam in three launches: what DilResNetTrainer
+uses on a GPU), torch (clip_grad_norm_ 0.1 + torch.optim.Adam), or both: the HIP bf16 chain then gets one row per optimiser,
+"fused" and "fused/torch-opt", alternating like the other columns (the remaining rows end with the torch pair).  The tail
+alone, between HIP events: tools/optim_tail_bench.py.
+
+    python tools/dilresnet_bench.py [--reps 5] [--steps 30] [--optimizer fused|torch|both]
 """
 
 import argparse
@@ -67,6 +72,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--steps", type=int, default=30, help="rollout length (eval_unroll_steps of dilresnet.yaml)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--optimizer", default="both", choices=["fused", "torch", "both"], help="the optimiser tail of the training steps")
     ap.add_argument("--only", default=None, help="time one implementation only (profiling runs): fused | unfused | f32 | torch")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -78,7 +84,10 @@ def main():
     torch.manual_seed(0)
     X, Y, Z = 194, 50, 50
     net = DilResNet(4, 8, 0, N=4, hidden_dim=48).to(dev)
-    opt = torch.optim.Adam(net.parameters(), lr=1e-6)
+    from turbdiff_amd.optim import ClipAdam
+
+    # (lr 1e-6: both optimisers step the same parameters, which barely move over the run)
+    opts = {"fused": ClipAdam(net.parameters(), lr=1e-6, max_norm=0.1), "torch": torch.optim.Adam(net.parameters(), lr=1e-6)}
     g = torch.Generator(device=dev).manual_seed(1)
     c = torch.randn(8, X, Y, Z, device=dev, generator=g)
     C = {Conditioning.Type.CELL_TYPE: c}
@@ -119,6 +128,10 @@ def main():
         net.zero_grad(set_to_none=True)
 
     def train_step(impl):
+        # the HIP bf16 chain ends with the chosen optimiser ("fused/torch-opt": the same chain with the torch pair)
+        opt = opts["fused" if impl == "fused" and args.optimizer != "torch" else "torch"]
+        impl = impl.split("/")[0]
+
         def run():
             opt.zero_grad(set_to_none=True)
             if impl == "torch-f32" or impl == "torch-bf16":
@@ -133,6 +146,8 @@ def main():
                     y = net(x3.to(dt), C)
                 loss = F.mse_loss(y, t3)
             loss.backward()
+            if opt is opts["torch"]:
+                torch.nn.utils.clip_grad_norm_(net.parameters(), 0.1)
             opt.step()
         return run
 
@@ -163,7 +178,9 @@ def main():
     for wname, make in work:
         # the 30-step unroll only for the two HIP bf16 paths: through MIOpen it would take minutes (the per-step row above
         # gives the others)
-        w_impls = [i for i in impls if i in ("fused", "unfused")] if "unroll" in wname else impls
+        w_impls = [i for i in impls if i in ("fused", "unfused")] if "unroll" in wname else list(impls)
+        if wname.startswith("train") and args.optimizer == "both" and "fused" in w_impls:
+            w_impls.insert(w_impls.index("fused") + 1, "fused/torch-opt")
         fns = {i: make(i) for i in w_impls}
         reps = 1 if "unroll" in wname else args.reps
         for i in w_impls:
@@ -174,7 +191,7 @@ def main():
             for i in w_impls:
                 times[i] += timed(fns[i], 1)
         for i in w_impls:
-            print(f"{wname:18s} {i:11s} {statistics.median(times[i]):10.2f} ms  (min {min(times[i]):.2f}, n {len(times[i])})")
+            print(f"{wname:18s} {i:15s} {statistics.median(times[i]):10.2f} ms  (min {min(times[i]):.2f}, n {len(times[i])})")
     sys.stdout.flush()
 
 

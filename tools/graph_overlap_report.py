@@ -10,7 +10,7 @@ mark = [i for i, r in enumerate(rows) if "cumsum" in r[0].lower() or "scan" in r
 assert mark, "marker kernel not found"
 halves = {"eager": rows[: mark[0]], "captured": rows[mark[-1] + 1:]}
 for name, seg in halves.items():
-    opt = [i for i, r in enumerate(seg) if "opt_radam" in r[0]]
+    opt = [i for i, r in enumerate(seg) if "opt_update_kernel" in r[0] or "opt_radam" in r[0]]  # (opt_radam: older traces)
     seg = seg[opt[-5] + 1: opt[-1] + 1]  # the last 4 steps
     t0, t1 = seg[0][1], max(r[2] for r in seg)
     ev = sorted([(r[1], 1) for r in seg] + [(r[2], -1) for r in seg])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One training step (fwd + bwd + clip + RAdam) of the BASELINE configs[1] U-Net on an arbitrary grid, for profiling:
+"""One training step (fwd + bwd + clip + RAdam; --optimizer adam | adamw: optim.ClipAdam / ClipAdamW) of the BASELINE configs[1] U-Net on an arbitrary grid, for profiling:
     python tools/step_bench.py --grid 194 50 50 --mode bf16 --batch 6 --steps 5
 --model cfg1: the 2-level U-Net of BASELINE configs[0] instead (with --grid 48 32 32 --batch 1 its host-bound eager step).
 --learned-variances --elbo-weight W: the same U-Net with 2F output channels and the simple + ELBO loss (ops.elbo_loss);
@@ -23,6 +23,7 @@ ap.add_argument("--batch", type=int, default=6)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--model", default="bench", choices=["bench", "cfg1"])
+ap.add_argument("--optimizer", default="radam", choices=["radam", "adam", "adamw"], help="the fused optimiser that ends the step")
 ap.add_argument("--learned-variances", action="store_true", help="2F output channels, per-voxel variance")
 ap.add_argument("--elbo-weight", type=float, default=None, help="with --learned-variances: weight of the ELBO term (None: simple loss only)")
 ap.add_argument("--torch-elbo", action="store_true", default=os.environ.get("TDX_STEP_BENCH_TORCH_ELBO", "0") not in ("", "0"),
@@ -46,6 +47,17 @@ def torch_elbo_p_losses(diff):
 
     return p_losses
 
+
+if a.optimizer != "radam":
+    def new_optimizer(diff, mode, n_loss_elements):
+        """bench.new_optimizer with the chosen update rule"""
+        from turbdiff_amd import optim
+        from turbdiff_amd.training import DiffusionTrainer
+
+        scale = DiffusionTrainer.initial_loss_scale(n_loss_elements) if mode == "fp16" else None
+        return {"adam": optim.ClipAdam, "adamw": optim.ClipAdamW}[a.optimizer](diff.parameters(), lr=1e-4, max_norm=0.1, loss_scale=scale)
+
+    bench.new_optimizer = new_optimizer  # (what bench.timed_train_steps builds its optimiser with)
 
 if a.model == "cfg1":
     from turbdiff_amd.models.ddpm import GaussianDiffusion
@@ -73,4 +85,4 @@ if a.learned_variances and a.elbo_weight is not None and (a.torch_elbo or a.ab):
             print(f"{name}: grid {a.grid} B {a.batch} {a.mode}: {ms:.3f} ms/step = {a.batch * v / ms / 1e3:.1f} M voxels/s")
     sys.exit(0)
 ms = bench.timed_train_steps(diff, x, C, md, a.mode, a.steps, a.warmup)
-print(f"grid {a.grid} B {a.batch} {a.mode}: {ms:.3f} ms/step = {a.batch * v / ms / 1e3:.1f} M voxels/s")
+print(f"grid {a.grid} B {a.batch} {a.mode} {a.optimizer}: {ms:.3f} ms/step = {a.batch * v / ms / 1e3:.1f} M voxels/s")

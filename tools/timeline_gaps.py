@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where does a step's wall time go that is NOT kernel time?  From a rocprofv3 --kernel-trace csv of tools/step_bench.py:
-per step (delimited by the optimiser's opt_radam_kernel launches) the span, the union of all kernel intervals (device
+per step (delimited by the optimiser's opt_update_kernel launches) the span, the union of all kernel intervals (device
 busy), the idle remainder, and which kernels the longest idle gaps precede.
     rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 tools/step_bench.py --grid 192 64 48 --steps 6 --warmup 3
     python3 tools/timeline_gaps.py OUT"""
@@ -8,7 +8,8 @@ import csv, glob, sys, collections
 
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
 rows = sorted(((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(open(f))))
-marks = [i for i, r in enumerate(rows) if r[2].startswith("void opt_radam_kernel") or "opt_radam_kernel" in r[2][:40]]
+# (opt_radam_kernel: traces taken before the update kernel became opt_update_kernel<Rule, WRITE_GRAD>)
+marks = [i for i, r in enumerate(rows) if any(k in r[2][:40] for k in ("opt_update_kernel", "opt_radam_kernel"))]
 steps = [(marks[i] + 1, marks[i + 1] + 1) for i in range(len(marks) - 1)]
 steps = steps[len(steps) // 2:]  # the timed (warm) half
 tot_span = tot_busy = 0.0
