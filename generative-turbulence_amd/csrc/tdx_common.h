@@ -18,6 +18,20 @@ static inline int tdx_launch_status() {
     return e == hipSuccess ? TDX_OK : (int)e;
 }
 
+// Launch of a kernel whose dynamic LDS exceeds the default limit: the attribute is set at the kernel's first launch (KERN
+// is a template argument, so every instantiation has its own flag)
+template <auto KERN, typename... Args>
+static int tdx_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(KERN, grid, block, lds, st, args...);
+    return tdx_launch_status();
+}
+
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 
 // ---- scalar element access ---------------------------------------------------------

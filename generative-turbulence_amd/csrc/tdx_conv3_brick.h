@@ -1,4 +1,6 @@
-// Brick geometry shared by the fp32-tensor MFMA conv kernels (tdx_conv3_mfma_f32.hip, tdx_conv3_mfma_split.hip).
+// Brick geometry shared by the brick kernels of the forward / data gradient: 16-bit (tdx_conv3_mfma.hip), fp32-IEEE
+// (tdx_conv3_mfma_f32.hip) and split-precision (tdx_conv3_mfma_split.hip).  What they share behind their K loops:
+// tdx_conv3_epilogue.h.
 //
 // A workgroup owns one brick of 256 output voxels: 4 x 8 x 8, or the "thin" 2 x 16 x 8 used for the 1-2 voxel
 // remainder slabs that a grid leaves next to the exactly tiled main region (194 x 66 x 50: 3087 main bricks
@@ -7,9 +9,12 @@
 // slab's thin axis; weight taps are re-indexed through ws[].  One launch carries up to three regions (the
 // three slabs of a grid go out together).  Since the data gradient runs on the ORIGINAL grid (its halo-shell term
 // is tdx_conv3_shell.hip) the slabs only occur on grids like the reference's real 194 x 50 x 50.
+// Which regions a call gets is each launcher's rule: brick_plan below for the fp32-tensor kernels, mfma_plan
+// (tdx_conv3_mfma.hip) for the 16-bit kernel; both fill BrickRegions.
 #pragma once
 #include "tdx_common.h"
 #include "tdx_conv3.h"
+#include <stdlib.h>
 
 struct BrickView {
     int B;
@@ -18,12 +23,14 @@ struct BrickView {
     int org[3], ext[3];  // region origin / extent in output coordinates (local axes)
     int nb[3];           // bricks per local axis
     int ws[3];           // weight-tap stride of local axis k: {9, 3, 1}[perm[k]]
+    int El[3];           // input extent of local axis k: Ei[perm[k]]
+    int si[3], so[3];    // voxel stride of local axis k in the input / output grid
     int off;             // output voxel o reads input voxel o + off + e
 };
 
 struct BrickRegions {
     BrickView v[3];
-    int start[4];  // first block id of region r (start[n] = number of blocks)
+    int start[4];  // first block id of region r (start[n ... 3] = number of blocks)
     int n;
 };
 
@@ -39,7 +46,8 @@ struct Brick {
     static constexpr int MT = SHAPE == BRICK_BIG ? 4 : 2;  // M tiles (32 voxels) per wave
     static constexpr int NVOX = BX * BY * BZ;
     static constexpr int HX = BX + 2, HY = BY + 2, HZ = BZ + 2;
-    static constexpr int SZ = 12;  // padded z stride of the LDS image (conflict-free 16-B fragment reads)
+    static constexpr int SZ = 12;  // padded z stride of the LDS image (conflict-free 16-B fragment reads); the 16-bit
+                                   // kernel keeps 10 for its thin brick
     static constexpr int NHALO = HX * HY * HZ, ENTRIES = HX * HY * SZ;
 
     // wave w, M tile mt, lane row r -> local voxel inside the brick
@@ -55,15 +63,14 @@ struct Brick {
     }
 };
 
-// block id -> region, sample and brick origin (local output coordinates)
+// block id -> region, sample and brick origin (local output coordinates).  The view stays where the launch put it, in the
+// kernel-argument segment: a dynamic index there is an offset of the scalar loads that fetch the fields when they are
+// used (a copy by value would hold the whole view in SGPRs from here on, or go to scratch)
 template <int SHAPE>
-__device__ __forceinline__ BrickView brick_decode(const BrickRegions& R, int bid, int& b, int (&o)[3]) {
-    // the view is selected by value (uniform selects): indexing R.v[] dynamically would push the struct to scratch
-    BrickView g = R.v[0];
-    int first = 0;
-    if (R.n > 1 && bid >= R.start[1]) { g = R.v[1]; first = R.start[1]; }
-    if (R.n > 2 && bid >= R.start[2]) { g = R.v[2]; first = R.start[2]; }
-    bid -= first;
+__device__ __forceinline__ const BrickView& brick_decode(const BrickRegions& R, int bid, int& b, int (&o)[3]) {
+    const int region = bid >= R.start[1] ? (bid >= R.start[2] ? 2 : 1) : 0;  // start[] past n repeats the block count
+    const BrickView& g = R.v[region];
+    bid -= R.start[region];
     const int b2 = bid % g.nb[2]; bid /= g.nb[2];
     const int b1 = bid % g.nb[1]; bid /= g.nb[1];
     const int b0 = bid % g.nb[0]; bid /= g.nb[0];
@@ -73,40 +80,31 @@ __device__ __forceinline__ BrickView brick_decode(const BrickRegions& R, int bid
 }
 
 // linear input voxel (inside one sample) read by halo position (hx, hy, hz) of the brick at o, or -1 for a
-// zero (ZERO_PAD: outside the grid; otherwise positions are clamped = replicate padding)
+// zero (ZERO_PAD: outside the grid; otherwise positions are clamped = replicate padding).  PERM: the local axes are
+// not the grid's, extents and strides come from the view; otherwise they follow from Ei at compile-time positions
 template <bool ZERO_PAD, bool PERM>
 __device__ __forceinline__ int brick_halo_source(const BrickView& g, const int (&o)[3], int hx, int hy, int hz) {
     const int h[3] = {hx, hy, hz};
-    // stride of local axis k in the input = stride of global axis perm[k] (identity when !PERM: compile-time)
     const int gs[3] = {g.Ei[1] * g.Ei[2], g.Ei[2], 1};
     int lin = 0;
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         int s = o[k] + h[k] - 1 + g.off;
-        const int ax = PERM ? g.perm[k] : k;
-        const int E = PERM ? (ax == 0 ? g.Ei[0] : ax == 1 ? g.Ei[1] : g.Ei[2]) : g.Ei[k];
-        const int st = PERM ? (ax == 0 ? gs[0] : ax == 1 ? gs[1] : gs[2]) : gs[k];
+        const int E = PERM ? g.El[k] : g.Ei[k];
         if (ZERO_PAD) ok = ok && s >= 0 && s < E;
         else s = min(max(s, 0), E - 1);
-        lin += s * st;
+        lin += s * (PERM ? g.si[k] : gs[k]);
     }
     return ok ? lin : -1;
 }
 
-// global output coordinates of local voxel (lx, ly, lz) of the brick at o; false if outside the region
+// linear output voxel (inside one sample) of local voxel (lx, ly, lz) of the brick at o; false if outside the region
 template <bool PERM>
-__device__ __forceinline__ bool brick_out_coords(const BrickView& g, const int (&o)[3], int lx, int ly, int lz, int (&c)[3]) {
+__device__ __forceinline__ bool brick_out_voxel(const BrickView& g, const int (&o)[3], int lx, int ly, int lz, int& vox) {
     const int l[3] = {o[0] + lx, o[1] + ly, o[2] + lz};
-    const bool ok = l[0] < g.org[0] + g.ext[0] && l[1] < g.org[1] + g.ext[1] && l[2] < g.org[2] + g.ext[2];
-    if (PERM) {
-        // c[perm[k]] = l[k] without dynamically indexed registers
-#pragma unroll
-        for (int a = 0; a < 3; ++a) c[a] = g.perm[0] == a ? l[0] : (g.perm[1] == a ? l[1] : l[2]);
-    } else {
-        c[0] = l[0]; c[1] = l[1]; c[2] = l[2];
-    }
-    return ok;
+    vox = PERM ? l[0] * g.so[0] + l[1] * g.so[1] + l[2] * g.so[2] : (l[0] * g.Eo[1] + l[1]) * g.Eo[2] + l[2];
+    return l[0] < g.org[0] + g.ext[0] && l[1] < g.org[1] + g.ext[1] && l[2] < g.org[2] + g.ext[2];
 }
 
 // row of the weight image (global tap index) of local tap (ex, ey, ez) in -1..1
@@ -115,6 +113,11 @@ __device__ __forceinline__ int brick_tap(const BrickView& g, int ex, int ey, int
 }
 
 // ---------------------------------------------------------------------------------------------- host side
+// A/B switches of the planning, read per call.  TDX_CONV3_THIN: 0 = no thin slabs, 2 = thin slabs on grids of any size
+// (16-bit kernel); TDX_CONV3_PERM: 0 = main bricks in grid orientation (16-bit kernel)
+static inline int conv3_thin_slabs() { const char* e = getenv("TDX_CONV3_THIN"); return e ? atoi(e) : 1; }
+static inline bool conv3_perm_bricks() { const char* e = getenv("TDX_CONV3_PERM"); return !(e && atoi(e) == 0); }
+
 static inline void brick_dims(int shape, int bd[3]) {
     bd[0] = shape == BRICK_THIN ? 2 : (shape == BRICK_BIG ? 8 : 4); bd[1] = shape == BRICK_THIN ? 16 : 8; bd[2] = 8;
 }
@@ -127,13 +130,27 @@ static inline void brick_fill_view(BrickView& v, const Conv3Geom& g, const int p
     v.B = g.B; v.off = g.off;
     v.Ei[0] = g.Xi; v.Ei[1] = g.Yi; v.Ei[2] = g.Zi;
     v.Eo[0] = g.Xo; v.Eo[1] = g.Yo; v.Eo[2] = g.Zo;
+    const int si[3] = {g.Yi * g.Zi, g.Zi, 1}, so[3] = {g.Yo * g.Zo, g.Zo, 1};
     for (int k = 0; k < 3; ++k) {
         v.perm[k] = perm[k];
         v.org[k] = org_g[perm[k]];
         v.ext[k] = ext_g[perm[k]];
         v.nb[k] = ceil_div(v.ext[k], bd[k]);
         v.ws[k] = tapw[perm[k]];
+        v.El[k] = v.Ei[perm[k]]; v.si[k] = si[perm[k]]; v.so[k] = so[perm[k]];
     }
+}
+
+// the block count behind the last region, repeated up to start[3] (brick_decode compares without looking at n)
+static inline void brick_close(BrickRegions& r, int nblk) {
+    for (int k = r.n; k < 4; ++k) r.start[k] = nblk;
+}
+// every launcher's guard of that invariant: a plan that was not closed would decode blocks into regions it never filled
+static inline bool brick_closed(const BrickRegions& r) {
+    if (r.n < 1 || r.n > 3 || r.start[r.n] <= 0) return false;
+    for (int k = r.n; k < 4; ++k)
+        if (r.start[k] != r.start[r.n]) return false;
+    return true;
 }
 
 static inline int64_t brick_count(const int ext_g[3], const int perm[3], int shape) {
@@ -177,7 +194,7 @@ static inline void brick_plan(const Conv3Geom& g, bool zero_pad, bool allow_thin
     main.n = 1;
     brick_fill_view(main.v[0], g, cand[mperm], org0, Em, main_shape);
     main.start[0] = 0;
-    main.start[1] = (int)((int64_t)g.B * main.v[0].nb[0] * main.v[0].nb[1] * main.v[0].nb[2]);
+    brick_close(main, (int)((int64_t)g.B * main.v[0].nb[0] * main.v[0].nb[1] * main.v[0].nb[2]));
     int nblk = 0;
     for (int a = 0; a < 3; ++a) {
         if (!slab[a]) continue;
@@ -194,5 +211,5 @@ static inline void brick_plan(const Conv3Geom& g, bool zero_pad, bool allow_thin
         nblk += (int)((int64_t)g.B * v.nb[0] * v.nb[1] * v.nb[2]);
         ++thin.n;
     }
-    thin.start[thin.n] = nblk;
+    brick_close(thin, nblk);
 }

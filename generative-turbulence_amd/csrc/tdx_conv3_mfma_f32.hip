@@ -1,4 +1,4 @@
-// fp32 MFMA implicit-GEMM 3x3x3 convolution (forward and, zero-padded on the padded grid, the data
+// fp32 MFMA implicit-GEMM 3x3x3 convolution (forward and, zero-padded, the main term of the data
 // gradient) for the fp32 parity mode.  gfx950, v_mfma_f32_32x32x2_f32 (256 FLOP/clk/CU: the same peak as
 // the packed-FMA vector ALU, but fed from an LDS halo brick with 27-fold reuse instead of a tile that is
 // re-fetched for every tap).
@@ -12,26 +12,18 @@
 // per operand and tap and feeds its four floats to four MFMAs (lanes 0-31 carry k = 0, lanes 32-63
 // k = 1 of each 32x32x2 step: channel 4*(lane >> 5) + j for the j-th MFMA, on both operands).
 // The MFMA is issued transposed (weights as A), so a lane owns one voxel and 4 consecutive channels per
-// accumulator quad: 16-B writes into an LDS output tile, then full-row coalesced stores.
+// accumulator quad: 16-B writes into an LDS output tile, then full-row coalesced stores (conv3_epilogue_f32,
+// tdx_conv3_epilogue.h).
 // Products and sums are IEEE fp32 (no reduced-precision operands): the 1e-4 parity gate holds as with
 // the vector-ALU kernels; only the summation order differs.
 #include "tdx_common.h"
 #include "tdx_conv3.h"
-#include "tdx_conv3_brick.h"
-#include "tdx_mfma.h"
-#include <stdlib.h>
-
+#include "tdx_conv3_epilogue.h"
 
 #define F3_KC 8
 
 bool conv3_mfma_f32_supported(int C1, int C2, int Cout) {
     return C1 > 0 && (C1 % F3_KC) == 0 && (C2 % F3_KC) == 0 && (Cout % 32) == 0;
-}
-
-// output tile rows of BN floats; 16-B chunk c of row v at c ^ swizzle(v)
-template <int BN>
-__device__ __forceinline__ int outf_addr(int v, int c) {
-    return v * (BN * 4) + ((c ^ (v & (BN / 4 - 1))) << 4);
 }
 
 template <int NT, bool ZERO_PAD, int SHAPE, bool PERM>
@@ -57,7 +49,7 @@ conv3_mfma_f32_kernel(const float* __restrict__ x1, int C1, const float* __restr
     const int r = lane & 31, hh = lane >> 5;
 
     int b, o[3];
-    const BrickView g = brick_decode<SHAPE>(R, xcd_contiguous((int)blockIdx.x, (int)gridDim.x), b, o);
+    const BrickView& g = brick_decode<SHAPE>(R, xcd_contiguous((int)blockIdx.x, (int)gridDim.x), b, o);
     const int n0 = blockIdx.y * BN;
     const int Cin = C1 + C2;
 
@@ -170,140 +162,35 @@ conv3_mfma_f32_kernel(const float* __restrict__ x1, int C1, const float* __restr
         }
     }
 
-    // epilogue: lane (r, hh) holds voxel (wave, 4 mt + (r & 3), r >> 2) and channels nt*32 + 8 j + 4 hh + (0..3)
-    __syncthreads();
-    unsigned char* sO = smem;  // [256 voxels][BN] fp32
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ch = nt * 32 + 8 * j + 4 * hh;
-            float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (bias) bv = *reinterpret_cast<const float4*>(bias + n0 + ch);
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                int lx, ly, lz;
-                BR::lane_voxel(wave, mt, r, lx, ly, lz);
-                const int v = BR::tile_index(lx, ly, lz);
-                *reinterpret_cast<float4*>(sO + outf_addr<BN>(v, ch >> 2)) =
-                    make_float4(acc[nt][mt][4 * j] + bv.x, acc[nt][mt][4 * j + 1] + bv.y, acc[nt][mt][4 * j + 2] + bv.z,
-                                acc[nt][mt][4 * j + 3] + bv.w);
-            }
-        }
-    __syncthreads();
-    constexpr int CHUNKS = BN / 4;
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};  // GroupNorm moments of this thread's 4 channels  // 16-B chunks per voxel row
-#pragma unroll
-    for (int i = 0; i < CHUNKS * (BR::NVOX / 256); ++i) {
-        const int p = tid + i * 256;
-        const int v = p / CHUNKS, cidx = p % CHUNKS;
-        int lx, ly, lz, c[3];
-        BR::tile_voxel(v, lx, ly, lz);
-        if (brick_out_coords<PERM>(g, o, lx, ly, lz, c)) {
-            const int c0 = c[0], c1 = c[1], c2 = c[2];
-            const int64_t ov = (((int64_t)b * g.Eo[0] + c0) * g.Eo[1] + c1) * g.Eo[2] + c2;
-            float4 val = *reinterpret_cast<const float4*>(sO + outf_addr<BN>(v, cidx));
-            bool direct = false;
-            if (ZERO_PAD && d1 != nullptr) {
-                // data gradient: padded position = original voxel + 1.  Positions inside the original grid go
-                // straight to dx (split over the two inputs of a concatenated conv, plus the optional addend);
-                // only the halo shell is written to the padded workspace for the face fix-up
-                const int u0 = c0 + g.off, u1 = c1 + g.off, u2 = c2 + g.off;
-                if (u0 >= 0 && u0 < g.Ei[0] && u1 >= 0 && u1 < g.Ei[1] && u2 >= 0 && u2 < g.Ei[2]) {
-                    const int64_t u = (((int64_t)b * g.Ei[0] + u0) * g.Ei[1] + u1) * g.Ei[2] + u2;
-                    const int n = n0 + cidx * 4;
-                    const bool lo = n < D1;
-                    float* dst = lo ? d1 + u * D1 + n : d2 + u * (Cout - D1) + (n - D1);
-                    const float* asrc = lo ? (a1 ? a1 + u * D1 + n : nullptr) : (a2 ? a2 + u * (Cout - D1) + (n - D1) : nullptr);
-                    if (asrc) {
-                        const float4 av = *reinterpret_cast<const float4*>(asrc);
-                        val.x += av.x; val.y += av.y; val.z += av.z; val.w += av.w;
-                    }
-                    *reinterpret_cast<float4*>(dst) = val;
-                    direct = true;
-                }
-            }
-            if (!direct) *reinterpret_cast<float4*>(y + ov * Cout + n0 + cidx * 4) = val;
-            if (gn_acc != nullptr) {
-                s1[0] += val.x; s2[0] += val.x * val.x; s1[1] += val.y; s2[1] += val.y * val.y;
-                s1[2] += val.z; s2[2] += val.z * val.z; s1[3] += val.w; s2[3] += val.w * val.w;
-            }
-        }
-    }
-    if (gn_acc != nullptr) {
-        // per-channel moments of the tile (tdx_conv3_fwd_gn): threads with equal tid % CHUNKS hold the same 4
-        // channels; LDS reduce behind the output tile, then one f64 atomic per channel and moment into one of
-        // TDX_GN_REPLICAS tables (as the bf16 kernel)
-        constexpr int NP = 256 / CHUNKS;
-        float* red = reinterpret_cast<float*>(smem + BR::NVOX * BN * 4);  // [NP][BN][2]
-        const int cidx = tid % CHUNKS, part = tid / CHUNKS;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            red[(part * BN + cidx * 4 + e) * 2] = s1[e];
-            red[(part * BN + cidx * 4 + e) * 2 + 1] = s2[e];
-        }
-        __syncthreads();
-        if (tid < BN * 2) {
-            float t = 0.f;
-#pragma unroll 8
-            for (int pp = 0; pp < NP; ++pp) t += red[pp * BN * 2 + tid];
-            const int rep = blockIdx.x & (TDX_GN_REPLICAS - 1);
-            atomicAdd(&gn_acc[(((size_t)rep * g.B + b) * Cout + n0) * 2 + tid], (double)t);
-        }
-    }
+    conv3_epilogue_f32<NT, ZERO_PAD, SHAPE, PERM>(acc, smem, g, o, b, n0, bias, y, Cout, gn_acc, d1, D1, d2, a1, a2);
+}
+
+template <int NT, bool ZP, int SHAPE, bool PERM>
+static int f32_go(const Conv3Call& c, const BrickRegions& reg) {
+    constexpr int BN = NT * 32;
+    size_t lds = (size_t)2 * (Brick<SHAPE>::ENTRIES * 16 + 64) + (size_t)2 * (27 * BN * 16 + 64);
+    const size_t tile = (size_t)Brick<SHAPE>::NVOX * BN * 4 + 8192;  // epilogue: output tile + moment reduction
+    if (tile > lds) lds = tile;
+    if (!brick_closed(reg)) return TDX_EINVAL;
+    return tdx_launch_lds<conv3_mfma_f32_kernel<NT, ZP, SHAPE, PERM>>(
+        dim3((unsigned)reg.start[reg.n], c.N / BN), dim3(256), lds, c.st, (const float*)c.x1, c.C1, (const float*)c.x2, c.C2,
+        (const float*)c.wp, c.bias, (float*)c.y, reg, c.N, c.gn_acc, (float*)c.d1, c.D1, (float*)c.d2, (const float*)c.a1,
+        (const float*)c.a2);
 }
 
 int conv3_mfma_f32_launch(const Conv3Call& c) {
-    if (c.fmt != TDX_F32) return TDX_EINVAL;
+    if (c.fmt != TDX_F32 || (c.zero_pad && c.d1 == nullptr)) return TDX_EINVAL;
     const Conv3Geom g = c.geom();
-    const bool zero_pad = c.zero_pad;
-    const int Cout = c.N;
     if ((int64_t)g.Xi * g.Yi * g.Zi * 2 >= (1ll << 31) || (int64_t)g.Xo * g.Yo * g.Zo >= (1ll << 31)) return TDX_ESHAPE;
-    static const bool no_thin = getenv("TDX_CONV3_THIN") && atoi(getenv("TDX_CONV3_THIN")) == 0;  // A/B switch
-    const int NT = (Cout % 64 == 0) ? 2 : 1;
-    // (8 x 8 x 8 bricks with four M tiles per wave, which pay in the split kernel, measured 25-35 % SLOWER here: this
-    // kernel is MFMA-bound with two workgroups per CU already)
-    const bool big = false;
+    // 4 x 8 x 8 bricks only (8 x 8 x 8 bricks with four M tiles per wave, which pay in the split kernel, measured 25-35 %
+    // SLOWER here: this kernel is MFMA-bound with two workgroups per CU already)
     BrickRegions main, thin;
-    brick_plan(g, zero_pad, !no_thin, main, thin, big ? BRICK_BIG : BRICK_MAIN);
-#define F3_GO(NTV, ZP, TH, PM, REG)                                                                                     \
-    do {                                                                                                                \
-        constexpr int BNV = NTV * 32;                                                                                   \
-        size_t lds = (size_t)2 * (Brick<TH>::ENTRIES * 16 + 64) + (size_t)2 * (27 * BNV * 16 + 64);                     \
-        const size_t tile = (size_t)Brick<TH>::NVOX * BNV * 4 + 8192; /* epilogue: output tile + moment reduction */    \
-        if (tile > lds) lds = tile;                                                                                     \
-        auto kern = conv3_mfma_f32_kernel<NTV, ZP, TH, PM>;                                                             \
-        static bool attr_set = false;                                                                                   \
-        if (!attr_set) {                                                                                                \
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) return (int)e;                                                                         \
-            attr_set = true;                                                                                            \
-        }                                                                                                               \
-        dim3 grid((unsigned)(REG).start[(REG).n], Cout / BNV);                                                          \
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, c.st, (const float*)c.x1, c.C1, (const float*)c.x2, c.C2,        \
-                           (const float*)c.wp, c.bias, (float*)c.y, REG, Cout, c.gn_acc, (float*)c.d1, c.D1,            \
-                           (float*)c.d2, (const float*)c.a1, (const float*)c.a2);                                       \
-    } while (0)
-    const bool perm = main.v[0].perm[0] != 0;
-    if (NT == 2) {
-        if (zero_pad && perm) F3_GO(2, true, BRICK_MAIN, true, main);
-        else if (zero_pad) F3_GO(2, true, BRICK_MAIN, false, main);
-        else if (perm) F3_GO(2, false, BRICK_MAIN, true, main);
-        else F3_GO(2, false, BRICK_MAIN, false, main);
-    } else if (big) {
-        if (zero_pad && perm) F3_GO(1, true, BRICK_BIG, true, main);
-        else if (zero_pad) F3_GO(1, true, BRICK_BIG, false, main);
-        else if (perm) F3_GO(1, false, BRICK_BIG, true, main);
-        else F3_GO(1, false, BRICK_BIG, false, main);
-    } else {
-        if (zero_pad && perm) F3_GO(1, true, BRICK_MAIN, true, main);
-        else if (zero_pad) F3_GO(1, true, BRICK_MAIN, false, main);
-        else if (perm) F3_GO(1, false, BRICK_MAIN, true, main);
-        else F3_GO(1, false, BRICK_MAIN, false, main);
-    }
-    if (thin.n > 0) {  // remainder slabs of the padded grid: 2 x 16 x 8 bricks
-        if (NT == 2) F3_GO(2, true, BRICK_THIN, true, thin); else F3_GO(1, true, BRICK_THIN, true, thin);
-    }
-#undef F3_GO
-    return tdx_launch_status();
+    brick_plan(g, c.zero_pad, conv3_thin_slabs() != 0, main, thin);
+    int rc = TDX_OK;
+    TDX_DISPATCH_BOOL(c.N % 64 == 0, WIDE, TDX_DISPATCH_BOOL(c.zero_pad, ZP, TDX_DISPATCH_BOOL(main.v[0].perm[0] != 0, PM,
+        rc = f32_go<WIDE ? 2 : 1, ZP, BRICK_MAIN, PM>(c, main))));
+    if (rc != TDX_OK || thin.n == 0) return rc;
+    // remainder slabs of the data gradient on big grids: 2 x 16 x 8 bricks
+    TDX_DISPATCH_BOOL(c.N % 64 == 0, WIDE, rc = f32_go<WIDE ? 2 : 1, true, BRICK_THIN, true>(c, thin));
+    return rc;
 }

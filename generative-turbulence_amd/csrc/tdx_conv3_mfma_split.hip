@@ -1,5 +1,5 @@
-// Split-precision ("bf16x2") MFMA 3x3x3 convolution for fp32 tensors: forward and, zero-padded on the
-// padded grid, the data gradient.  gfx950.
+// Split-precision ("bf16x2") MFMA 3x3x3 convolution for fp32 tensors: forward and, zero-padded, the main
+// term of the data gradient.  gfx950.
 //
 // Every fp32 operand is split into two bf16 terms, v = hi + lo with hi = bf16(v), lo = bf16(v - hi)
 // (16 significant bits together), and the product is formed from three bf16 MFMAs with fp32 accumulation,
@@ -48,16 +48,15 @@ int conv3_mfma_split_go_1rmn(SPLIT_GO_ARGS);
 int conv3_mfma_split_go_1ztp(SPLIT_GO_ARGS);
 
 int conv3_mfma_split_launch(const Conv3Call& c) {
-    if (c.fmt != TDX_F32_SPLIT) return TDX_EINVAL;
+    if (c.fmt != TDX_F32_SPLIT || (c.zero_pad && c.d1 == nullptr)) return TDX_EINVAL;
     const Conv3Geom g = c.geom();
     const bool zero_pad = c.zero_pad;
     if ((int64_t)g.Xi * g.Yi * g.Zi * 2 >= (1ll << 31) || (int64_t)g.Xo * g.Yo * g.Zo >= (1ll << 31)) return TDX_ESHAPE;
-    static const bool no_thin = getenv("TDX_CONV3_THIN") && atoi(getenv("TDX_CONV3_THIN")) == 0;  // A/B switch
     const int NT = (c.N % 64 == 0) ? 2 : 1;
     // 32-wide output tiles: 8 x 8 x 8 bricks (four M tiles per wave) where the grid is large enough to fill the chip
     const bool big = NT == 1 && (int64_t)g.B * ceil_div(g.Xo, 8) * ceil_div(g.Yo, 8) * ceil_div(g.Zo, 8) >= 1024;
     BrickRegions main, thin;
-    brick_plan(g, zero_pad, !no_thin, main, thin, big ? BRICK_BIG : BRICK_MAIN);
+    brick_plan(g, zero_pad, conv3_thin_slabs() != 0, main, thin, big ? BRICK_BIG : BRICK_MAIN);
     const bool perm = main.v[0].perm[0] != 0;  // forward on ragged grids: the short brick edge on another axis
     // instantiation <tiles><z: zero-padded, r: replicate><b: big, m: main bricks><p: permuted, n: not>
 #define SP_GO(T, S) (zero_pad ? (perm ? conv3_mfma_split_go_##T##z##S##p(c, main) : conv3_mfma_split_go_##T##z##S##n(c, main)) \
@@ -65,6 +64,6 @@ int conv3_mfma_split_launch(const Conv3Call& c) {
     const int rc = NT == 2 ? SP_GO(2, m) : (big ? SP_GO(1, b) : SP_GO(1, m));
 #undef SP_GO
     if (rc != TDX_OK) return rc;
-    // remainder slabs of the padded grid: 2 x 16 x 8 bricks, 32-wide tiles
+    // remainder slabs of the data gradient on big grids: 2 x 16 x 8 bricks, 32-wide tiles
     return thin.n > 0 ? conv3_mfma_split_go_1ztp(c, thin) : TDX_OK;
 }

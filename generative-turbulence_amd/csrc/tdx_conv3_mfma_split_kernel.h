@@ -5,16 +5,9 @@
 #pragma once
 #include "tdx_common.h"
 #include "tdx_conv3.h"
-#include "tdx_conv3_brick.h"
-#include "tdx_mfma.h"
-#include <stdlib.h>
+#include "tdx_conv3_epilogue.h"
 
 #define SP_KC 16
-
-template <int BN>
-__device__ __forceinline__ int outs_addr(int v, int c) {
-    return v * (BN * 4) + ((c ^ (v & (BN / 4 - 1))) << 4);
-}
 
 // LDS image of one 8-channel slice: activations [part = hi, lo][halo voxel, z stride 12][8 ch] (16-B entries), weights
 // [part][tap pair j = 0..13][n][tap 2 j, 2 j + 1][8 ch]: an MFMA K step of 16 = 8 channels x 2 taps, lanes 0-31 hold tap 2 j
@@ -63,6 +56,8 @@ conv3_mfma_split_kernel(const float* __restrict__ x1, int C1, const float* __res
     const int r = lane & 31, hh = lane >> 5;
 
     int b, o[3];
+    // (a copy of the view: left in the kernel-argument segment as in the other two brick kernels, the permuted instantiations,
+    // which read the tap strides in every slice, run out of SGPRs and spill them to VGPR lanes)
     const BrickView g = brick_decode<SHAPE>(R, xcd_contiguous((int)blockIdx.x, (int)gridDim.x), b, o);
     const int n0 = blockIdx.y * BN;
     const int Cin = C1 + C2;
@@ -223,107 +218,19 @@ conv3_mfma_split_kernel(const float* __restrict__ x1, int C1, const float* __res
         }
     }
 
-    // ---- epilogue: as the fp32 kernel (lane (r, hh): voxel (wave, 4 mt + (r & 3), r >> 2), channels nt*32 + 8 j + 4 hh + 0..3)
-    __syncthreads();
-    unsigned char* sO = smem;  // [NVOX voxels][BN] fp32
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ch = nt * 32 + 8 * j + 4 * hh;
-            float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (bias) bv = *reinterpret_cast<const float4*>(bias + n0 + ch);
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                int lx, ly, lz;
-                BR::lane_voxel(wave, mt, r, lx, ly, lz);
-                const int v = BR::tile_index(lx, ly, lz);
-                *reinterpret_cast<float4*>(sO + outs_addr<BN>(v, ch >> 2)) =
-                    make_float4(acc[nt][mt][4 * j] + bv.x, acc[nt][mt][4 * j + 1] + bv.y, acc[nt][mt][4 * j + 2] + bv.z,
-                                acc[nt][mt][4 * j + 3] + bv.w);
-            }
-        }
-    __syncthreads();
-    constexpr int CHUNKS = BN / 4;
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};  // GroupNorm moments of this thread's 4 channels
-#pragma unroll
-    for (int i = 0; i < CHUNKS * (BR::NVOX / 256); ++i) {
-        const int p = tid + i * 256;
-        const int v = p / CHUNKS, cidx = p % CHUNKS;
-        int lx, ly, lz, c[3];
-        BR::tile_voxel(v, lx, ly, lz);
-        if (brick_out_coords<PERM>(g, o, lx, ly, lz, c)) {
-            const int c0 = c[0], c1 = c[1], c2 = c[2];
-            const int64_t ov = (((int64_t)b * g.Eo[0] + c0) * g.Eo[1] + c1) * g.Eo[2] + c2;
-            float4 val = *reinterpret_cast<const float4*>(sO + outs_addr<BN>(v, cidx));
-            bool direct = false;
-            if (ZERO_PAD && d1 != nullptr) {
-                // data gradient: padded position = original voxel + 1.  Positions inside the original grid go
-                // straight to dx (split over the two inputs of a concatenated conv, plus the optional addend);
-                // only the halo shell is written to the padded workspace for the face fix-up
-                const int u0 = c0 + g.off, u1 = c1 + g.off, u2 = c2 + g.off;
-                if (u0 >= 0 && u0 < g.Ei[0] && u1 >= 0 && u1 < g.Ei[1] && u2 >= 0 && u2 < g.Ei[2]) {
-                    const int64_t u = (((int64_t)b * g.Ei[0] + u0) * g.Ei[1] + u1) * g.Ei[2] + u2;
-                    const int n = n0 + cidx * 4;
-                    const bool lo = n < D1;
-                    float* dst = lo ? d1 + u * D1 + n : d2 + u * (Cout - D1) + (n - D1);
-                    const float* asrc = lo ? (a1 ? a1 + u * D1 + n : nullptr) : (a2 ? a2 + u * (Cout - D1) + (n - D1) : nullptr);
-                    if (asrc) {
-                        const float4 av = *reinterpret_cast<const float4*>(asrc);
-                        val.x += av.x; val.y += av.y; val.z += av.z; val.w += av.w;
-                    }
-                    *reinterpret_cast<float4*>(dst) = val;
-                    direct = true;
-                }
-            }
-            if (!direct) *reinterpret_cast<float4*>(y + ov * Cout + n0 + cidx * 4) = val;
-            if (gn_acc != nullptr) {
-                s1[0] += val.x; s2[0] += val.x * val.x; s1[1] += val.y; s2[1] += val.y * val.y;
-                s1[2] += val.z; s2[2] += val.z * val.z; s1[3] += val.w; s2[3] += val.w * val.w;
-            }
-        }
-    }
-    if (gn_acc != nullptr) {
-        // per-channel moments of the tile (tdx_conv3_fwd_gn): threads with equal tid % CHUNKS hold the same 4
-        // channels; LDS reduce behind the output tile, then one f64 atomic per channel and moment into one of
-        // TDX_GN_REPLICAS tables (as the bf16 kernel)
-        constexpr int NP = 256 / CHUNKS;
-        float* red = reinterpret_cast<float*>(smem + BR::NVOX * BN * 4);  // [NP][BN][2]
-        const int cidx = tid % CHUNKS, part = tid / CHUNKS;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            red[(part * BN + cidx * 4 + e) * 2] = s1[e];
-            red[(part * BN + cidx * 4 + e) * 2 + 1] = s2[e];
-        }
-        __syncthreads();
-        if (tid < BN * 2) {
-            float t = 0.f;
-#pragma unroll 8
-            for (int pp = 0; pp < NP; ++pp) t += red[pp * BN * 2 + tid];
-            const int rep = blockIdx.x & (TDX_GN_REPLICAS - 1);
-            atomicAdd(&gn_acc[(((size_t)rep * g.B + b) * Cout + n0) * 2 + tid], (double)t);
-        }
-    }
+    conv3_epilogue_f32<NT, ZERO_PAD, SHAPE, PERM>(acc, smem, g, o, b, n0, bias, y, Cout, gn_acc, d1, D1, d2, a1, a2);
 }
 
 #define SPLIT_GO_ARGS const Conv3Call& c, const BrickRegions& reg
 template <int NTV, bool ZP, int TH, bool PM>
 static int split_go(SPLIT_GO_ARGS) {
     constexpr int BNV = NTV * 32;
-    const size_t lds = SplitLds<TH, BNV>::BYTES;
-    auto kern = conv3_mfma_split_kernel<NTV, ZP, TH, PM>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    dim3 grid((unsigned)reg.start[reg.n], c.N / BNV);
     const int64_t lo_offset = (int64_t)27 * (c.C1 + c.C2) * c.N;  // elements between the hi and the lo weight image
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, c.st, (const float*)c.x1, c.C1, (const float*)c.x2, c.C2, (const bf16*)c.wp, c.bias,
-                       (float*)c.y, reg, c.N, lo_offset, c.gn_acc, (float*)c.d1, c.D1, (float*)c.d2, (const float*)c.a1,
-                       (const float*)c.a2);
-    return tdx_launch_status();
+    if (!brick_closed(reg)) return TDX_EINVAL;
+    return tdx_launch_lds<conv3_mfma_split_kernel<NTV, ZP, TH, PM>>(
+        dim3((unsigned)reg.start[reg.n], c.N / BNV), dim3(256), SplitLds<TH, BNV>::BYTES, c.st, (const float*)c.x1, c.C1,
+        (const float*)c.x2, c.C2, (const bf16*)c.wp, c.bias, (float*)c.y, reg, c.N, lo_offset, c.gn_acc, (float*)c.d1, c.D1,
+        (float*)c.d2, (const float*)c.a1, (const float*)c.a2);
 }
 #define SPLIT_INSTANCE(NTV, ZP, TH, PM, NAME) \
     int NAME(SPLIT_GO_ARGS) { return split_go<NTV, ZP, TH, PM>(c, reg); }

@@ -39,8 +39,7 @@
 // remainder slabs go to the thin-brick kernel in a second launch); everything else stays on the brick kernel.
 #include "tdx_common.h"
 #include "tdx_conv3.h"
-#include "tdx_mfma.h"
-#include <stdlib.h>
+#include "tdx_conv3_epilogue.h"
 #include <algorithm>
 
 #define RG_HY 10
@@ -89,12 +88,6 @@ __device__ __forceinline__ void rg_dma_off(const void* sbase, unsigned voff, uns
 #else
 #define RG_T() do { } while (0)
 #endif
-
-template <int BN>
-__device__ __forceinline__ int rg_tile_addr(int v, int c) {  // wave-private [32 voxels][BN] bf16 tile, 16-B chunk c of row v
-    if (BN == 64) return v * 128 + ((c ^ (v & 7)) << 4);
-    return v * 64 + ((c ^ ((v >> 1) & 3)) << 4);
-}
 
 // LW = 0: the 8 computing waves issue the copies themselves (one per K step).  LW = 4: four extra LOADER waves (one more
 // wave per SIMD) issue every copy, wait for their arrival and meet the computing waves at the unit barrier; the
@@ -466,19 +459,20 @@ __global__ void __launch_bounds__(512 + 64 * LW, LW ? 3 : 2) conv3_ring_kernel(R
                     const int ch = nt * 32 + 8 * j + 4 * hh;
                     const unsigned lo2 = H::pack2(acc[nt][mt][4 * j], acc[nt][mt][4 * j + 1]);
                     const unsigned hi2 = H::pack2(acc[nt][mt][4 * j + 2], acc[nt][mt][4 * j + 3]);
-                    *reinterpret_cast<uint2*>(tile + rg_tile_addr<BN>(vw, ch >> 3) + (ch & 7) * 2) = make_uint2(lo2, hi2);
+                    *reinterpret_cast<uint2*>(tile + conv3_tile_addr16<BN>(vw, ch >> 3) + (ch & 7) * 2) = make_uint2(lo2, hi2);
                 }
 #pragma unroll
             for (int i = 0; i < 32 / VPI; ++i) {
                 const int v = lane / CH + VPI * i, cidx = lane % CH;
                 const int c0 = o0 + (Z4 ? wave * XP + mt : wave * XP + mt / 2);
                 const int c1 = o1 + (Z4 ? (v >> 2) : 4 * (mt % 2) + (v >> 3)), c2 = o2 + (Z4 ? (v & 3) : (v & 7));
-                uint4 val = *reinterpret_cast<const uint4*>(tile + rg_tile_addr<BN>(v, cidx));
+                uint4 val = *reinterpret_cast<const uint4*>(tile + conv3_tile_addr16<BN>(v, cidx));
                 const int64_t ov = (int64_t)b * V + c0 * YZ + c1 * A.Z + c2;
                 const int n = n0 + cidx * 8;
                 if (ZP) {
                     // data gradient: dx split over the two inputs of a concatenated conv, plus the gradient that
-                    // arrives over the block's residual path
+                    // arrives over the block's residual path.  (conv3_store_dx of tdx_conv3_epilogue.h written out: behind
+                    // the call the bf16 kernels split every 16-B store in two and the level-0 data gradient ran 1.2 % slower)
                     const bool lo1 = n < A.D1;
                     bf16* dst = lo1 ? A.d1 + ov * A.D1 + n : A.d2 + ov * (A.Cout - A.D1) + (n - A.D1);
                     const bf16* asrc = lo1 ? (A.a1 ? A.a1 + ov * A.D1 + n : nullptr)
@@ -590,17 +584,9 @@ static int ring_go(const RingArgs& a, hipStream_t st) {
 #ifdef RG_STAMPS
     if (NT == 1) lds += (size_t)RG_WAVES * RG_NSTAMP * 8;
 #endif
-    auto kern = conv3_ring_kernel<NT, ZP, LW, HF, Z4>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
     // one workgroup per CU on (up to) TDX_PERSISTENT_CUS CUs, the same number on every XCD, a multiple of the N tiles
     const int px = tdx_persistent_cus() / 8, grid = 8 * (px - px % a.ntn);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512 + 64 * LW), lds, st, a);
-    return tdx_launch_status();
+    return tdx_launch_lds<conv3_ring_kernel<NT, ZP, LW, HF, Z4>>(dim3(grid), dim3(512 + 64 * LW), lds, st, a);
 }
 
 // forward (zero_pad = false: y, bias, gn_acc) or main term of the data gradient (zero_pad = true: d1 / d2 / a1 / a2) with
@@ -627,22 +613,16 @@ int conv3_ring_launch(const Conv3Call& c, int depth) {
 #endif
     const char* env = getenv("TDX_RING_LOADERS");  // A/B switch: 0 = the computing waves issue the copies themselves
     const bool lw = env ? atoi(env) != 0 : RG_DEFAULT_LOADERS;
-    int rc;
-    if (depth == 4) {  // 4-deep bricks: the loader-wave form only
-#define RG_Z4(NTV) (hf ? (zero_pad ? ring_go<NTV, true, 4, true, true>(a, st) : ring_go<NTV, false, 4, true, true>(a, st)) \
-                       : (zero_pad ? ring_go<NTV, true, 4, false, true>(a, st) : ring_go<NTV, false, 4, false, true>(a, st)))
-        rc = NT == 2 ? RG_Z4(2) : RG_Z4(1);
-#undef RG_Z4
-    } else if (hf) {  // fp16 operands: the loader-wave form only (the loader-less form is an A/B build of the bf16 kernels)
-        if (NT == 2) rc = zero_pad ? ring_go<2, true, 4, true>(a, st) : ring_go<2, false, 4, true>(a, st);
-        else rc = zero_pad ? ring_go<1, true, 4, true>(a, st) : ring_go<1, false, 4, true>(a, st);
-    } else if (NT == 2) {
-        if (lw) rc = zero_pad ? ring_go<2, true, 4, false>(a, st) : ring_go<2, false, 4, false>(a, st);
-        else rc = zero_pad ? ring_go<2, true, 0, false>(a, st) : ring_go<2, false, 0, false>(a, st);
-    } else {
-        if (lw) rc = zero_pad ? ring_go<1, true, 4, false>(a, st) : ring_go<1, false, 4, false>(a, st);
-        else rc = zero_pad ? ring_go<1, true, 0, false>(a, st) : ring_go<1, false, 0, false>(a, st);
-    }
+    // 4-deep bricks and fp16 operands: the loader-wave form only (the loader-less form is an A/B build of the bf16 kernels)
+    int rc = TDX_OK;
+    if (depth == 4)
+        TDX_DISPATCH_BOOL(NT == 2, WIDE, TDX_DISPATCH_BOOL(zero_pad, ZP, TDX_DISPATCH_H16(hf,
+            rc = ring_go<WIDE ? 2 : 1, ZP, 4, HF, true>(a, st))));
+    else if (hf || lw)
+        TDX_DISPATCH_BOOL(NT == 2, WIDE, TDX_DISPATCH_BOOL(zero_pad, ZP, TDX_DISPATCH_H16(hf,
+            rc = ring_go<WIDE ? 2 : 1, ZP, 4, HF>(a, st))));
+    else
+        TDX_DISPATCH_BOOL(NT == 2, WIDE, TDX_DISPATCH_BOOL(zero_pad, ZP, rc = ring_go<WIDE ? 2 : 1, ZP, 0, false>(a, st)));
     if (rc != TDX_OK || ((X % bxr) == 0 && (Y % 8) == 0 && (Z % depth) == 0)) return rc;
     // the 1-2 voxel remainder slabs beyond the whole bricks: thin 2 x 16 x 8 bricks, all slabs in one launch (same
     // operands, same epilogue incl. the statistics accumulators and the data gradient's split / addends)

@@ -631,3 +631,11 @@ def test_kernel_asm_diff_ignores_only_the_function_ordinal_of_local_labels():
     assert kad.kernels(asm(3, 2), []) == kad.kernels(asm(17, 2), [])
     assert ".LBB0_2" in kad.kernels(asm(17, 2), [])["k"][0] and ".Lfunc_end0-k" in kad.kernels(asm(17, 2), [])["k"][0]
     assert kad.kernels(asm(3, 2), []) != kad.kernels(asm(3, 1), [])  # another branch target is another kernel
+
+    # the loop-nest comments name the function too, and the comment column of a label line moves with the ordinal's digits
+    def loop(f):
+        label = f".LBB{f}_3:"
+        return (f"k:\n{label}{' ' * (40 - len(label))}; =>This Loop Header: Depth=1\n\t\t\t; Child Loop BB{f}_4 Depth 2\n\ts_endpgm\n"
+                f".Lfunc_end{f}:\n\t.size\tk, .Lfunc_end{f}-k\n\t.amdhsa_kernel k\n\t.end_amdhsa_kernel\n")
+
+    assert kad.kernels(loop(9), []) == kad.kernels(loop(10), [])

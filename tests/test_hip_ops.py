@@ -775,10 +775,10 @@ def test_attention_config5_rows_vs_oracle_fp16():
 
 @pytest.mark.parametrize("grid", [(18, 10, 10), (10, 18, 9), (9, 10, 18), (14, 18, 18), (6, 9, 10)])
 def test_conv3_thin_slab_bricks(grid, monkeypatch):
-    """grids with a 1-2 voxel remainder per axis (the reference's real 194x50x50 family and every
-    padded data-gradient grid) are tiled with thin 2x16x8 bricks on permuted axes: same numbers
-    as the all-main-brick tiling (TDX_CONV3_THIN=0 is read once per process, so compare with the
-    vector-ALU kernels instead) and as the oracle."""
+    """grids with a 1-2 voxel remainder per axis (the reference's real 194x50x50 family) are tiled
+    with thin 2x16x8 bricks on permuted axes on big grids: same numbers as the vector-ALU kernels,
+    which know no bricks, and as the oracle.  (TDX_CONV3_THIN is read per call: 0 = all-main-brick
+    tiling, 2 = thin slabs on grids of any size.)"""
     from turbdiff_amd import ops
 
     X, Y, Z = grid

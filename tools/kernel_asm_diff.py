@@ -38,10 +38,11 @@ def compile_one(hipcc, flags, src, out):
 def kernels(asm_text, renames):
     """{kernel name: (body, descriptor)} of one assembly file."""
     text = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", asm_text)
-    # local labels carry the function's ordinal in its file (.LBB<f>_<n>, BB<f>_<n> in comments, .Lfunc_end<f>): it moves when a kernel in front
+    # local labels carry the function's ordinal in its file (.LBB<f>_<n>, BB<f>_<n> in comments -- branch targets and loop nests --, .Lfunc_end<f>): it moves when a kernel in front
     # of this one is added, lost or turned into a template, and says nothing about this one
-    text = re.sub(r"(\.L|=)BB\d+_(\d+)", r"\1BB0_\2", text)
+    text = re.sub(r"(\.L|=|Loop )BB\d+_(\d+)", r"\1BB0_\2", text)
     text = re.sub(r"\.Lfunc_end\d+", ".Lfunc_end0", text)
+    text = re.sub(r"^(\.LBB0_\d+:)[ \t]+;", r"\1 ;", text, flags=re.M)  # the comment column depends on the ordinal's digits
     for old, new in renames:
         text = text.replace(old, new)
     out = {}
