@@ -1,4 +1,4 @@
-// GroupNorm (+ FiLM + SiLU + residual) forward / backward on NDHWC activations.
+// GroupNorm (+ FiLM + activation + residual) forward / backward on NDHWC activations.
 //
 // HBM-bound: every pass streams the activation once with 8 channels (16 B bf16 / 32 B f32)
 // per lane.  A thread always owns the same 8-channel vector (tid % (C/8)), so per-channel
@@ -12,6 +12,7 @@
 //   backward: reduce pass (P = sum dn, Q = sum dn*xhat per channel; per-block partial sums, no
 //             atomics, deterministic) -> finalize -> apply pass
 #define TDX_NT_LOADS 1  // activations are streamed once per pass: nontemporal 16-B loads (+0.4 % step)
+#include "tdx_act.h"         // Act<ACT>: the activation family (TDX_ACT_*)
 #include "tdx_codec_elem.h"  // the encoder lane and the decoder dot of the two fused tails
 #include "tdx_conv3.h"
 
@@ -335,11 +336,9 @@ __device__ __forceinline__ void gn_stream(const GnLane& p, const T* const* in, i
                                  [&](const Vec8<T>(&a)[NIN], None, int64_t v) { body(a, v); });
 }
 
-// silu(n) + r as ONE explicit fma: the three tail kernels (apply / apply_encoded / apply_decode) promise bit-identical
-// results, which must not hinge on the compiler contracting n * sigmoid(n) + r the same way in each
-__device__ __forceinline__ float silu_add(float n, float r) { return __builtin_fmaf(n, sigmoid_f(n), r); }
-
-template <typename T, bool HAS_RES, bool ACT>
+// The three tail kernels (apply / apply_encoded / apply_decode) promise bit-identical results for every activation: all
+// three form n with the same explicit fma and add the skip through Act<ACT>::f_add (tdx_act.h)
+template <typename T, bool HAS_RES, int ACT>
 __global__ void __launch_bounds__(GN_THREADS)
 gn_apply_kernel(const T* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
                 const float* __restrict__ beta, const float* __restrict__ scale, const float* __restrict__ shift,
@@ -354,11 +353,7 @@ gn_apply_kernel(const T* __restrict__ x, const float* __restrict__ stats, const 
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float n = __builtin_fmaf(a[0].v[j], k.a[j], k.c0[j]);
-            if (ACT && HAS_RES) o.v[j] = silu_add(n, rr.v[j]);
-            else {
-                o.v[j] = ACT ? silu_f(n) : n;
-                if (HAS_RES) o.v[j] += rr.v[j];
-            }
+            o.v[j] = HAS_RES ? Act<ACT>::f_add(n, rr.v[j]) : Act<ACT>::f(n);
         }
         o.store(y + p.base + v * C);
     });
@@ -369,20 +364,21 @@ extern "C" int tdx_gn_apply(const void* x, const float* stats, const float* gamm
                             int G, int act, int dtype, void* stream) {
     TDX_CHECK_ARG(x && stats && gamma && beta && y && B > 0 && V > 0);
     TDX_CHECK_ARG((scale == nullptr) == (shift == nullptr));
+    TDX_CHECK_ARG(act >= 0 && act < TDX_ACT_COUNT);
     if (!gn_shape_ok(C, G)) return TDX_ESHAPE;
     dim3 grid(gn_blocks_per_sample(B, V, C), B);
-    TDX_DISPATCH_BOOL(res != nullptr, R, TDX_DISPATCH_BOOL(act, A, TDX_DISPATCH_DTYPE(dtype,
+    TDX_DISPATCH_BOOL(res != nullptr, R, TDX_DISPATCH_ACT(act, A, TDX_DISPATCH_DTYPE(dtype,
         hipLaunchKernelGGL((gn_apply_kernel<T, R, A>), grid, dim3(GN_THREADS), 0, as_stream(stream), (const T*)x, stats, gamma,
                            beta, scale, shift, (const T*)res, (T*)y, V, C, G))));
     return tdx_launch_status();
 }
 
-// ---- y = silu(GN(x)) + encode(raw): the tail of the U-Net's FIRST block, whose identity skip is the encoder output
+// ---- y = act(GN(x)) + encode(raw): the tail of the U-Net's FIRST block, whose identity skip is the encoder output
 // cat(Wx x_raw + bx, Wc c_raw + bc) (ddpm.py:495-501).  The skip is recomputed here from the 4 + 4 raw f32 planes instead
 // of being written by tdx_encode_fwd and read back: per voxel 2 x (C x 2 B) of HBM traffic become 8 x 4 B.  The skip value
 // is the encoder's own element (tdx_codec_elem.h) rounded to T before the add, exactly what a stored encoder output would
-// have held, so the result is bit-identical to tdx_encode_fwd + tdx_gn_apply(res = that tensor).
-template <typename T, int F>
+// have held, so the result is bit-identical to tdx_encode_fwd + tdx_gn_apply(res = that tensor, act), for every activation.
+template <typename T, int F, int ACT>
 __global__ void __launch_bounds__(GN_THREADS)
 gn_apply_encoded_kernel(const T* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
                         const float* __restrict__ beta, const float* __restrict__ xr, const float* __restrict__ wx,
@@ -400,33 +396,42 @@ gn_apply_encoded_kernel(const T* __restrict__ x, const float* __restrict__ stats
         for (int j = 0; j < 8; ++j) {
             const float e = enc.eval(j, raw);
             const float n = __builtin_fmaf(a[0].v[j], k.a[j], k.c0[j]);
-            o.v[j] = silu_add(n, round_as<T>(e));
+            o.v[j] = Act<ACT>::f_add(n, round_as<T>(e));
         }
         o.store(y + p.base + v * C);
     });
+}
+
+extern "C" int tdx_gn_apply_encoded_act(const void* x, const float* stats, const float* gamma, const float* beta,
+                                        const float* x_raw, int Fx, const float* wx, const float* bx, const float* c_raw,
+                                        int Fc, const float* wc, const float* bc, void* y, int B, int64_t V, int D, int G,
+                                        int dtype, int act, void* stream) {
+    TDX_CHECK_ARG(x && stats && gamma && beta && x_raw && wx && bx && y && B > 0 && V > 0 && D > 0);
+    TDX_CHECK_ARG(c_raw == nullptr || (wc && bc));
+    TDX_CHECK_ARG(act >= 0 && act < TDX_ACT_COUNT);
+    const int C = c_raw ? 2 * D : D;
+    if (!gn_shape_ok(C, G) || (D % 8) || Fx != 4 || (c_raw && Fc != 4)) return TDX_ESHAPE;
+    dim3 grid(gn_blocks_per_sample(B, V, C), B);
+    TDX_DISPATCH_ACT(act, A, TDX_DISPATCH_DTYPE(dtype,
+        hipLaunchKernelGGL((gn_apply_encoded_kernel<T, 4, A>), grid, dim3(GN_THREADS), 0, as_stream(stream), (const T*)x, stats,
+                           gamma, beta, x_raw, wx, bx, c_raw, wc, bc, (T*)y, V, C, D, G)));
+    return tdx_launch_status();
 }
 
 extern "C" int tdx_gn_apply_encoded(const void* x, const float* stats, const float* gamma, const float* beta,
                                     const float* x_raw, int Fx, const float* wx, const float* bx, const float* c_raw,
                                     int Fc, const float* wc, const float* bc, void* y, int B, int64_t V, int D, int G,
                                     int dtype, void* stream) {
-    TDX_CHECK_ARG(x && stats && gamma && beta && x_raw && wx && bx && y && B > 0 && V > 0 && D > 0);
-    TDX_CHECK_ARG(c_raw == nullptr || (wc && bc));
-    const int C = c_raw ? 2 * D : D;
-    if (!gn_shape_ok(C, G) || (D % 8) || Fx != 4 || (c_raw && Fc != 4)) return TDX_ESHAPE;
-    dim3 grid(gn_blocks_per_sample(B, V, C), B);
-    TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gn_apply_encoded_kernel<T, 4>), grid, dim3(GN_THREADS), 0,
-                                                 as_stream(stream), (const T*)x, stats, gamma, beta, x_raw, wx, bx, c_raw,
-                                                 wc, bc, (T*)y, V, C, D, G));
-    return tdx_launch_status();
+    return tdx_gn_apply_encoded_act(x, stats, gamma, beta, x_raw, Fx, wx, bx, c_raw, Fc, wc, bc, y, B, V, D, G, dtype,
+                                    TDX_ACT_SILU, stream);
 }
 
-// ---- out = decode(silu(GN(x)) + res): the tail of the model's LAST ResnetBlock (decode[0], ddpm.py:429) followed by the
+// ---- out = decode(act(GN(x)) + res): the tail of the model's LAST ResnetBlock (decode[0], ddpm.py:429) followed by the
 // dim -> F 1x1 decoder and the NDHWC -> NCDHW layout change (decode[1], ddpm.py:505), inference only.  The block output
 // (B, V, C) is neither written nor read back: per voxel 2 x (C x 2 B) of HBM traffic disappear.  The block output is
 // rounded to T before the dot product and the dot product is the decoder's own (tdx_codec_elem.h), so the result is
-// bit-identical to tdx_gn_apply(res, act = 1) + tdx_decode_fwd.
-template <typename T, int F>
+// bit-identical to tdx_gn_apply(res, act) + tdx_decode_fwd, for every activation.
+template <typename T, int F, int ACT>
 __global__ void __launch_bounds__(GN_THREADS)
 gn_apply_decode_kernel(const T* __restrict__ x, const float* __restrict__ stats, const float* __restrict__ gamma,
                        const float* __restrict__ beta, const T* __restrict__ res, const float* __restrict__ w,
@@ -442,7 +447,7 @@ gn_apply_decode_kernel(const T* __restrict__ x, const float* __restrict__ stats,
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float n = __builtin_fmaf(a[0].v[j], k.a[j], k.c0[j]);
-            o[j] = round_as<T>(silu_add(n, a[1].v[j]));
+            o[j] = round_as<T>(Act<ACT>::f_add(n, a[1].v[j]));
         }
 #pragma unroll
         for (int f = 0; f < F; ++f) {
@@ -452,17 +457,24 @@ gn_apply_decode_kernel(const T* __restrict__ x, const float* __restrict__ stats,
     });
 }
 
-extern "C" int tdx_gn_apply_decode(const void* x, const float* stats, const float* gamma, const float* beta, const void* res,
-                                   const float* w, const float* bias, float* out, int B, int64_t V, int C, int G, int F,
-                                   int dtype, void* stream) {
+extern "C" int tdx_gn_apply_decode_act(const void* x, const float* stats, const float* gamma, const float* beta,
+                                       const void* res, const float* w, const float* bias, float* out, int B, int64_t V, int C,
+                                       int G, int F, int dtype, int act, void* stream) {
     TDX_CHECK_ARG(x && stats && gamma && beta && res && w && bias && out && B > 0 && V > 0);
+    TDX_CHECK_ARG(act >= 0 && act < TDX_ACT_COUNT);
     const int L = C / 8;
     if (!gn_shape_ok(C, G) || F != 4 || L > 64 || (L & (L - 1)) != 0) return TDX_ESHAPE;
     dim3 grid(gn_blocks_per_sample(B, V, C), B);
-    TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gn_apply_decode_kernel<T, 4>), grid, dim3(GN_THREADS), 0,
-                                                 as_stream(stream), (const T*)x, stats, gamma, beta, (const T*)res, w, bias,
-                                                 out, V, C, G));
+    TDX_DISPATCH_ACT(act, A, TDX_DISPATCH_DTYPE(dtype,
+        hipLaunchKernelGGL((gn_apply_decode_kernel<T, 4, A>), grid, dim3(GN_THREADS), 0, as_stream(stream), (const T*)x, stats,
+                           gamma, beta, (const T*)res, w, bias, out, V, C, G)));
     return tdx_launch_status();
+}
+
+extern "C" int tdx_gn_apply_decode(const void* x, const float* stats, const float* gamma, const float* beta, const void* res,
+                                   const float* w, const float* bias, float* out, int B, int64_t V, int C, int G, int F,
+                                   int dtype, void* stream) {
+    return tdx_gn_apply_decode_act(x, stats, gamma, beta, res, w, bias, out, B, V, C, G, F, dtype, TDX_ACT_SILU, stream);
 }
 
 // ------------------------------------------------------------------ backward -------------
@@ -472,7 +484,7 @@ extern "C" int tdx_gn_apply_decode(const void* x, const float* stats, const floa
 //   apply pass  : dx = rstd (k dn - A - xhat Bq)
 // partial[(b * nblk + blk) * C + c][2] holds one block's sums; the finalize kernels add them in f64
 // in a fixed order, so the result is deterministic.
-template <typename T, bool ACT>
+template <typename T, int ACT>
 __global__ void __launch_bounds__(GN_THREADS)
 gn_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, const float* __restrict__ stats,
                      const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ scale,
@@ -491,7 +503,7 @@ gn_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, const fl
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float n = __builtin_fmaf(a[0].v[j], k.a[j], k.c0[j]);
-            const float dn = ACT ? a[1].v[j] * dsilu_f(n) : a[1].v[j];
+            const float dn = ACT ? a[1].v[j] * Act<ACT>::df(n) : a[1].v[j];
             const float xh = __builtin_fmaf(a[0].v[j], k.rstd[j], k.mr[j]);
             s[0][j] += dn;
             s[1][j] = __builtin_fmaf(dn, xh, s[1][j]);
@@ -583,7 +595,7 @@ __device__ __forceinline__ void gn_bwd_params(const double* __restrict__ acc, co
     }
 }
 
-template <typename T, bool ACT>
+template <typename T, int ACT>
 __global__ void __launch_bounds__(GN_THREADS)
 gn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ dy, const float* __restrict__ stats,
                     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ scale,
@@ -611,7 +623,7 @@ gn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ dy, const flo
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float n = __builtin_fmaf(a[0].v[j], k.a[j], k.c0[j]);
-            const float dn = ACT ? a[1].v[j] * dsilu_f(n) : a[1].v[j];
+            const float dn = ACT ? a[1].v[j] * Act<ACT>::df(n) : a[1].v[j];
             const float xh = __builtin_fmaf(a[0].v[j], k.rstd[j], k.mr[j]);
             o.v[j] = __builtin_fmaf(k1[j], dn, -__builtin_fmaf(xh, k3[j], k2[j]));
         }
@@ -626,6 +638,7 @@ extern "C" int tdx_gn_bwd(const void* x, const void* dy, const float* stats, con
     TDX_CHECK_ARG(x && dy && stats && gamma && beta && dx && dgamma && dbeta && workspace && B > 0 && V > 0);
     TDX_CHECK_ARG((scale == nullptr) == (shift == nullptr));
     TDX_CHECK_ARG((scale == nullptr) == (dscale == nullptr) && (dscale == nullptr) == (dshift == nullptr));
+    TDX_CHECK_ARG(act >= 0 && act < TDX_ACT_COUNT);
     if (!gn_shape_ok(C, G)) return TDX_ESHAPE;
     const int nblk = gn_blocks_per_sample(B, V, C);
     double* acc = (double*)workspace;                      // [B][C][2]
@@ -633,11 +646,11 @@ extern "C" int tdx_gn_bwd(const void* x, const void* dy, const float* stats, con
     float* partial = gsum + (size_t)B * C * 2;             // [B][nblk][C][2]
     dim3 grid(nblk, B);
     hipStream_t st = as_stream(stream);
-    TDX_DISPATCH_BOOL(act, A, TDX_DISPATCH_DTYPE(dtype,
+    TDX_DISPATCH_ACT(act, A, TDX_DISPATCH_DTYPE(dtype,
         hipLaunchKernelGGL((gn_bwd_reduce_kernel<T, A>), grid, dim3(GN_THREADS), 0, st, (const T*)x, (const T*)dy, stats, gamma,
                            beta, scale, shift, partial, V, C, G)));
     hipLaunchKernelGGL(gn_bwd_group_kernel, dim3(B * G), dim3(256), 0, st, partial, acc, gamma, scale, gsum, nblk, C, G, V);
-    TDX_DISPATCH_BOOL(act, A, TDX_DISPATCH_DTYPE(dtype,
+    TDX_DISPATCH_ACT(act, A, TDX_DISPATCH_DTYPE(dtype,
         hipLaunchKernelGGL((gn_bwd_apply_kernel<T, A>), grid, dim3(GN_THREADS), 0, st, (const T*)x, (const T*)dy, stats, gamma,
                            beta, scale, shift, gsum, (T*)dx, V, C, G, acc, dgamma, dbeta, dscale, dshift)));
     return tdx_launch_status();

@@ -22,6 +22,7 @@ F16 = 3  # TDX_F16: IEEE half tensors (fp16 MFMA operands, fp32 accumulation)
 CONV_AUTO, CONV_DIRECT, CONV_MFMA, CONV_SPLIT = 0, 1, 2, 3
 F32_SPLIT = 2  # TDX_F32_SPLIT: pack code of fp32 weights for CONV_SPLIT
 WS_CLEAN = 0x100  # TDX_WS_CLEAN (include/tdx.h)
+ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU, ACT_SOFTPLUS, ACT_TANH = range(6)  # TDX_ACT_*
 
 _vp, _i, _i64, _u64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_size_t
 
@@ -60,6 +61,8 @@ SIGNATURES = {
     "tdx_gn_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _vp]),
     "tdx_gn_apply_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _vp]),
     "tdx_gn_apply_encoded": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp]),
+    "tdx_gn_apply_decode_act": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _i, _vp]),
+    "tdx_gn_apply_encoded_act": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _vp]),
     "tdx_gn_bwd": (_i, [_vp] * 12 + [_i, _i64, _i, _i, _i, _i, _vp, _vp]),
     "tdx_resize_fwd": (_i, [_vp, _vp] + [_i] * 9 + [_vp]),
     "tdx_resize_bwd": (_i, [_vp, _vp, _vp] + [_i] * 9 + [_vp]),

@@ -87,6 +87,10 @@ DEFER_ENCODE = True
 FUSE_DECODE = True
 # CACHE_COND_CONV = False: sampling recomputes the conditioning half of the first conv every step
 CACHE_COND_CONV = True
+# FUSE_ACTFNS = False: only SiLU runs inside the GroupNorm kernels; a Block with any other activation runs the torch module
+# after an act = 0 pass and its ResnetBlock is not fused (the route every non-SiLU model took before the kernels had codes
+# for GELU / ReLU / Softplus / Tanh)
+FUSE_ACTFNS = True
 
 
 def _norm_groups(norm: nn.GroupNorm) -> int:
@@ -96,25 +100,32 @@ def _norm_groups(norm: nn.GroupNorm) -> int:
 class Block(nn.Module):
     """conv3x3x3(replicate) -> GroupNorm -> [FiLM] -> activation  (reference ddpm.py:154-177).
 
-    ``forward`` fuses GroupNorm, the FiLM affine, SiLU and an optional residual add into one
-    stats pass + one apply pass over the conv output."""
+    ``forward`` fuses GroupNorm, the FiLM affine, the activation and an optional residual add into one
+    stats pass + one apply pass over the conv output, for every activation ``ops.act_code`` has a code for (the
+    reference's five ``actfn`` choices at their default arguments); any other module runs as itself after the pass."""
 
     def __init__(self, dim, dim_out, actfn, norm_klass=None):
         super().__init__()
         self.conv = nn.Conv3d(dim, dim_out, 3, padding=1, padding_mode="replicate")
         self.norm = norm_klass(dim_out)
         self.act = actfn()
-        self._fused_act = isinstance(self.act, nn.SiLU)
+        self._act_code = ops.act_code(self.act)
+
+    def fused_act(self):
+        """The TDX_ACT_* code the kernels evaluate this Block's activation with, or None: the torch module runs."""
+        code = self._act_code
+        return code if code is not None and (FUSE_ACTFNS or code == ops.ACT_SILU) else None
 
     def forward(self, x, scale_shift=None, x2=None, res=None):
         G = _norm_groups(self.norm)
         h, stats = ops.conv3_gn_stats(x, self.conv.weight, self.conv.bias, G, self.norm.eps, x2=x2)
         scale, shift = scale_shift if scale_shift is not None else (None, None)
-        if self._fused_act:
-            return ops.gn_film_silu(h, self.norm.weight, self.norm.bias, G, scale, shift, res=res, act=True,
-                                    eps=self.norm.eps, stats=stats)
-        h = ops.gn_film_silu(h, self.norm.weight, self.norm.bias, G, scale, shift, act=False, eps=self.norm.eps,
-                             stats=stats)
+        act = self.fused_act()
+        if act is not None:
+            return ops.gn_film_act(h, self.norm.weight, self.norm.bias, G, scale, shift, res=res, act=act,
+                                   eps=self.norm.eps, stats=stats)
+        h = ops.gn_film_act(h, self.norm.weight, self.norm.bias, G, scale, shift, act=ops.ACT_NONE, eps=self.norm.eps,
+                            stats=stats)
         h = self.act(h)
         return h if res is None else h + res
 
@@ -134,7 +145,8 @@ class ResnetBlock(nn.Module):
 
     def fused(self, x2=None):
         identity = isinstance(self.conv, nn.Identity)
-        return self.block1._fused_act and self.block2._fused_act and not (identity and x2 is not None) and FUSE_BLOCKS
+        act = self.block1.fused_act()
+        return act is not None and act == self.block2.fused_act() and not (identity and x2 is not None) and FUSE_BLOCKS
 
     def forward(self, x, c, x2=None, partial=None, conv1=None, films=None, skip_encoded=None, decode_wb=None):
         """partial = (n_lead, init): inference only -- block1's conv runs over the leading n_lead channels
@@ -159,11 +171,11 @@ class ResnetBlock(nn.Module):
                                         (b2.conv.weight, b2.conv.bias), (b2.norm.weight, b2.norm.bias), None,
                                         _norm_groups(b1.norm), b1.norm.eps, conv1_input=conv1[0],
                                         conv1_real_channels=conv1[3] if len(conv1) > 3 else None, film=film,
-                                        skip_encoded=skip_encoded)
+                                        skip_encoded=skip_encoded, act=b1.fused_act())
             return ops.resnet_block(x, x2, scale, shift, (b1.conv.weight, b1.conv.bias), (b1.norm.weight, b1.norm.bias),
                                     (b2.conv.weight, b2.conv.bias), (b2.norm.weight, b2.norm.bias),
                                     None if identity else (self.conv.weight, self.conv.bias), _norm_groups(b1.norm),
-                                    b1.norm.eps, partial=partial, film=film, decode_wb=decode_wb)
+                                    b1.norm.eps, partial=partial, film=film, decode_wb=decode_wb, act=b1.fused_act())
         assert partial is None and conv1 is None and skip_encoded is None and decode_wb is None
         h = self.block1(x, scale_shift=(scale, shift), x2=x2)
         if isinstance(self.conv, nn.Identity):
@@ -199,7 +211,7 @@ class PreNorm(nn.Module):
         self.fn = fn
 
     def forward(self, x, residual=None):
-        xn = ops.gn_film_silu(x, self.norm.weight, self.norm.bias, _norm_groups(self.norm), act=False, eps=self.norm.eps)
+        xn = ops.gn_film_act(x, self.norm.weight, self.norm.bias, _norm_groups(self.norm), act=ops.ACT_NONE, eps=self.norm.eps)
         return self.fn(xn) if residual is None else self.fn(xn, residual=residual)
 
 

@@ -6,7 +6,7 @@ the reference's shapes and float32 (so state_dicts round-trip). 
 
     conv3            nn.Conv3d(k=3, padding_mode="replicate")            ddpm.py:164
     conv1            nn.Conv3d(k=1) incl. the torch.cat that feeds it     ddpm.py:188,292,293,433,436,459
-    gn_film_silu     GroupNorm -> addcmul(shift, scale+1, x) -> SiLU (+x)  ddpm.py:165-176,197
+    gn_film_act      GroupNorm -> addcmul(shift, scale+1, x) -> act (+x)   ddpm.py:165-176,197
     resize           F.interpolate(trilinear, align_corners=True)         ddpm.py:359-369
     attention        F.scaled_dot_product_attention                       attention.py:9-15
     q_sample / p_sample_step / masked_loss                                ddpm.py:745-852
@@ -156,8 +156,32 @@ def _conv1_fwd(x1, C1, x2, C2, w, ldw, col, bias, add, lead, rows, Cout, code, s
     return y
 
 
+ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU, ACT_SOFTPLUS, ACT_TANH = L.ACT_NONE, L.ACT_SILU, L.ACT_GELU, L.ACT_RELU, L.ACT_SOFTPLUS, L.ACT_TANH
+
+
+def act_code(module) -> "int | None":
+    """The TDX_ACT_* code of an activation module the GroupNorm kernels evaluate -- nn.SiLU, nn.GELU, nn.ReLU, nn.Softplus,
+    nn.Tanh at their default arguments, what the reference's `actfn_from_str` constructs -- or None for anything else
+    (nn.GELU(approximate="tanh"), nn.Softplus(beta=2), nn.LeakyReLU, a subclass with a forward of its own, ...): those
+    run as the torch module after an `act = 0` pass."""
+    nn = torch.nn
+    kind = type(module)
+    if kind is nn.SiLU:
+        return ACT_SILU
+    if kind is nn.GELU:
+        return ACT_GELU if module.approximate == "none" else None
+    if kind is nn.ReLU:
+        return ACT_RELU
+    if kind is nn.Softplus:
+        return ACT_SOFTPLUS if (module.beta, module.threshold) == (1, 20) else None
+    if kind is nn.Tanh:
+        return ACT_TANH
+    return None
+
+
 def _gn_apply(x, stats, gamma, beta, scale, shift, res, B, V, Cc, groups, act, code, st):
-    """y = [silu]( GN(x; stats) * (1 + scale) + shift ) + res; scale / shift (B, C) f32, and res, may be None."""
+    """y = act( GN(x; stats) * (1 + scale) + shift ) + res (act: a TDX_ACT_* code); scale / shift (B, C) f32, and res, may
+    be None."""
     y = torch.empty_like(x)
     L.call("tdx_gn_apply", L.ptr(x), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(scale), L.ptr(shift), L.ptr(res), L.ptr(y),
            B, V, Cc, groups, act, code, st)
@@ -166,7 +190,7 @@ def _gn_apply(x, stats, gamma, beta, scale, shift, res, B, V, Cc, groups, act, c
 
 def _gn_bwd(x, gy, stats, gamma, beta, scale, shift, dscale, dshift, B, V, Cc, groups, act, code, st, ws=None):
     """(gx, dgamma, dbeta) of `_gn_apply`; dscale / dshift are written too where scale / shift were given (the caller
-    allocates them: two tensors for gn_film_silu, the halves of one (2, B, C) tensor for a fused block)."""
+    allocates them: two tensors for gn_film_act, the halves of one (2, B, C) tensor for a fused block)."""
     gx, dgamma, dbeta = torch.empty_like(x), stats.new_empty(Cc), stats.new_empty(Cc)
     if ws is None:
         ws = _gn_ws(B, Cc, x.device)
@@ -530,7 +554,7 @@ def conv3(x1, weight, bias=None, x2=None):
 
 def conv3_gn_stats(x1, weight, bias, groups, eps=1e-5, x2=None):
     """conv3 plus the GroupNorm(groups) statistics (B, groups, 2) of its output, accumulated in
-    the conv epilogue.  Returns (y, stats); feed stats to gn_film_silu(..., stats=stats)."""
+    the conv epilogue.  Returns (y, stats); feed stats to gn_film_act(..., stats=stats)."""
     return _Conv3.apply(x1, x2, weight, bias, groups, eps)
 
 
@@ -609,10 +633,10 @@ def conv1(x1, weight, bias=None, x2=None, add=None):
     return _Conv1.apply(x1, x2, weight, bias, add)
 
 
-# --------------------------------------------------------------------------- GroupNorm + FiLM + SiLU
+# --------------------------------------------------------------------------- GroupNorm + FiLM + activation
 
 
-class _GnFilmSilu(torch.autograd.Function):
+class _GnFilmAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, scale, shift, res, groups, act, eps, stats=None):
         B, X, Y, Z, Cc = _grid(x)
@@ -647,10 +671,15 @@ class _GnFilmSilu(torch.autograd.Function):
         return gx, dgamma, dbeta, dscale, dshift, (gy if has_res else None), None, None, None, None
 
 
-def gn_film_silu(x, gamma, beta, groups, scale=None, shift=None, res=None, act=True, eps=1e-5, stats=None):
-    """y = [silu]( GN(x) * (1 + scale) + shift ) + res;  scale/shift are (B, C) or None.
+def gn_film_act(x, gamma, beta, groups, scale=None, shift=None, res=None, act=ACT_SILU, eps=1e-5, stats=None):
+    """y = act( GN(x) * (1 + scale) + shift ) + res;  scale/shift are (B, C) or None; act: a TDX_ACT_* code (`act_code`).
     `stats` (B, groups, 2) may come from conv3_gn_stats (else a statistics pass is run)."""
-    return _GnFilmSilu.apply(x, gamma, beta, scale, shift, res, groups, act, eps, stats)
+    return _GnFilmAct.apply(x, gamma, beta, scale, shift, res, groups, int(act), eps, stats)
+
+
+def gn_film_silu(x, gamma, beta, groups, scale=None, shift=None, res=None, act=True, eps=1e-5, stats=None):
+    """gn_film_act with act = SiLU (True) or none (False)."""
+    return gn_film_act(x, gamma, beta, groups, scale, shift, res, ACT_SILU if act else ACT_NONE, eps, stats)
 
 
 # --------------------------------------------------------------------------- trilinear resize
@@ -1079,8 +1108,11 @@ class _WgradSide:
 class _ResnetBlock(torch.autograd.Function):
     """ResnetBlock (reference ddpm.py:180-197) as ONE autograd node:
 
-        h1 = conv3([x1|x2]; w1) ; a1 = silu(GN(h1) * (1 + scale) + shift)
-        h2 = conv3(a1; w2)      ; y  = silu(GN(h2)) + res,   res = [x1|x2] (identity) or conv1x1([x1|x2]; wr)
+        h1 = conv3([x1|x2]; w1) ; a1 = act(GN(h1) * (1 + scale) + shift)
+        h2 = conv3(a1; w2)      ; y  = act(GN(h2)) + res,   res = [x1|x2] (identity) or conv1x1([x1|x2]; wr)
+
+    act is one of the TDX_ACT_* codes; the backward recomputes the pre-activation from h and the statistics, so no
+    activation saves a tensor of its own.
 
     Doing the backward by hand (instead of chaining the per-op Functions) lets the gradient that
     arrives over the residual path be added inside the data-gradient conv's epilogue / the 1x1
@@ -1089,7 +1121,7 @@ class _ResnetBlock(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x1, x2, film, w1, b1, g1, be1, w2, b2, g2, be2, wr, br, groups, eps, partial=None, xc=None,
-                xc_real=None, enc=None, dec=None):
+                xc_real=None, enc=None, dec=None, act=ACT_SILU):
         """xc: optional separate input of block1's conv (w1 then has xc's channel count); the residual
         path still uses x1.  Used for the U-Net's first block, whose conv is composed with the 1x1
         encoders and therefore runs on the raw input channels (models/ddpm.py, compose_first_conv)."""
@@ -1117,7 +1149,7 @@ class _ResnetBlock(torch.autograd.Function):
         scale, shift = film[0], film[1]
         grid, gn, gws = (B, X, Y, Z), (groups, eps), _gn_ws(B, Cout, dev, clean=True)  # one statistics workspace for both convs
 
-        # ---- h1 = conv3(w1) + statistics; a1 = silu(GN(h1) * (1 + scale) + shift); h2 = conv3(a1; w2) + statistics
+        # ---- h1 = conv3(w1) + statistics; a1 = act(GN(h1) * (1 + scale) + shift); h2 = conv3(a1; w2) + statistics
         if partial is not None:
             # inference only: conv1 over the leading n_lead channels of x1, continued from the
             # precomputed convolution of the batch-shared tail (tdx_conv3_fwd_partial)
@@ -1132,10 +1164,10 @@ class _ResnetBlock(torch.autograd.Function):
             h1, st1 = _conv3_fwd(xc, Cc, None, 0, wf1, b1, grid, Cout, code, impl, st, gn, gws, real=xc_real)
         else:
             h1, st1 = _conv3_fwd(x1, C1, x2, C2, wf1, b1, grid, Cout, code, impl, st, gn, gws)
-        a1 = _gn_apply(h1, st1, g1, be1, scale, shift, None, B, V, Cout, groups, 1, code, st)
+        a1 = _gn_apply(h1, st1, g1, be1, scale, shift, None, B, V, Cout, groups, act, code, st)
         h2, st2 = _conv3_fwd(a1, Cout, None, 0, wf2, b2, grid, Cout, code, impl, st, gn, gws)
 
-        # ---- y = silu(GN(h2)) + skip
+        # ---- y = act(GN(h2)) + skip (SiLU keeps the entries without an `act` argument: the same launches as ever)
         wr2 = None
         if dec is not None:
             # inference only: the block output goes straight through the model's 1x1 decoder (tdx_gn_apply_decode) and is
@@ -1146,32 +1178,35 @@ class _ResnetBlock(torch.autograd.Function):
             wd, bd = dec
             F = wd.shape[0]
             out = torch.empty((B, F, X, Y, Z), dtype=torch.float32, device=dev)
-            L.call("tdx_gn_apply_decode", L.ptr(h2), L.ptr(st2), L.ptr(g2), L.ptr(be2), L.ptr(x1),
+            silu = act == ACT_SILU
+            L.call("tdx_gn_apply_decode" if silu else "tdx_gn_apply_decode_act", L.ptr(h2), L.ptr(st2), L.ptr(g2), L.ptr(be2), L.ptr(x1),
                    L.ptr(wd.detach().reshape(F, Cout).float().contiguous()), L.ptr(bd.detach().float().contiguous()), L.ptr(out),
-                   B, V, Cout, groups, F, code, st)
+                   B, V, Cout, groups, F, code, *(() if silu else (act,)), st)
             return out
         if enc is not None:  # skip = the encoders' output, evaluated in the kernel
             xr, Fx, wx2, bx2, cr, Fc, wc2, bc2, D = enc
             y = torch.empty_like(h1)
-            L.call("tdx_gn_apply_encoded", L.ptr(h2), L.ptr(st2), L.ptr(g2), L.ptr(be2), L.ptr(xr), Fx, L.ptr(wx2), L.ptr(bx2),
-                   L.ptr(cr), Fc, L.ptr(wc2), L.ptr(bc2), L.ptr(y), B, V, D, groups, code, st)
+            silu = act == ACT_SILU
+            L.call("tdx_gn_apply_encoded" if silu else "tdx_gn_apply_encoded_act", L.ptr(h2), L.ptr(st2), L.ptr(g2), L.ptr(be2),
+                   L.ptr(xr), Fx, L.ptr(wx2), L.ptr(bx2), L.ptr(cr), Fc, L.ptr(wc2), L.ptr(bc2), L.ptr(y), B, V, D, groups, code,
+                   *(() if silu else (act,)), st)
         elif wr is None:  # skip = x1
             assert x2 is None and Cin == Cout
-            y = _gn_apply(h2, st2, g2, be2, None, None, x1, B, V, Cout, groups, 1, code, st)
+            y = _gn_apply(h2, st2, g2, be2, None, None, x1, B, V, Cout, groups, act, code, st)
         else:  # skip = conv1x1([x1|x2]; wr)
             wr2 = wr.detach().reshape(Cout, Cin).contiguous()
-            if FUSE_SKIP_TAIL and dt in L.H16_DTYPES and C1 % 32 == 0 and C2 % 32 == 0 and Cout % 32 == 0:
-                # in one pass: the skip tensor is never written or re-read
+            if FUSE_SKIP_TAIL and act == ACT_SILU and dt in L.H16_DTYPES and C1 % 32 == 0 and C2 % 32 == 0 and Cout % 32 == 0:
+                # in one pass: the skip tensor is never written or re-read (tdx_conv1_fwd_gn evaluates SiLU only)
                 y = torch.empty_like(h1)
                 L.call("tdx_conv1_fwd_gn", L.ptr(x1), C1, L.ptr(x2), C2, L.ptr(_conv1_wt(wr)), Cout, L.ptr(br), L.ptr(h2),
                        L.ptr(st2), L.ptr(g2), L.ptr(be2), groups, L.ptr(y), B, V, Cout, code, st)
             else:
                 res = _conv1_fwd(x1, C1, x2, C2, _conv1_wt(wr), Cout, 0, br, None, grid, B * V, Cout, code, st)
-                y = _gn_apply(h2, st2, g2, be2, None, None, res, B, V, Cout, groups, 1, code, st)
+                y = _gn_apply(h2, st2, g2, be2, None, None, res, B, V, Cout, groups, act, code, st)
         ctx.save_for_backward(x1, x2, h1, st1, a1, h2, st2, film, g1, be1, g2, be2, wb1, wb2, wr2, xc)
         ctx.cfg = (groups, tuple(w1.shape), tuple(w2.shape), None if wr is None else tuple(wr.shape),
                    b1 is not None, b2 is not None, br is not None)
-        ctx.xc_real, ctx.impl, ctx.c1 = xc_real, impl, C1
+        ctx.xc_real, ctx.impl, ctx.c1, ctx.act = xc_real, impl, C1, act
         return y
 
     @staticmethod
@@ -1189,7 +1224,7 @@ class _ResnetBlock(torch.autograd.Function):
         scale, shift = film[0], film[1]
         groups, w1s, w2s, wrs, hb1, hb2, hbr = ctx.cfg
         B, X, Y, Z, _ = _grid(h1)
-        C1 = ctx.c1  # (x1 is None when the skip was evaluated from the encoders' operands)
+        C1, act = ctx.c1, ctx.act  # (x1 is None when the skip was evaluated from the encoders' operands)
         C2 = 0 if x2 is None else x2.shape[-1]
         Cin, Cout = C1 + C2, w1s[0]
         Cc = w1s[1]  # input channels of block1's conv (= Cin unless the conv has its own input xc)
@@ -1198,8 +1233,8 @@ class _ResnetBlock(torch.autograd.Function):
         dev, code, impl, st = gy.device, L.dtype_code(gy.dtype), ctx.impl, L.stream()
         gws = _gn_ws(B, Cout, dev)  # shared by both GroupNorm backwards
 
-        # ---- block2: GroupNorm + SiLU (+ residual: its gradient is gy itself), then conv2's two gradients
-        dh2, dg2, dbe2 = _gn_bwd(h2, gy, st2, g2, be2, None, None, None, None, B, V, Cout, groups, 1, code, st, gws)
+        # ---- block2: GroupNorm + activation (+ residual: its gradient is gy itself), then conv2's two gradients
+        dh2, dg2, dbe2 = _gn_bwd(h2, gy, st2, g2, be2, None, None, None, None, B, V, Cout, groups, act, code, st, gws)
         # the weight gradients run on the side stream: outputs and workspaces are allocated here, on the launching stream
         dw2, db2 = _conv3_wgrad_out(w2s, hb2, dev)
         wws2, wws1 = _conv3_wgrad_ws(Cout, Cout, impl, dev), _conv3_wgrad_ws(Cc, Cout, impl, dev)
@@ -1207,9 +1242,9 @@ class _ResnetBlock(torch.autograd.Function):
         dws = _conv3_bwd_data_ws(grid, max(Cin, Cout, Cc), code, impl, dev)  # for all data gradients of the block
         da1, _ = _conv3_bwd_data(dh2, wb2, a1, Cout, None, 0, grid, Cout, code, impl, st, dws)
         del dh2
-        # ---- block1: GroupNorm + FiLM + SiLU, then conv1's weight gradient
+        # ---- block1: GroupNorm + FiLM + activation, then conv1's weight gradient
         dfilm = torch.empty((2, B, Cout), dtype=torch.float32, device=dev)
-        dh1, dg1, dbe1 = _gn_bwd(h1, da1, st1, g1, be1, scale, shift, dfilm[0], dfilm[1], B, V, Cout, groups, 1, code, st, gws)
+        dh1, dg1, dbe1 = _gn_bwd(h1, da1, st1, g1, be1, scale, shift, dfilm[0], dfilm[1], B, V, Cout, groups, act, code, st, gws)
         del da1
         dw1, db1 = _conv3_wgrad_out(w1s, hb1, dev)
         if xc is not None:
@@ -1224,7 +1259,7 @@ class _ResnetBlock(torch.autograd.Function):
                 dxc, _ = _conv3_bwd_data(dh1, wb1, xc, Cc, None, 0, grid, Cout, code, impl, st, dws, real=real)
             side.join()
             return (gy, None, dfilm, dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2, None, None, None, None, None, dxc, None, None,
-                    None)
+                    None, None)
         side.run(lambda: _conv3_wgrad(x1, C1, x2, C2, dh1, dw1, db1, grid, Cout, code, impl, wws1, L.stream()),
                  x1, x2, dh1, dw1, db1)
         # ---- input gradient = conv1 data gradient + residual-path gradient
@@ -1238,13 +1273,14 @@ class _ResnetBlock(torch.autograd.Function):
             dwr, dbr = _conv1_weight_grad(x1, C1, x2, C2, gy, Cout, hbr, B * V, code, st)
             dwr = dwr.view(wrs)
         side.join()
-        return (gx1, gx2, dfilm, dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2, dwr, dbr, None, None, None, None, None, None, None)
+        return (gx1, gx2, dfilm, dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2, dwr, dbr, None, None, None, None, None, None, None, None)
 
 
 def resnet_block(x1, x2, scale, shift, conv1_wb, norm1_wb, conv2_wb, norm2_wb, skip_wb, groups, eps=1e-5, partial=None,
-                 conv1_input=None, conv1_real_channels=None, film=None, skip_encoded=None, decode_wb=None):
+                 conv1_input=None, conv1_real_channels=None, film=None, skip_encoded=None, decode_wb=None, act=ACT_SILU):
     """Fused ResnetBlock; *_wb are (weight, bias) pairs, skip_wb is None for an identity skip.
-    Requires SiLU activations and bf16/f32 NDHWC inputs; scale/shift are (B, Cout), or film = the (2, B, Cout)
+    act: the TDX_ACT_* code of both Blocks' activation (`act_code(module)`; a module it has no code for cannot run here).
+    Requires bf16 / fp16 / f32 NDHWC inputs; scale/shift are (B, Cout), or film = the (2, B, Cout)
     [scale, shift] tensor of film_projections (then scale and shift are ignored: no slicing copies either way).
     partial = (n_lead, init): no-grad only, see conv3_shared_tail.
     conv1_input: separate input tensor of block1's conv (conv1_wb then matches ITS channel count);
@@ -1256,6 +1292,8 @@ def resnet_block(x1, x2, scale, shift, conv1_wb, norm1_wb, conv2_wb, norm2_wb, s
     decode(block output) as (B, F, X, Y, Z) f32 (ops.decode's result) without writing the block output
     (decode_fused_supported says when)."""
     wr, br = skip_wb if skip_wb is not None else (None, None)
+    if act not in (ACT_SILU, ACT_GELU, ACT_RELU, ACT_SOFTPLUS, ACT_TANH):
+        raise ValueError(f"resnet_block: act must be one of the TDX_ACT_* activation codes 1..5, got {act!r}")
     assert decode_wb is None or not torch.is_grad_enabled(), "decode_wb: inference only (the block output is not kept)"
     assert partial is None or not torch.is_grad_enabled(), "partial: inference only (the backward needs the full conv)"
     enc = None
@@ -1267,7 +1305,7 @@ def resnet_block(x1, x2, scale, shift, conv1_wb, norm1_wb, conv2_wb, norm2_wb, s
         film = torch.stack((scale.reshape(B, Cout).float(), shift.reshape(B, Cout).float()))
     return _ResnetBlock.apply(x1, x2, film, conv1_wb[0], conv1_wb[1], norm1_wb[0], norm1_wb[1], conv2_wb[0],
                               conv2_wb[1], norm2_wb[0], norm2_wb[1], wr, br, groups, eps, partial, conv1_input,
-                              conv1_real_channels, enc, decode_wb)
+                              conv1_real_channels, enc, decode_wb, int(act))
 
 
 # --------------------------------------------------------------------------- baseline conv variants

@@ -246,15 +246,25 @@ int tdx_decode_fwd(const void* h, const float* w, const float* bias, float* y, i
 int tdx_decode_bwd(const float* dy, const void* h, const float* w, void* dh, float* dw, float* db, int B, int64_t V, int D,
                    int F, int dtype, void* stream);
 
-/* ------------------------------------------------------------------ GroupNorm+FiLM+SiLU - */
-/* nn.GroupNorm(G, C, eps) -> [x*(scale+1)+shift] -> [SiLU] (-> [+ residual]),
+/* ------------------------------------------------------------------ GroupNorm+FiLM+act -- */
+/* nn.GroupNorm(G, C, eps) -> [x*(scale+1)+shift] -> [activation] (-> [+ residual]),
  * ddpm.py:165-176, 197, 429, 472.
  * stats [B][G][2] f32 = (mean, rstd) with biased variance. */
 size_t tdx_gn_workspace_bytes(int B, int C);
 int tdx_gn_stats(const void* x, float* stats, int B, int64_t V, int C, int G, float eps, int dtype, void* workspace,
                  void* stream);
+/* Activation codes (`act` of the entries below): the reference's `actfn` choices (turbdiff/models/diffusion.py:30-38), each
+ * torch's module at its default arguments.  GELU is the exact one (approximate = "none"), Softplus has beta = 1 and
+ * threshold = 20 (n > 20 ? n : log(1 + e^n), strictly greater), ReLU's derivative at 0 is 0. */
+#define TDX_ACT_NONE 0
+#define TDX_ACT_SILU 1
+#define TDX_ACT_GELU 2
+#define TDX_ACT_RELU 3
+#define TDX_ACT_SOFTPLUS 4
+#define TDX_ACT_TANH 5
 /* n = (x-mean)*rstd*gamma + beta; if scale: n = n*(1+scale[b,c]) + shift[b,c];
- * a = act ? silu(n) : n; y = a + (res ? res : 0).   scale/shift: [B][C] f32 or NULL. */
+ * a = f_act(n) (TDX_ACT_NONE: n); y = a + (res ? res : 0).   scale/shift: [B][C] f32 or NULL.
+ * Any other `act` is TDX_EINVAL (nothing is launched). */
 int tdx_gn_apply(const void* x, const float* stats, const float* gamma, const float* beta, const float* scale,
                  const float* shift, const void* res, void* y, int B, int64_t V, int C, int G, int act, int dtype,
                  void* stream);
@@ -266,6 +276,11 @@ int tdx_gn_apply(const void* x, const float* stats, const float* gamma, const fl
 int tdx_gn_apply_encoded(const void* x, const float* stats, const float* gamma, const float* beta, const float* x_raw, int Fx,
                          const float* wx, const float* bx, const float* c_raw, int Fc, const float* wc, const float* bc,
                          void* y, int B, int64_t V, int D, int G, int dtype, void* stream);
+/* The same with any activation: y = f_act(GroupNorm(x)) + encode(x_raw, c_raw), bit-identical to tdx_encode_fwd +
+ * tdx_gn_apply(res = its output, act).  tdx_gn_apply_encoded is this entry with TDX_ACT_SILU. */
+int tdx_gn_apply_encoded_act(const void* x, const float* stats, const float* gamma, const float* beta, const float* x_raw,
+                             int Fx, const float* wx, const float* bx, const float* c_raw, int Fc, const float* wc,
+                             const float* bc, void* y, int B, int64_t V, int D, int G, int dtype, int act, void* stream);
 /* out = decode(silu(GroupNorm(x)) + res): the tail of the model's last ResnetBlock (decode[0], ddpm.py:429) fused with the
  * dim -> F 1x1 decoder and the NDHWC -> NCDHW layout change (decode[1], ddpm.py:505); inference only (the block output, which
  * the decoder's weight gradient would need, is never written).  w [F][C] f32, bias [F]; out (B, F, V) f32; F = 4, C / 8 a power
@@ -273,8 +288,13 @@ int tdx_gn_apply_encoded(const void* x, const float* stats, const float* gamma, 
 int tdx_gn_apply_decode(const void* x, const float* stats, const float* gamma, const float* beta, const void* res,
                         const float* w, const float* bias, float* out, int B, int64_t V, int C, int G, int F, int dtype,
                         void* stream);
-/* Backward of tdx_gn_apply w.r.t. x, gamma, beta, scale, shift (the residual's gradient is
- * dy itself).  dgamma/dbeta [C], dscale/dshift [B][C] (NULL when no FiLM); overwritten.
+/* The same with any activation: out = decode(f_act(GroupNorm(x)) + res), bit-identical to tdx_gn_apply(res, act) +
+ * tdx_decode_fwd.  tdx_gn_apply_decode is this entry with TDX_ACT_SILU. */
+int tdx_gn_apply_decode_act(const void* x, const float* stats, const float* gamma, const float* beta, const void* res,
+                            const float* w, const float* bias, float* out, int B, int64_t V, int C, int G, int F, int dtype,
+                            int act, void* stream);
+/* Backward of tdx_gn_apply(act) w.r.t. x, gamma, beta, scale, shift (the residual's gradient is
+ * dy itself): dn = dy f_act'(n), n recomputed from x and the statistics.  dgamma/dbeta [C], dscale/dshift [B][C] (NULL when no FiLM); overwritten.
  * workspace: tdx_gn_workspace_bytes(). */
 int tdx_gn_bwd(const void* x, const void* dy, const float* stats, const float* gamma, const float* beta,
                const float* scale, const float* shift, void* dx, float* dgamma, float* dbeta, float* dscale,

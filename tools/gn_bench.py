@@ -7,12 +7,15 @@ measurements of 20 calls each) and the bandwidth over the entry's activation pas
   tdx_gn_apply_decode   192x64x48 x 64 channels only: 2 passes + the 4 output planes
 (Round 3 measured an apply pass that walks each sample back to front, so that what the reduce pass left in the 256 MiB
 Infinity Cache is read first: 199 vs 192 us at 192x64x48 x 32 channels, 437 vs 431 at 64 channels -- no gain, not kept.)
-GPU box: python tools/gn_bench.py [--lib <another build's libtdx_hip.so>]    (--lib sets TDX_LIB: A/B against that library)"""
+GPU box: python tools/gn_bench.py [--lib <another build's libtdx_hip.so>]    (--lib sets TDX_LIB: A/B against that library)
+         python tools/gn_bench.py --act 2    (TDX_ACT_*: 1 SiLU (default), 2 GELU, 3 ReLU, 4 Softplus, 5 Tanh; the two tails
+                                              then go through their *_act entries)"""
 import argparse, os, sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "generative-turbulence_amd"))
 ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
 ap.add_argument("--lib", help="libtdx_hip.so to measure instead of the package's own")
+ap.add_argument("--act", type=int, default=1, help="TDX_ACT_* code of the activation")
 args = ap.parse_args()
 if args.lib:
     os.environ["TDX_LIB"] = str(Path(args.lib).resolve())  # read when turbdiff_amd._lib is imported
@@ -20,7 +23,9 @@ import torch
 from turbdiff_amd import _lib as L
 
 assert not args.lib or Path(L.LIB_PATH).resolve() == Path(args.lib).resolve(), L.LIB_PATH
-print(f"library: {L.LIB_PATH}", flush=True)
+print(f"library: {L.LIB_PATH}  act = {args.act}", flush=True)
+ACT = args.act
+TAIL = ("", ()) if ACT == 1 else ("_act", (ACT,))  # SiLU: the entries without an `act` argument
 dev = torch.device("cuda:0")
 B, G = 6, 8
 
@@ -55,18 +60,18 @@ for (grid, C) in (((192, 64, 48), 64), ((192, 64, 48), 32), ((96, 32, 24), 128),
     act_bytes = x.numel() * 2
     report("gn_bwd", grid, C, timed(lambda: L.call(
         "tdx_gn_bwd", L.ptr(x), L.ptr(dy), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(scale), L.ptr(shift), L.ptr(dx), L.ptr(dg),
-        L.ptr(db), L.ptr(ds), L.ptr(dsh), B, V, C, G, 1, L.BF16, L.ptr(ws), st)), 5 * act_bytes)
+        L.ptr(db), L.ptr(ds), L.ptr(dsh), B, V, C, G, ACT, L.BF16, L.ptr(ws), st)), 5 * act_bytes)
     report("gn_apply", grid, C, timed(lambda: L.call(
-        "tdx_gn_apply", L.ptr(x), L.ptr(stats), L.ptr(gamma), L.ptr(beta), None, None, L.ptr(dy), L.ptr(dx), B, V, C, G, 1, L.BF16,
+        "tdx_gn_apply", L.ptr(x), L.ptr(stats), L.ptr(gamma), L.ptr(beta), None, None, L.ptr(dy), L.ptr(dx), B, V, C, G, ACT, L.BF16,
         st)), 3 * act_bytes)
     if (grid, C) != ((192, 64, 48), 64):
         continue
     D = C // 2
     xr, cr, wx, wc, bx, bc = f(B, 4, V), f(4, V), f(D, 4), f(D, 4), f(D), f(D)
     report("gn_apply_encoded", grid, C, timed(lambda: L.call(
-        "tdx_gn_apply_encoded", L.ptr(x), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(xr), 4, L.ptr(wx), L.ptr(bx), L.ptr(cr), 4,
-        L.ptr(wc), L.ptr(bc), L.ptr(dx), B, V, D, G, L.BF16, st)), 2 * act_bytes + (B + 1) * 4 * V * 4)
+        "tdx_gn_apply_encoded" + TAIL[0], L.ptr(x), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(xr), 4, L.ptr(wx), L.ptr(bx), L.ptr(cr), 4,
+        L.ptr(wc), L.ptr(bc), L.ptr(dx), B, V, D, G, L.BF16, *TAIL[1], st)), 2 * act_bytes + (B + 1) * 4 * V * 4)
     w, bias, out = f(4, C), f(4), torch.empty(B, 4, V, device=dev)
     report("gn_apply_decode", grid, C, timed(lambda: L.call(
-        "tdx_gn_apply_decode", L.ptr(x), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(dy), L.ptr(w), L.ptr(bias), L.ptr(out), B, V,
-        C, G, 4, L.BF16, st)), 2 * act_bytes + B * 4 * V * 4)
+        "tdx_gn_apply_decode" + TAIL[0], L.ptr(x), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(dy), L.ptr(w), L.ptr(bias), L.ptr(out), B, V,
+        C, G, 4, L.BF16, *TAIL[1], st)), 2 * act_bytes + B * 4 * V * 4)

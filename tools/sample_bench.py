@@ -13,6 +13,10 @@ one hipGraph-captured reverse step per replay (no collective inside the loop).
       # alternating: this captured step, the eager torch loop it replaces on the default route (`general_loop`, what
       # TDX_GRAPH_SAMPLER=0 runs) and the fixed-variance captured step (`fixed_variance`)
 
+  python tools/sample_bench.py --trajectories 8 --actfn gelu --steps 50 --ab 3
+      # the U-Net built with another of the reference's activations; --ab N: the captured step with models.ddpm.FUSE_ACTFNS on
+      # (activation inside the GroupNorm kernels) and off (act = 0 pass + torch module per Block), N times each, alternating
+
 Prints one JSON line (rank 0): whole-job samples/s = trajectories / max-over-ranks wall time."""
 import argparse, json, sys, time
 from pathlib import Path
@@ -34,6 +38,8 @@ ap.add_argument("--eta", type=float, default=0.0, help="with --sampling-steps: 0
 ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "f32", "f32s"])
 ap.add_argument("--no-graph", action="store_true")
 ap.add_argument("--learned-variances", action="store_true", help="out_features = 2F, learned_variances=True; see above")
+ap.add_argument("--actfn", default="silu", choices=["silu", "gelu", "relu", "softplus", "tanh"], help="activation of the U-Net")
+ap.add_argument("--ab", type=int, default=0, help="with --actfn: time FUSE_ACTFNS on and off alternately, this many times each")
 ap.add_argument("--rounds", type=int, default=3, help="with --learned-variances: how often the three sides are timed in turn")
 a = ap.parse_args()
 if a.dtype == "f32s":  # fp32 tensors, split-precision convs
@@ -53,6 +59,16 @@ if a.learned_variances:
                          u_net_levels=4, norm_type="group")
     diff = GaussianDiffusion(net, timesteps=a.timesteps, beta_schedule="log-snr-linear", loss_type="l2", noise_bcs=True,
                              learned_variances=True).to(dev)
+    diff.model.set_compute_dtype(bench.MODE_DTYPE[a.dtype])
+if a.actfn != "silu":
+    from turbdiff_amd.models.ddpm import DenoisingModel, GaussianDiffusion
+    from turbdiff_amd.training import ACTFNS
+    if a.learned_variances or a.sampling_steps is not None:
+        ap.error("--actfn times the ancestral fixed-variance sampler")
+    torch.manual_seed(0)
+    net = DenoisingModel(in_features=4, out_features=4, c_local_features=4, c_global_features=0, timesteps=a.timesteps, dim=32,
+                         u_net_levels=4, norm_type="group", actfn=ACTFNS[a.actfn])  # bench.new_denoiser with the activation
+    diff = GaussianDiffusion(net, timesteps=a.timesteps, beta_schedule="log-snr-linear", loss_type="l2", noise_bcs=True).to(dev)
     diff.model.set_compute_dtype(bench.MODE_DTYPE[a.dtype])
 ids = list(parallel.shard_trajectories(a.trajectories, rank, world))
 x, c, cell_idx = bench.synthetic_inputs(len(ids), dev)
@@ -110,6 +126,18 @@ if a.learned_variances:
              "general_loop": {"timed_steps": n_gen, "ms_per_reverse_step": med(sides["general_loop"])},
              "fixed_variance": {"timed_steps": n, "ms_per_reverse_step": med(sides["fixed_variance"])}}
     dt = 1e-3 * med(sides["captured"]) * n
+elif a.ab:
+    from turbdiff_amd.models import ddpm as D
+    sides, samplers = {"fused": [], "unfused": []}, {}
+    for _ in range(a.ab):
+        for name, on in (("fused", True), ("unfused", False)):
+            D.FUSE_ACTFNS = on  # read per forward: at capture for the graph, at every step with --no-graph
+            dt, n, samplers[name] = measure(total, s=samplers.get(name))
+            sides[name].append(1e3 * dt / n)
+    D.FUSE_ACTFNS = True
+    med = lambda v: sorted(v)[len(v) // 2]
+    extra = {"actfn": a.actfn, "rounds_ms_per_reverse_step": sides, "unfused": {"timed_steps": n, "ms_per_reverse_step": med(sides["unfused"])}}
+    dt, s = 1e-3 * med(sides["fused"]) * n, samplers["fused"]
 elif a.sampling_steps is not None:
     dt, n, s = measure(a.timesteps)
     extra = {"sampling_steps": a.sampling_steps, "eta": a.eta, "ancestral": record(dt, n, a.timesteps)}
@@ -122,6 +150,6 @@ if rank == 0:
     print(json.dumps({"metric": "DDPM samples/sec (192x64x48x4)", "value": a.trajectories / full, "unit": "samples/s",
                       "n_gpus": world, "trajectories": a.trajectories, "per_gpu": len(ids), "timesteps": a.timesteps,
                       **record(dt, n, total), "dtype": a.dtype, "hipgraph": not a.no_graph,
-                      "finite": bool(torch.isfinite(s.x_t).all()), **extra}))
+                      "finite": bool(torch.isfinite(s.x_t).all()), **({"actfn": a.actfn} if a.actfn != "silu" else {}), **extra}))
 if world > 1:
     torch.distributed.barrier(); torch.distributed.destroy_process_group()

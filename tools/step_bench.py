@@ -5,6 +5,9 @@
 --learned-variances --elbo-weight W: the same U-Net with 2F output channels and the simple + ELBO loss (ops.elbo_loss);
 --torch-elbo (or TDX_STEP_BENCH_TORCH_ELBO=1, so that tools/ab_step.sh can flip it) evaluates that loss with the torch formulation the
 kernel replaced (GaussianDiffusion._p_losses_elbo_torch), --ab N times both N times in this process, alternating.
+--actfn NAME: the same U-Net built with another of the reference's activations (training.ACTFNS); with --ab N the step is timed
+N times each with models.ddpm.FUSE_ACTFNS on (the activation inside the GroupNorm kernels, fused ResnetBlocks) and off (act = 0
+pass + torch module + torch add per Block: the route of every non-SiLU model before the kernels had activation codes), alternating.
 prints ms per step; under `rocprofv3 --kernel-trace --stats` the per-kernel table of exactly these steps."""
 import argparse, os, sys, time
 from pathlib import Path
@@ -28,7 +31,9 @@ ap.add_argument("--learned-variances", action="store_true", help="2F output chan
 ap.add_argument("--elbo-weight", type=float, default=None, help="with --learned-variances: weight of the ELBO term (None: simple loss only)")
 ap.add_argument("--torch-elbo", action="store_true", default=os.environ.get("TDX_STEP_BENCH_TORCH_ELBO", "0") not in ("", "0"),
                 help="the ELBO loss by torch ops (the route before ops.elbo_loss) instead of the fused kernel")
-ap.add_argument("--ab", type=int, default=0, help="with --elbo-weight: time fused and torch ELBO alternately, this many times each")
+ap.add_argument("--ab", type=int, default=0, help="with --elbo-weight: time fused and torch ELBO alternately, this many times each; "
+                                                  "with --actfn: FUSE_ACTFNS on and off")
+ap.add_argument("--actfn", default="silu", choices=["silu", "gelu", "relu", "softplus", "tanh"], help="activation of the U-Net (--model bench)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 
@@ -69,6 +74,13 @@ elif a.learned_variances:
                          u_net_levels=4, norm_type="group")
     diff = GaussianDiffusion(net, timesteps=500, beta_schedule="log-snr-linear", loss_type="l2", noise_bcs=True,
                              learned_variances=True, elbo_weight=a.elbo_weight).to(dev)
+elif a.actfn != "silu":
+    from turbdiff_amd.models.ddpm import DenoisingModel, GaussianDiffusion
+    from turbdiff_amd.training import ACTFNS
+    torch.manual_seed(0)
+    net = DenoisingModel(in_features=4, out_features=4, c_local_features=4, c_global_features=0, timesteps=500, dim=32,
+                         u_net_levels=4, norm_type="group", actfn=ACTFNS[a.actfn])  # bench.new_denoiser with the activation
+    diff = GaussianDiffusion(net, timesteps=500, beta_schedule="log-snr-linear", loss_type="l2", noise_bcs=True).to(dev)
 else:
     diff = bench.build_model(dev)
 x, c, idx = bench.synthetic_inputs(a.batch, dev, tuple(a.grid))
@@ -84,5 +96,13 @@ if a.learned_variances and a.elbo_weight is not None and (a.torch_elbo or a.ab):
             ms = bench.timed_train_steps(diff, x, C, md, a.mode, a.steps, a.warmup)
             print(f"{name}: grid {a.grid} B {a.batch} {a.mode}: {ms:.3f} ms/step = {a.batch * v / ms / 1e3:.1f} M voxels/s")
     sys.exit(0)
+if a.ab and not a.learned_variances:
+    from turbdiff_amd.models import ddpm as D
+    for i in range(a.ab):
+        for name, on in (("fused-act", True), ("unfused-act", False)):
+            D.FUSE_ACTFNS = on  # read per call by Block / ResnetBlock
+            ms = bench.timed_train_steps(diff, x, C, md, a.mode, a.steps, a.warmup)
+            print(f"{name}: actfn {a.actfn} grid {a.grid} B {a.batch} {a.mode}: {ms:.3f} ms/step = {a.batch * v / ms / 1e3:.1f} M voxels/s")
+    sys.exit(0)
 ms = bench.timed_train_steps(diff, x, C, md, a.mode, a.steps, a.warmup)
-print(f"grid {a.grid} B {a.batch} {a.mode} {a.optimizer}: {ms:.3f} ms/step = {a.batch * v / ms / 1e3:.1f} M voxels/s")
+print(f"actfn {a.actfn} grid {a.grid} B {a.batch} {a.mode} {a.optimizer}: {ms:.3f} ms/step = {a.batch * v / ms / 1e3:.1f} M voxels/s")
