@@ -194,8 +194,8 @@ convg_wgrad_kernel(const T* __restrict__ in, const T* __restrict__ dy, float* __
 #pragma unroll
         for (int c = 0; c < 8; ++c) red[tid][c] = (vl < lanes) ? acc[a][c] : 0.f;
         __syncthreads();
-        if (tid < cgs * 8) {
-            const int g8 = tid / 8, c = tid % 8;
+        for (int o = tid; o < cgs * 8; o += 256) {  // Cout outputs: more than the workgroup's threads above 256 channels
+            const int g8 = o / 8, c = o % 8;
             float s = 0.f;
             for (int l = 0; l < lanes; ++l) s += red[l * cgs + g8][c];
             atomicAdd(&dw[((int64_t)tap * g.Cin + ci0 + a) * g.Cout + g8 * 8 + c], s);
@@ -206,8 +206,8 @@ convg_wgrad_kernel(const T* __restrict__ in, const T* __restrict__ dy, float* __
 #pragma unroll
         for (int c = 0; c < 8; ++c) red[tid][c] = (vl < lanes) ? bsum[c] : 0.f;
         __syncthreads();
-        if (tid < cgs * 8) {
-            const int g8 = tid / 8, c = tid % 8;
+        for (int o = tid; o < cgs * 8; o += 256) {
+            const int g8 = o / 8, c = o % 8;
             float s = 0.f;
             for (int l = 0; l < lanes; ++l) s += red[l * cgs + g8][c];
             atomicAdd(&dbias[g8 * 8 + c], s);

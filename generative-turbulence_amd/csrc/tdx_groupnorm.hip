@@ -15,8 +15,8 @@
 #include "tdx_act.h"         // Act<ACT>: the activation family (TDX_ACT_*)
 #include "tdx_codec_elem.h"  // the encoder lane and the decoder dot of the two fused tails
 #include "tdx_conv3.h"
+#include "tdx_gn_stream.h"  // GN_THREADS, GN_UNROLL, GnLane, gn_stream
 
-#define GN_THREADS 256
 #define GN_MAX_BLOCKS 512  // streaming blocks per sample; bounds the backward partial-sum buffer
 #define GN_VOX_PER_BLOCK 1024
 
@@ -265,8 +265,6 @@ __device__ __forceinline__ void gn_load_coef(GnCoef& k, const float* __restrict_
 // with stride gridDim.x * rows, GN_UNROLL voxels per thread per trip (independent 16-B loads in
 // flight, no branches between them); the grid is sized to about 8 resident blocks per CU so the
 // per-block set-up (coefficient loads) is paid once per ~MB streamed.
-#define GN_UNROLL 4
-
 static int gn_blocks_per_sample(int B, int64_t V, int C) {
     const int rows = GN_THREADS / (C >> 3);
     int64_t want = (2048 + B - 1) / B;
@@ -274,66 +272,6 @@ static int gn_blocks_per_sample(int B, int64_t V, int C) {
     if (want > most) want = most;
     if (want > GN_MAX_BLOCKS) want = GN_MAX_BLOCKS;
     return want < 1 ? 1 : (int)want;
-}
-
-// Where a thread streams: lane vector lc (channels [8 lc, 8 lc + 8)) of the voxels first, first + stride, ... of sample
-// blockIdx.y; element (v, its channels) of an activation tensor t is t + base + v * C.  Threads with r >= rows are spares
-// (GN_THREADS % L != 0): their `first` belongs to the next block.
-struct GnLane {
-    int lc, r, rows;
-    int64_t base, stride, first;
-};
-__device__ __forceinline__ GnLane gn_lane(int64_t V, int C) {
-    const int L = C >> 3;
-    GnLane p;
-    p.rows = GN_THREADS / L;
-    p.lc = threadIdx.x % L;
-    p.r = threadIdx.x / L;
-    p.base = ((int64_t)blockIdx.y * V) * C + p.lc * 8;
-    p.stride = (int64_t)gridDim.x * p.rows;
-    p.first = (int64_t)blockIdx.x * p.rows + p.r;
-    return p;
-}
-
-// The two loops.  body(a, s, v) gets voxel v of the NIN tensors `in` as a[0..NIN) and s = side(v), a per-voxel load of
-// the kernel's own that is issued with the trip's other loads.  Spare threads do nothing unless ALL_LANES: a body that
-// ends in a cross-lane butterfly sets it, and every lane of a voxel's group then runs the same trips (v is theirs alike).
-template <typename T, int NIN, bool ALL_LANES, typename Side, typename Body>
-__device__ __forceinline__ void gn_stream(const GnLane& p, const T* const* in, int64_t V, int C, Side side, Body body) {
-    if (!ALL_LANES && p.r >= p.rows) return;
-    int64_t v = p.first;
-    // full trips: GN_UNROLL independent loads in flight, no branches between them
-    for (; v + (GN_UNROLL - 1) * p.stride < V; v += p.stride * GN_UNROLL) {
-        Raw8<T> raw[GN_UNROLL][NIN];
-        decltype(side(v)) s[GN_UNROLL];
-#pragma unroll
-        for (int u = 0; u < GN_UNROLL; ++u) {
-#pragma unroll
-            for (int i = 0; i < NIN; ++i) raw[u][i].load(in[i] + p.base + (v + u * p.stride) * C);
-            s[u] = side(v + u * p.stride);
-        }
-        __builtin_amdgcn_sched_barrier(0);  // all loads of the trip are issued before any arithmetic
-#pragma unroll
-        for (int u = 0; u < GN_UNROLL; ++u) {
-            Vec8<T> a[NIN];
-#pragma unroll
-            for (int i = 0; i < NIN; ++i) a[i] = raw[u][i].get();
-            body(a, s[u], v + u * p.stride);
-        }
-    }
-    for (; v < V; v += p.stride) {
-        Vec8<T> a[NIN];
-#pragma unroll
-        for (int i = 0; i < NIN; ++i) a[i].load(in[i] + p.base + v * C);
-        body(a, side(v), v);
-    }
-}
-// without a side load: body(a, v)
-template <typename T, int NIN, bool ALL_LANES = false, typename Body>
-__device__ __forceinline__ void gn_stream(const GnLane& p, const T* const* in, int64_t V, int C, Body body) {
-    struct None {};
-    gn_stream<T, NIN, ALL_LANES>(p, in, V, C, [](int64_t) { return None(); },
-                                 [&](const Vec8<T>(&a)[NIN], None, int64_t v) { body(a, v); });
 }
 
 // The three tail kernels (apply / apply_encoded / apply_decode) promise bit-identical results for every activation: all

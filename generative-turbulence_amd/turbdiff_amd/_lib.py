@@ -64,6 +64,10 @@ SIGNATURES = {
     "tdx_gn_apply_decode_act": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _i, _vp]),
     "tdx_gn_apply_encoded_act": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _vp]),
     "tdx_gn_bwd": (_i, [_vp] * 12 + [_i, _i64, _i, _i, _i, _i, _vp, _vp]),
+    "tdx_bn_workspace_bytes": (_sz, [_i64, _i]),
+    "tdx_bn_stats": (_i, [_vp, _vp, _vp, _i64, _i, _f, _i, _vp, _vp]),
+    "tdx_bn_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _f, _i, _vp]),
+    "tdx_bn_bwd": (_i, [_vp] * 8 + [_i64, _i, _f, _i, _i, _vp, _vp]),
     "tdx_resize_fwd": (_i, [_vp, _vp] + [_i] * 9 + [_vp]),
     "tdx_resize_bwd": (_i, [_vp, _vp, _vp] + [_i] * 9 + [_vp]),
     "tdx_attn_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

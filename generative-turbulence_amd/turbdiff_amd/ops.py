@@ -7,6 +7,7 @@ the reference's shapes and float32 (so state_dicts round-trip). 
     conv3            nn.Conv3d(k=3, padding_mode="replicate")            ddpm.py:164
     conv1            nn.Conv3d(k=1) incl. the torch.cat that feeds it     ddpm.py:188,292,293,433,436,459
     gn_film_act      GroupNorm -> addcmul(shift, scale+1, x) -> act (+x)   ddpm.py:165-176,197
+    batch_norm_act   nn.BatchNorm3d -> nn.LeakyReLU (+ add)               tfnet.py:194-195
     resize           F.interpolate(trilinear, align_corners=True)         ddpm.py:359-369
     attention        F.scaled_dot_product_attention                       attention.py:9-15
     q_sample / p_sample_step / masked_loss                                ddpm.py:745-852
@@ -196,6 +197,35 @@ def _gn_bwd(x, gy, stats, gamma, beta, scale, shift, dscale, dshift, B, V, Cc, g
         ws = _gn_ws(B, Cc, x.device)
     L.call("tdx_gn_bwd", L.ptr(x), L.ptr(gy), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(scale), L.ptr(shift), L.ptr(gx),
            L.ptr(dgamma), L.ptr(dbeta), L.ptr(dscale), L.ptr(dshift), B, V, Cc, groups, act, code, L.ptr(ws), st)
+    return gx, dgamma, dbeta
+
+
+def _bn_ws(rows, Cc, dev):
+    return _ws(L.query("tdx_bn_workspace_bytes", rows, Cc), dev)
+
+
+def _bn_stats(x, rows, Cc, eps, code, st):
+    """Batch statistics of the (rows, Cc) view of `x`: (stats (Cc, 2) = (mean, rstd), the biased variance (Cc,))."""
+    stats = torch.empty((Cc, 2), dtype=torch.float32, device=x.device)
+    var = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    L.call("tdx_bn_stats", L.ptr(x), L.ptr(stats), L.ptr(var), rows, Cc, float(eps), code, L.ptr(_bn_ws(rows, Cc, x.device)), st)
+    return stats, var
+
+
+def _bn_apply(x, stats, gamma, beta, add, rows, Cc, slope, code, st):
+    """y = leaky_relu(BN(x; stats), slope) + add; `add` (None, or rows / k rows for an integer k) is broadcast over the
+    leading axis."""
+    y = torch.empty_like(x)
+    L.call("tdx_bn_apply", L.ptr(x), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(add),
+           0 if add is None else add.numel() // Cc, L.ptr(y), rows, Cc, float(slope), code, st)
+    return y
+
+
+def _bn_bwd(x, gy, stats, gamma, beta, rows, Cc, slope, training, code, st):
+    """(gx, dgamma, dbeta) of `_bn_apply`; training: the statistics were the batch's own."""
+    gx, dgamma, dbeta = torch.empty_like(x), stats.new_empty(Cc), stats.new_empty(Cc)
+    L.call("tdx_bn_bwd", L.ptr(x), L.ptr(gy), L.ptr(stats), L.ptr(gamma), L.ptr(beta), L.ptr(gx), L.ptr(dgamma), L.ptr(dbeta),
+           rows, Cc, float(slope), int(training), code, L.ptr(_bn_ws(rows, Cc, x.device)), st)
     return gx, dgamma, dbeta
 
 
@@ -680,6 +710,75 @@ def gn_film_act(x, gamma, beta, groups, scale=None, shift=None, res=None, act=AC
 def gn_film_silu(x, gamma, beta, groups, scale=None, shift=None, res=None, act=True, eps=1e-5, stats=None):
     """gn_film_act with act = SiLU (True) or none (False)."""
     return gn_film_act(x, gamma, beta, groups, scale, shift, res, ACT_SILU if act else ACT_NONE, eps, stats)
+
+
+# --------------------------------------------------------------------------- BatchNorm + LeakyReLU (+ add)
+
+
+class _BatchNormAct(torch.autograd.Function):
+    """y = leaky_relu(BN(x; stats)) + add on NDHWC tensors.  Saves x and the (C, 2) statistics table; the normalised
+    tensor is recomputed in the backward."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, add, stats, slope, training):
+        Cc = x.shape[-1]
+        rows = x.numel() // Cc
+        x = x.contiguous()
+        add = None if add is None else add.contiguous()
+        gamma, beta = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+        y = _bn_apply(x, stats, gamma, beta, add, rows, Cc, slope, L.dtype_code(x.dtype), L.stream())
+        ctx.save_for_backward(x, stats, gamma, beta)
+        ctx.cfg = (float(slope), bool(training), None if add is None else add.shape[0])
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, stats, gamma, beta = ctx.saved_tensors
+        slope, training, add_batch = ctx.cfg
+        Cc = x.shape[-1]
+        gy = gy.contiguous()
+        gx, dgamma, dbeta = _bn_bwd(x, gy, stats, gamma, beta, x.numel() // Cc, Cc, slope, training, L.dtype_code(x.dtype),
+                                    L.stream())
+        gadd = None
+        if add_batch is not None and ctx.needs_input_grad[3]:
+            gadd = gy if add_batch == x.shape[0] else gy.sum(dim=0, keepdim=True, dtype=torch.float32).to(gy.dtype)
+        return gx, dgamma, dbeta, gadd, None, None, None
+
+
+def batch_norm_act_supported(x, bn, add=None) -> bool:
+    """Whether `batch_norm_act` serves this call: a GPU tensor in f32 / bf16 with C % 8 == 0, C <= 512, affine BatchNorm
+    with running statistics and a momentum, at least two rows in training mode, `add` of x's shape or with batch 1."""
+    Cc = x.shape[-1]
+    if not (x.is_cuda and x.dim() == 5 and x.dtype in (torch.float32, torch.bfloat16) and Cc % 8 == 0 and 0 < Cc <= 512):
+        return False
+    rows = x.numel() // Cc
+    if not (bn.affine and bn.track_running_stats and bn.momentum is not None and bn.num_features == Cc):
+        return False
+    if rows >= 2**31 or rows < (2 if bn.training else 1):
+        return False
+    return add is None or (add.dtype == x.dtype and add.shape[1:] == x.shape[1:] and add.shape[0] in (1, x.shape[0]))
+
+
+def batch_norm_act(x, bn, slope, add=None):
+    """nn.BatchNorm3d `bn` -> LeakyReLU(slope) -> (+ add) on an NDHWC tensor x (B, X, Y, Z, C), f32 or bf16: the tail of
+    tfnet's conv() (tfnet.py:194-195) in one statistics pass and one apply pass.  `add` has x's shape, or batch 1 to be
+    broadcast over the batch.  Training mode normalises with the batch statistics and updates the module's running
+    statistics like nn.BatchNorm3d (momentum, unbiased variance, num_batches_tracked); eval mode uses the running ones."""
+    if not batch_norm_act_supported(x, bn, add):
+        raise RuntimeError(f"batch_norm_act: unsupported call (x {tuple(x.shape)} {x.dtype}, training {bn.training})")
+    Cc = x.shape[-1]
+    rows = x.numel() // Cc
+    with torch.no_grad():
+        if bn.training:
+            stats, var = _bn_stats(x.detach().contiguous(), rows, Cc, bn.eps, L.dtype_code(x.dtype), L.stream())
+            m = bn.momentum
+            bn.running_mean.mul_(1.0 - m).add_(stats[:, 0], alpha=m)
+            bn.running_var.mul_(1.0 - m).add_(var, alpha=m * rows / (rows - 1))
+            bn.num_batches_tracked.add_(1)
+        else:
+            stats = torch.stack((bn.running_mean.float(), torch.rsqrt(bn.running_var.float() + bn.eps)), dim=1).contiguous()
+    return _BatchNormAct.apply(x, bn.weight, bn.bias, add, stats, float(slope), bn.training)
 
 
 # --------------------------------------------------------------------------- trilinear resize

@@ -300,6 +300,28 @@ int tdx_gn_bwd(const void* x, const void* dy, const float* stats, const float* g
                const float* scale, const float* shift, void* dx, float* dgamma, float* dbeta, float* dscale,
                float* dshift, int B, int64_t V, int C, int G, int act, int dtype, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------ BatchNorm+LeakyReLU -- */
+/* nn.BatchNorm3d(C) -> nn.LeakyReLU(slope) (-> [+ add]) on channels-last tensors (rows, C), rows = B X Y Z: the tail of
+ * tfnet's conv() blocks (tfnet.py:185-199).  f32 or bf16 storage (TDX_EDTYPE otherwise), f32 parameters and arithmetic.
+ * C % 8 == 0, C <= 512, rows < 2^31; training-mode entries need rows >= 2 (TDX_ESHAPE otherwise, nothing is launched).
+ * stats [C][2] f32 = (mean, rstd): tdx_bn_stats writes the batch statistics (biased variance; `var` [C], may be NULL,
+ * receives that variance for the running statistics), eval mode hands in (running_mean, 1 / sqrt(running_var + eps)).
+ * Every cross-workgroup merge is a fixed-order sum of per-block tables (no atomics): results are reproducible run to run. */
+size_t tdx_bn_workspace_bytes(int64_t rows, int C); /* 0 for an unsupported shape */
+int tdx_bn_stats(const void* x, float* stats, float* var, int64_t rows, int C, float eps, int dtype, void* workspace,
+                 void* stream);
+/* n = (x - mean) rstd gamma + beta;  a = n > 0 ? n : slope n;  y = a + (add ? add : 0).  `add` has add_rows rows:
+ * add_rows == rows, or a divisor of rows (rows / add_rows <= 65535) to broadcast it over the leading (batch) axis. */
+int tdx_bn_apply(const void* x, const float* stats, const float* gamma, const float* beta, const void* add, int64_t add_rows,
+                 void* y, int64_t rows, int C, float slope, int dtype, void* stream);
+/* Backward of tdx_bn_apply w.r.t. x, gamma, beta (the gradient of `add` is dy itself): dn = dy (n > 0 ? 1 : slope), n and
+ * xhat = (x - mean) rstd recomputed; dgamma = sum dn xhat, dbeta = sum dn; training != 0: dx = gamma rstd (dn - mean(dn) -
+ * xhat mean(dn xhat)), the statistics being the batch's; training == 0: dx = gamma rstd dn.  workspace:
+ * tdx_bn_workspace_bytes(). */
+int tdx_bn_bwd(const void* x, const void* dy, const float* stats, const float* gamma, const float* beta, void* dx,
+               float* dgamma, float* dbeta, int64_t rows, int C, float slope, int training, int dtype, void* workspace,
+               void* stream);
+
 /* ------------------------------------------------------------------ trilinear resize --- */
 /* F.interpolate(mode="trilinear", align_corners=True), ddpm.py:359-361, 367-369. */
 int tdx_resize_fwd(const void* x, void* y, int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int C, int dtype,
