@@ -19,17 +19,22 @@ static inline int tdx_launch_status() {
 }
 
 // Launch of a kernel whose dynamic LDS exceeds the default limit: the attribute is set at the kernel's first launch (KERN
-// is a template argument, so every instantiation has its own flag)
+// is a template argument, so every instantiation has its own flag).  lds_max is the attribute's value: the largest lds any
+// launch of KERN asks for, where that varies with the shape
 template <auto KERN, typename... Args>
-static int tdx_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+static int tdx_launch_lds_max(dim3 grid, dim3 block, size_t lds_max, size_t lds, hipStream_t st, Args... args) {
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
     hipLaunchKernelGGL(KERN, grid, block, lds, st, args...);
     return tdx_launch_status();
+}
+template <auto KERN, typename... Args>
+static int tdx_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    return tdx_launch_lds_max<KERN>(grid, block, lds, lds, st, args...);
 }
 
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }

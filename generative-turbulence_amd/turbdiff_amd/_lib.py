@@ -68,6 +68,9 @@ SIGNATURES = {
     "tdx_bn_stats": (_i, [_vp, _vp, _vp, _i64, _i, _f, _i, _vp, _vp]),
     "tdx_bn_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _f, _i, _vp]),
     "tdx_bn_bwd": (_i, [_vp] * 8 + [_i64, _i, _f, _i, _i, _vp, _vp]),
+    "tdx_flow_decompose_workspace_bytes": (_sz, [_i] * 7),
+    "tdx_flow_decompose_fwd": (_i, [_vp] * 6 + [_i] * 8 + [_vp]),
+    "tdx_flow_decompose_bwd": (_i, [_vp] * 9 + [_i] * 8 + [_vp, _vp]),
     "tdx_resize_fwd": (_i, [_vp, _vp] + [_i] * 9 + [_vp]),
     "tdx_resize_bwd": (_i, [_vp, _vp, _vp] + [_i] * 9 + [_vp]),
     "tdx_attn_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

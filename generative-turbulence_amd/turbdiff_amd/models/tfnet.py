@@ -5,8 +5,11 @@ Same constructor, attribute paths and ``state_dict`` as the reference (``spatial
 either way with ``strict=True``.  ``forward(xx, C)`` takes (B, T, F, X, Y, Z) and returns (B, F, X, Y, Z) fp32.
 
 * The flow decomposition (tfnet.py:304-337: spatial filter, temporal filter over windows, the two residuals, the ``(t f)``
-  stacking) runs as torch ops in fp32 on NCDHW tensors.  The three stacks then cross to NDHWC in the compute dtype (that of
-  ``xx``, or ``dtype``), zero-padded to a channel multiple of 8 like ``models.dilresnet`` pads its state.
+  stacking) and the crossing of its three stacks to NDHWC in the compute dtype (that of ``xx``, or ``dtype``), zero-padded to
+  a channel multiple of 8 like ``models.dilresnet`` pads its state, are one kernel forward and one backward
+  (``ops.flow_decompose``, csrc/tdx_flow_decompose.hip; ``FUSE_DECOMPOSE``, on by default).  A call the kernels do not take
+  (CPU tensors, a non-fp32 ``xx``, T > 8, F > 8, T F > 32, a grid past the bounds of include/tdx.h) or the
+  switch off runs ``decompose`` -- fp32 torch ops on NCDHW tensors -- and ``_to_nvc_padded``, as before.
 * Every conv() block is a ``ConvBlock``: ``ops.conv3d`` and the fused BatchNorm + LeakyReLU (+ add) tail
   (``ops.batch_norm_act``; ``baseline_convs.FUSE_BATCHNORM``, on by default).  The conditioning branch
   ``conv1_local(c_local[None])`` enters level 1 as the tail's batch-broadcast addend.  At level 4, whose three outputs are only ever summed, the second and third
@@ -27,6 +30,10 @@ from .. import ops
 from .baseline_convs import ConvBlock, conv, deconv
 from .conditioning import global_conditioning, local_conditioning
 from .dilresnet import _pad_conv, _to_nvc_padded, _up8
+
+# LES.forward takes ops.flow_decompose (csrc/tdx_flow_decompose.hip) for every call it supports; False: decompose() and
+# three _to_nvc_padded calls in torch, everywhere
+FUSE_DECOMPOSE = True
 
 
 def _first_block(blk: ConvBlock, x: torch.Tensor, add=None) -> torch.Tensor:
@@ -131,11 +138,16 @@ class LES(nn.Module):
         if c_enc is None or self.training:
             c_enc = self.encode_conditioning(C, dtype)
         c_enc = c_enc or (None, None, None)
-        stacks = self.decompose(xx)
-        cp = _up8(stacks[0].shape[1])
+        sw, tw = self.spatial_filter.weight, self.temporal_filter.weight
+        if FUSE_DECOMPOSE and ops.flow_decompose_supported(xx, sw, tw, dtype):
+            stacks = ops.flow_decompose(xx, sw, tw, dtype)
+        else:
+            stacks = self.decompose(xx)
+            cp = _up8(stacks[0].shape[1])
+            stacks = (_to_nvc_padded(u, cp, dtype) for u in stacks)  # made one at a time, as each encoder takes its own
         levels, sum4 = [], None
         for enc, u, c in zip(self.encoders, stacks, c_enc):
-            o1, o2, o3, sum4 = enc(_to_nvc_padded(u, cp, dtype), c, sum4)
+            o1, o2, o3, sum4 = enc(u, c, sum4)
             levels.append((o1, o2, o3))
         out1, out2, out3 = (a + b + c for a, b, c in zip(*levels))
         d3 = self.deconv3(sum4)

@@ -229,6 +229,29 @@ def _bn_bwd(x, gy, stats, gamma, beta, rows, Cc, slope, training, code, st):
     return gx, dgamma, dbeta
 
 
+def _flow_decompose_fwd(xx, sw, tw, dtype, st):
+    """(bar, tilde, prime) (B, X, Y, Z, up8(n F)) in `dtype` of xx (B, T, F, X, Y, Z) f32; sw (27,), tw (L,) f32."""
+    B, T, Fn, X, Y, Z = xx.shape
+    Ln = tw.numel()
+    cp = -(-(T - Ln + 1) * Fn // 8) * 8
+    out = [torch.empty((B, X, Y, Z, cp), dtype=dtype, device=xx.device) for _ in range(3)]
+    L.call("tdx_flow_decompose_fwd", L.ptr(xx), L.ptr(sw), L.ptr(tw), L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), B, T, Ln, Fn,
+           X, Y, Z, L.dtype_code(dtype), st)
+    return tuple(out)
+
+
+def _flow_decompose_bwd(xx, sw, tw, gb, gt, gp, need_gxx, dtype, st):
+    """(gxx or None, gS (27,), gw (L,)) of `_flow_decompose_fwd`; gb / gt / gp in the outputs' layout and dtype, or None."""
+    B, T, Fn, X, Y, Z = xx.shape
+    Ln = tw.numel()
+    gxx = torch.empty_like(xx) if need_gxx else None
+    gs, gw = sw.new_empty(27), sw.new_empty(Ln)
+    ws = _ws(L.query("tdx_flow_decompose_workspace_bytes", B, T, Ln, Fn, X, Y, Z), xx.device)
+    L.call("tdx_flow_decompose_bwd", L.ptr(xx), L.ptr(sw), L.ptr(tw), L.ptr(gb), L.ptr(gt), L.ptr(gp), L.ptr(gxx), L.ptr(gs),
+           L.ptr(gw), B, T, Ln, Fn, X, Y, Z, L.dtype_code(dtype), L.ptr(ws), st)
+    return gxx, gs, gw
+
+
 def _resize_fwd(x, size):
     """(x resampled to grid `size`, the geometry that `_resize_bwd` takes)."""
     B, Xi, Yi, Zi, Cc = _grid(x)
@@ -779,6 +802,62 @@ def batch_norm_act(x, bn, slope, add=None):
         else:
             stats = torch.stack((bn.running_mean.float(), torch.rsqrt(bn.running_var.float() + bn.eps)), dim=1).contiguous()
     return _BatchNormAct.apply(x, bn.weight, bn.bias, add, stats, float(slope), bn.training)
+
+
+# --------------------------------------------------------------------------- TF-Net flow decomposition
+
+
+class _FlowDecompose(torch.autograd.Function):
+    """(bar, tilde, prime) of tfnet's decomposition as NDHWC tensors.  Saves xx and the two filters; u* is recomputed in
+    the backward."""
+
+    @staticmethod
+    def forward(ctx, xx, spatial_w, temporal_w, dtype):
+        xx = xx.contiguous()
+        sw, tw = spatial_w.detach().float().reshape(27).contiguous(), temporal_w.detach().float().reshape(-1).contiguous()
+        out = _flow_decompose_fwd(xx, sw, tw, dtype, L.stream())
+        ctx.save_for_backward(xx, sw, tw)
+        ctx.cfg = (dtype, spatial_w.shape, temporal_w.shape)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gb, gt, gp):
+        xx, sw, tw = ctx.saved_tensors
+        dtype, s_shape, t_shape = ctx.cfg
+        gb, gt, gp = (None if g is None else g.contiguous() for g in (gb, gt, gp))
+        gxx, gs, gw = _flow_decompose_bwd(xx, sw, tw, gb, gt, gp, ctx.needs_input_grad[0], dtype, L.stream())
+        return gxx, gs.reshape(s_shape), gw.reshape(t_shape), None
+
+
+def flow_decompose_supported(xx, spatial_w, temporal_w, dtype) -> bool:
+    """Whether `flow_decompose` serves this call: xx a contiguous f32 GPU tensor (B, T, F, X, Y, Z), filters of
+    nn.Conv3d(1, 1, 3) and nn.Conv3d(L, 1, 1) in f32, dtype f32 / bf16, and a shape the library takes
+    (1 <= L <= T <= 8, F <= 8, T F <= 32, X Y Z < 2^31 in fewer than 2^24 tiles: include/tdx.h)."""
+    if not (xx.is_cuda and xx.dim() == 6 and xx.dtype == torch.float32 and xx.is_contiguous()):
+        return False
+    if dtype not in (torch.float32, torch.bfloat16):
+        return False
+    if not (spatial_w.is_cuda and temporal_w.is_cuda and spatial_w.dtype == temporal_w.dtype == torch.float32):
+        return False
+    if tuple(spatial_w.shape) != (1, 1, 3, 3, 3) or temporal_w.dim() != 5 or tuple(temporal_w.shape) != (1, temporal_w.shape[1], 1, 1, 1):
+        return False
+    B, T, Fn, X, Y, Z = xx.shape
+    if min(xx.shape) < 1 or max(xx.shape) >= 2**31:
+        return False
+    return L.query("tdx_flow_decompose_workspace_bytes", B, T, temporal_w.shape[1], Fn, X, Y, Z) > 0
+
+
+def flow_decompose(xx, spatial_w, temporal_w, dtype):
+    """tfnet.py:304-337 in one pass: xx (B, T, F, X, Y, Z) f32, `spatial_w` (1, 1, 3, 3, 3), `temporal_w` (1, L, 1, 1, 1)
+    -> (u_bar, u_tilde, u_prime), each NDHWC (B, X, Y, Z, up8((T - L + 1) F)) in `dtype`, channel t' F + f, the padding
+    channels zero: what LES.decompose followed by three _to_nvc_padded calls gives.  Gradients to xx (only when it needs
+    one) and to both filters."""
+    if not flow_decompose_supported(xx, spatial_w, temporal_w, dtype):
+        raise RuntimeError(f"flow_decompose: unsupported call (xx {tuple(xx.shape)} {xx.dtype}, filters {tuple(spatial_w.shape)} "
+                           f"{tuple(temporal_w.shape)}, dtype {dtype})")
+    return _FlowDecompose.apply(xx, spatial_w, temporal_w, dtype)
 
 
 # --------------------------------------------------------------------------- trilinear resize

@@ -322,6 +322,26 @@ int tdx_bn_bwd(const void* x, const void* dy, const float* stats, const float* g
                float* dgamma, float* dbeta, int64_t rows, int C, float slope, int training, int dtype, void* workspace,
                void* stream);
 
+/* ------------------------------------------------------------------ TF-Net flow decomposition -- */
+/* tfnet's decomposition (tfnet.py:304-337) in one pass.  xx (B, T, F, X, Y, Z) f32; spatial_w [27] (3x3x3, zero padding,
+ * cross-correlation like nn.Conv3d), temporal_w [L]; n = T - L + 1:
+ *   u*[t] = sum_d S[d] xx[t, f, v + d];  bar[t'] = sum_l w[l] u*[t' + l];  tilde[t'] = u*[L-1+t'] - bar[t'];
+ *   prime[t'] = xx[L-1+t'] - u*[L-1+t']
+ * bar / tilde / prime: NDHWC (B, X, Y, Z, Cp), Cp = up8(n F), channel t' F + f, channels >= n F written as zeros, f32 or
+ * bf16 storage (TDX_EDTYPE otherwise), f32 arithmetic, one rounding at the store.  1 <= L <= T <= 8, F <= 8, T F <= 32,
+ * any B, X Y Z < 2^31 and ceil(X/4) ceil(Y/4) ceil(Z/16) < 2^24 tiles (only a grid thinner than a tile reaches that,
+ * 1 x 1 x Z from Z > 2^28 - 16) (TDX_ESHAPE otherwise: nothing is launched, nothing written). */
+size_t tdx_flow_decompose_workspace_bytes(int B, int T, int L, int F, int X, int Y, int Z); /* 0 for an unsupported shape */
+int tdx_flow_decompose_fwd(const float* xx, const float* spatial_w, const float* temporal_w, void* bar, void* tilde, void* prime,
+                           int B, int T, int L, int F, int X, int Y, int Z, int dtype, void* stream);
+/* Backward: gbar / gtilde / gprime in the outputs' layout and dtype (NULL: zeros); gxx f32 in xx's layout (NULL: not
+ * wanted, the transposed stencil is skipped), gspatial [27], gtemporal [L] f32.  u* is recomputed from xx.  The sums over
+ * workgroups are fixed-order sums of per-workgroup f64 tables in `workspace` (tdx_flow_decompose_workspace_bytes; no
+ * atomics): results are reproducible run to run, and gspatial / gtemporal do not depend on whether gxx is asked for. */
+int tdx_flow_decompose_bwd(const float* xx, const float* spatial_w, const float* temporal_w, const void* gbar, const void* gtilde,
+                           const void* gprime, float* gxx, float* gspatial, float* gtemporal, int B, int T, int L, int F, int X,
+                           int Y, int Z, int dtype, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------ trilinear resize --- */
 /* F.interpolate(mode="trilinear", align_corners=True), ddpm.py:359-361, 367-369. */
 int tdx_resize_fwd(const void* x, void* y, int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int C, int dtype,

@@ -3,7 +3,9 @@
 (config/model/tfnet.yaml: context 6, temporal filter 4, kernel 3) on the shapes dataset's 194 x 50 x 50 grid, synthetic
 seeded data, the implementations timed alternately in one process after warm-up:
 
-  fused      bf16, every ConvBlock tail on ops.batch_norm_act (csrc/tdx_batchnorm.hip), the default
+  fused      bf16, every ConvBlock tail on ops.batch_norm_act (csrc/tdx_batchnorm.hip) and the flow decomposition on
+             ops.flow_decompose (csrc/tdx_flow_decompose.hip), the default
+  decomp-off bf16, tfnet.FUSE_DECOMPOSE = False: LES.decompose + three _to_nvc_padded calls in torch, tails fused
   unfused    bf16, baseline_convs.FUSE_BATCHNORM = False: F.batch_norm + F.leaky_relu + casts + adds in torch
   f32        the fp32 parity path (vector-ALU convg kernels), fused tails
   torch      (--torch) stock PyTorch-ROCm nn modules, bf16 autocast and fp32, NCDHW
@@ -12,9 +14,12 @@ and the BatchNorm tail alone at each level's shape, fused against the torch sequ
 backward: between HIP events on the stream (launch gaps and the (C,)-sized running-statistics ops included), median and min-max
 over --tail-reps alternating runs; and the kernel time alone (sum of the device-kernel durations from torch.profiler).  The
 bytes the passes must move (computed from the shapes below) over either time are set against the HBM roof (8.0 TB/s spec; a
-float4 copy reaches 6.3).
+float4 copy reaches 6.3).  The flow decomposition alone is measured the same way (kernel time of the torch chain against the
+op: forward at the eval batch, forward + backward at the training batch with and without a gradient to xx), each step prints
+its peak memory per implementation, and the chain's kernel time is set against the step of the torch route.
 
     python tools/tfnet_bench.py [--reps 3] [--train-batch 8] [--eval-batch 16] [--unroll 4] [--torch]
+                                [--skip-tails] [--skip-decompose] [--skip-model] [--impls fused,decomp-off,unfused,f32]
 
 GPU only: exits with an error without one.
 """
@@ -194,6 +199,85 @@ def bench_tails(args, dev):
         sys.stdout.flush()
 
 
+def decompose_bytes(B, V, es, backward=False, gxx=False):
+    """Bytes the decomposition must move: xx read once, three Cp-channel grids written; the backward adds the three gradient
+    grids read and, with a gradient to xx, gxx written.  (The backward's second read of xx for the recomputed u* is not
+    counted: it is the price of saving nothing.)"""
+    T, Fn, Ln = CFG["context_window"], CFG["n_features"], CFG["temporal_filtering_length"]
+    cp = -(-(T - Ln + 1) * Fn // 8) * 8
+    n = B * T * Fn * V * 4 + 3 * B * V * cp * es
+    if backward:
+        n += 3 * B * V * cp * es + (B * T * Fn * V * 4 if gxx else 0)
+    return n
+
+
+def bench_decompose(args, dev, net):
+    """The decomposition + layout chain (LES.decompose + three _to_nvc_padded, autograd) against ops.flow_decompose, bf16:
+    kernel time (device records) of both routes, alternating.  Returns {case: (chain ms, op ms)}."""
+    from turbdiff_amd import ops
+    from turbdiff_amd.models.dilresnet import _to_nvc_padded, _up8
+
+    T, Fn = CFG["context_window"], CFG["n_features"]
+    V = GRID[0] * GRID[1] * GRID[2]
+    sw, tw = net.spatial_filter.weight, net.temporal_filter.weight
+    dt = torch.bfloat16
+
+    def chain(xx):
+        stacks = net.decompose(xx)
+        return tuple(_to_nvc_padded(u, _up8(u.shape[1]), dt) for u in stacks)
+
+    def op(xx):
+        return ops.flow_decompose(xx, sw, tw, dt)
+
+    print(f"# flow decomposition at {GRID}, T = {T}, L = {CFG['temporal_filtering_length']}, F = {Fn}, bf16: kernel time (sum of the "
+          f"device records), median [min-max] over {args.decompose_reps} alternating runs; bytes = xx + 3 grids (+ 3 gradient grids "
+          f"+ gxx), over the op's time against the {HBM_SPEC / 1e12:.1f} TB/s spec roof and the {HBM_COPY / 1e12:.1f} TB/s copy roof")
+    out = {}
+    cases = (("fwd", args.eval_batch, False, False), ("fwd+bwd, gxx", args.train_batch, True, True),
+             ("fwd+bwd, no gxx", args.train_batch, True, False))
+    for name, B, backward, gxx in cases:
+        g = torch.Generator(device=dev).manual_seed(7)
+        xx = torch.randn(B, T, Fn, *GRID, device=dev, generator=g)
+        grads = None
+        if backward:
+            cp = _up8((T - CFG["temporal_filtering_length"] + 1) * Fn)
+            grads = [torch.randn(B, *GRID, cp, device=dev, generator=g).to(dt) for _ in range(3)]
+
+        def run(route):
+            def fn():
+                if not backward:
+                    with torch.no_grad():
+                        route(xx)
+                    return
+                xl = xx.detach().requires_grad_(gxx)
+                torch.autograd.backward(route(xl), grads)
+                net.spatial_filter.weight.grad = net.temporal_filter.weight.grad = None
+            return fn
+
+        fns = {"chain": run(chain), "op": run(op)}
+        for f in fns.values():
+            f(), f()
+        ms = {k: [] for k in fns}
+        for _ in range(args.decompose_reps):
+            for k, f in fns.items():
+                t = kernel_ms(f, reps=1)
+                if t is not None:
+                    ms[k].append(t)
+        if not ms["chain"] or not ms["op"]:
+            print(f"decompose {name:16s} B {B:2d}: kernel time not measured")
+            continue
+        mc, mo = statistics.median(ms["chain"]), statistics.median(ms["op"])
+        nbytes = decompose_bytes(B, V, 2, backward, gxx)
+        rate = nbytes / (mo * 1e-3)
+        print(f"decompose {name:16s} B {B:2d}: chain {mc:8.3f} [{min(ms['chain']):.3f}-{max(ms['chain']):.3f}]  op {mo:7.3f} "
+              f"[{min(ms['op']):.3f}-{max(ms['op']):.3f}]  x{mc / mo:5.2f}  {nbytes / 1e6:8.1f} MB -> {rate / 1e9:6.0f} GB/s = "
+              f"{100 * rate / HBM_SPEC:4.1f} % of spec, {100 * rate / HBM_COPY:4.1f} % of copy")
+        out[name] = (mc, mo)
+        del xx, grads
+        sys.stdout.flush()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -203,12 +287,15 @@ def main():
     ap.add_argument("--eval-batch", type=int, default=16)
     ap.add_argument("--unroll", type=int, default=4)
     ap.add_argument("--torch", action="store_true", help="also time stock PyTorch-ROCm nn modules (bf16 autocast and fp32)")
-    ap.add_argument("--skip-model", action="store_true", help="only the BatchNorm tails")
-    ap.add_argument("--impls", default="fused,unfused,f32", help="comma list of the HIP implementations to time")
+    ap.add_argument("--decompose-reps", type=int, default=5)
+    ap.add_argument("--skip-tails", action="store_true", help="skip the BatchNorm tails")
+    ap.add_argument("--skip-decompose", action="store_true", help="skip the flow decomposition alone")
+    ap.add_argument("--skip-model", action="store_true", help="only the BatchNorm tails and the flow decomposition")
+    ap.add_argument("--impls", default="fused,decomp-off,unfused,f32", help="comma list of the HIP implementations to time")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("tfnet_bench.py needs a GPU")
-    from turbdiff_amd.models import baseline_convs
+    from turbdiff_amd.models import baseline_convs, tfnet
     from turbdiff_amd.models.conditioning import Conditioning
     from turbdiff_amd.models.tfnet import LES
     from turbdiff_amd.optim import ClipAdam
@@ -217,15 +304,16 @@ def main():
     torch.manual_seed(0)
     print(f"# kernel-source hash {kernel_source_hash()}  torch {torch.__version__}  device {torch.cuda.get_device_name(0)}")
     print(f"# grid {GRID}, train B = {args.train_batch} unroll {args.unroll}, eval B = {args.eval_batch}")
-    bench_tails(args, dev)
-    if args.skip_model:
-        return
-
+    if not args.skip_tails:
+        bench_tails(args, dev)
     net = LES(**CFG).to(dev)
     with torch.no_grad():  # the reference's 0.002 / n initialisation gives activations of 1e-9: use visible weights
         for p in net.parameters():
             if p.ndim == 5:
                 p.normal_(0, (1.0 / p[0].numel()) ** 0.5)
+    chain = {} if args.skip_decompose else bench_decompose(args, dev, net)
+    if args.skip_model:
+        return
     tnet = TorchLES(net)
     opt = ClipAdam(net.parameters(), lr=1e-7, max_norm=None)
     g = torch.Generator(device=dev).manual_seed(1)
@@ -242,10 +330,12 @@ def main():
             with torch.autocast("cuda", dtype=torch.bfloat16, enabled=impl == "torch-bf16"):
                 return tnet(xx, c).float()
         baseline_convs.FUSE_BATCHNORM = impl != "unfused"
+        tfnet.FUSE_DECOMPOSE = impl != "decomp-off"
         try:
             return net(xx, C, dtype=torch.float32 if impl == "f32" else torch.bfloat16)
         finally:
             baseline_convs.FUSE_BATCHNORM = True
+            tfnet.FUSE_DECOMPOSE = fuse_decompose_default
 
     def unroll(impl, xx, steps):
         out = []
@@ -270,6 +360,9 @@ def main():
             unroll(impl, xe, 1)
         return run
 
+    fuse_decompose_default = tfnet.FUSE_DECOMPOSE
+    print(f"# fused = bf16, FUSE_BATCHNORM and FUSE_DECOMPOSE on; decomp-off = fused with tfnet.FUSE_DECOMPOSE = False (LES.decompose + "
+          f"_to_nvc_padded in torch); shipped default FUSE_DECOMPOSE = {fuse_decompose_default}")
     impls = args.impls.split(",") + (["torch-bf16", "torch-f32"] if args.torch else [])
     for wname, make in ((f"train B={args.train_batch} unroll {args.unroll}", train_step), (f"eval step B={args.eval_batch}", eval_step)):
         fns = {i: make(i) for i in impls}
@@ -277,16 +370,33 @@ def main():
         for i in impls:
             for _ in range(args.warmup):
                 fns[i]()
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            fns[i]()
+            torch.cuda.synchronize()
+            print(f"{wname:22s} {i:11s} peak memory {torch.cuda.max_memory_allocated() / 2**30:7.2f} GiB")
         for _ in range(args.reps):  # alternate the implementations
             for i in impls:
                 times[i].append(timed(fns[i]))
         for i in impls:
             print(f"{wname:22s} {i:11s} {statistics.median(times[i]):10.2f} ms  [min {min(times[i]):.2f} max {max(times[i]):.2f}, n {len(times[i])}]")
-        if not {"fused", "unfused"} <= set(impls):
-            continue
-        f, u = times["fused"], times["unfused"]
-        print(f"{wname:22s} unfused - fused = {statistics.median(u) - statistics.median(f):.2f} ms; run-to-run spread: fused "
-              f"{max(f) - min(f):.2f} ms, unfused {max(u) - min(u):.2f} ms")
+        for other in ("unfused", "decomp-off"):
+            if not {"fused", other} <= set(impls):
+                continue
+            f, u = times["fused"], times[other]
+            print(f"{wname:22s} {other} - fused = {statistics.median(u) - statistics.median(f):.2f} ms; run-to-run spread: fused "
+                  f"{max(f) - min(f):.2f} ms, {other} {max(u) - min(u):.2f} ms")
+        if "decomp-off" in impls and chain:  # the chain's share of the step on the torch route (kernel time over wall time)
+            if make is train_step and {"fwd+bwd, gxx", "fwd+bwd, no gxx"} <= set(chain):
+                ms = chain["fwd+bwd, no gxx"][0] + (args.unroll - 1) * chain["fwd+bwd, gxx"][0]
+            elif make is eval_step and "fwd" in chain:
+                ms = chain["fwd"][0]
+            else:
+                ms = None
+            if ms is not None:
+                step = statistics.median(times["decomp-off"])
+                print(f"{wname:22s} decomposition + layout chain on the torch route: {ms:.2f} ms of kernel time = {100 * ms / step:.1f} % "
+                      f"of the {step:.2f} ms step")
         sys.stdout.flush()
     print(f"# peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
 
