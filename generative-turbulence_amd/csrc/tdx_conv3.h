@@ -49,6 +49,9 @@ struct Conv3Call {
     double* gn_acc;          // forward: per-channel f64 moments are added here (tdx_conv3_fwd_gn)
     void* d1; int D1; void* d2;
     const void* a1; const void* a2;
+    // conv3_ring_launch only, data gradient of a block with a projected 1x1 skip: d1 | d2 += skip_x [voxel][C1] . skip_w [C1][N]
+    // (f32) inside the kernel (conv3_ring_skip_supported says when)
+    const void* skip_x; const float* skip_w;
     hipStream_t st;
     int fmt;                 // TDX_BF16 / TDX_F16 / TDX_F32 / TDX_F32_SPLIT: tensors and operand (split: fp32 tensors)
     const Conv3Ext* ext;     // conv3_mfma_launch only
@@ -114,6 +117,9 @@ int conv3_fold_launch(const Conv3Call& c);
 // the arena's zero block)
 int conv3_ring_depth(int C1, int C2, int N, int B, int X, int Y, int Z, bool data_gradient);
 int conv3_ring_launch(const Conv3Call& c, int depth);
+// may the data gradient (K channels of dy -> N of dx) on bricks of this depth carry the skip term of Conv3Call::skip_x?
+// Reads TDX_SKIP_DGRAD_FUSE (0: never) and TDX_RING_LOADERS per call.
+bool conv3_ring_skip_supported(int fmt, int depth, int K, int N, int X, int Y, int Z);
 
 // small-grid conv (tdx_conv3_small.hip; 16-bit tensors, or fp32 tensors with split-precision products): forward or data
 // gradient (halo fold included).  Needs the scratch arena.  conv3_small_plan: false = not a small-grid case.

@@ -166,16 +166,23 @@ extern "C" size_t tdx_conv3_bwd_data_workspace_bytes(int B, int X, int Y, int Z,
 // grid (the conv kernel, epilogue writes dx incl. the fused addend), then the halo-shell term added by conv3_shell_launch.
 // Small-grid kernel: adjoint on the padded grid, halo fold in its reduce pass.  Vector-ALU path: correlation on the
 // padded grid into the workspace, then the fold.
+// skip_dy / skip_w (tdx_conv3_bwd_data_skip): the skip term rides in the ring kernel's main-term launch; a call the route does
+// not give to that kernel variant is refused, never served another way.
+static bool conv3_skip_routed(const Conv3Route& r, int Cin, int Cout, int X, int Y, int Z) {
+    return r.status == TDX_OK && r.family == TDX_KERNEL_RING && conv3_ring_skip_supported(r.fmt, r.ring_depth, Cout, Cin, X, Y, Z);
+}
 static int conv3_bwd_data_impl(const void* dy, const void* wb, void* dx1, int C1, void* dx2, int C2, const void* add1,
                                const void* add2, int B, int X, int Y, int Z, int Cout, int dtype, int impl,
-                               void* workspace, void* stream) {
+                               void* workspace, void* stream, const void* skip_dy = nullptr, const float* skip_w = nullptr) {
     TDX_CHECK_ARG(dy && wb && dx1 && workspace && B > 0 && X > 0 && Y > 0 && Z > 0 && C1 > 0 && C2 >= 0 && Cout > 0);
     TDX_CHECK_ARG(C2 == 0 || dx2);
     const int Cin = C1 + C2;
     if ((C1 % 8) || (C2 % 8) || (Cout % 8)) return TDX_ESHAPE;
     const Conv3Route r = conv3_route(dtype, impl, Cout, 0, Cin, B, X, Y, Z, true);
     if (r.status != TDX_OK) return r.status;
+    if (skip_dy != nullptr && !conv3_skip_routed(r, Cin, Cout, X, Y, Z)) return TDX_ESHAPE;
     Conv3Call c = {};
+    c.skip_x = skip_dy; c.skip_w = skip_w;
     c.x1 = dy; c.C1 = Cout; c.wp = wb;
     c.B = B; c.X = X; c.Y = Y; c.Z = Z; c.N = Cin;
     c.zero_pad = true;
@@ -200,6 +207,19 @@ extern "C" int tdx_conv3_bwd_data_add(const void* dy, const void* wb, void* dx1,
                                       const void* add1, const void* add2, int B, int X, int Y, int Z, int Cout, int dtype,
                                       int impl, void* workspace, void* stream) {
     return conv3_bwd_data_impl(dy, wb, dx1, C1, dx2, C2, add1, add2, B, X, Y, Z, Cout, dtype, impl, workspace, stream);
+}
+
+extern "C" int tdx_conv3_bwd_data_skip_supported(int C1, int C2, int Cout, int B, int X, int Y, int Z, int dtype, int impl) {
+    if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || C1 <= 0 || C2 < 0 || Cout <= 0 || (C1 % 8) || (C2 % 8) || (Cout % 8)) return 0;
+    return conv3_skip_routed(conv3_route(dtype, impl, Cout, 0, C1 + C2, B, X, Y, Z, true), C1 + C2, Cout, X, Y, Z) ? 1 : 0;
+}
+
+extern "C" int tdx_conv3_bwd_data_skip(const void* dy, const void* wb, void* dx1, int C1, void* dx2, int C2, const void* skip_dy,
+                                       const float* skip_w, int B, int X, int Y, int Z, int Cout, int dtype, int impl,
+                                       void* workspace, void* stream) {
+    TDX_CHECK_ARG(skip_dy && skip_w);
+    return conv3_bwd_data_impl(dy, wb, dx1, C1, dx2, C2, nullptr, nullptr, B, X, Y, Z, Cout, dtype, impl, workspace, stream,
+                               skip_dy, skip_w);
 }
 
 #define W3_MAX_SLABS 8

@@ -61,6 +61,9 @@ struct RingArgs {
     bf16* d1; bf16* d2; int D1; const bf16* a1; const bf16* a2;   // data gradient: dx split over two tensors, fused addends
     const void* zeros;                   // >= 16 zero bytes (zero padding)
     unsigned long long* stamps;          // diagnostic builds only
+    // SK > 0 (data gradient of a block with a projected skip): dx += skx [voxel][skC] . skw [skC][skN], one more K = skC
+    // contraction on the accumulator tile at the end of a brick's K loop (conv3_ring_kernel, SK)
+    const bf16* skx; int skC; const float* skw; int skN;
 };
 
 // lds_dma16 (tdx_mfma.h) with a uniform 64-bit base and a 32-bit per-lane byte offset
@@ -130,8 +133,19 @@ struct RingShape {
                                   64 /* zero entry */ + BN * 4 /* bias */ + (size_t)RG_WAVES * BN * 2 * 4 /* statistics */;
 };
 
-template <int NT, bool ZP, int LW, bool HF, bool Z4>
+// SK (data gradient, ZP, only): K steps of the skip term dx[v][n] += sum_k gy[v][k] wr[k][n], k < 16 SK -- the input gradient of
+// a ResnetBlock's 1x1 skip projection, which otherwise costs a pass of its own over the dx tensor (read the adjoint back, add,
+// write again).  Its operands do not go through the brick image or the weight ring: wr for this workgroup's N tile (32 x BN
+// 16-bit words = 4 KiB at SK = 2, BN = 64) sits in the statistics scratch sRed, which the data gradient never touches, in the
+// weight slot's entry layout [2 s + hh][BN] x 16 B; a lane's gy fragment is 16 B of its own voxel's row, loaded straight from
+// HBM at the top of the brick's last unit and consumed behind that unit's 56 MFMAs.  No barrier, no LDS-DMA, no counted wait
+// is added; the loader waves do not take part.
+// The body must stay the __global__ function itself: behind a call, even a forced-inline one, hipcc splits the epilogue's 16-B
+// stores (global_store_dwordx4 -> dwordx3 + dword) in every instantiation.  SK = 0 compiles to the code from before the argument.
+template <int NT, bool ZP, int LW, bool HF, bool Z4, int SK = 0>
 __global__ void __launch_bounds__(512 + 64 * LW, LW ? 3 : 2) conv3_ring_kernel(RingArgs A) {
+    static_assert(SK == 0 || (ZP && LW > 0 && !Z4 && 2 * SK * (NT * 32) * 16 == RG_WAVES * (NT * 32) * 2 * 4),
+                  "skip term: data gradient, loader form, 8-deep bricks, wr fills exactly the statistics scratch");
     typedef RingShape<NT, LW, Z4> S;
     typedef H16<HF> H;                  // operand format: bf16 or fp16 words (the pointers of RingArgs are raw 16-bit rows)
     typedef typename H::T HT;
@@ -173,6 +187,16 @@ __global__ void __launch_bounds__(512 + 64 * LW, LW ? 3 : 2) conv3_ring_kernel(R
 
     if (tid < BN) sBias[tid] = A.bias ? A.bias[n0 + tid] : 0.f;
     if (tid < 16) reinterpret_cast<unsigned*>(sZ)[tid] = 0u;
+    if (SK > 0 && tid < 2 * SK * BN) {
+        // entry [kg = 2 s + hh][c]: wr[8 kg .. 8 kg + 7][n0 + c], converted like the 1x1 kernel's weights
+        const int kg = tid / BN, c = tid % BN;
+        const float* wsrc = A.skw + (size_t)(8 * kg) * A.skN + n0 + c;
+        float wv[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) wv[j] = wsrc[(size_t)j * A.skN];
+        reinterpret_cast<uint4*>(sRed)[tid] =
+            make_uint4(H::pack2(wv[0], wv[1]), H::pack2(wv[2], wv[3]), H::pack2(wv[4], wv[5]), H::pack2(wv[6], wv[7]));
+    }
     lds_barrier();
 
     // ---- per-lane DMA geometry (fixed for the kernel)
@@ -375,7 +399,18 @@ __global__ void __launch_bounds__(512 + 64 * LW, LW ? 3 : 2) conv3_ring_kernel(R
                 }
             }
 
+        // skip term: this lane's gy fragments (K step s, M tile mt: channels 16 s + 8 hh .. + 7 of the lane's own voxel)
+        uint4 skf[SK > 0 ? SK : 1][MT];
         for (int c8 = 0; c8 < nun; ++c8, ++u) {
+            if (SK > 0 && c8 == nun - 1) {
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    const int64_t sv = (int64_t)b * V + (o0 + wave * XP + mt / 2) * YZ + (o1 + 4 * (mt % 2) + ly) * A.Z + o2 + lz;
+#pragma unroll
+                    for (int s = 0; s < SK; ++s)
+                        skf[s][mt] = *reinterpret_cast<const uint4*>(A.skx + sv * A.skC + 16 * s + 8 * hh);
+                }
+            }
             // ---- arrival of this unit's brick (issued one unit ago) and weights (two units ago): the only younger
             // copies are the weights of the next unit; the stores of a brick's epilogue sit behind its successor's
             // first unit's operands
@@ -440,6 +475,21 @@ __global__ void __launch_bounds__(512 + 64 * LW, LW ? 3 : 2) conv3_ring_kernel(R
                     if (++ws == nun) ws = 0;
                     if (++qs == nun) { qs = 0; ++qb; plan_brick(qb); }
                 }
+            }
+        }
+
+        if (SK > 0) {
+#pragma unroll
+            for (int s = 0; s < SK; ++s) {
+                bf16x8 wsk[NT];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    wsk[nt] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const unsigned char*>(sRed) + s * (2 * BN * 16) + b_off[nt]);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+                        acc[nt][mt] = H::mfma(wsk[nt], __builtin_bit_cast(bf16x8, skf[s][mt]), acc[nt][mt]);
             }
         }
 
@@ -578,7 +628,7 @@ static bool ring_z8_supported(int C1, int C2, int Cout, int B, int X, int Y, int
 static unsigned long long* rg_stamp_buffer = nullptr;
 #endif
 
-template <int NT, bool ZP, int LW, bool HF, bool Z4 = false>
+template <int NT, bool ZP, int LW, bool HF, bool Z4 = false, int SK = 0>
 static int ring_go(const RingArgs& a, hipStream_t st) {
     size_t lds = RingShape<NT, LW, Z4>::LDS;
 #ifdef RG_STAMPS
@@ -586,7 +636,23 @@ static int ring_go(const RingArgs& a, hipStream_t st) {
 #endif
     // one workgroup per CU on (up to) TDX_PERSISTENT_CUS CUs, the same number on every XCD, a multiple of the N tiles
     const int px = tdx_persistent_cus() / 8, grid = 8 * (px - px % a.ntn);
-    return tdx_launch_lds<conv3_ring_kernel<NT, ZP, LW, HF, Z4>>(dim3(grid), dim3(512 + 64 * LW), lds, st, a);
+    return tdx_launch_lds<conv3_ring_kernel<NT, ZP, LW, HF, Z4, SK>>(dim3(grid), dim3(512 + 64 * LW), lds, st, a);
+}
+
+static bool ring_loader_form(bool hf) {
+    const char* env = getenv("TDX_RING_LOADERS");  // A/B switch: 0 = the computing waves issue the copies themselves
+    return hf || (env ? atoi(env) != 0 : RG_DEFAULT_LOADERS);
+}
+// The skip term (conv3_ring_kernel, SK = 2) rides in this call's data gradient: K = 32 channels of dy and of the skip's gy,
+// 64-wide output tiles, the 8-deep loader-form kernel on a grid of whole bricks (no remainder-slab launch, whose kernel
+// has no skip term).  The one variant that keeps 3 waves per SIMD without scratch: K = 64 spills and its weights do not fit
+// the statistics scratch, 32-wide tiles spill, the loader-less form is an A/B build.
+bool conv3_ring_skip_supported(int fmt, int depth, int K, int N, int X, int Y, int Z) {
+    const char* env = getenv("TDX_SKIP_DGRAD_FUSE");  // A/B switch, read per call: 0 = the two 1x1 launches behind the data gradient
+    if (env && atoi(env) == 0) return false;
+    if (!tdx_is_h16(fmt) || depth != 8 || K != 32 || N <= 0 || (N % 64) != 0) return false;
+    if ((X % 8) || (Y % 8) || (Z % 8)) return false;
+    return ring_loader_form(fmt == TDX_F16);
 }
 
 // forward (zero_pad = false: y, bias, gn_acc) or main term of the data gradient (zero_pad = true: d1 / d2 / a1 / a2) with
@@ -611,14 +677,25 @@ int conv3_ring_launch(const Conv3Call& c, int depth) {
 #ifdef RG_STAMPS
     a.stamps = rg_stamp_buffer;
 #endif
-    const char* env = getenv("TDX_RING_LOADERS");  // A/B switch: 0 = the computing waves issue the copies themselves
-    const bool lw = env ? atoi(env) != 0 : RG_DEFAULT_LOADERS;
+    a.skx = nullptr; a.skC = 0; a.skw = nullptr; a.skN = 0;
+    if (c.skip_x != nullptr || c.skip_w != nullptr) {
+#ifdef RG_STAMPS
+        return TDX_ESHAPE;  // (the stamps live where the skip weights do)
+#else
+        if (!c.skip_x || !c.skip_w || !zero_pad || c.C2 != 0 || !conv3_ring_skip_supported(c.fmt, depth, c.C1, c.N, X, Y, Z)) return TDX_ESHAPE;
+        a.skx = (const bf16*)c.skip_x; a.skC = c.C1; a.skw = c.skip_w; a.skN = c.N;
+        int rcs = TDX_OK;
+        TDX_DISPATCH_H16(hf, rcs = ring_go<2, true, 4, HF, false, 2>(a, st));
+        return rcs;
+#endif
+    }
+    const bool lw = ring_loader_form(hf);
     // 4-deep bricks and fp16 operands: the loader-wave form only (the loader-less form is an A/B build of the bf16 kernels)
     int rc = TDX_OK;
     if (depth == 4)
         TDX_DISPATCH_BOOL(NT == 2, WIDE, TDX_DISPATCH_BOOL(zero_pad, ZP, TDX_DISPATCH_H16(hf,
             rc = ring_go<WIDE ? 2 : 1, ZP, 4, HF, true>(a, st))));
-    else if (hf || lw)
+    else if (lw)
         TDX_DISPATCH_BOOL(NT == 2, WIDE, TDX_DISPATCH_BOOL(zero_pad, ZP, TDX_DISPATCH_H16(hf,
             rc = ring_go<WIDE ? 2 : 1, ZP, 4, HF>(a, st))));
     else

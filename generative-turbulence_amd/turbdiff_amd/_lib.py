@@ -46,6 +46,8 @@ SIGNATURES = {
     "tdx_conv3_bwd_data_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "tdx_conv3_bwd_data": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "tdx_conv3_bwd_data_add": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "tdx_conv3_bwd_data_skip_supported": (_i, [_i] * 9),
+    "tdx_conv3_bwd_data_skip": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "tdx_conv3_bwd_weight_workspace_bytes": (_sz, [_i, _i, _i]),
     "tdx_conv3_bwd_weight": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "tdx_conv1_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i64, _i, _i, _vp]),
@@ -177,7 +179,7 @@ SCRATCH_SMALL_BYTES = 4096  # streams that only need the zero block at the arena
 SCRATCH_MAX_ARENAS = int(os.environ.get("TDX_SCRATCH_MAX_ARENAS", "6"))
 # entry points that may use the arena (K-split slabs of the small-grid kernels, the zero block of the DMA kernels)
 ARENA_USERS = {"tdx_conv3_fwd", "tdx_conv3_fwd_gn", "tdx_conv3_fwd_partial", "tdx_conv3_bwd_data", "tdx_conv3_bwd_data_add",
-               "tdx_conv3_bwd_weight", "tdx_attn_fwd"}  # tdx_attn_fwd: partial (O, m, l) of the stream-K schedule
+               "tdx_conv3_bwd_data_skip", "tdx_conv3_bwd_weight", "tdx_attn_fwd"}  # tdx_attn_fwd: partial (O, m, l) of the stream-K schedule
 # TDX_DETERMINISTIC=1: these merge their parameter gradients through per-split slabs in the launching stream's arena as well
 DET_ARENA_USERS = {"tdx_conv1_bwd_weight", "tdx_conv1_bwd_weight_oc", "tdx_encode_bwd", "tdx_decode_bwd", "tdx_gn_stats"}
 

@@ -111,21 +111,44 @@ def _conv3_bwd_data_ws(grid, Cin, code, impl, dev):
     return _ws(L.query("tdx_conv3_bwd_data_workspace_bytes", *grid, Cin, code, impl), dev)
 
 
-def _conv3_bwd_data(gy, wb, x1, C1, x2, C2, grid, Cout, code, impl, st, ws=None, add=None, real=None):
+def _conv3_bwd_data(gy, wb, x1, C1, x2, C2, grid, Cout, code, impl, st, ws=None, add=None, real=None, skip=None):
     """(gx1, gx2): the data gradient of conv3([x1 | x2]) from the packed backward operand `wb`, shaped like x1 and x2
-    (which are not read); `add` is added to gx1 in the kernel's epilogue (tdx_conv3_bwd_data_add)."""
+    (which are not read); `add` is added to gx1 in the kernel's epilogue (tdx_conv3_bwd_data_add); skip = (sgy, sw): the
+    product sgy @ sw (sw: [Cout][C1 + C2] f32) is added to [gx1 | gx2] inside the kernel (tdx_conv3_bwd_data_skip: only
+    where `_skip_dgrad_fused` says so)."""
     B, X, Y, Z = grid
     gx1, gx2 = torch.empty_like(x1), None if x2 is None else torch.empty_like(x2)
     if ws is None:
         ws = _conv3_bwd_data_ws(grid, C1 + C2, code, impl, gy.device)
     work = 54.0 * (real or (C1 + C2)) * Cout * B * X * Y * Z
-    if add is None:
+    if skip is not None:
+        sgy, sw = skip
+        L.call("tdx_conv3_bwd_data_skip", L.ptr(gy), L.ptr(wb), L.ptr(gx1), C1, L.ptr(gx2), C2, L.ptr(sgy), L.ptr(sw), B, X, Y, Z,
+               Cout, code, impl, L.ptr(ws), st, work=work + 2.0 * Cout * (C1 + C2) * B * X * Y * Z)
+    elif add is None:
         L.call("tdx_conv3_bwd_data", L.ptr(gy), L.ptr(wb), L.ptr(gx1), C1, L.ptr(gx2), C2, 0, B, X, Y, Z, Cout, code, impl,
                L.ptr(ws), st, work=work)
     else:
         L.call("tdx_conv3_bwd_data_add", L.ptr(gy), L.ptr(wb), L.ptr(gx1), C1, L.ptr(gx2), C2, L.ptr(add), None, B, X, Y, Z,
                Cout, code, impl, L.ptr(ws), st, work=work)
     return gx1, gx2
+
+
+def skip_dgrad_static(Cout, grid, dt, wdt=torch.float32):
+    """What a caller can see without the library of the calls tdx_conv3_bwd_data_skip serves: 16-bit tensors, 32 block
+    channels, a grid of whole 8 x 8 x 8 bricks (and the projection's weight in f32, as every 1x1 entry reads it)."""
+    _, X, Y, Z = grid
+    return dt in L.H16_DTYPES and wdt == torch.float32 and Cout == 32 and X % 8 == 0 and Y % 8 == 0 and Z % 8 == 0
+
+
+def _skip_dgrad_fused(C1, C2, Cout, grid, dt, wdt, code, impl):
+    """Does the block's conv1 data gradient take the 1x1 skip's input gradient along (tdx_conv3_bwd_data_skip)?  The library
+    is asked only behind `skip_dgrad_static`; its answer depends on the launching stream's arena, like the call's route."""
+    if not skip_dgrad_static(Cout, grid, dt, wdt):
+        return False
+    with L._LAUNCH_LOCK:
+        L.ensure_scratch()
+        return L.query("tdx_conv3_bwd_data_skip_supported", C1, C2, Cout, *grid, code, impl) == 1
 
 
 def _conv3_wgrad_out(wshape, has_bias, dev):
@@ -1444,10 +1467,14 @@ class _ResnetBlock(torch.autograd.Function):
         dwr = dbr = None
         if wr2 is None:  # identity skip: gy is added inside the data-gradient epilogue
             gx1, gx2 = _conv3_bwd_data(dh1, wb1, x1, C1, None, 0, grid, Cout, code, impl, st, dws, add=gy)
+        elif _skip_dgrad_fused(C1, C2, Cout, grid, gy.dtype, wr2.dtype, code, impl):
+            # 1x1 skip, dx = gy @ wr + t in ONE pass: the product is a last K step of the data gradient's ring kernel
+            gx1, gx2 = _conv3_bwd_data(dh1, wb1, x1, C1, x2, C2, grid, Cout, code, impl, st, dws, skip=(gy, wr2))
         else:  # 1x1 skip: dx = gy @ wr + t -- the add rides in the 1x1 kernel's epilogue
             t1, t2 = _conv3_bwd_data(dh1, wb1, x1, C1, x2, C2, grid, Cout, code, impl, st, dws)
             gx1 = _conv1_fwd(gy, Cout, None, 0, wr2, Cin, 0, None, t1, grid, B * V, C1, code, st)
             gx2 = None if x2 is None else _conv1_fwd(gy, Cout, None, 0, wr2, Cin, C1, None, t2, grid, B * V, C2, code, st)
+        if wr2 is not None:
             dwr, dbr = _conv1_weight_grad(x1, C1, x2, C2, gy, Cout, hbr, B * V, code, st)
             dwr = dwr.view(wrs)
         side.join()

@@ -193,6 +193,19 @@ int tdx_conv3_bwd_data_add(const void* dy, const void* wb, void* dx1, int C1, vo
                            const void* add2, int B, int X, int Y, int Z, int Cout, int dtype, int impl,
                            void* workspace, void* stream);
 
+/* Same, for a ResnetBlock whose skip is a 1x1 projection (ddpm.py:197): dx1 | dx2 = adjoint + skip_dy . skip_w, with skip_dy
+ * [B, X, Y, Z, Cout] in the tensors' dtype (the gradient arriving over the residual path) and skip_w [Cout][C1 + C2] f32 (the
+ * projection's weight, converted to the tensors' 16-bit format as tdx_conv1_fwd does).  The product is one more K = Cout
+ * contraction on the accumulators of the ring kernel's main-term launch: dx is written once, rounded once, and the two 1x1
+ * launches that would read it back do not run.  Served for 16-bit tensors, Cout == 32, (C1 + C2) % 64 == 0, where the data
+ * gradient runs on the 8-deep ring kernel in its loader form over a grid of whole 8 x 8 x 8 bricks
+ * (tdx_conv3_bwd_data_skip_supported == 1: ask first); TDX_ESHAPE for every other call -- no other route is taken inside.
+ * TDX_SKIP_DGRAD_FUSE=0 (environment, read per call) makes the query answer 0: the A/B switch. */
+int tdx_conv3_bwd_data_skip_supported(int C1, int C2, int Cout, int B, int X, int Y, int Z, int dtype, int impl);
+int tdx_conv3_bwd_data_skip(const void* dy, const void* wb, void* dx1, int C1, void* dx2, int C2, const void* skip_dy,
+                            const float* skip_w, int B, int X, int Y, int Z, int Cout, int dtype, int impl,
+                            void* workspace, void* stream);
+
 /* Weight + bias gradient.  dw is written in the reference's parameter layout
  * (Cout, Cin, 3, 3, 3) f32, dbias (Cout) f32 (may be NULL).  Overwrites.
  * workspace: tdx_conv3_bwd_weight_workspace_bytes(Cin, Cout) = accumulators (27*Cin*Cout + Cout floats:
