@@ -10,6 +10,7 @@
 // exact fp32 and is the path used at the U-Net bottleneck (N = 144 tokens at 192x64x48,
 // 0.01 GFLOP).  The MFMA flash kernel for long sequences lives in tdx_attention_mfma.hip.
 #include "tdx_common.h"
+#include "tdx_attention.h"
 #include <stdlib.h>
 
 // The "other side" rows are walked in tiles of 64 staged in LDS as f32 (thread t stages row t with
@@ -181,13 +182,7 @@ attn_bwd_dkv_kernel(const T* __restrict__ qkv, const T* __restrict__ dout, const
     }
 }
 
-// tdx_attention_mfma.hip; TDX_ATTN_IMPL=vector forces the kernels of this file
-bool attn_mfma_supported(int N, int D);
-int attn_fwd_mfma_launch(const void* qkv, void* out, float* lse, int B, int N, int H, int dtype, hipStream_t st);
-// tdx_attention_bwd_mfma.hip
-int attn_bwd_mfma_launch(const void* qkv, const void* dout, const float* lse, const float* delta, void* dqkv, int B, int N,
-                         int H, int dtype, hipStream_t st);
-
+// the matrix-core kernels' launchers: tdx_attention.h; TDX_ATTN_IMPL=vector forces the kernels of this file
 extern "C" int tdx_attn_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, int D, int dtype,
                             void* stream) {
     TDX_CHECK_ARG(qkv && out && lse && B > 0 && N > 0 && H > 0);

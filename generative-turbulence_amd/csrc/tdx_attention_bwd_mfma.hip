@@ -24,17 +24,10 @@
 // independent 2^-9 |s| in bf16: with |s| ~ 50-200 the recomputed rows sum to 1 +- 0.2 -- tests/test_attention_backward.py.)
 //
 // 6 + 8 MFMAs per 32 x 32 tile against the forward's 4; no atomics, no running maximum.
-#include "tdx_common.h"
+#include "tdx_attention.h"
 #include <type_traits>
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-#define FB_D 32
 #define FB_RB 256          // resident rows per workgroup
 // TW = resident 32-row tiles per wave: 2 (the default: 4 waves per workgroup, 2 waves per SIMD, ~250 / 230 registers) or 1
 // (round 6 experiment: 8 waves per workgroup, 3-4 waves per SIMD at <= 168 / 128 registers, as the forward kernel since round 5).
@@ -61,55 +54,10 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 #define FB_ABL 0
 #endif
 
-
-// operand element: bf16 (the model's bf16 mode) or fp16 (BASELINE configs[4]); see tdx_attention_mfma.hip
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-struct AttnBf16 {
-    typedef bf16 T;
-    typedef bf16x8 V8;
-    static __device__ __forceinline__ unsigned pack2(float a, float b) { return pack_bf16x2(a, b); }
-    static __device__ __forceinline__ f32x16 mfma(V8 a, V8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-struct AttnF16 {
-    typedef f16 T;
-    typedef f16x8 V8;
-    static __device__ __forceinline__ unsigned pack2(float a, float b) { return pack_f16x2(a, b); }
-    static __device__ __forceinline__ f32x16 mfma(V8 a, V8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-
-// 64-B rows: chunk c of row r at c ^ ((r >> 2) & 3) (conflict-free ds_read_b128 fragments)
-__device__ __forceinline__ int fb_sw64(int r, int c) { return r * 64 + ((c ^ ((r >> 2) & 3)) << 4); }
-
-template <typename V8>
-__device__ __forceinline__ V8 fb_tr_frag(const unsigned char* lo, const unsigned char* hi) {
-    s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lo));
-    s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(hi));
-    s16x8 r = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(V8, r);
-}
-
-// accumulator registers 8 s .. 8 s + 7 of a 32 x 32 tile -> bf16 B operand of k step s
-template <typename E>
-__device__ __forceinline__ typename E::V8 fb_as_b(const f32x16& t, int s) {
-    return __builtin_bit_cast(typename E::V8, make_uint4(E::pack2(t[8 * s], t[8 * s + 1]), E::pack2(t[8 * s + 2], t[8 * s + 3]),
-                                                         E::pack2(t[8 * s + 4], t[8 * s + 5]), E::pack2(t[8 * s + 6], t[8 * s + 7])));
-}
-
-// resident-side fragment as a B operand (col = row r of the side, k = d), optionally scaled
-template <typename E>
-__device__ __forceinline__ typename E::V8 fb_row_frag(const typename E::T* row, float scale) {
-    Vec8<typename E::T> v;
-    v.load(row);
-    unsigned w[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) w[e] = E::pack2(v.v[2 * e] * scale, v.v[2 * e + 1] * scale);
-    return __builtin_bit_cast(typename E::V8, make_uint4(w[0], w[1], w[2], w[3]));
-}
-
 // one staged 16-B piece (8 elements) times `scale`, rounded to the format: the forward's expression on Q, so the bits agree
 template <typename E>
 __device__ __forceinline__ uint4 fb_scale_piece(const uint4& piece, float scale) {
-    return __builtin_bit_cast(uint4, fb_row_frag<E>(reinterpret_cast<const typename E::T*>(&piece), scale));
+    return __builtin_bit_cast(uint4, row_frag<E>(reinterpret_cast<const typename E::T*>(&piece), scale));
 }
 
 // ------------------------------------------------------------------ dQ ---------------------------
@@ -126,12 +74,12 @@ attn_bwd_dq_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E:
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hh = lane >> 5;
     const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
-    const int ld = 3 * H * FB_D;
+    const int ld = 3 * H * FA_D;
     const typename E::T* base = qkv + (int64_t)b * N * ld;
     const int q0 = blockIdx.x * FB_RB + wave * RW;
-    const float sm_scale = rsqrtf((float)FB_D);
+    const float sm_scale = rsqrtf((float)FA_D);
 
-    typename E::V8 qf[TW][2], gf[TW][2];  // Q (pre-scaled) and dO as B operands: col = query r, k = d
+    bf16x8 qf[TW][2], gf[TW][2];  // Q (pre-scaled) and dO as B operands: col = query r, k = d
     // -lse log2(e) and -delta of the lane's query, broadcast over the 16 accumulator registers: as the C operands of the
     // score / dP products they deliver S^T - lse and dP^T - delta straight from the matrix pipe (the kernel is bound by its
     // vector-ALU work: that was 32 subtractions and 32 zeroing moves of ~110 issue slots per 32 x 32 tile)
@@ -142,8 +90,8 @@ attn_bwd_dq_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E:
         const int q = min(q0 + qt * 32 + r, N - 1);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            qf[qt][ks] = fb_row_frag<E>(base + (int64_t)q * ld + h * FB_D + ks * 16 + hh * 8, FB_LOG2E * sm_scale);
-            gf[qt][ks] = fb_row_frag<E>(dout + ((int64_t)b * N + q) * (H * FB_D) + h * FB_D + ks * 16 + hh * 8, 1.0f);
+            qf[qt][ks] = row_frag<E>(base + (int64_t)q * ld + h * FA_D + ks * 16 + hh * 8, FB_LOG2E * sm_scale);
+            gf[qt][ks] = row_frag<E>(dout + ((int64_t)b * N + q) * (H * FA_D) + h * FA_D + ks * 16 + hh * 8, 1.0f);
         }
         const float ml = -lse[((int64_t)b * H + h) * N + q] * FB_LOG2E, md = -delta[((int64_t)b * H + h) * N + q];
 #pragma unroll
@@ -154,9 +102,9 @@ attn_bwd_dq_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E:
     uint4 kreg, vreg;
     auto load_tile = [&](int k0) {
         const int key = min(k0 + st_row, N - 1);
-        const typename E::T* kp = base + (int64_t)key * ld + H * FB_D + h * FB_D + st_c * 8;
+        const typename E::T* kp = base + (int64_t)key * ld + H * FA_D + h * FA_D + st_c * 8;
         kreg = *reinterpret_cast<const uint4*>(kp);
-        vreg = *reinterpret_cast<const uint4*>(kp + H * FB_D);
+        vreg = *reinterpret_cast<const uint4*>(kp + H * FA_D);
     };
     const int g = lane >> 4, i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;
     const int t_col = (16 * (g & 1) + 4 * tp) * 2;
@@ -164,24 +112,24 @@ attn_bwd_dq_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E:
     load_tile(0);
     for (int k0 = 0; k0 < N; k0 += T) {
         __syncthreads();
-        *reinterpret_cast<uint4*>(sK + fb_sw64(st_row, st_c)) = kreg;
+        *reinterpret_cast<uint4*>(sK + sw64(st_row, st_c)) = kreg;
         *reinterpret_cast<uint4*>(sKp + st_row * 64 + st_c * 16) = kreg;
-        *reinterpret_cast<uint4*>(sV + fb_sw64(st_row, st_c)) = vreg;
+        *reinterpret_cast<uint4*>(sV + sw64(st_row, st_c)) = vreg;
         __syncthreads();
         if (k0 + T < N) load_tile(k0 + T);
 
         auto key_block = [&](int kb, auto tail_c) {
             constexpr bool TAIL = decltype(tail_c)::value;
-            typename E::V8 kf[2], vf[2], ktf[2];
+            bf16x8 kf[2], vf[2], ktf[2];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                kf[ks] = *reinterpret_cast<const typename E::V8*>(sK + fb_sw64(kb * 32 + r, 2 * ks + hh));
-                vf[ks] = *reinterpret_cast<const typename E::V8*>(sV + fb_sw64(kb * 32 + r, 2 * ks + hh));
+                kf[ks] = *reinterpret_cast<const bf16x8*>(sK + sw64(kb * 32 + r, 2 * ks + hh));
+                vf[ks] = *reinterpret_cast<const bf16x8*>(sV + sw64(kb * 32 + r, 2 * ks + hh));
             }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {  // K^T: rows = d, k = key 16 s + 8 (j >> 2) + 4 hh + (j & 3)
                 const unsigned char* kp = sKp + (kb * 32 + 16 * s + 4 * (g >> 1) + tq) * 64 + t_col;
-                ktf[s] = (FB_ABL & 16) ? kf[s] : fb_tr_frag<typename E::V8>(kp, kp + 8 * 64);
+                ktf[s] = (FB_ABL & 16) ? kf[s] : tr_frag(kp, kp + 8 * 64);
             }
 #pragma unroll
             for (int qt = 0; qt < TW; ++qt) {
@@ -195,11 +143,11 @@ attn_bwd_dq_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E:
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     float p = (FB_ABL & 1) ? st[i] : __builtin_amdgcn_exp2f(st[i]);
-                    if (TAIL && k0 + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh >= N) p = 0.f;  // keys beyond N
+                    if (TAIL && acc_row(i, hh, k0 + kb * 32) >= N) p = 0.f;  // keys beyond N
                     st[i] = (FB_ABL & 2) ? p : p * dp[i];  // dS^T
                 }
 #pragma unroll
-                for (int s = 0; s < 2; ++s) dq[qt] = E::mfma(ktf[s], (FB_ABL & 4) ? qf[qt][s] : fb_as_b<E>(st, s), dq[qt]);
+                for (int s = 0; s < 2; ++s) dq[qt] = E::mfma(ktf[s], (FB_ABL & 4) ? qf[qt][s] : acc_as_b<E>(st, s), dq[qt]);
                 if (FB_ABL & 4) dq[qt][0] += st[0] + st[15];  // (keeps the elementwise work alive)
             }
         };
@@ -211,18 +159,14 @@ attn_bwd_dq_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E:
             for (int kb = 0; kb < T / 32; ++kb) key_block(kb, std::true_type{});
         }
     }
-    // dQ[q][h*D + d] = scale * dQ^T[d][q];  lane holds d = (i & 3) + 8 (i >> 2) + 4 hh
+    // dQ[q][h*D + d] = scale * dQ^T[d][q];  lane holds d = acc_row(i, hh)
 #pragma unroll
     for (int qt = 0; qt < TW; ++qt) {
         const int q = q0 + qt * 32 + r;
         if (q < N) {
-            typename E::T* op = dqkv + ((int64_t)b * N + q) * ld + h * FB_D;
+            typename E::T* op = dqkv + ((int64_t)b * N + q) * ld + h * FA_D;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint2 v = make_uint2(E::pack2(dq[qt][4 * j] * sm_scale, dq[qt][4 * j + 1] * sm_scale),
-                                           E::pack2(dq[qt][4 * j + 2] * sm_scale, dq[qt][4 * j + 3] * sm_scale));
-                *reinterpret_cast<uint2*>(op + 8 * j + 4 * hh) = v;
-            }
+            for (int j = 0; j < 4; ++j) attn_store_row_piece<E>(op, dq[qt], j, sm_scale, hh);
         }
     }
 }
@@ -244,21 +188,21 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hh = lane >> 5;
     const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
-    const int ld = 3 * H * FB_D;
+    const int ld = 3 * H * FA_D;
     const typename E::T* base = qkv + (int64_t)b * N * ld;
     const int j0 = blockIdx.x * FB_RB + wave * RW;
-    const float qscale = FB_LOG2E * rsqrtf((float)FB_D);
+    const float qscale = FB_LOG2E * rsqrtf((float)FA_D);
     const float dk_scale = 0.6931471805599453f;  // ln 2 = (1/sqrt(D)) / (log2(e)/sqrt(D)): the staged Q carries the rest
 
-    typename E::V8 kf[TW][2], vf[TW][2];  // K and V as stored, as B operands: col = key r, k = d
+    bf16x8 kf[TW][2], vf[TW][2];  // K and V as stored, as B operands: col = key r, k = d
     f32x16 dk[TW], dv[TW];        // dK^T[d][key], dV^T[d][key]
 #pragma unroll
     for (int kt = 0; kt < TW; ++kt) {
         const int key = min(j0 + kt * 32 + r, N - 1);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            kf[kt][ks] = fb_row_frag<E>(base + (int64_t)key * ld + H * FB_D + h * FB_D + ks * 16 + hh * 8, 1.0f);
-            vf[kt][ks] = fb_row_frag<E>(base + (int64_t)key * ld + 2 * H * FB_D + h * FB_D + ks * 16 + hh * 8, 1.0f);
+            kf[kt][ks] = row_frag<E>(base + (int64_t)key * ld + H * FA_D + h * FA_D + ks * 16 + hh * 8, 1.0f);
+            vf[kt][ks] = row_frag<E>(base + (int64_t)key * ld + 2 * H * FA_D + h * FA_D + ks * 16 + hh * 8, 1.0f);
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) dk[kt][i] = dv[kt][i] = 0.f;
@@ -269,8 +213,8 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
     float lreg = 0.f, dreg = 0.f;
     auto load_tile = [&](int i0) {
         const int q = min(i0 + st_row, N - 1);
-        qreg = *reinterpret_cast<const uint4*>(base + (int64_t)q * ld + h * FB_D + st_c * 8);
-        greg = *reinterpret_cast<const uint4*>(dout + ((int64_t)b * N + q) * (H * FB_D) + h * FB_D + st_c * 8);
+        qreg = *reinterpret_cast<const uint4*>(base + (int64_t)q * ld + h * FA_D + st_c * 8);
+        greg = *reinterpret_cast<const uint4*>(dout + ((int64_t)b * N + q) * (H * FA_D) + h * FA_D + st_c * 8);
         if (tid < T) {
             const int qq = i0 + tid;
             lreg = qq < N ? -lse[((int64_t)b * H + h) * N + qq] * FB_LOG2E : -INFINITY;  // exp2(s - inf) = 0: no query there
@@ -286,9 +230,9 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
         // Q enters LDS as the forward's operand, round(q * log2(e)/sqrt(D)): the scores are the forward's, and the Q^T
         // fragments of dK^T += Q^T dS carry the factor too (taken out again in the epilogue)
         const uint4 qs = fb_scale_piece<E>(qreg, qscale);
-        *reinterpret_cast<uint4*>(sQ + fb_sw64(st_row, st_c)) = qs;
+        *reinterpret_cast<uint4*>(sQ + sw64(st_row, st_c)) = qs;
         *reinterpret_cast<uint4*>(sQp + st_row * 64 + st_c * 16) = qs;
-        *reinterpret_cast<uint4*>(sG + fb_sw64(st_row, st_c)) = greg;
+        *reinterpret_cast<uint4*>(sG + sw64(st_row, st_c)) = greg;
         *reinterpret_cast<uint4*>(sGp + st_row * 64 + st_c * 16) = greg;
         if (tid < T) { sL[tid] = lreg; sD[tid] = dreg; }
         __syncthreads();
@@ -296,17 +240,17 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
 
 #pragma unroll
         for (int qb = 0; qb < T / 32; ++qb) {
-            typename E::V8 qa[2], ga[2], qtf[2], gtf[2];
+            bf16x8 qa[2], ga[2], qtf[2], gtf[2];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {  // A operands: row = query r, k = d
-                qa[ks] = *reinterpret_cast<const typename E::V8*>(sQ + fb_sw64(qb * 32 + r, 2 * ks + hh));
-                ga[ks] = *reinterpret_cast<const typename E::V8*>(sG + fb_sw64(qb * 32 + r, 2 * ks + hh));
+                qa[ks] = *reinterpret_cast<const bf16x8*>(sQ + sw64(qb * 32 + r, 2 * ks + hh));
+                ga[ks] = *reinterpret_cast<const bf16x8*>(sG + sw64(qb * 32 + r, 2 * ks + hh));
             }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {  // Q^T, dO^T: rows = d, k = query 16 s + 8 (j >> 2) + 4 hh + (j & 3)
                 const int off = (qb * 32 + 16 * s + 4 * (g >> 1) + tq) * 64 + t_col;
-                qtf[s] = (FB_ABL & 16) ? qa[s] : fb_tr_frag<typename E::V8>(sQp + off, sQp + off + 8 * 64);
-                gtf[s] = (FB_ABL & 16) ? ga[s] : fb_tr_frag<typename E::V8>(sGp + off, sGp + off + 8 * 64);
+                qtf[s] = (FB_ABL & 16) ? qa[s] : tr_frag(sQp + off, sQp + off + 8 * 64);
+                gtf[s] = (FB_ABL & 16) ? ga[s] : tr_frag(sGp + off, sGp + off + 8 * 64);
             }
             // per-register row scalars: register i <-> query row (i & 3) + 8 (i >> 2) + 4 hh of the block.  The sixteen
             // (negated) values ARE the C operands of the score / dP products: S - lse and dP - delta come out of the
@@ -335,27 +279,24 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
                 }
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    dv[kt] = E::mfma(gtf[s], (FB_ABL & 4) ? kf[kt][s] : fb_as_b<E>(st, s), dv[kt]);
-                    dk[kt] = E::mfma(qtf[s], (FB_ABL & 4) ? vf[kt][s] : fb_as_b<E>(dp, s), dk[kt]);
+                    dv[kt] = E::mfma(gtf[s], (FB_ABL & 4) ? kf[kt][s] : acc_as_b<E>(st, s), dv[kt]);
+                    dk[kt] = E::mfma(qtf[s], (FB_ABL & 4) ? vf[kt][s] : acc_as_b<E>(dp, s), dk[kt]);
                 }
                 if (FB_ABL & 4) dv[kt][0] += st[0] + st[15] + dp[0] + dp[15];  // (keeps the elementwise work alive)
             }
         }
     }
-    // dK[key][..] = ln 2 * dK^T (Q^T was pre-scaled), dV[key][..] = dV^T;  lane holds d = (i & 3) + 8 (i >> 2) + 4 hh
+    // dK[key][..] = ln 2 * dK^T (Q^T was pre-scaled), dV[key][..] = dV^T;  lane holds d = acc_row(i, hh)
 #pragma unroll
     for (int kt = 0; kt < TW; ++kt) {
         const int key = j0 + kt * 32 + r;
         if (key < N) {
-            typename E::T* okp = dqkv + ((int64_t)b * N + key) * ld + H * FB_D + h * FB_D;
-            typename E::T* ovp = okp + H * FB_D;
+            typename E::T* okp = dqkv + ((int64_t)b * N + key) * ld + H * FA_D + h * FA_D;
+            typename E::T* ovp = okp + H * FA_D;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                *reinterpret_cast<uint2*>(okp + 8 * j + 4 * hh) =
-                    make_uint2(E::pack2(dk[kt][4 * j] * dk_scale, dk[kt][4 * j + 1] * dk_scale),
-                               E::pack2(dk[kt][4 * j + 2] * dk_scale, dk[kt][4 * j + 3] * dk_scale));
-                *reinterpret_cast<uint2*>(ovp + 8 * j + 4 * hh) =
-                    make_uint2(E::pack2(dv[kt][4 * j], dv[kt][4 * j + 1]), E::pack2(dv[kt][4 * j + 2], dv[kt][4 * j + 3]));
+                attn_store_row_piece<E>(okp, dk[kt], j, dk_scale, hh);
+                attn_store_row_piece<E>(ovp, dv[kt], j, 1.0f, hh);
             }
         }
     }

@@ -21,74 +21,14 @@
 // With D = 32 the kernel is bound by the softmax VALU work (N^2 exponentials), not by the
 // matrix cores: 4 MFMAs (128 pipe cycles) per 32x32 tile against 16 quarter-rate v_exp_f32 (256
 // cycles) + ~60 plain VALU instructions (v_max3, packed f32 sub / sum, packed bf16 conversion).
-#include "tdx_common.h"
+#include "tdx_attention.h"
+#include "tdx_runtime.h"
 #include <type_traits>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-#define FA_D 32
 #define FA_KT 64          // keys per staged tile
 #define FA_QW 32          // queries per wave (one 32-query tile: <= 128 registers, four waves per SIMD)
 #define FA_THREADS 512    // 8 waves
 #define FA_QB (8 * FA_QW) // queries per workgroup
-
-// K tile rows of 64 B: chunk c of row r at c ^ ((r >> 2) & 3)  (conflict-free ds_read_b128, see conv1)
-__device__ __forceinline__ int fa_sw64(int r, int c) { return r * 64 + ((c ^ ((r >> 2) & 3)) << 4); }
-
-
-// operand element of the matrix-core attention kernels: bf16 (the model's bf16 mode) or fp16 (BASELINE configs[4]:
-// "fp16 MFMA QK^T / AV" -- 11 significand bits in P, K and V instead of 8)
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-struct AttnBf16 {
-    typedef bf16 T;
-    typedef bf16x8 V8;
-    static __device__ __forceinline__ unsigned pack2(float a, float b) { return pack_bf16x2(a, b); }
-    static __device__ __forceinline__ unsigned packp(float a, float b) { return pack_bf16x2(a, b); }
-    static __device__ __forceinline__ f32x16 mfma(V8 a, V8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ f32x4 mfma16(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ float unpack_lo(unsigned w) { return __uint_as_float(w << 16); }
-    static __device__ __forceinline__ float unpack_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
-    static constexpr float lazy = 32.0f;
-    static constexpr float headroom = 0.0f;
-};
-struct AttnF16 {
-    typedef f16 T;
-    typedef f16x8 V8;
-    static __device__ __forceinline__ unsigned pack2(float a, float b) { return pack_f16x2(a, b); }
-    // probabilities: round to nearest, one v_cvt_pk_f16_f32 per pair on gfx950.  Not v_cvt_pkrtz_f16_f32: truncation makes
-    // every row sum, and with it the exported log-sum-exp, 3.5e-4 too small -- that cancels in O, but the backward normalises
-    // its round-to-nearest probabilities by that lse and its rows would sum to 1 + 3.5e-4 (test_attention_backward.py)
-    static __device__ __forceinline__ unsigned packp(float a, float b) { return pack_f16x2(a, b); }
-    static __device__ __forceinline__ f32x16 mfma(V8 a, V8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ f32x4 mfma16(V8 a, V8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ float unpack_lo(unsigned w) {
-        typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-        return (float)__builtin_bit_cast(h2, w)[0];
-    }
-    static __device__ __forceinline__ float unpack_hi(unsigned w) {
-        typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-        return (float)__builtin_bit_cast(h2, w)[1];
-    }
-    static constexpr float lazy = 15.0f;  // 2^15 < 65504
-    // fp16's allowance is narrow: a segment may START with m up to 2^3 above its first block's maximum when that is what
-    // lets the wave run without the check (probabilities then begin at 2^-3; what fp16 flushes to zero moves from 2^-24
-    // to 2^-21 of the maximum)
-    static constexpr float headroom = 3.0f;
-};
-
-template <typename V8>
-__device__ __forceinline__ V8 fa_tr_frag(const unsigned char* lo, const unsigned char* hi) {
-    s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lo));
-    s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(hi));
-    s16x8 r = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(V8, r);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Forward kernel, round 5.  What bound the round-3 kernel (0.21 of the matrix peak at N = 73 728): per 32 x 32 score tile
@@ -115,9 +55,7 @@ __device__ __forceinline__ V8 fa_tr_frag(const unsigned char* lo, const unsigned
 //   * stream-K schedule: a persistent grid (2 workgroups per CU) splits the linear (query block, key tile) iteration
 //     space evenly; a block whose key range straddles two workgroups is finished by a small merge kernel from the
 //     partial (O, m, l) both wrote.  XCD x owns a contiguous eighth of the space (one head's K / V per L2).
-// (allowance per operand type, E::lazy(): probabilities must stay finite in the operand format -- fp16 tops out at 2^16 --
-// and their sums in fp32)
-
+// (allowance per operand type: E::lazy, tdx_attention.h)
 
 struct AttnSkArgs {
     int N, H, nqb, ntile;      // tokens, heads, query blocks per (b, h), key tiles per block
@@ -134,7 +72,6 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * FA_KT * 64];
     unsigned char* sK = smem;                // [64 keys][32 d], swizzled 16-B chunks
     unsigned char* sV = smem + FA_KT * 64;   // [64 keys][32 d], plain rows (transposed reads)
-    using V8 = typename E::V8;
     using T = typename E::T;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -152,10 +89,10 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
     const int st_key = (tid & 255) >> 2, st_c = tid & 3, st_v = tid >> 8;
     const int g = lane >> 4, i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;
     const int v_col = (16 * (g & 1) + 4 * tp) * 2;
-    V8 sel;  // A operand of the row-sum product: A[m = lane & 15][k group = lane >> 4]
+    bf16x8 sel;  // A operand of the row-sum product: A[m = lane & 15][k group = lane >> 4]
     {
         const unsigned one2 = (lane == 0 || lane == 32 || lane == 17 || lane == 49) ? E::pack2(1.0f, 1.0f) : 0u;
-        sel = __builtin_bit_cast(V8, make_uint4(one2, one2, one2, one2));
+        sel = __builtin_bit_cast(bf16x8, make_uint4(one2, one2, one2, one2));
     }
 
     while (it < it_end) {
@@ -168,18 +105,11 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
         const int q0 = qb * FA_QB + wave * FA_QW;
 
         // ---- Q fragments (B operand: col = query r, k = d), pre-scaled by log2(e)/sqrt(D)
-        V8 qf[2];
+        bf16x8 qf[2];
         {
             const int q = min(q0 + r, N - 1);
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                Vec8<T> v;
-                v.load(base + (int64_t)q * ld + h * FA_D + ks * 16 + hh * 8);
-                unsigned wv[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) wv[e] = E::pack2(v.v[2 * e] * qscale, v.v[2 * e + 1] * qscale);
-                qf[ks] = __builtin_bit_cast(V8, make_uint4(wv[0], wv[1], wv[2], wv[3]));
-            }
+            for (int ks = 0; ks < 2; ++ks) qf[ks] = row_frag<E>(base + (int64_t)q * ld + h * FA_D + ks * 16 + hh * 8, qscale);
         }
         // |q|^2 of the lane's (rounded, pre-scaled) query: 16 of its 32 components here, the rest in lane ^ 32
         float bound = INFINITY;  // upper bound of every score of this query against this head's keys (log2 units)
@@ -191,7 +121,7 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
                 const unsigned wv[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float lo = E::unpack_lo(wv[e]), hi = E::unpack_hi(wv[e]);
+                    const float lo = E::lo(wv[e]), hi = E::hi(wv[e]);
                     q2 = __builtin_fmaf(lo, lo, __builtin_fmaf(hi, hi, q2));
                 }
             }
@@ -213,7 +143,7 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
         };
         auto stage = [&](int t) {  // tile t: registers -> LDS, next tile's loads in flight
             __syncthreads();
-            if (st_v == 0) *reinterpret_cast<uint4*>(sK + fa_sw64(st_key, st_c)) = sreg;
+            if (st_v == 0) *reinterpret_cast<uint4*>(sK + sw64(st_key, st_c)) = sreg;
             else *reinterpret_cast<uint4*>(sV + st_key * 64 + st_c * 16) = sreg;
             __syncthreads();
             if (t + 1 < t1) load_tile((t + 1) * FA_KT);
@@ -251,24 +181,26 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
             for (int i = 3; i < 15; i += 2) mx = max(max(mx, __float_as_int(st[i])), __float_as_int(st[i + 1]));
             return max(mx, __float_as_int(st[15]));
         };
-        auto frags = [&](int kb, V8 (&kf)[2], V8 (&vf)[2]) {
+        auto frags = [&](int kb, bf16x8 (&kf)[2], bf16x8 (&vf)[2]) {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                kf[ks] = *reinterpret_cast<const V8*>(sK + fa_sw64(kb * 32 + r, 2 * ks + hh));
+                kf[ks] = *reinterpret_cast<const bf16x8*>(sK + sw64(kb * 32 + r, 2 * ks + hh));
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 const unsigned char* vp = sV + (kb * 32 + 16 * s2 + 4 * (g >> 1) + tq) * 64 + v_col;
-                vf[s2] = fa_tr_frag<V8>(vp, vp + 8 * 64);
+                vf[s2] = tr_frag(vp, vp + 8 * 64);
             }
         };
-        auto accumulate = [&](f32x16& st, const V8 (&vf)[2]) {  // P = 2^st; O^T += V^T P^T; l += sum P
+        auto accumulate = [&](f32x16& st, const bf16x8 (&vf)[2]) {  // P = 2^st; O^T += V^T P^T; l += sum P
 #pragma unroll
             for (int i = 0; i < 16; ++i) st[i] = __builtin_amdgcn_exp2f(st[i]);
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                const V8 pf = __builtin_bit_cast(
-                    V8, make_uint4(E::packp(st[8 * s2], st[8 * s2 + 1]), E::packp(st[8 * s2 + 2], st[8 * s2 + 3]),
-                                   E::packp(st[8 * s2 + 4], st[8 * s2 + 5]), E::packp(st[8 * s2 + 6], st[8 * s2 + 7])));
+                // the probabilities are rounded to nearest (pack2: one v_cvt_pk_* per pair on gfx950), in fp16 too.  Not
+                // v_cvt_pkrtz_f16_f32: truncation makes every row sum, and with it the exported log-sum-exp, 3.5e-4 too small
+                // -- that cancels in O, but the backward normalises its round-to-nearest probabilities by that lse and its
+                // rows would sum to 1 + 3.5e-4 (test_attention_backward.py)
+                const bf16x8 pf = acc_as_b<E>(st, s2);
                 o = E::mfma(vf[s2], pf, o);
                 ls = E::mfma16(sel, pf, ls);  // row sums of the rounded probabilities
             }
@@ -282,11 +214,11 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
             for (int i = 0; i < 16; ++i) s0[i] = 0.f;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                s0 = E::mfma(*reinterpret_cast<const V8*>(sK + fa_sw64(r, 2 * ks + hh)), qf[ks], s0);
+                s0 = E::mfma(*reinterpret_cast<const bf16x8*>(sK + sw64(r, 2 * ks + hh)), qf[ks], s0);
             if (t0 * FA_KT + 32 > N) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i)
-                    if (t0 * FA_KT + (i & 3) + 8 * (i >> 2) + 4 * hh >= N) s0[i] = -INFINITY;
+                    if (acc_row(i, hh, t0 * FA_KT) >= N) s0[i] = -INFINITY;
             }
             float mx = row_max(s0);
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -308,7 +240,7 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
         bool check = __builtin_amdgcn_ballot_w64(bound - m > E::lazy - 0.05f) != 0;
         while (check && j < 2 * t_full) {  // loop 1: looks at every block's scores
             if (!staged) { stage(j >> 1); staged = true; }
-            V8 kf[2], vf[2];
+            bf16x8 kf[2], vf[2];
             frags(j & 1, kf, vf);
             f32x16 st = E::mfma(kf[0], qf[0], negm);  // S^T - m straight from the matrix pipe
             st = E::mfma(kf[1], qf[1], st);
@@ -323,7 +255,7 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
         }
         for (; j < 2 * t_full; ++j) {  // loop 2: no score of the rest can outgrow the allowance
             if (!staged) stage(j >> 1);
-            V8 kf[2], vf[2];
+            bf16x8 kf[2], vf[2];
             frags(j & 1, kf, vf);
             f32x16 st = E::mfma(kf[0], qf[0], negm);
             st = E::mfma(kf[1], qf[1], st);
@@ -336,13 +268,13 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
             const int k0 = t_full * FA_KT;
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {
-                V8 kf[2], vf[2];
+                bf16x8 kf[2], vf[2];
                 frags(kb, kf, vf);
                 f32x16 st = E::mfma(kf[0], qf[0], negm);
                 st = E::mfma(kf[1], qf[1], st);
 #pragma unroll
                 for (int i = 0; i < 16; ++i)  // register i <-> key (i & 3) + 8 (i >> 2) + 4 hh
-                    if (k0 + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh >= N) st[i] = -INFINITY;
+                    if (acc_row(i, hh, k0 + kb * 32) >= N) st[i] = -INFINITY;
                 const float mx = row_max(st);
                 if (__builtin_amdgcn_ballot_w64(mx > 0.f) != 0) {
                     const float d = raise(mx);
@@ -353,7 +285,7 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
             }
         }
 
-        // ---- segment epilogue; lane holds d = (i & 3) + 8 (i >> 2) + 4 hh of query r
+        // ---- segment epilogue; lane holds d = acc_row(i, hh) of query r
         const float l0 = __shfl(ls[0], r & 15, 64), l1 = __shfl(ls[1], r & 15, 64);
         const float lq = r < 16 ? l0 : l1;  // l of the lane's query: from lane r & 15, register r >> 4
         const int q = q0 + r;
@@ -362,11 +294,7 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
                 const float inv = 1.0f / lq;
                 T* op = out + ((int64_t)b * N + q) * (H * FA_D) + h * FA_D;
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    const uint2 v = make_uint2(E::pack2(o[4 * jj] * inv, o[4 * jj + 1] * inv),
-                                               E::pack2(o[4 * jj + 2] * inv, o[4 * jj + 3] * inv));
-                    *reinterpret_cast<uint2*>(op + 8 * jj + 4 * hh) = v;
-                }
+                for (int jj = 0; jj < 4; ++jj) attn_store_row_piece<E>(op, o, jj, inv, hh);
                 if (hh == 0) lse[((int64_t)b * H + h) * N + q] = (m + log2f(lq)) * 0.6931471805599453f;
             }
         } else {
@@ -449,12 +377,10 @@ attn_fwd_merge_kernel(typename E::T* __restrict__ out, float* __restrict__ lse, 
 
 bool attn_mfma_supported(int N, int D) { return D == FA_D && N >= 128; }  // incl. the U-Net bottleneck (N = 144 at 192x64x48)
 
-void* tdx_scratch_ptr();
-size_t tdx_scratch_bytes();
-
 // Persistent stream-K schedule when the launch is big enough to care about whole rounds of workgroups (and the stream's
-// scratch arena can hold the partials: 2 slots x 512 workgroups x 34 816 B = 35.7 MB behind its 64-B zero block);
-// otherwise one workgroup per query block.
+// scratch arena can hold the partials: 2 slots x 512 workgroups x 34 816 B = 35.7 MB behind its zero block and the key-norm
+// table); otherwise one workgroup per query block.
+#define FA_KMAX_BYTES 1024  // max_k |k|^2 of up to 256 (b, h) pairs, right behind the arena's zero block
 int attn_fwd_mfma_launch(const void* qkv, void* out, float* lse, int B, int N, int H, int dtype, hipStream_t st) {
     AttnSkArgs a;
     a.N = N; a.H = H;
@@ -463,23 +389,21 @@ int attn_fwd_mfma_launch(const void* qkv, void* out, float* lse, int B, int N, i
     const int nblk = B * H * a.nqb;
     a.total = (long long)nblk * a.ntile;
     const int slots = 512;  // 256 CUs x 2 workgroups
-    const size_t head = 64 + 1024;  // zero block, then max_k |k|^2 of up to 256 (b, h) pairs
-    const size_t need = head + (size_t)slots * 2 * FA_PART_STRIDE * sizeof(float);
+    const size_t head = TDX_SCRATCH_ZERO_BYTES + FA_KMAX_BYTES;
     const char* env = getenv("TDX_ATTN_STREAMK");
     const bool want = !(env && env[0] == '0') && nblk > slots && (nblk % slots) != 0 && a.ntile >= 16;
-    if (want && tdx_scratch_ptr() != nullptr && tdx_scratch_bytes() >= need) {
+    a.part = want ? reinterpret_cast<float*>(tdx_scratch_region(head, (size_t)slots * 2 * FA_PART_STRIDE * sizeof(float))) : nullptr;
+    if (a.part != nullptr) {
         a.nwg = slots;
         a.chunk = (int)((a.total + slots - 1) / slots);
-        a.part = reinterpret_cast<float*>((char*)tdx_scratch_ptr() + head);
     } else {
         a.nwg = nblk;
         a.chunk = a.ntile;
-        a.part = nullptr;
     }
     a.kmax2 = nullptr;
     const char* envb = getenv("TDX_ATTN_BOUND");
-    if (!(envb && envb[0] == '0') && tdx_scratch_ptr() != nullptr && tdx_scratch_bytes() >= head && B * H <= 256 && a.ntile >= 8) {
-        float* km = reinterpret_cast<float*>((char*)tdx_scratch_ptr() + 64);
+    float* km = reinterpret_cast<float*>(tdx_scratch_region(TDX_SCRATCH_ZERO_BYTES, FA_KMAX_BYTES));
+    if (!(envb && envb[0] == '0') && km != nullptr && B * H <= 256 && a.ntile >= 8) {
         if (tdx_zero_async(km, (size_t)B * H * sizeof(float), st) != TDX_OK) return TDX_EINVAL;
         const dim3 kg(min(ceil_div(N, 64), 64), B * H);
         if (dtype == TDX_F16) hipLaunchKernelGGL(attn_kmax_kernel<f16>, kg, dim3(256), 0, st, (const f16*)qkv, km, N, H);

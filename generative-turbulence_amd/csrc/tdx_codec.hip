@@ -11,7 +11,7 @@
 // is read/written as per-plane scalars.  Parameter gradients are reduced per block through LDS
 // and merged with one f32 atomic per value.
 #include "tdx_codec_elem.h"  // the encoder lane and the decoder dot, shared with the GroupNorm tails
-#include "tdx_conv3.h"  // tdx_deterministic, ordered_sum_launch, the scratch arena
+#include "tdx_runtime.h"  // tdx_deterministic, ordered_sum_launch, the scratch arena
 
 #define CD_THREADS 256
 #define CD_VOX 512  // voxels per block (~4 resident blocks per CU at 192x64x48)
@@ -140,11 +140,9 @@ static bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static hipError_t codec_zero(float* p, size_t n, hipStream_t st) {  // (a kernel, not hipMemsetAsync: tdx_common.h)
     return tdx_zero_async(p, n * sizeof(float), st) == TDX_OK ? hipSuccess : hipErrorUnknown;
 }
-// TDX_DETERMINISTIC: `floats` of per-block slabs in the launching stream's scratch arena (behind its zero block), or nullptr
+// TDX_DETERMINISTIC: `floats` of per-block slabs in the launching stream's scratch arena, or nullptr
 static float* det_slabs(int64_t floats) {
-    char* arena = (char*)tdx_scratch_ptr();
-    if (!arena || (int64_t)tdx_scratch_bytes() < 256 + floats * (int64_t)sizeof(float)) return nullptr;
-    return reinterpret_cast<float*>(arena + 256);
+    return reinterpret_cast<float*>(tdx_scratch_region(TDX_SCRATCH_SLAB_OFFSET, (size_t)floats * sizeof(float)));
 }
 
 extern "C" int tdx_encode_fwd(const float* x, int Fx, const float* wx, const float* bx, const float* c, int Fc,

@@ -183,9 +183,9 @@ struct Raw8<f16> {
 };
 
 // ---- the two 16-bit formats of the matrix-core kernels.  Those kernels move operands as raw 16-bit words (LDS-DMA, 16-B
-// register pieces, `bf16x8` fragments); what depends on the format is the MFMA opcode, the rounding of fp32 results to 16
-// bits, the widening of stored words, and the constant 1.0 of the bias-gradient slots.  HF = false: bfloat16 (TDX_BF16),
-// HF = true: IEEE half (TDX_F16; same matrix-pipe cycles on gfx950, 11 instead of 8 significand bits -- the arithmetic of
+// register pieces, `bf16x8` fragments); what depends on the format is the MFMA opcode (mfma: 32x32x16, mfma16: 16x16x32),
+// the rounding of fp32 results to 16 bits, the widening of stored words, and the constant 1.0 of the bias-gradient slots.
+// HF = false: bfloat16 (TDX_BF16), HF = true: IEEE half (TDX_F16; same matrix-pipe cycles on gfx950, 11 instead of 8 significand bits -- the arithmetic of
 // the reference's TF32 GPU runs, train.py:144-156).
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
@@ -199,6 +199,9 @@ struct H16<false> {
     static constexpr int code = TDX_BF16;
     static __device__ __forceinline__ f32x16_t mfma(bf16x8_t a, bf16x8_t b, f32x16_t c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ f32x4_t mfma16(bf16x8_t a, bf16x8_t b, f32x4_t c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
     }
     static __device__ __forceinline__ unsigned pack2(float lo, float hi) { return pack_bf16x2(lo, hi); }
     static __device__ __forceinline__ float lo(unsigned w) { return __uint_as_float(w << 16); }
@@ -214,6 +217,9 @@ struct H16<true> {
     static constexpr int code = TDX_F16;
     static __device__ __forceinline__ f32x16_t mfma(bf16x8_t a, bf16x8_t b, f32x16_t c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ f32x4_t mfma16(bf16x8_t a, bf16x8_t b, f32x4_t c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
     }
     static __device__ __forceinline__ unsigned pack2(float lo, float hi) { return pack_f16x2(lo, hi); }
     static __device__ __forceinline__ float lo(unsigned w) {

@@ -3,32 +3,14 @@
 // 64 rows x 64 cols per 256-thread block, 4x4 register tile per thread, K staged through
 // LDS in 32-deep slices (x slice stored k-major so the inner loop reads conflict-free
 // float4 rows).  f32 accumulation.  These layers are HBM-bound at the U-Net's channel
-// counts (4-174 FLOP/B); the MFMA variant lives in tdx_conv3_mfma.hip (taps = 1).
+// counts (4-174 FLOP/B); the MFMA versions live in tdx_conv1_mfma.hip and tdx_conv1_mfma_f32.hip (launchers: tdx_conv1.h;
+// TDX_CONV1_IMPL=direct forces the kernels of this file).
 #include "tdx_common.h"
-#include "tdx_conv3.h"
-
+#include "tdx_conv1.h"
+#include "tdx_runtime.h"
 #include <stdlib.h>
-// MFMA versions (tdx_conv1_mfma.hip); TDX_CONV1_IMPL=direct forces the vector-ALU kernels
-bool conv1_mfma_supported(int C1, int C2, int Cout);
-int conv1_mfma_fwd_launch(const void* x1, int C1, const void* x2, int C2, const float* w, int ldw, const float* bias,
-                          const void* add, void* y, int64_t rows, int Cout, hipStream_t st, const float* gn_stats = nullptr,
-                          const float* gn_gamma = nullptr, const float* gn_beta = nullptr, int gn_groups = 1,
-                          int64_t gn_voxels = 1, bool hf = false);
-bool conv1_wgrad_mfma_supported(int Cin, int Cout);
-// max_split / split_stride (TDX_DETERMINISTIC): at most max_split K splits (0 = the launcher's own choice), split k adds into
-// dw + k * split_stride (and dbias + k * split_stride): zeroed slabs with ONE contributor per element, summed in order afterwards;
-// plan_only: report the number of splits the launch would use (nsplit_out) without launching
-int conv1_wgrad_mfma_launch(const void* x, int Cin, const void* dy, int Cout, float* dw, int ldw, float* dbias,
-                            int64_t rows, bool transposed, hipStream_t st, bool hf = false, int max_split = 0,
-                            int64_t split_stride = 0, int* nsplit_out = nullptr, bool plan_only = false);
-// fp32 MFMA versions (tdx_conv1_mfma_f32.hip)
-bool conv1_mfma_f32_supported(int C1, int C2, int Cout, const float* w, int ldw);
-int conv1_mfma_f32_fwd_launch(const void* x1, int C1, const void* x2, int C2, const float* w, int ldw, const float* bias,
-                              const void* add, void* y, int64_t rows, int Cout, hipStream_t st);
-bool conv1_wgrad_mfma_f32_supported(int Cin, int Cout);
-int conv1_wgrad_mfma_f32_launch(const void* x, int Cin, const void* dy, int Cout, float* dw, int ldw, float* dbias,
-                                int64_t rows, bool transposed, hipStream_t st, int max_split = 0, int64_t split_stride = 0,
-                                int* nsplit_out = nullptr, bool plan_only = false);
+#include <algorithm>
+
 static bool conv1_force_direct() {
     const char* e = getenv("TDX_CONV1_IMPL");
     return e && e[0] == 'd';
@@ -229,11 +211,13 @@ static int conv1_bwd_weight_impl(const void* x, int Cin, const void* dy, int Cou
         // K split k adds its tile into slab k of the scratch arena (zeroed; one contributor per element, so the f32 atomics
         // are plain stores in effect), then the slabs are added in order into dw / dbias.  Without an arena: one split.
         const int64_t slab = ((int64_t)nrow * ncol + Cout + 63) / 64 * 64;  // [nrow][ncol] compact, then the bias gradient
-        char* arena = (char*)tdx_scratch_ptr();
-        const int64_t room = arena ? ((int64_t)tdx_scratch_bytes() - 256) / (int64_t)sizeof(float) / slab : 0;
+        const int64_t room =
+            tdx_scratch_ptr() ? ((int64_t)tdx_scratch_bytes() - TDX_SCRATCH_SLAB_OFFSET) / (int64_t)sizeof(float) / slab : 0;
         int max_split = (int)std::min<int64_t>(room, 256);
-        if (max_split >= 2) {
-            float* slabs = reinterpret_cast<float*>(arena + 256);
+        float* slabs = max_split >= 2 ? reinterpret_cast<float*>(tdx_scratch_region(
+                                            TDX_SCRATCH_SLAB_OFFSET, (size_t)max_split * slab * sizeof(float)))
+                                      : nullptr;
+        if (slabs != nullptr) {
             float* bias_slab = dbias ? slabs + (int64_t)nrow * ncol : nullptr;
             int nsplit = 0;  // what the launcher will use (often far fewer than allowed): only those slabs are zeroed and summed
             int rc = conv1_wgrad_dispatch(x, Cin, dy, Cout, slabs, ncol, bias_slab, rows, dtype, transposed, st, max_split, slab,

@@ -20,6 +20,7 @@
 //   reduces its own 64 rows of every 256-row chunk into a private (32*MT) x (32*NT) tile;
 //   tiles are merged with f32 atomics.
 #include "tdx_common.h"
+#include "tdx_conv1.h"
 #include "tdx_mfma.h"
 
 #define C1M_ROWS 256
@@ -28,11 +29,6 @@
 bool conv1_mfma_supported(int C1, int C2, int Cout) {
     return C1 > 0 && (C1 % C1M_KC) == 0 && (C2 % C1M_KC) == 0 && (Cout % 32) == 0;
 }
-
-// 64-B rows, 4 chunks of 16 B; chunk c of row r lives at chunk position c ^ ((r >> 2) & 3)
-__device__ __forceinline__ int sw64(int r, int c) { return r * 64 + ((c ^ ((r >> 2) & 3)) << 4); }
-// 128-B rows (64 bf16), 8 chunks; chunk c of row r at c ^ (r & 7)
-__device__ __forceinline__ int sw128(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
 
 // `add` through a normalisation: with gn.stats != nullptr the addend is silu(GroupNorm(add)) -- the tail of a ResnetBlock
 // with a projected skip, y = silu(GN(h2)) + conv1x1(x) (reference ddpm.py:176,197), in ONE pass: the skip tensor is never
@@ -358,7 +354,7 @@ conv1_wgrad_mfma_kernel(const bf16* __restrict__ x, int Cin, const bf16* __restr
         for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int q = (i & 3) + 8 * (i >> 2) + 4 * hh;  // the MFMA tile row this accumulator register holds
+                const int q = acc_row(i, hh);  // the MFMA tile row this accumulator register holds
                 // result row / column: TR stores dw[co][ci] (rows = co), else dw[ci][co]
                 const int rr = TR ? n * 32 + q : m * 32 + q, cc = TR ? m * 32 + r : n * 32 + r;
                 tiles[(wave * (TR ? 32 * NT : 32 * MT) + rr) * (TR ? 32 * MT : 32 * NT) + cc] = acc[m][n][i];

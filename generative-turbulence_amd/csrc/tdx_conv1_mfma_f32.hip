@@ -14,8 +14,8 @@
 // channels per workgroup share one dy tile); K = rows, both operands are row-major = K-major, so fragments
 // are again plain b32 reads of [row][channel] tiles; partial tiles are merged with fp32 atomics.
 #include "tdx_common.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+#include "tdx_conv1.h"
+#include "tdx_mfma.h"
 
 #define F1_ROWS 128
 #define F1_BK 32
@@ -102,7 +102,7 @@ conv1_f32_mfma_fwd_kernel(const float* __restrict__ x1, int C1, const float* __r
         const float bv = bias ? bias[ch] : 0.f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int64_t row = r0 + wave * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+            const int64_t row = acc_row(i, hh, r0 + wave * 32);
             if (row < rows) {
                 float v = acc[nt][i] + bv;
                 if (HAS_ADD) v += add[row * Cout + ch];
@@ -215,7 +215,7 @@ conv1_f32_mfma_wgrad_kernel(const float* __restrict__ x, int Cin, const float* _
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int q = (i & 3) + 8 * (i >> 2) + 4 * hh;
+                const int q = acc_row(i, hh);
                 if (TR)
                     atomicAdd(&dw[(int64_t)(co0 + nt * 32 + q) * ldw + ci_blk + wave * 32 + r], acc[nt][i]);
                 else

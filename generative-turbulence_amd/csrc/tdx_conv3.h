@@ -3,6 +3,7 @@
 // route; tdx_conv3_direct.hip weight packing and the vector-ALU kernels; every other tdx_conv3_*.hip one kernel family.
 #pragma once
 #include "tdx_common.h"
+#include "tdx_runtime.h"  // tdx_deterministic, the ordered sums, tdx_persistent_cus, the scratch arena
 
 struct Conv3Geom {
     int B;
@@ -141,9 +142,6 @@ struct Conv3WgradCall {
     float* slabs; int max_slabs; int* nslab;
     bool hf;
 };
-// TDX_DETERMINISTIC=1 in the environment (read per call): the fp32 atomic merges of the backward's small parameter gradients are
-// replaced by per-split partials added in a fixed order (tdx_ordered.hip), the halo shell takes its ordered route
-bool tdx_deterministic();
 // where a launch of nsplit K-splits puts its partial tiles: returns the base (slabs or dwp) and the slab stride (0: atomics
 // into dwp), reports the slab count.  Slab mode: every (tile, split) pair stores its whole partial tile, so the slabs need no
 // zeroing.  TDX_DETERMINISTIC: never the atomic merge -- nsplit is held to the slabs the workspace has (added in order by
@@ -179,20 +177,6 @@ int conv3_wgrad_direct_launch(const Conv3WgradCall& c, int dtype);
 // accumulator dbw -> dbias.  The accumulators are left all-zero.  many: the per-tap summing kernel for more slabs than the
 // tiled one walks.
 int conv3_unpack_wgrad_launch(const Conv3WgradCall& c, float* dw, float* dbw, float* dbias, bool many);
-// CUs the persistent one-workgroup-per-CU kernels (ring conv, producer / consumer weight gradient) may occupy:
-// TDX_PERSISTENT_CUS in the environment (read per call), a multiple of 8 in [8, 256], default 256.  A data-parallel run
-// sets it below 256 to leave CUs to RCCL's kernels.
-int tdx_persistent_cus();
-// dst[r * ld + c] (+)= sum_{k < nslab} slabs[k * stride + r * cols + c], k ascending
-int ordered_sum_launch(const float* slabs, int nslab, int64_t stride, float* dst, int rows, int cols, int64_t ld, bool add,
-                       hipStream_t st);
-// dbias[c] = sum over the nvox rows of dy[v][c] (NDHWC, C % 8 == 0) in a fixed order; part: >= C floats of scratch (256 C used if there)
-size_t bias_grad_ordered_scratch_floats(int C);
-int bias_grad_ordered_launch(const void* dy, int64_t nvox, int C, int dtype, float* dbias, float* part, size_t part_floats,
-                             hipStream_t st);
-// the caller-provided scratch arena (tdx_set_scratch, include/tdx.h); nullptr if none
-void* tdx_scratch_ptr();
-size_t tdx_scratch_bytes();
 
 // halo-shell term of the data gradient, added onto dx with atomics (tdx_conv3_shell.hip); mode 0 bf16, 1 fp32 MFMA,
 // 2 split-precision, 3 fp16; wb = the packed data-gradient operand for (K -> N) in that mode's layout

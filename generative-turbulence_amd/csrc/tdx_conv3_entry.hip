@@ -1,31 +1,10 @@
-// 3x3x3 convolution: the entry points of include/tdx.h, the route that says which kernel serves a call, and the scratch
-// arena.  Host code only.  The kernels and their launchers: tdx_conv3_direct.hip (weight packing, vector ALU),
+// 3x3x3 convolution: the entry points of include/tdx.h and the route that says which kernel serves a call.  Host code only.  The kernels and their launchers: tdx_conv3_direct.hip (weight packing, vector ALU),
 // tdx_conv3_mfma*.hip (brick kernels), tdx_conv3_small*.hip, tdx_conv3_ring.hip, tdx_conv3_shell.hip (halo shell of the
 // data gradient), tdx_conv3_wgrad_*.hip (weight gradient); their interface: tdx_conv3.h.
 #include "tdx_common.h"
 #include "tdx_conv3.h"
 #include <stdlib.h>
 #include <algorithm>
-
-// ------------------------------------------------------------------ scratch arena --------
-// caller-provided transient workspace of kernels whose entry points have no argument for one (the K-split slabs of
-// the small-grid conv, tdx_conv3_small.hip).  The first 64 bytes must be zero and stay zero.
-int tdx_persistent_cus() {
-    const char* env = getenv("TDX_PERSISTENT_CUS");
-    int n = env ? atoi(env) : 256;
-    n = n < 8 ? 8 : (n > 256 ? 256 : n);
-    return n & ~7;
-}
-static void* g_scratch = nullptr;
-static size_t g_scratch_bytes = 0;
-void* tdx_scratch_ptr() { return g_scratch; }
-size_t tdx_scratch_bytes() { return g_scratch_bytes; }
-extern "C" int tdx_set_scratch(void* ptr, size_t bytes) {
-    if (ptr != nullptr && bytes < 64) return TDX_EINVAL;  // at least the zero block
-    g_scratch = ptr;
-    g_scratch_bytes = ptr ? bytes : 0;
-    return TDX_OK;
-}
 
 // ------------------------------------------------------------------ route ----------------
 Conv3Route conv3_route(int dtype, int impl, int C1, int C2, int N, int B, int X, int Y, int Z, bool data_gradient) {

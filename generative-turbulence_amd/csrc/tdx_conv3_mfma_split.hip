@@ -33,20 +33,6 @@ bool conv3_mfma_split_supported(int C1, int C2, int Cout) {
     return C1 > 0 && (C1 % SP_KC) == 0 && (C2 % SP_KC) == 0 && (Cout % 32) == 0;
 }
 
-int conv3_mfma_split_go_2zmp(SPLIT_GO_ARGS);
-int conv3_mfma_split_go_2zmn(SPLIT_GO_ARGS);
-int conv3_mfma_split_go_2rmp(SPLIT_GO_ARGS);
-int conv3_mfma_split_go_2rmn(SPLIT_GO_ARGS);
-int conv3_mfma_split_go_1zbp(SPLIT_GO_ARGS);
-int conv3_mfma_split_go_1zbn(SPLIT_GO_ARGS);
-int conv3_mfma_split_go_1rbp(SPLIT_GO_ARGS);
-int conv3_mfma_split_go_1rbn(SPLIT_GO_ARGS);
-int conv3_mfma_split_go_1zmp(SPLIT_GO_ARGS);
-int conv3_mfma_split_go_1zmn(SPLIT_GO_ARGS);
-int conv3_mfma_split_go_1rmp(SPLIT_GO_ARGS);
-int conv3_mfma_split_go_1rmn(SPLIT_GO_ARGS);
-int conv3_mfma_split_go_1ztp(SPLIT_GO_ARGS);
-
 int conv3_mfma_split_launch(const Conv3Call& c) {
     if (c.fmt != TDX_F32_SPLIT || (c.zero_pad && c.d1 == nullptr)) return TDX_EINVAL;
     const Conv3Geom g = c.geom();

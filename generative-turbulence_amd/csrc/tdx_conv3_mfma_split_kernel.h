@@ -234,3 +234,18 @@ static int split_go(SPLIT_GO_ARGS) {
 }
 #define SPLIT_INSTANCE(NTV, ZP, TH, PM, NAME) \
     int NAME(SPLIT_GO_ARGS) { return split_go<NTV, ZP, TH, PM>(c, reg); }
+// the instantiations (tdx_conv3_mfma_split_i*.hip), declared here for the dispatcher in tdx_conv3_mfma_split.hip:
+// <tiles><z: zero-padded, r: replicate><b: big, m: main, t: thin bricks><p: permuted, n: not>
+int conv3_mfma_split_go_2zmp(SPLIT_GO_ARGS);
+int conv3_mfma_split_go_2zmn(SPLIT_GO_ARGS);
+int conv3_mfma_split_go_2rmp(SPLIT_GO_ARGS);
+int conv3_mfma_split_go_2rmn(SPLIT_GO_ARGS);
+int conv3_mfma_split_go_1zbp(SPLIT_GO_ARGS);
+int conv3_mfma_split_go_1zbn(SPLIT_GO_ARGS);
+int conv3_mfma_split_go_1rbp(SPLIT_GO_ARGS);
+int conv3_mfma_split_go_1rbn(SPLIT_GO_ARGS);
+int conv3_mfma_split_go_1zmp(SPLIT_GO_ARGS);
+int conv3_mfma_split_go_1zmn(SPLIT_GO_ARGS);
+int conv3_mfma_split_go_1rmp(SPLIT_GO_ARGS);
+int conv3_mfma_split_go_1rmn(SPLIT_GO_ARGS);
+int conv3_mfma_split_go_1ztp(SPLIT_GO_ARGS);

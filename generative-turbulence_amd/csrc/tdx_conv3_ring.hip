@@ -598,7 +598,7 @@ static int ring_brick_depth(int C1, int C2, int Cout, int B, int X, int Y, int Z
 }
 // the route's question and the launcher's precondition: the data gradient reads its zero-padding from the arena's zero block
 int conv3_ring_depth(int C1, int C2, int N, int B, int X, int Y, int Z, bool data_gradient) {
-    if (data_gradient && (tdx_scratch_ptr() == nullptr || tdx_scratch_bytes() < 16)) return 0;
+    if (data_gradient && tdx_scratch_zero() == nullptr) return 0;
     return ring_brick_depth(C1, C2, N, B, X, Y, Z);
 }
 static bool ring_z8_supported(int C1, int C2, int Cout, int B, int X, int Y, int Z, int mode) {
@@ -659,7 +659,7 @@ bool conv3_ring_skip_supported(int fmt, int depth, int K, int N, int X, int Y, i
 // bricks of depth = conv3_ring_depth of this call
 int conv3_ring_launch(const Conv3Call& c, int depth) {
     if ((depth != 4 && depth != 8) || !tdx_is_h16(c.fmt)) return TDX_EINVAL;
-    if (c.zero_pad && (tdx_scratch_ptr() == nullptr || tdx_scratch_bytes() < 16)) return TDX_EINVAL;  // zero source
+    if (c.zero_pad && tdx_scratch_zero() == nullptr) return TDX_EINVAL;  // zero source
     const int X = c.X, Y = c.Y, Z = c.Z;
     const bool zero_pad = c.zero_pad, hf = c.hf();
     hipStream_t st = c.st;
@@ -672,7 +672,7 @@ int conv3_ring_launch(const Conv3Call& c, int depth) {
     a.nbx = X / bxr; a.nby = Y / 8; a.nbz = Z / depth; a.ntn = c.N / (32 * NT);
     a.gn_acc = c.gn_acc;
     a.d1 = (bf16*)c.d1; a.d2 = (bf16*)c.d2; a.D1 = c.D1; a.a1 = (const bf16*)c.a1; a.a2 = (const bf16*)c.a2;
-    a.zeros = tdx_scratch_ptr();
+    a.zeros = tdx_scratch_zero();
     a.stamps = nullptr;
 #ifdef RG_STAMPS
     a.stamps = rg_stamp_buffer;

@@ -160,32 +160,16 @@ static bool small_plan(SmallGeom& g, int B, int X, int Y, int Z, int K, int N, b
     int splits = 1;
     double best = 1e30;
     for (int sp = 1; sp <= 16 && sp * 2 <= std::max(nslices, 2); ++sp) {
-        if ((size_t)sp * rows_total * N * 4 + 64 > arena_bytes) break;
+        if ((size_t)sp * rows_total * N * 4 + TDX_SCRATCH_ZERO_BYTES > arena_bytes) break;
         const double rounds = (double)ceil_div(base * sp, 256), per = (double)ceil_div(nslices, sp);
         const double est = rounds * per * (split ? 9e-6 : 3.5e-6) + (sp > 1 ? 2.0 * sp * rows_total * N * 4 / 5e12 : rows_total * N * 8.0 / 5e12);
         if (est < best * 0.97) { best = est; splits = sp; }
     }
-    if ((size_t)splits * rows_total * N * 4 + 64 > arena_bytes) return false;
+    if ((size_t)splits * rows_total * N * 4 + TDX_SCRATCH_ZERO_BYTES > arena_bytes) return false;
     g.per_split = ceil_div(nslices, splits);
     g.nsplit = ceil_div(nslices, g.per_split);
     return true;
 }
-
-int conv3_small_go_3b(SMALL_GO_ARGS);
-int conv3_small_go_3s(SMALL_GO_ARGS);
-int conv3_small_go_4b(SMALL_GO_ARGS);
-int conv3_small_go_4s(SMALL_GO_ARGS);
-int conv3_small_go_5b(SMALL_GO_ARGS);
-int conv3_small_go_5s(SMALL_GO_ARGS);
-int conv3_small_go_6b(SMALL_GO_ARGS);
-int conv3_small_go_6s(SMALL_GO_ARGS);
-int conv3_small_go_7b(SMALL_GO_ARGS);
-int conv3_small_go_7s(SMALL_GO_ARGS);
-int conv3_small_go_3h(SMALL_GO_ARGS);
-int conv3_small_go_4h(SMALL_GO_ARGS);
-int conv3_small_go_5h(SMALL_GO_ARGS);
-int conv3_small_go_6h(SMALL_GO_ARGS);
-int conv3_small_go_7h(SMALL_GO_ARGS);
 
 static int small_dispatch(SMALL_GO_ARGS) {
 #define GO(M) (c.fmt == TDX_F32_SPLIT ? conv3_small_go_##M##s(c, p, slab, zero16, lo_offset)   \
@@ -215,13 +199,14 @@ bool conv3_small_plan(Conv3SmallPlan& p, int C1, int C2, int N, int B, int X, in
 // result N channels split over d1 [0, D1) / d2, plus addends).  TDX_BF16 / TDX_F16: 16-bit tensors and packed weight;
 // TDX_F32_SPLIT: fp32 tensors, wp = the split-precision packed weight (hi image, lo image).  p: conv3_small_plan of this call.
 int conv3_small_launch(const Conv3Call& c, const Conv3SmallPlan& p) {
-    char* arena = (char*)tdx_scratch_ptr();
     const bool split = c.fmt == TDX_F32_SPLIT;
-    if (arena == nullptr || !(split || tdx_is_h16(c.fmt))) return TDX_EINVAL;
-    float* slab = reinterpret_cast<float*>(arena + 64);
+    // the K-split slabs: [nsplit][rows of the virtual grid][N] fp32 right behind the zero block (small_plan fitted them)
+    const size_t slab_bytes = (size_t)p.g.nsplit * p.g.B * p.g.Ev[0] * p.g.Ev[1] * p.g.Ev[2] * c.N * sizeof(float);
+    float* slab = reinterpret_cast<float*>(tdx_scratch_region(TDX_SCRATCH_ZERO_BYTES, slab_bytes));
+    if (slab == nullptr || !(split || tdx_is_h16(c.fmt))) return TDX_EINVAL;
     const int N = c.N, D1 = c.zero_pad ? c.D1 : N, fold = c.zero_pad ? 1 : 0;
     void* out1 = c.zero_pad ? c.d1 : c.y;
-    const int rc = small_dispatch(c, p, slab, arena, split ? (int64_t)27 * (c.C1 + c.C2) * N : 0);
+    const int rc = small_dispatch(c, p, slab, tdx_scratch_zero(), split ? (int64_t)27 * (c.C1 + c.C2) * N : 0);
     if (rc != TDX_OK) return rc;
     const int64_t total = (int64_t)c.B * c.X * c.Y * c.Z * (N / 8);
 #define SM_REDUCE(T)                                                                                                          \

@@ -276,3 +276,19 @@ static int small_go(SMALL_GO_ARGS) {
     int NAME(SMALL_GO_ARGS) { return small_go<MTW, SPLIT>(c, p, slab, zero16, lo_offset); }
 #define SMALL_INSTANCE_F16(MTW, NAME) \
     int NAME(SMALL_GO_ARGS) { return small_go<MTW, false, true>(c, p, slab, zero16, lo_offset); }
+// <M tiles per wave><b: bf16, h: fp16, s: split precision>
+int conv3_small_go_3b(SMALL_GO_ARGS);
+int conv3_small_go_3s(SMALL_GO_ARGS);
+int conv3_small_go_4b(SMALL_GO_ARGS);
+int conv3_small_go_4s(SMALL_GO_ARGS);
+int conv3_small_go_5b(SMALL_GO_ARGS);
+int conv3_small_go_5s(SMALL_GO_ARGS);
+int conv3_small_go_6b(SMALL_GO_ARGS);
+int conv3_small_go_6s(SMALL_GO_ARGS);
+int conv3_small_go_7b(SMALL_GO_ARGS);
+int conv3_small_go_7s(SMALL_GO_ARGS);
+int conv3_small_go_3h(SMALL_GO_ARGS);
+int conv3_small_go_4h(SMALL_GO_ARGS);
+int conv3_small_go_5h(SMALL_GO_ARGS);
+int conv3_small_go_6h(SMALL_GO_ARGS);
+int conv3_small_go_7h(SMALL_GO_ARGS);

@@ -269,7 +269,7 @@ conv3_wgrad_ring_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
 bool conv3_wgrad_ring_supported(int C1, int C2, int Cout) {
     const char* env = getenv("TDX_WGRAD_RING");  // A/B switch, read per call: 0 = off
     if (env && atoi(env) == 0) return false;
-    return conv3_wgrad_mfma_supported(C1, C2, Cout) && (Cout % 32) == 0 && tdx_scratch_ptr() != nullptr && tdx_scratch_bytes() >= 16;
+    return conv3_wgrad_mfma_supported(C1, C2, Cout) && (Cout % 32) == 0 && tdx_scratch_zero() != nullptr;
 }
 
 // same contract as conv3_wgrad_mfma_launch; TDX_ESHAPE = not a case for this kernel
@@ -307,7 +307,7 @@ int conv3_wgrad_ring_launch(const Conv3WgradCall& c) {
         }                                                                                                                         \
         hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles * nsplit)), dim3(768), lds, c.st, (const bf16*)c.x1, c.C1,                \
                            (const bf16*)c.x2, c.C2, (const bf16*)c.dy, out, c.dbias, g, Cout, nsplit, n_ci, slab_stride,          \
-                           tdx_scratch_ptr());                                                                                    \
+                           tdx_scratch_zero());                                                                                   \
     } while (0)
     if (NTN == 2) { if (c.hf) WR_GO(2, true); else WR_GO(2, false); }
     else { if (c.hf) WR_GO(1, true); else WR_GO(1, false); }

@@ -18,12 +18,9 @@
 //   wgrad      dW[t][ci][co] = sum_{b, o} in[src(o, t)][ci] * dy[o][co]
 // Weights are passed as [taps][Cin][Cout] fp32 (the host transposes the reference layouts once per call).
 #include "tdx_common.h"
+#include "tdx_convg.h"
 #include <stdlib.h>
 
-int convg_mfma_apply(const void* in, const float* w, const float* bias, void* out, int B, const int* Ei, const int* Eo, int Cin,
-                     int Cout, int k, int stride, int dil, int pad, int replicate, int transposed, hipStream_t st);
-int convg_mfma_bwd_weight(const void* in, const void* dy, float* dw, float* dbias, int B, const int* Ei, const int* Eo, int Cin,
-                          int Cout, int k, int stride, int dil, int pad, int replicate, hipStream_t st);
 static bool convg_use_mfma(int dtype) {  // read per call: the switch is a test / benchmark knob
     const char* e = getenv("TDX_CONVG_MFMA");
     return dtype == TDX_BF16 && !(e && atoi(e) == 0);

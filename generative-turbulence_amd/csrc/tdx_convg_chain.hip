@@ -7,11 +7,7 @@
 // Without them a layer's forward is conv + relu + one or two adds and its backward fold + relu mask + add: five extra passes
 // over B x V x 48 bf16 per layer.  Semantics and operand layouts are in include/tdx.h.
 #include "tdx_common.h"
-
-int convg_mfma_apply_epilogue(const void* in, const float* w, const float* bias, void* out, int B, const int* Ei, const int* Eo,
-                              int Cin, int Cout, int k, int dil, int pad, int replicate, const TdxConvgEpilogue* ep, hipStream_t st);
-int convg_mfma_apply(const void* in, const float* w, const float* bias, void* out, int B, const int* Ei, const int* Eo, int Cin,
-                     int Cout, int k, int stride, int dil, int pad, int replicate, int transposed, hipStream_t st);
+#include "tdx_convg.h"
 
 extern "C" int tdx_convg_apply_fused(const void* in, const float* w, const float* bias, void* out, int B, int Xi, int Yi, int Zi,
                                      int Cin, int Xo, int Yo, int Zo, int Cout, int k, int dilation, int pad, int replicate,

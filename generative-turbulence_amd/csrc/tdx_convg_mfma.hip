@@ -17,6 +17,7 @@
 // with (o + pad - t dil) divisible by s along every axis.  Workgroups therefore own voxels of ONE residue class o mod s, the
 // divisibility test is uniform per workgroup and the dead taps (7 of 8 at stride 2) are skipped, not masked.
 #include "tdx_common.h"
+#include "tdx_convg.h"
 #include "tdx_mfma.h"
 
 struct ConvGM {
@@ -426,7 +427,7 @@ convg_wgrad_mfma_kernel(const bf16* __restrict__ in, const bf16* __restrict__ dy
         for (int n = 0; n < 2; ++n)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int ci = ci0 + m * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh, co = co0 + n * 32 + r;
+                const int ci = acc_row(i, hh, ci0 + m * 32), co = co0 + n * 32 + r;
                 if (ci < g.Cin && co < g.Cout) atomicAdd(&dwt[(int64_t)ci * g.Cout + co], acc[m][n][i]);
             }
     if (do_bias && hh == 0) {  // every row of accb is the column sum; row 0 sits in register 0 of lane half 0

@@ -3,7 +3,7 @@
 // the (B,C,V) <-> (B,V,C) transposes which go through an LDS tile so that both sides are
 // coalesced.
 #include "tdx_common.h"
-#include "tdx_conv3.h"  // tdx_deterministic
+#include "tdx_runtime.h"  // tdx_deterministic
 
 extern "C" int tdx_version(void) { return 1; }
 extern "C" const char* tdx_arch(void) { return "gfx950"; }

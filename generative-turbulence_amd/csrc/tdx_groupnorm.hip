@@ -165,9 +165,6 @@ int gn_finalize_launch(double* acc, float* stats, int B, int C, int G, int64_t V
     return tdx_launch_status();
 }
 
-int gn_stats_launch(const void* x, float* stats, int B, int64_t V, int C, int G, float eps, int dtype, void* workspace,
-                    bool clean, hipStream_t stream);  // also declared in tdx_conv3.h for tdx_conv3_fwd_gn
-
 extern "C" int tdx_gn_stats(const void* x, float* stats, int B, int64_t V, int C, int G, float eps, int dtype,
                             void* workspace, void* stream) {
     return gn_stats_launch(x, stats, B, V, C, G, eps, dtype, workspace, false, as_stream(stream));
@@ -195,8 +192,8 @@ int gn_stats_launch(const void* x, float* stats, int B, int64_t V, int C, int G,
         // writer per element), gn_stats_merge_kernel adds them in block order
         if (ceil_div(V, vpb) > 64) vpb = (ceil_div(V, 64) + 31) / 32 * 32;
         const size_t need = (size_t)B * ceil_div(V, vpb) * C * 2 * sizeof(double);
-        if (tdx_scratch_ptr() != nullptr && tdx_scratch_bytes() >= 256 + need) part = reinterpret_cast<double*>((char*)tdx_scratch_ptr() + 256);
-        else vpb = (V + 31) / 32 * 32;  // no arena (TDX_SCRATCH_MB=0): ONE block per sample adds into the zeroed table -- slow, still ordered
+        part = reinterpret_cast<double*>(tdx_scratch_region(TDX_SCRATCH_SLAB_OFFSET, need));
+        if (part == nullptr) vpb = (V + 31) / 32 * 32;  // no arena (TDX_SCRATCH_MB=0): ONE block per sample adds into the zeroed table -- slow, still ordered
     }
     dim3 grid(ceil_div(V, vpb), B);
     TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gn_stats_kernel<T>), grid, dim3(GN_THREADS), 0, stream,

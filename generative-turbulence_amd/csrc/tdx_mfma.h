@@ -1,13 +1,15 @@
 // Device helpers shared by the matrix-core kernels (gfx950): the vector types of MFMA fragments, the transposed LDS
-// fragment read, the fp32 -> bf16 hi / lo split, one LDS-DMA instruction, and the workgroup barrier behind an LDS wait.
-// Everything here is __forceinline__ and format-agnostic: 16-bit operands travel as raw words in bf16x8 (H16<HF>,
-// tdx_common.h, picks the MFMA opcode).  The attention kernels' fragment reads return a type that depends on the
-// operand format and stay in their own files.
+// fragment read, the swizzled LDS row layouts, the register <-> row map of a 32 x 32 accumulator tile and the fragments
+// made from registers or global rows, the fp32 -> bf16 hi / lo split, one LDS-DMA instruction, and the workgroup barrier
+// behind an LDS wait.  Everything here is __forceinline__ and format-agnostic: 16-bit operands travel as raw words in
+// bf16x8, in the attention kernels too; H16<HF> (tdx_common.h) picks the MFMA opcode and the rounding, and its bit-cast
+// of the words costs no instruction.
 #pragma once
 #include "tdx_common.h"
 
 typedef bf16x8_t bf16x8;
 typedef f32x16_t f32x16;
+typedef f32x4_t f32x4;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -21,6 +23,39 @@ __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* lo, const unsigne
     s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(hi));
     s16x8 r = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_bit_cast(bf16x8, r);
+}
+
+// Swizzled LDS tiles whose 16-B chunks are read as ds_read_b128 fragments without bank conflicts: byte offset of chunk c of
+// row r.  64-B rows (32 16-bit elements, 4 chunks): chunk position c ^ ((r >> 2) & 3)
+__device__ __forceinline__ int sw64(int r, int c) { return r * 64 + ((c ^ ((r >> 2) & 3)) << 4); }
+// 128-B rows (64 elements, 8 chunks): chunk position c ^ (r & 7)
+__device__ __forceinline__ int sw128(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
+
+// Row of a 32 x 32 accumulator tile (v_mfma_f32_32x32x*) that register i of a lane in half hh = lane >> 5 holds; the
+// column is lane & 31.  Registers 4 j .. 4 j + 3 are the consecutive rows 8 j + 4 hh .. + 3.  base: the tile's first row in
+// whatever the caller counts (added first, as the kernels always wrote it: the sum's order decides the instructions).
+template <typename B = int>
+__device__ __forceinline__ B acc_row(int i, int hh, B base = 0) { return base + (i & 3) + 8 * (i >> 2) + 4 * hh; }
+
+// Accumulator registers 8 s .. 8 s + 7 of a 32 x 32 tile, rounded to the format: the B operand of k step s of a product
+// that sums over the tile's rows (by acc_row the lane's 8 registers are k = 16 s + 8 (j >> 2) + 4 hh + (j & 3): the A operand
+// comes from tr_frag with the two reads 8 rows apart)
+template <typename H>
+__device__ __forceinline__ bf16x8 acc_as_b(const f32x16& t, int s) {
+    return __builtin_bit_cast(bf16x8, make_uint4(H::pack2(t[8 * s], t[8 * s + 1]), H::pack2(t[8 * s + 2], t[8 * s + 3]),
+                                                 H::pack2(t[8 * s + 4], t[8 * s + 5]), H::pack2(t[8 * s + 6], t[8 * s + 7])));
+}
+
+// 8 consecutive elements of a global row, times `scale`, rounded to the format again: a B operand (col = the lane's row,
+// k = the 8 elements)
+template <typename H>
+__device__ __forceinline__ bf16x8 row_frag(const typename H::T* row, float scale) {
+    Vec8<typename H::T> v;
+    v.load(row);
+    unsigned w[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w[e] = H::pack2(v.v[2 * e] * scale, v.v[2 * e + 1] * scale);
+    return __builtin_bit_cast(bf16x8, make_uint4(w[0], w[1], w[2], w[3]));
 }
 
 // Split precision: 8 fp32 -> 8 bf16 hi (= bf16(v)) and 8 bf16 lo (= bf16(v - hi)), packed two per word

@@ -11,8 +11,37 @@
 // (no moments from the conv epilogues), whose blocks store their own f64 tables for an ordered merge (tdx_groupnorm.hip);
 // the loss adds block partials rounded to a 2^-20 grid, on which f64 additions are exact -- order-independent -- up to 2^33.
 // tdx_conv3_fwd_partial (the sampler's first conv) does the same: a sampling run is bit-reproducible too.
+//
+// The other library-wide host services of tdx_runtime.h live here too: the CU budget of the persistent kernels, the scratch
+// arena, and the zero fills.
 #include "tdx_common.h"
-#include "tdx_conv3.h"
+#include "tdx_runtime.h"
+#include <stdlib.h>
+#include <algorithm>
+
+int tdx_persistent_cus() {
+    const char* env = getenv("TDX_PERSISTENT_CUS");
+    int n = env ? atoi(env) : 256;
+    n = n < 8 ? 8 : (n > 256 ? 256 : n);
+    return n & ~7;
+}
+
+// ---- scratch arena (layout and the rule of its reuse: tdx_runtime.h) ----------------------------------------------------
+static void* g_scratch = nullptr;
+static size_t g_scratch_bytes = 0;
+void* tdx_scratch_ptr() { return g_scratch; }
+size_t tdx_scratch_bytes() { return g_scratch_bytes; }
+const void* tdx_scratch_zero() { return g_scratch; }
+void* tdx_scratch_region(size_t offset, size_t bytes) {
+    if (g_scratch == nullptr || offset > g_scratch_bytes || bytes > g_scratch_bytes - offset) return nullptr;
+    return (char*)g_scratch + offset;
+}
+extern "C" int tdx_set_scratch(void* ptr, size_t bytes) {
+    if (ptr != nullptr && bytes < TDX_SCRATCH_ZERO_BYTES) return TDX_EINVAL;  // at least the zero block
+    g_scratch = ptr;
+    g_scratch_bytes = ptr ? bytes : 0;
+    return TDX_OK;
+}
 
 bool tdx_deterministic() {
     const char* e = getenv("TDX_DETERMINISTIC");  // read per call: a test / training-run switch
