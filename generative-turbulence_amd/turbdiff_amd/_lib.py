@@ -103,6 +103,12 @@ SIGNATURES = {
     "tdx_ot_features": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _f, _f, _f, _vp]),
     "tdx_ot_workspace_bytes": (_sz, [_i, _i]),
     "tdx_ot_auction": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _i, _i, _i, C.c_double, _i, _i64, _vp, _i, _i, _vp, _vp, _vp]),
+    "tdx_moments_update": (_i, [_vp, _i, _i64, _vp, _vp, _i64, _vp]),
+    "tdx_field_stats_workspace_bytes": (_sz, [_i64, _i]),
+    "tdx_field_stats": (_i, [_vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "tdx_w2n_blocks": (_i, [_i64]),
+    "tdx_w2n_assign": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "tdx_w2n_reduce": (_i, [_vp, _i, _i, _vp, _vp]),
     "tdx_randn": (_i, [_vp, _i64, _u64, _u64, _vp, _vp]),
     "tdx_randn_batched": (_i, [_vp, _i, _i64, _u64, _vp, _vp, _vp]),
     "tdx_convg_apply": (_i, [_vp, _vp, _vp, _vp] + [_i] * 16 + [_vp]),

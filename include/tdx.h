@@ -587,6 +587,33 @@ int tdx_ot_auction(const float* fa, const float* fb, int64_t n_cells, const int*
                    const int* jobs, int J, int Sa, int Sb, double rel_eps, int max_rounds, int64_t max_bids,
                    void* workspace, int max_n, int slots, double* out, int* status, void* stream);
 
+/* ------------------------------------------------------------------ case preparation ------ */
+/* The reductions of turbdiff_amd/data/prepare.py (tdx_prepare.hip); every sum in an order fixed by the shapes alone.
+ * tdx_moments_update: x (T, n) f32 is one chunk of frames, column = cell x component.  mean (n), m2 (n) f64 hold the
+ *   temporal mean and the centred sum of squares of the `count` frames merged so far (count == 0: the state is not read).
+ *   The chunk's own mean and centred sum of squares are formed in fp64 in two passes and merged with Chan's update
+ *   (delta = mean_chunk - mean; mean += delta T / (count + T); m2 += m2_chunk + delta^2 count T / (count + T)).
+ *   Any n and T >= 1; one column belongs to one thread.
+ * tdx_field_stats: x (rows, C) f32, C <= 8, 16-byte aligned.  out (C + 2, 4) f64 = [min, max, sum, sum of squares] per column
+ *   and, in rows C and C + 1, of the row-wise L2 norms over columns [lo0, hi0) and [lo1, hi1) (fp32, left to right, as
+ *   np.linalg.norm on float32 rows; an empty range gives [inf, -inf, 0, 0]).  Squares are rounded to fp32 before they are
+ *   summed, as `field ** 2` on a float32 array is; all sums are fp64.  workspace: tdx_field_stats_workspace_bytes(rows, C)
+ *   bytes of block partials, folded by one block.
+ * tdx_w2n_assign: cells mean, var (n, 3) f32; centroids cmean, cvar (k, 3) f64, k <= 512.  idx (n) int32 = the nearest
+ *   centroid (the lowest index on ties), dist (n) f64 = its distance
+ *     sqrt(max(0, |cm - m|^2 + sum cvar + sum var - 2 sum sqrt(cvar var)))
+ *   in fp64, except that `sum var` is the fp32 sum (v0 + v1) + v2 (scripts/homogeneous-regions.py:16-25 on float32 cells).
+ *   partials (tdx_w2n_blocks(n), k, 7) f64 or NULL: per block and cluster [count, sum mean (3), sum var (3)] of the block's
+ *   cells, added in cell order; tdx_w2n_reduce adds them in block order into table (k, 7). */
+int tdx_moments_update(const float* x, int T, int64_t n, double* mean, double* m2, int64_t count, void* stream);
+size_t tdx_field_stats_workspace_bytes(int64_t rows, int C);
+int tdx_field_stats(const float* x, int64_t rows, int C, int lo0, int hi0, int lo1, int hi1, double* out, void* workspace,
+                    void* stream);
+int tdx_w2n_blocks(int64_t n);
+int tdx_w2n_assign(const float* mean, const float* var, int64_t n, const double* cmean, const double* cvar, int k, int* idx,
+                   double* dist, double* partials, void* stream);
+int tdx_w2n_reduce(const double* partials, int blocks, int k, double* table, void* stream);
+
 /* Counter-based N(0,1) generator (Philox4x32-10 + Box-Muller), graph-replay safe: the
  * 64-bit offset is read from device memory and advanced by the kernel itself.
  * Replaces torch.randn_like (ddpm.py:777,801,810,835) inside captured sampling graphs.

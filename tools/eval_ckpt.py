@@ -18,7 +18,9 @@ eval_ckpt.py computes them with ``expensive_metrics=False``), ``--expensive-metr
 the batched device auction).  ``--sampling-steps N [--eta E]`` draws the samples with the DDIM sampler over N of the training
 timesteps instead of the full ancestral chain (what that does to the metrics has not been measured).  Their side files (``regions.npz``, ``max-mean-tke.npy``, ``mean-flow.h5``) come from an
 optional ``side`` entry of the ``--cases`` blob, ``{case_name: {file name: value}}``; ``--synthetic`` cases bring their
-own (channel-aligned region blocks, a nominal max-mean-TKE position).
+own (channel-aligned region blocks, a nominal max-mean-TKE position).  Those stand-ins are not the reference's regions, so
+``wasserstein`` on them is not the paper's metric: for real cases ``tools/prepare_dataset.py`` writes the three side files
+(and ``stats.pickle``) from the raw ``data.h5`` files, as the reference's scripts do.
 """
 
 import argparse
