@@ -11,6 +11,7 @@
 // 0.01 GFLOP).  The MFMA flash kernel for long sequences lives in tdx_attention_mfma.hip.
 #include "tdx_common.h"
 #include "tdx_attention.h"
+#include "tdx_runtime.h"
 #include <stdlib.h>
 
 // The "other side" rows are walked in tiles of 64 staged in LDS as f32 (thread t stages row t with
@@ -188,8 +189,7 @@ extern "C" int tdx_attn_fwd(const void* qkv, void* out, float* lse, int B, int N
     TDX_CHECK_ARG(qkv && out && lse && B > 0 && N > 0 && H > 0);
     if (D != 32) return TDX_ESHAPE;
     {
-        const char* e = getenv("TDX_ATTN_IMPL");
-        const bool force_vector = e && e[0] == 'v';
+        const bool force_vector = tdx_switch(SW_ATTN_IMPL) != 0;
         if ((dtype == TDX_BF16 || dtype == TDX_F16) && !force_vector && attn_mfma_supported(N, D))
             return attn_fwd_mfma_launch(qkv, out, lse, B, N, H, dtype, as_stream(stream));
     }
@@ -213,8 +213,7 @@ extern "C" int tdx_attn_bwd(const void* qkv, const void* out, const float* lse, 
     dim3 grid(ceil_div(N, 64), B * H);
     hipStream_t st = as_stream(stream);
     {
-        const char* e = getenv("TDX_ATTN_IMPL");
-        const bool force_vector = e && e[0] == 'v';
+        const bool force_vector = tdx_switch(SW_ATTN_IMPL) != 0;
         if (dtype == TDX_BF16 && !force_vector && attn_mfma_supported(N, D)) {  // long sequences: MFMA flash backward
             hipLaunchKernelGGL((attn_delta_kernel<bf16, 32>), dim3(ceil_div(total, 256)), dim3(256), 0, st, (const bf16*)out,
                                (const bf16*)dout, delta, N, H, total);

@@ -25,6 +25,7 @@
 //
 // 6 + 8 MFMAs per 32 x 32 tile against the forward's 4; no atomics, no running maximum.
 #include "tdx_attention.h"
+#include "tdx_runtime.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -305,11 +306,11 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
 int attn_bwd_mfma_launch(const void* qkv, const void* dout, const float* lse, const float* delta, void* dqkv, int B, int N,
                          int H, int dtype, hipStream_t st) {
     dim3 grid(ceil_div(N, FB_RB), B * H);
-    // TDX_ATTN_BWD_TW (A/B knob, read per call): tiles per wave of the dQ / dK-dV kernel, "<dq><dkv>", e.g. 21.  Default 22
+    // TDX_ATTN_BWD_TW (A/B knob): tiles per wave of the dQ / dK-dV kernel, "<dq><dkv>", e.g. 21.  Default 22
     // (two tiles per wave, two waves per SIMD): one tile per wave at three or four waves per SIMD measured 10.99-12.3 ms
     // against 11.4-11.5 (profiles/r13_attention_bwd_ablation.txt) -- more waves do not hide the vector work either
-    const char* env = getenv("TDX_ATTN_BWD_TW");
-    const int twq = env && env[0] == '1' ? 1 : 2, twk = env && env[0] && env[1] == '1' ? 1 : 2;
+    const int tw = tdx_switch(SW_ATTN_BWD_TW);
+    const int twq = tw / 10, twk = tw % 10;
 #define FB_GO(E, T)                                                                                                            \
     do {                                                                                                                       \
         if (twq == 2) hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<E, 2>), grid, dim3(64 * FB_WAVES(2)), 0, st, (const T*)qkv,   \

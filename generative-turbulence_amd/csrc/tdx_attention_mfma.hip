@@ -390,8 +390,7 @@ int attn_fwd_mfma_launch(const void* qkv, void* out, float* lse, int B, int N, i
     a.total = (long long)nblk * a.ntile;
     const int slots = 512;  // 256 CUs x 2 workgroups
     const size_t head = TDX_SCRATCH_ZERO_BYTES + FA_KMAX_BYTES;
-    const char* env = getenv("TDX_ATTN_STREAMK");
-    const bool want = !(env && env[0] == '0') && nblk > slots && (nblk % slots) != 0 && a.ntile >= 16;
+    const bool want = tdx_switch(SW_ATTN_STREAMK) != 0 && nblk > slots && (nblk % slots) != 0 && a.ntile >= 16;
     a.part = want ? reinterpret_cast<float*>(tdx_scratch_region(head, (size_t)slots * 2 * FA_PART_STRIDE * sizeof(float))) : nullptr;
     if (a.part != nullptr) {
         a.nwg = slots;
@@ -401,9 +400,8 @@ int attn_fwd_mfma_launch(const void* qkv, void* out, float* lse, int B, int N, i
         a.chunk = a.ntile;
     }
     a.kmax2 = nullptr;
-    const char* envb = getenv("TDX_ATTN_BOUND");
     float* km = reinterpret_cast<float*>(tdx_scratch_region(TDX_SCRATCH_ZERO_BYTES, FA_KMAX_BYTES));
-    if (!(envb && envb[0] == '0') && km != nullptr && B * H <= 256 && a.ntile >= 8) {
+    if (tdx_switch(SW_ATTN_BOUND) != 0 && km != nullptr && B * H <= 256 && a.ntile >= 8) {
         if (tdx_zero_async(km, (size_t)B * H * sizeof(float), st) != TDX_OK) return TDX_EINVAL;
         const dim3 kg(min(ceil_div(N, 64), 64), B * H);
         if (dtype == TDX_F16) hipLaunchKernelGGL(attn_kmax_kernel<f16>, kg, dim3(256), 0, st, (const f16*)qkv, km, N, H);

@@ -11,10 +11,7 @@
 #include <stdlib.h>
 #include <algorithm>
 
-static bool conv1_force_direct() {
-    const char* e = getenv("TDX_CONV1_IMPL");
-    return e && e[0] == 'd';
-}
+static bool conv1_force_direct() { return tdx_switch(SW_CONV1_IMPL) != 0; }
 
 #define C1_BM 64
 #define C1_BN 64

@@ -113,10 +113,10 @@ __device__ __forceinline__ int brick_tap(const BrickView& g, int ex, int ey, int
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-// A/B switches of the planning, read per call.  TDX_CONV3_THIN: 0 = no thin slabs, 2 = thin slabs on grids of any size
-// (16-bit kernel); TDX_CONV3_PERM: 0 = main bricks in grid orientation (16-bit kernel)
-static inline int conv3_thin_slabs() { const char* e = getenv("TDX_CONV3_THIN"); return e ? atoi(e) : 1; }
-static inline bool conv3_perm_bricks() { const char* e = getenv("TDX_CONV3_PERM"); return !(e && atoi(e) == 0); }
+// A/B switches of the planning.  TDX_CONV3_THIN: 0 = no thin slabs, 2 = thin slabs on grids of any size (16-bit kernel);
+// TDX_CONV3_PERM: 0 = main bricks in grid orientation (16-bit kernels, the weight gradient's bricks included)
+static inline int conv3_thin_slabs() { return tdx_switch(SW_CONV3_THIN); }
+static inline bool conv3_perm_bricks() { return tdx_switch(SW_CONV3_PERM) != 0; }
 
 static inline void brick_dims(int shape, int bd[3]) {
     bd[0] = shape == BRICK_THIN ? 2 : (shape == BRICK_BIG ? 8 : 4); bd[1] = shape == BRICK_THIN ? 16 : 8; bd[2] = 8;

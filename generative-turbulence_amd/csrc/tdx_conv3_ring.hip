@@ -48,9 +48,6 @@
 #define RG_WSLOTS 3                     // weight ring (lookahead 2 units)
 #define RG_WAVES 8
 #define RG_STEPS 14                     // K steps per unit: tap pairs (2p, 2p + 1); tap 27 is the zero dummy
-#ifndef RG_DEFAULT_LOADERS
-#define RG_DEFAULT_LOADERS 1            // loader waves by default? (TDX_RING_LOADERS overrides per call)
-#endif
 
 struct RingArgs {
     const bf16* x1; const bf16* x2; int C1, C2;
@@ -573,8 +570,7 @@ __global__ void __launch_bounds__(512 + 64 * LW, LW ? 3 : 2) conv3_ring_kernel(R
 
 static bool ring_z8_supported(int C1, int C2, int Cout, int B, int X, int Y, int Z, int mode);
 static bool ring_z4_supported(int C1, int C2, int Cout, int B, int X, int Y, int Z, int mode) {
-    const char* env = getenv("TDX_RING_Z4");  // A/B switch, read per call: 0 = no 4-deep bricks (round 5's dispatch), 2 = prefer them
-    if (env && atoi(env) == 0) return false;
+    if (tdx_switch(SW_RING_Z4) == 0) return false;  // A/B switch: 0 = no 4-deep bricks (round 5's dispatch), 2 = prefer them
     const int NT = Cout % 64 == 0 ? 2 : 1, bx = NT == 2 ? 16 : 32;
     if (X < bx || Y < 8 || Z < 4 || (X % bx) > 2 || (Y % 8) > 2 || (Z % 4) > 2) return false;
     const int ntn = Cout / (32 * NT);
@@ -588,11 +584,10 @@ static bool ring_z4_supported(int C1, int C2, int Cout, int B, int X, int Y, int
 }
 // brick shape of the ring kernel for this call: 0 = not a case for it, 8 = 8-deep bricks, 4 = 4-deep bricks (Z4)
 static int ring_brick_depth(int C1, int C2, int Cout, int B, int X, int Y, int Z) {
-    const char* env = getenv("TDX_CONV3_RING");  // A/B switch, read per call: 0 off, 1 auto (default), 2 whenever legal
-    const int mode = env ? atoi(env) : 1;
+    const int mode = tdx_switch(SW_CONV3_RING);  // A/B switch: 0 off, 1 auto (default), 2 whenever legal
     if (mode == 0 || !conv3_mfma_supported(C1, C2, Cout)) return 0;
-    const char* z4 = getenv("TDX_RING_Z4");  // 2: 4-deep bricks wherever they are legal (tests)
-    if (z4 && atoi(z4) == 2 && ring_z4_supported(C1, C2, Cout, B, X, Y, Z, 2)) return 4;
+    // TDX_RING_Z4 = 2: 4-deep bricks wherever they are legal (tests)
+    if (tdx_switch(SW_RING_Z4) == 2 && ring_z4_supported(C1, C2, Cout, B, X, Y, Z, 2)) return 4;
     if (ring_z8_supported(C1, C2, Cout, B, X, Y, Z, mode)) return 8;
     return ring_z4_supported(C1, C2, Cout, B, X, Y, Z, mode) ? 4 : 0;
 }
@@ -608,8 +603,8 @@ static bool ring_z8_supported(int C1, int C2, int Cout, int B, int X, int Y, int
     // to the thin-brick kernel of tdx_conv3_mfma.hip in a second launch (conv3_ring_launch).  Larger remainders (level 2 of
     // the benchmark grid, 48 x 16 x 12) stay on the brick kernels altogether.
     if (X < bx || Y < 8 || Z < 8 || (X % bx) > 2 || (Y % 8) > 2 || (Z % 8) > 2) return false;
-    const char* rag = getenv("TDX_RING_RAGGED");  // A/B switch: 0 = whole-brick grids only (round 3's rule)
-    if (rag && atoi(rag) == 0 && ((X % bx) || (Y % 8) || (Z % 8))) return false;
+    // A/B switch: TDX_RING_RAGGED = 0: whole-brick grids only (round 3's rule)
+    if (tdx_switch(SW_RING_RAGGED) == 0 && ((X % bx) || (Y % 8) || (Z % 8))) return false;
     const int ntn = Cout / (32 * NT);
     if (ntn > tdx_persistent_cus() / 8) return false;  // an XCD's workgroups = brick lanes x N tiles
     if ((int64_t)X * Y * Z * 1024 >= (1ll << 31)) return false;  // 32-bit per-lane byte offsets
@@ -620,8 +615,7 @@ static bool ring_z8_supported(int C1, int C2, int Cout, int B, int X, int Y, int
     if (NT == 1 && std::max(C1, C2) > 32) return false;
     // persistent one-workgroup-per-CU launch: every CU should get several bricks
     const int64_t nb = (int64_t)B * (X / bx) * (Y / 8) * (Z / 8);
-    const char* mi = getenv("TDX_RING_MIN_ITEMS");  // A/B knob, read per call: (brick, N tile) pairs a launch must have
-    return nb * ntn >= (mi ? atoi(mi) : 3 * 256);
+    return nb * ntn >= tdx_switch(SW_RING_MIN_ITEMS);  // A/B knob: (brick, N tile) pairs a launch must have, 3 per CU
 }
 
 #ifdef RG_STAMPS
@@ -640,16 +634,14 @@ static int ring_go(const RingArgs& a, hipStream_t st) {
 }
 
 static bool ring_loader_form(bool hf) {
-    const char* env = getenv("TDX_RING_LOADERS");  // A/B switch: 0 = the computing waves issue the copies themselves
-    return hf || (env ? atoi(env) != 0 : RG_DEFAULT_LOADERS);
+    return hf || tdx_switch(SW_RING_LOADERS) != 0;  // A/B switch: 0 = the computing waves issue the copies themselves
 }
 // The skip term (conv3_ring_kernel, SK = 2) rides in this call's data gradient: K = 32 channels of dy and of the skip's gy,
 // 64-wide output tiles, the 8-deep loader-form kernel on a grid of whole bricks (no remainder-slab launch, whose kernel
 // has no skip term).  The one variant that keeps 3 waves per SIMD without scratch: K = 64 spills and its weights do not fit
 // the statistics scratch, 32-wide tiles spill, the loader-less form is an A/B build.
 bool conv3_ring_skip_supported(int fmt, int depth, int K, int N, int X, int Y, int Z) {
-    const char* env = getenv("TDX_SKIP_DGRAD_FUSE");  // A/B switch, read per call: 0 = the two 1x1 launches behind the data gradient
-    if (env && atoi(env) == 0) return false;
+    if (tdx_switch(SW_SKIP_DGRAD_FUSE) == 0) return false;  // A/B switch: 0 = the two 1x1 launches behind the data gradient
     if (!tdx_is_h16(fmt) || depth != 8 || K != 32 || N <= 0 || (N % 64) != 0) return false;
     if ((X % 8) || (Y % 8) || (Z % 8)) return false;
     return ring_loader_form(fmt == TDX_F16);

@@ -97,8 +97,7 @@ conv3_small_reduce_kernel(const float* __restrict__ slab, const float* __restric
 // Plan a launch; false if the small-grid kernel does not apply (grid too large, shapes, no arena, arena too small).
 static bool small_plan(SmallGeom& g, int B, int X, int Y, int Z, int K, int N, bool data_gradient, bool split,
                        size_t arena_bytes, size_t& lds_bytes) {
-    static const int mode = getenv("TDX_CONV3_SMALL") ? atoi(getenv("TDX_CONV3_SMALL")) : 1;
-    if (mode == 0) return false;
+    if (tdx_switch(SW_CONV3_SMALL) == 0) return false;
     if ((K % SM_KC) || (N % SM_BN) || K < 128) return false;
     const int pad = data_gradient ? 1 : 0;
     g.B = B;
@@ -111,9 +110,9 @@ static bool small_plan(SmallGeom& g, int B, int X, int Y, int Z, int K, int N, b
     //   12 x 4 x 3, 512 -> 512:    forward 33 vs 91;   data gradient 73 vs 141 + 55
     //   24 x 8 x 6, 512 -> 512:    forward 154 vs 162; 1024 -> 256: 149 vs 181; 256 -> 512: 90 vs 85
     //   24 x 8 x 6 data gradients: 183-353 vs 166-297 (the padded grid has 1.8x the rows there) -> brick kernels
-    // TDX_CONV3_SMALL_ROWS moves the row gate (tests, A/B runs; read per call).
-    const char* env_rows = getenv("TDX_CONV3_SMALL_ROWS");
-    const int max_total = env_rows ? atoi(env_rows) : 6000;
+    // TDX_CONV3_SMALL_ROWS moves the row gate (tests, A/B runs).
+    const bool env_rows = tdx_switch_is_set(SW_CONV3_SMALL_ROWS);
+    const int max_total = tdx_switch(SW_CONV3_SMALL_ROWS);
     const bool deep_forward = !data_gradient && K >= 512 && rows_total <= 24000;
     if (rows_total > max_total && !(deep_forward && !env_rows)) return false;
     const int plane = g.Ev[1] * g.Ev[2], sample = g.Ev[0] * plane;
@@ -141,8 +140,7 @@ static bool small_plan(SmallGeom& g, int B, int X, int Y, int Z, int K, int N, b
         // strides below 1.43x (59: the best any stride <= 16 reaches).  The padding entries are copied like rim entries and never
         // read.  Taken only where the group still fits the DMA plan and the LDS as planned (TDX_SMALL_ZPAD=0: off, A/B switch)
         static const int good[9] = {0, 0, 0, 9, 0, 9, 10, 0, 12};  // Ev[2] -> stride
-        const char* env = getenv("TDX_SMALL_ZPAD");
-        const int want = (g.Ev[2] <= 8 && !(env && atoi(env) == 0)) ? good[g.Ev[2]] : 0;
+        const int want = (g.Ev[2] <= 8 && tdx_switch(SW_SMALL_ZPAD) != 0) ? good[g.Ev[2]] : 0;
         if (want > g.Iz) {
             const int padded = g.Ix * g.Iy * want, keep = img;
             img = padded;

@@ -299,9 +299,8 @@ int conv3_wgrad_mfma_launch(const Conv3WgradCall& c) {
     const int Cin = c.C1 + c.C2;
     const int NT = (Cout % 64 == 0) ? 2 : 1;
     // local axes: brick 4 x 8 x 8; the short axis goes where it leaves the fewest bricks
-    static const bool no_perm = getenv("TDX_CONV3_PERM") && atoi(getenv("TDX_CONV3_PERM")) == 0;  // A/B switch
     WgradView g;
-    const int nbricks = conv3_wgrad_view(g, c, W3::BX, W3::BY, W3::BZ, !no_perm);
+    const int nbricks = conv3_wgrad_view(g, c, W3::BX, W3::BY, W3::BZ, tdx_switch(SW_CONV3_PERM) != 0);  // A/B switch
     const int n_ci = (Cin + 31) / 32, n_co = Cout / (32 * NT);
     const int ntiles = n_ci * n_co;
     // one workgroup per CU (224 accumulator registers -> one wave per SIMD): aim at 256

@@ -267,8 +267,7 @@ conv3_wgrad_ring_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
 }
 
 bool conv3_wgrad_ring_supported(int C1, int C2, int Cout) {
-    const char* env = getenv("TDX_WGRAD_RING");  // A/B switch, read per call: 0 = off
-    if (env && atoi(env) == 0) return false;
+    if (tdx_switch(SW_WGRAD_RING) == 0) return false;  // A/B switch
     return conv3_wgrad_mfma_supported(C1, C2, Cout) && (Cout % 32) == 0 && tdx_scratch_zero() != nullptr;
 }
 
@@ -281,10 +280,7 @@ int conv3_wgrad_ring_launch(const Conv3WgradCall& c) {
     WgradView g;
     const int nbricks = conv3_wgrad_view(g, c, WR::BX, WR::BY, WR::BZ);
     const int NTN = (Cout % 64) == 0 ? 2 : 1;
-    {
-        const char* env = getenv("TDX_WGRAD_RING");  // A/B switch: 2 = 64-wide tiles only (round 4's rule)
-        if (NTN == 1 && env && atoi(env) == 2) return TDX_ESHAPE;
-    }
+    if (NTN == 1 && tdx_switch(SW_WGRAD_RING) == 2) return TDX_ESHAPE;  // A/B switch: 2 = 64-wide tiles only (round 4's rule)
     const int n_ci = (Cin + 31) / 32, n_co = Cout / (32 * NTN);
     const int ntiles = n_ci * n_co;
     const int cus = tdx_persistent_cus();

@@ -227,13 +227,11 @@ conv3_wgrad_small_kernel(const bf16* __restrict__ x1, int C1, const bf16* __rest
 // Launch if this is a small-grid case; TDX_ESHAPE otherwise (the caller then takes the brick kernel).
 int conv3_wgrad_small_launch(const Conv3WgradCall& c) {
     const int B = c.B, X = c.X, Y = c.Y, Z = c.Z, Cout = c.Cout;
-    static const int mode = getenv("TDX_WGRAD_SMALL") ? atoi(getenv("TDX_WGRAD_SMALL")) : 1;  // A/B switch
-    if (mode == 0) return TDX_ESHAPE;
+    if (tdx_switch(SW_WGRAD_SMALL) == 0) return TDX_ESHAPE;  // A/B switch
     const int Cin = c.C1 + c.C2;
     if ((c.C1 % 32) || (c.C2 % 32) || (Cout % 32) || Cin < 128) return TDX_ESHAPE;
-    const char* env_rows = getenv("TDX_WGRAD_SMALL_ROWS");  // row gate (tests, A/B runs; read per call)
     const int64_t rows_total = (int64_t)B * X * Y * Z;
-    if (rows_total > (env_rows ? atoi(env_rows) : 8000)) return TDX_ESHAPE;
+    if (rows_total > tdx_switch(SW_WGRAD_SMALL_ROWS)) return TDX_ESHAPE;  // row gate (tests, A/B runs)
     WsGeom g;
     g.B = B; g.E[0] = X; g.E[1] = Y; g.E[2] = Z;
     const int plane = Y * Z, V = X * plane;

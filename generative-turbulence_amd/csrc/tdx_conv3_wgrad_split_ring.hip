@@ -215,10 +215,7 @@ conv3_wgrad_split_ring_kernel(const float* __restrict__ x1, int C1, const float*
 
 int conv3_wgrad_split_ring_launch(const Conv3WgradCall& c) {
     const int Cout = c.Cout;
-    {
-        const char* env = getenv("TDX_WGRAD_SPLIT_RING");  // A/B switch, read per call: 0 = off
-        if (env && atoi(env) == 0) return TDX_ESHAPE;
-    }
+    if (tdx_switch(SW_WGRAD_SPLIT_RING) == 0) return TDX_ESHAPE;  // A/B switch
     if (!conv3_wgrad_mfma_split_supported(c.C1, c.C2, Cout)) return TDX_ESHAPE;
     const int Cin = c.C1 + c.C2;
     // local axes: brick 2 x 8 x 8; the short axis goes where it leaves the fewest bricks

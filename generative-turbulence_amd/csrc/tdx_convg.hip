@@ -19,12 +19,10 @@
 // Weights are passed as [taps][Cin][Cout] fp32 (the host transposes the reference layouts once per call).
 #include "tdx_common.h"
 #include "tdx_convg.h"
+#include "tdx_runtime.h"
 #include <stdlib.h>
 
-static bool convg_use_mfma(int dtype) {  // read per call: the switch is a test / benchmark knob
-    const char* e = getenv("TDX_CONVG_MFMA");
-    return dtype == TDX_BF16 && !(e && atoi(e) == 0);
-}
+static bool convg_use_mfma(int dtype) { return dtype == TDX_BF16 && tdx_switch(SW_CONVG_MFMA) != 0; }
 
 struct ConvG {
     int B;

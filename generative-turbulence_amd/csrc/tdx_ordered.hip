@@ -12,19 +12,119 @@
 // the loss adds block partials rounded to a 2^-20 grid, on which f64 additions are exact -- order-independent -- up to 2^33.
 // tdx_conv3_fwd_partial (the sampler's first conv) does the same: a sampling run is bit-reproducible too.
 //
-// The other library-wide host services of tdx_runtime.h live here too: the CU budget of the persistent kernels, the scratch
-// arena, and the zero fills.
+// The other library-wide host services of tdx_runtime.h live here too: the environment switches, the CU budget of the
+// persistent kernels, the scratch arena, and the zero fills.
 #include "tdx_common.h"
 #include "tdx_runtime.h"
+#include <errno.h>
+#include <limits.h>
 #include <stdlib.h>
+#include <string.h>
 #include <algorithm>
 
-int tdx_persistent_cus() {
-    const char* env = getenv("TDX_PERSISTENT_CUS");
-    int n = env ? atoi(env) : 256;
-    n = n < 8 ? 8 : (n > 256 ? 256 : n);
-    return n & ~7;
+// ---- environment switches (rules: tdx_runtime.h) ---------------------------------------------------------------------------
+enum SwitchKind { SW_RANGE, SW_CLAMP, SW_SET };
+struct SwitchRow {
+    TdxSwitchId id;
+    const char* name;
+    int def;
+    SwitchKind kind;  // accepted integers: v[0] .. v[1] (SW_RANGE; SW_CLAMP: values outside move to the nearest end), or the four of v
+    int v[4];
+    const char* word;  // a string accepted beside the integers, or nullptr ...
+    int word_value;    // ... and what it stands for
+    const char* desc;
+};
+static constexpr SwitchRow g_switches[] = {
+    {SW_ATTN_BOUND, "TDX_ATTN_BOUND", 1, SW_RANGE, {0, 1}, nullptr, 0,
+     "0: attention forward checks every tile's maximum instead of skipping under the key-norm bound"},
+    {SW_ATTN_BWD_TW, "TDX_ATTN_BWD_TW", 22, SW_SET, {11, 12, 21, 22}, nullptr, 0,
+     "attention backward, tiles per wave: tens digit the dQ kernel's, ones digit the dK/dV kernel's"},
+    {SW_ATTN_IMPL, "TDX_ATTN_IMPL", 0, SW_RANGE, {0, 1}, "vector", 1,
+     "vector: row-wise attention kernels also for long sequences (cross-check)"},
+    {SW_ATTN_STREAMK, "TDX_ATTN_STREAMK", 1, SW_RANGE, {0, 1}, nullptr, 0,
+     "0: attention forward with one workgroup per query block instead of the stream-K schedule"},
+    {SW_CONV1_IMPL, "TDX_CONV1_IMPL", 0, SW_RANGE, {0, 1}, "direct", 1, "direct: vector-ALU 1x1 convs (cross-check)"},
+    {SW_CONV3_PERM, "TDX_CONV3_PERM", 1, SW_RANGE, {0, 1}, nullptr, 0,
+     "0: main bricks of the 16-bit brick kernels (forward, data and weight gradient) in grid orientation"},
+    {SW_CONV3_RING, "TDX_CONV3_RING", 1, SW_RANGE, {0, 2}, nullptr, 0, "ring conv kernel: 0 off, 1 where it pays, 2 wherever legal (tests)"},
+    {SW_CONV3_SMALL, "TDX_CONV3_SMALL", 1, SW_RANGE, {0, 1}, nullptr, 0, "0: no small-grid conv kernel (brick kernels instead)"},
+    {SW_CONV3_SMALL_ROWS, "TDX_CONV3_SMALL_ROWS", 6000, SW_RANGE, {0, INT_MAX}, nullptr, 0,
+     "voxel rows up to which the small-grid conv kernel runs; when set, deep forwards get no larger gate of their own"},
+    {SW_CONV3_THIN, "TDX_CONV3_THIN", 1, SW_RANGE, {0, 2}, nullptr, 0,
+     "thin remainder bricks: 0 never, 1 on grids of 60000 voxels and more, 2 on every grid (tests)"},
+    {SW_CONVG_MFMA, "TDX_CONVG_MFMA", 1, SW_RANGE, {0, 1}, nullptr, 0, "0: general convs of bf16 tensors on the vector-ALU kernels"},
+    {SW_DETERMINISTIC, "TDX_DETERMINISTIC", 0, SW_RANGE, {0, 1}, nullptr, 0,
+     "1: every merge of a training step in a fixed order (run-to-run reproducible bits)"},
+    {SW_PERSISTENT_CUS, "TDX_PERSISTENT_CUS", 256, SW_CLAMP, {8, 256}, nullptr, 0,
+     "CUs the persistent one-workgroup-per-CU kernels occupy (used rounded down to a multiple of 8)"},
+    {SW_RING_LOADERS, "TDX_RING_LOADERS", 1, SW_RANGE, {0, 1}, nullptr, 0,
+     "0: the ring kernel's computing waves issue the copies themselves (bf16; fp16 always has loader waves)"},
+    {SW_RING_MIN_ITEMS, "TDX_RING_MIN_ITEMS", 768, SW_RANGE, {0, INT_MAX}, nullptr, 0,
+     "(brick, N tile) pairs an 8-deep ring launch must have"},
+    {SW_RING_RAGGED, "TDX_RING_RAGGED", 1, SW_RANGE, {0, 1}, nullptr, 0, "0: 8-deep ring kernel on grids of whole bricks only"},
+    {SW_RING_Z4, "TDX_RING_Z4", 1, SW_RANGE, {0, 2}, nullptr, 0, "4-deep ring bricks: 0 never, 1 where 8-deep ones do not apply, 2 wherever legal (tests)"},
+    {SW_SHELL_DETERMINISTIC, "TDX_SHELL_DETERMINISTIC", 0, SW_RANGE, {0, 1}, nullptr, 0,
+     "1: halo-shell term of the data gradient through a fixed-order fold instead of atomics"},
+    {SW_SKIP_DGRAD_FUSE, "TDX_SKIP_DGRAD_FUSE", 1, SW_RANGE, {0, 1}, nullptr, 0,
+     "0: a projected-skip block's 1x1 input gradient as two launches behind the data gradient, not inside the ring launch"},
+    {SW_SMALL_ZPAD, "TDX_SMALL_ZPAD", 1, SW_RANGE, {0, 1}, nullptr, 0, "0: small-grid conv kernel without the padded image stride"},
+    {SW_WGRAD_RING, "TDX_WGRAD_RING", 1, SW_RANGE, {0, 2}, nullptr, 0,
+     "producer / consumer weight gradient (16-bit): 0 off, 1 on, 2 only its 64-wide form"},
+    {SW_WGRAD_SMALL, "TDX_WGRAD_SMALL", 1, SW_RANGE, {0, 1}, nullptr, 0, "0: no packed-K weight gradient on small grids (brick kernel instead)"},
+    {SW_WGRAD_SMALL_ROWS, "TDX_WGRAD_SMALL_ROWS", 8000, SW_RANGE, {0, INT_MAX}, nullptr, 0,
+     "voxel rows up to which the packed-K weight gradient runs"},
+    {SW_WGRAD_SPLIT_RING, "TDX_WGRAD_SPLIT_RING", 1, SW_RANGE, {0, 1}, nullptr, 0,
+     "0: no producer / consumer weight gradient for split-precision fp32 (single-role kernel instead)"},
+};
+
+static constexpr bool switch_accepts(const SwitchRow& r, long v) {
+    if (r.kind == SW_SET) return v == r.v[0] || v == r.v[1] || v == r.v[2] || v == r.v[3];
+    return v >= r.v[0] && v <= r.v[1];
 }
+static constexpr bool switch_table_ok() {
+    if (sizeof(g_switches) / sizeof(g_switches[0]) != SW_COUNT) return false;
+    for (int i = 0; i < SW_COUNT; ++i) {
+        const SwitchRow& r = g_switches[i];
+        if (r.id != i || !switch_accepts(r, r.def) || (r.word != nullptr && !switch_accepts(r, r.word_value))) return false;
+    }
+    return true;
+}
+static_assert(switch_table_ok(), "a row per TdxSwitchId, in the enum's order, each default among the row's accepted values");
+
+// the value the environment gives the switch; false if it gives none (unset, empty, unparsable, not accepted)
+static bool switch_read(const SwitchRow& r, int& value) {
+    const char* s = getenv(r.name);
+    if (s == nullptr || s[0] == 0) return false;
+    if (r.word != nullptr && strcmp(s, r.word) == 0) {
+        value = r.word_value;
+        return true;
+    }
+    char* end = nullptr;
+    errno = 0;
+    long v = strtol(s, &end, 10);
+    if (end == s || *end != 0 || errno == ERANGE) return false;
+    if (r.kind == SW_CLAMP) v = std::min<long>(std::max<long>(v, r.v[0]), r.v[1]);
+    if (!switch_accepts(r, v)) return false;
+    value = (int)v;
+    return true;
+}
+int tdx_switch(TdxSwitchId id) {
+    int v;
+    return switch_read(g_switches[id], v) ? v : g_switches[id].def;
+}
+bool tdx_switch_is_set(TdxSwitchId id) {
+    int v;
+    return switch_read(g_switches[id], v);
+}
+extern "C" int tdx_switch_count(void) { return SW_COUNT; }
+extern "C" const char* tdx_switch_name(int i) { return i >= 0 && i < SW_COUNT ? g_switches[i].name : nullptr; }
+extern "C" int tdx_switch_default(int i) { return i >= 0 && i < SW_COUNT ? g_switches[i].def : 0; }
+extern "C" int tdx_switch_value(int i) {
+    if (i < 0 || i >= SW_COUNT) return 0;
+    return i == SW_PERSISTENT_CUS ? tdx_persistent_cus() : tdx_switch((TdxSwitchId)i);
+}
+
+int tdx_persistent_cus() { return tdx_switch(SW_PERSISTENT_CUS) & ~7; }
 
 // ---- scratch arena (layout and the rule of its reuse: tdx_runtime.h) ----------------------------------------------------
 static void* g_scratch = nullptr;
@@ -43,10 +143,7 @@ extern "C" int tdx_set_scratch(void* ptr, size_t bytes) {
     return TDX_OK;
 }
 
-bool tdx_deterministic() {
-    const char* e = getenv("TDX_DETERMINISTIC");  // read per call: a test / training-run switch
-    return e && atoi(e) != 0;
-}
+bool tdx_deterministic() { return tdx_switch(SW_DETERMINISTIC) != 0; }
 
 // dst[r * ld + c] (+)= sum_k slabs[k * stride + r * cols + c], k ascending.  One element per 32 lanes when there are many
 // slabs (lane l adds slabs l, l + 32, ... in order, then a fixed butterfly), else one element per thread.

@@ -30,6 +30,10 @@ _vp, _i, _i64, _u64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_f
 SIGNATURES = {
     "tdx_version": (_i, []),
     "tdx_arch": (C.c_char_p, []),
+    "tdx_switch_count": (_i, []),
+    "tdx_switch_name": (C.c_char_p, [_i]),
+    "tdx_switch_default": (_i, [_i]),
+    "tdx_switch_value": (_i, [_i]),
     "tdx_set_scratch": (_i, [_vp, _sz]),
     "tdx_ncv_to_nvc": (_i, [_vp, _vp, _i, _i, _i64, _i, _i, _vp]),
     "tdx_nvc_to_ncv": (_i, [_vp, _vp, _i, _i, _i64, _i, _i, _vp]),
@@ -190,9 +194,36 @@ ARENA_USERS = {"tdx_conv3_fwd", "tdx_conv3_fwd_gn", "tdx_conv3_fwd_partial", "td
 DET_ARENA_USERS = {"tdx_conv1_bwd_weight", "tdx_conv1_bwd_weight_oc", "tdx_encode_bwd", "tdx_decode_bwd", "tdx_gn_stats"}
 
 
+_SWITCH_INDEX = None  # name -> row of the library's switch table (the table is static; values are never kept)
+
+
+def _switch_index() -> dict:
+    global _SWITCH_INDEX
+    if _SWITCH_INDEX is None:
+        lib = load()
+        _SWITCH_INDEX = {lib.tdx_switch_name(i).decode(): i for i in range(lib.tdx_switch_count())}
+    return _SWITCH_INDEX
+
+
+def switch_names() -> tuple:
+    """The library's environment switches (its own table), in the table's order."""
+    return tuple(_switch_index())
+
+
+def switch(name: str) -> int:
+    """What a launch issued now reads for the library switch `name`: parsed by the library, from the environment as it is now."""
+    i = _switch_index()[name]
+    return _lib.tdx_switch_value(i)
+
+
+def switch_default(name: str) -> int:
+    i = _switch_index()[name]
+    return _lib.tdx_switch_default(i)
+
+
 def deterministic() -> bool:
-    """TDX_DETERMINISTIC=1 in the environment (read per call, like the library does): run-to-run reproducible gradients."""
-    return os.environ.get("TDX_DETERMINISTIC", "0") not in ("", "0")
+    """TDX_DETERMINISTIC=1 in the environment, as the library reads it (per call): run-to-run reproducible gradients."""
+    return switch("TDX_DETERMINISTIC") != 0
 
 
 # bind + launch of an arena user is one critical section: the library keeps ONE arena pointer per process and ctypes

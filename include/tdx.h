@@ -72,6 +72,15 @@ int tdx_version(void);
 int tdx_set_scratch(void* ptr, size_t bytes);
 /* name of the gfx target the library was built for ("gfx950") */
 const char* tdx_arch(void);
+/* The library's environment switches, i in [0, tdx_switch_count()): the variable's name, its
+ * default, and the value a launch issued now would use -- the environment is read on every call and nothing is cached.
+ * The whole string must be a decimal integer the switch accepts, or its word (TDX_CONV1_IMPL=direct, TDX_ATTN_IMPL=vector:
+ * 1); an unset, empty, unparsable or unaccepted value counts as unset.  Host-only queries: no device, no stream, no launch.
+ * An i out of range yields NULL / 0. */
+int tdx_switch_count(void);
+const char* tdx_switch_name(int i);
+int tdx_switch_default(int i);
+int tdx_switch_value(int i);
 
 /* ------------------------------------------------------------------ layout ------------- */
 /* (B, C, V) -> (B, V, C) and back; replaces the implicit NCDHW layout of every op in

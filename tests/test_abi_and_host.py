@@ -566,8 +566,7 @@ def test_conv3_routing_is_pinned(monkeypatch):
 
     from turbdiff_amd import _lib as L
 
-    for v in ("TDX_CONV3_RING", "TDX_RING_Z4", "TDX_RING_RAGGED", "TDX_RING_MIN_ITEMS", "TDX_PERSISTENT_CUS",
-              "TDX_CONV3_SMALL_ROWS", "TDX_CONV_IMPL"):
+    for v in L.switch_names() + ("TDX_CONV_IMPL",):  # the library's own list, and the Python-side override
         monkeypatch.delenv(v, raising=False)
     names = {L.KERNEL_DIRECT: "direct", L.KERNEL_BRICK: "brick", L.KERNEL_SMALL: "small", L.KERNEL_RING: "ring"}
     modes = [(L.BF16, L.CONV_AUTO), (L.F16, L.CONV_AUTO), (L.F32, L.CONV_AUTO), (L.F32, L.CONV_SPLIT),

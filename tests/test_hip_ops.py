@@ -1643,8 +1643,8 @@ def test_conv3_weight_gradient_is_run_to_run_reproducible(case, monkeypatch):
     """Round 4: the fine levels' weight gradients (K split over 32-512 workgroups) store per-split slabs that
     conv3_unpack_sum_kernel adds in slab order, instead of merging by fp32 atomics in arrival order: the weight gradient
     of the ring and brick kernels is bit-identical from run to run (the bias gradient still merges by atomics), equal to
-    the atomic route (TDX_WGRAD_MANY_SLABS=0) up to fp32 summation order, and the accumulator part of the workspace stays
-    all-zero (TDX_WS_CLEAN)."""
+    the oracle's fp64 weight gradient at bf16-operand accuracy (the atomic route it replaced and its switch are gone), and
+    the accumulator part of the workspace stays all-zero (TDX_WS_CLEAN)."""
     from turbdiff_amd import _lib as L
 
     B, C1, C2, Co, (X, Y, Z) = case

@@ -41,8 +41,6 @@ ROUTES = [
     ((32, 32, 32, (1, 16, 8, 8), F32, {"TDX_CONV3_RING": "2"}, True), 0),
     ((12, 20, 32, BENCH, BF16, {}, True), 0),                         # channels that are no multiple of 8
 ]
-SWITCHES = ("TDX_SKIP_DGRAD_FUSE", "TDX_CONV3_RING", "TDX_RING_LOADERS", "TDX_RING_Z4", "TDX_RING_RAGGED", "TDX_RING_MIN_ITEMS",
-            "TDX_PERSISTENT_CUS", "TDX_CONV3_SMALL_ROWS", "TDX_CONV_IMPL")
 
 
 def test_supported_rule_and_static_preconditions_agree(monkeypatch):
@@ -50,10 +48,11 @@ def test_supported_rule_and_static_preconditions_agree(monkeypatch):
     from turbdiff_amd import ops
 
     lib = L.load()
+    switches = L.switch_names() + ("TDX_CONV_IMPL",)  # the library's own list, and the Python-side override
     fake = ctypes.create_string_buffer(256)  # zeroed; never dereferenced by the query
     try:
         for (C1, C2, Cout, grid, dn, envs, arena), want in ROUTES:
-            for v in SWITCHES:
+            for v in switches:
                 monkeypatch.delenv(v, raising=False)
             for k, v in envs.items():
                 monkeypatch.setenv(k, v)

@@ -1,0 +1,170 @@
+"""The library's environment switches, no GPU needed: one table (csrc/tdx_ordered.hip) behind tdx_switch_count / _name /
+_default / _value, one parser, every switch read per call, Python asking the library instead of parsing on its own, and the
+documents and sources agreeing with the table.  Nothing is launched."""
+
+import ctypes
+import re
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+CSRC = ROOT / "generative-turbulence_amd" / "csrc"
+
+# Every value INTEGRATION.md section 5 documents (and the defaults), per switch: each must come back as it was set.  A switch
+# added to the library fails test_documented_values_come_back until it has a row here.
+DOCUMENTED = {
+    "TDX_ATTN_BOUND": (0, 1),
+    "TDX_ATTN_BWD_TW": (11, 12, 21, 22),
+    "TDX_ATTN_IMPL": (0, 1),
+    "TDX_ATTN_STREAMK": (0, 1),
+    "TDX_CONV1_IMPL": (0, 1),
+    "TDX_CONV3_PERM": (0, 1),
+    "TDX_CONV3_RING": (0, 1, 2),
+    "TDX_CONV3_SMALL": (0, 1),
+    "TDX_CONV3_SMALL_ROWS": (0, 1, 6000, 30000),
+    "TDX_CONV3_THIN": (0, 1, 2),
+    "TDX_CONVG_MFMA": (0, 1),
+    "TDX_DETERMINISTIC": (0, 1),
+    "TDX_PERSISTENT_CUS": (8, 64, 192, 224, 256),
+    "TDX_RING_LOADERS": (0, 1),
+    "TDX_RING_MIN_ITEMS": (0, 1, 768, 100000),
+    "TDX_RING_RAGGED": (0, 1),
+    "TDX_RING_Z4": (0, 1, 2),
+    "TDX_SHELL_DETERMINISTIC": (0, 1),
+    "TDX_SKIP_DGRAD_FUSE": (0, 1),
+    "TDX_SMALL_ZPAD": (0, 1),
+    "TDX_WGRAD_RING": (0, 1, 2),
+    "TDX_WGRAD_SMALL": (0, 1),
+    "TDX_WGRAD_SMALL_ROWS": (0, 1, 8000, 30000),
+    "TDX_WGRAD_SPLIT_RING": (0, 1),
+}
+WORDS = {"TDX_CONV1_IMPL": "direct", "TDX_ATTN_IMPL": "vector"}
+
+
+@pytest.fixture
+def L(monkeypatch):
+    """turbdiff_amd._lib with every library switch cleared (the suite also runs with TDX_DETERMINISTIC=1 exported)."""
+    from turbdiff_amd import _lib
+
+    for name in _lib.switch_names():
+        monkeypatch.delenv(name, raising=False)
+    return _lib
+
+
+def test_table_sanity(L):
+    names = L.switch_names()
+    assert len(names) == len(set(names)) == L.load().tdx_switch_count() >= 24
+    assert all(re.fullmatch(r"TDX_[A-Z0-9_]+", n) for n in names)
+    for n in names:
+        assert L.switch(n) == L.switch_default(n), n  # cleared: the default
+    # every default is among the row's accepted values (the library also asserts it over the whole table at compile time)
+    assert set(names) == set(DOCUMENTED)
+    for n in names:
+        assert L.switch_default(n) in DOCUMENTED[n], n
+    lib = L.load()
+    for i in (-1, len(names)):
+        assert lib.tdx_switch_name(i) is None and lib.tdx_switch_default(i) == 0 and lib.tdx_switch_value(i) == 0
+
+
+def test_documented_values_come_back(L, monkeypatch):
+    assert set(L.switch_names()) == set(DOCUMENTED), "a library switch without a row in DOCUMENTED (or the reverse)"
+    for n, values in DOCUMENTED.items():
+        for v in values:
+            monkeypatch.setenv(n, str(v))
+            assert L.switch(n) == v, (n, v)
+        monkeypatch.delenv(n)
+        assert L.switch(n) == L.switch_default(n), n
+
+
+def test_one_parser(L, monkeypatch):
+    for n in L.switch_names():
+        d = L.switch_default(n)
+        other = next(v for v in DOCUMENTED[n] if v != d)
+        # not a whole decimal integer (nor the row's word): as if unset, whatever the string begins with
+        for s in ("", "off", "x", f"{other}x", f"{other} ", f"{other}.0", "0x1", "direct-ish", "vectors"):
+            monkeypatch.setenv(n, s)
+            assert L.switch(n) == d, (n, s)
+        if n == "TDX_PERSISTENT_CUS":
+            continue
+        for s in ("-1", "2147483648", "99999999999999999999"):  # out of every row's range
+            monkeypatch.setenv(n, s)
+            assert L.switch(n) == d, (n, s)
+    for s, want in (("300", 256), ("4", 8), ("100", 96), ("-5", 8), ("224", 224), ("231", 224), ("", 256), ("many", 256)):
+        monkeypatch.setenv("TDX_PERSISTENT_CUS", s)  # the one row that clamps; used rounded down to a multiple of 8
+        assert L.switch("TDX_PERSISTENT_CUS") == want, s
+    for s, want in (("12", 12), ("21", 21), ("11", 11), ("22", 22), ("13", 22), ("3", 22), ("1", 22), ("2", 22), ("121", 22)):
+        monkeypatch.setenv("TDX_ATTN_BWD_TW", s)
+        assert L.switch("TDX_ATTN_BWD_TW") == want, s
+    for n, word in WORDS.items():
+        for s, want in ((word, 1), ("1", 1), ("0", 0), (word[0], 0), (word.upper(), 0), (word + "x", 0), ("mfma", 0), ("auto", 0)):
+            monkeypatch.setenv(n, s)
+            assert L.switch(n) == want, (n, s)
+    for n in set(L.switch_names()) - set(WORDS):  # a word is a value of its own row only
+        monkeypatch.setenv(n, "direct")
+        assert L.switch(n) == L.switch_default(n), n
+
+
+def test_formerly_frozen_switches_are_read_per_call(L, monkeypatch):
+    """TDX_CONV3_SMALL was read once per process (as were TDX_WGRAD_SMALL and the weight gradient's TDX_CONV3_PERM): setting
+    it in a running process did nothing.  The route query is pure host code; a host buffer stands in for the arena, as in
+    test_conv3_routing_is_pinned."""
+    monkeypatch.delenv("TDX_CONV_IMPL", raising=False)
+    lib = L.load()
+    fake = ctypes.create_string_buffer(256)  # zeroed; never dereferenced by the query
+    shape = (512, 0, 512, 6, 12, 4, 3)
+
+    def kernel():
+        return L.query("tdx_conv3_fwd_kernel", *shape, L.BF16, L.CONV_AUTO)
+
+    try:
+        assert lib.tdx_set_scratch(ctypes.addressof(fake), 96 << 20) == 0
+        assert kernel() == L.KERNEL_SMALL
+        monkeypatch.setenv("TDX_CONV3_SMALL", "0")
+        assert kernel() == L.KERNEL_BRICK
+        monkeypatch.delenv("TDX_CONV3_SMALL")
+        assert kernel() == L.KERNEL_SMALL
+        monkeypatch.setenv("TDX_CONV3_SMALL_ROWS", "0")  # "set" takes the deep forwards' own gate away as well
+        assert kernel() == L.KERNEL_BRICK
+        monkeypatch.setenv("TDX_CONV3_SMALL_ROWS", "many")  # an ignored value is not "set"
+        assert kernel() == L.KERNEL_SMALL
+    finally:
+        lib.tdx_set_scratch(None, 0)
+        L._ACTIVE = None  # a later GPU test in this process binds its real arena again
+
+
+def test_python_and_library_agree_on_deterministic(L, monkeypatch):
+    assert L.deterministic() is False
+    for s, want in (("", False), ("0", False), ("1", True), ("2", False), ("off", False)):
+        monkeypatch.setenv("TDX_DETERMINISTIC", s)
+        assert L.deterministic() == (L.switch("TDX_DETERMINISTIC") != 0) == want, s
+
+
+def _table_names(text):
+    """Backticked TDX_... names in the rows of INTEGRATION.md's switch tables (section 5), and {name: default} of the
+    library-switch table's first two columns."""
+    section = text.split("## 5. Switches", 1)[1]
+    rows = [l for l in section.splitlines() if l.startswith("|") and not l.startswith("|---")]
+    names = set(re.findall(r"`(TDX_[A-Z0-9_]+)", "\n".join(rows)))
+    lib_rows = {}
+    for l in rows:
+        m = re.match(r"\| `(TDX_[A-Z0-9_]+)` \| `(-?\d+)` \|", l)
+        if m and "library switch" in section.split(l, 1)[0]:
+            lib_rows[m.group(1)] = int(m.group(2))
+    return names, lib_rows
+
+
+def test_single_read_site_and_documented_table(L):
+    readers = []
+    for f in sorted(list(CSRC.glob("*.hip")) + list(CSRC.glob("*.h"))):
+        if any(re.search(r"\bgetenv\s*\(", line.split("//")[0]) for line in f.read_text().splitlines()):
+            readers.append(f.name)
+    assert readers == ["tdx_ordered.hip"], readers
+
+    names, lib_rows = _table_names((ROOT / "INTEGRATION.md").read_text())
+    table = {n: L.switch_default(n) for n in L.switch_names()}
+    assert lib_rows == table, "INTEGRATION.md's library-switch table: one row per switch of the library, with its default"
+    python_side = "\n".join(f.read_text() for f in sorted((ROOT / "generative-turbulence_amd" / "turbdiff_amd").glob("*.py"))
+                            + [ROOT / "bench.py"] + sorted((ROOT / "tools").rglob("*.py")) + sorted((ROOT / "tools").rglob("*.sh")))
+    for n in sorted(names - set(table)):
+        assert re.search(rf"\b{n}\b", python_side), f"{n}: in INTEGRATION.md's table, but neither a library switch nor read by the Python side"
