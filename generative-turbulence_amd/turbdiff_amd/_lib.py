@@ -113,6 +113,13 @@ SIGNATURES = {
     "tdx_w2n_blocks": (_i, [_i64]),
     "tdx_w2n_assign": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "tdx_w2n_reduce": (_i, [_vp, _i, _i, _vp, _vp]),
+    "tdx_lagprod_workspace_bytes": (_sz, [_i, _i64, _i]),
+    "tdx_lagprod_update": (_i, [_vp, _i, _i64, _vp, _vp, _i64, _i, _vp, _vp, _i64, _vp, _vp]),
+    "tdx_smooth_residual_workspace_bytes": (_sz, [_i64, _i]),
+    "tdx_smooth_residual_update": (_i, [_vp, _i, _i64, _vp, _i, _i, _vp, _vp, _i64, _vp, _vp]),
+    "tdx_sqdev_workspace_bytes": (_sz, [_i64, _i]),
+    "tdx_sqdev_sum": (_i, [_vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp]),
+    "tdx_fma64_probe": (_i, [_vp, _i, _i, _vp]),
     "tdx_randn": (_i, [_vp, _i64, _u64, _u64, _vp, _vp]),
     "tdx_randn_batched": (_i, [_vp, _i, _i64, _u64, _vp, _vp, _vp]),
     "tdx_convg_apply": (_i, [_vp, _vp, _vp, _vp] + [_i] * 16 + [_vp]),

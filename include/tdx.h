@@ -623,6 +623,44 @@ int tdx_w2n_assign(const float* mean, const float* var, int64_t n, const double*
                    double* dist, double* partials, void* stream);
 int tdx_w2n_reduce(const double* partials, int blocks, int k, double* table, void* stream);
 
+/* ------------------------------------------------------------------ case diagnostics ------ */
+/* The reductions of turbdiff_amd/data/diagnostics.py (tdx_diagnostics.hip).  fp64 sums without atomics: per-block partials
+ * in the workspace, each result folded by one block in an order fixed by the shapes, so it is bit-identical from run to run.
+ * tdx_lagprod_update (scripts/autocorrelation.py:43-50): x (F, n, 3) f32 is a chunk of raw frames, mean (n, 3) f32,
+ *   cells (m) int32 ascending in [0, n).  State across calls: ring (L, 3 m) f32 = the last L fluctuation frames, frame g
+ *   in row g mod L (never read before it is written), acc (L + 1) f64 (the caller zeroes it), seen = frames of earlier
+ *   calls.  The fluctuation f = x[t, cells] - mean[cells] is one float32 subtraction; then
+ *     acc[i] += sum_{t < F} sum_{col < 3 m} f[seen + t, col] f[seen + t - i, col]     for 0 <= i <= L, seen + t - i >= 0,
+ *   the products exact in fp64; lags without a partner frame so far keep their value.  The chunk is staged in the
+ *   workspace, multiplied against ring + stage, and only then its last min(F, L) frames are written to the ring: the
+ *   hand-over costs the chunk, not the window.  Limits: 1 <= F <= 64 per call (any relation to L), 1 <= L <= 255, any m.
+ *   workspace: tdx_lagprod_workspace_bytes(F, m, L) bytes (0: outside the limits), 16-byte aligned.
+ * tdx_smooth_residual_update (scripts/gaussian-smoothing-error.py:29-36): x (F, n) f32 is a chunk of frames of n columns,
+ *   taps (W, 2 h + 1) f64 a bank of FIR filters over time.  State: halo (2 h, n) f32 = the last 2 h frames, frame g in row
+ *   g mod 2 h, acc (W) f64 (the caller zeroes it), seen as above.  With X the frames so far and this chunk,
+ *     acc[w] += sum_t sum_{col < n} (sum_k taps[w, k] X[t + k, col])^2     over the output frames t that this chunk
+ *   completes (max(0, seen - 2 h) <= t < seen + F - 2 h: none while fewer than 2 h + 1 frames have arrived), everything in
+ *   fp64, k ascending (a correlation; np.convolve flips, which a symmetric filter does not see).  The caller passes
+ *   the residual filter delta - g to get the energy of u - smooth(u) without a cancelling difference.  Then the chunk's
+ *   last min(F, 2 h) frames go to the halo.  Limits: 1 <= F <= 64, 1 <= W <= 32, 1 <= h <= 50, any n.
+ *   workspace: tdx_smooth_residual_workspace_bytes(n, W) bytes, 8-byte aligned.
+ * tdx_sqdev_sum (scripts/mean-forecast-errors.py:42-43): x (T, n, C) f32, mean (n, C) f32, C <= 4.  out[0] = (accumulate:
+ *   out[0] +) the fp64 sum of the float32 values (x - mean)^2 -- difference and square rounded to float32 one after the
+ *   other, as numpy evaluates the float32 expression.  workspace: tdx_sqdev_workspace_bytes(n, C) bytes, 8-byte aligned.
+ * tdx_fma64_probe: a measurement aid (tools/diagnostics_bench.py), not part of any result: `blocks` blocks of 256 threads
+ *   each run `iters` steps of 8 independent dependent-FMA chains in fp64 registers, blocks x 256 x iters x 8 FMAs in all,
+ *   and write one value per thread to out (blocks x 256) f64. */
+size_t tdx_lagprod_workspace_bytes(int F, int64_t m, int L);
+int tdx_lagprod_update(const float* x, int F, int64_t n, const float* mean, const int* cells, int64_t m, int L, float* ring,
+                       double* acc, int64_t seen, void* workspace, void* stream);
+size_t tdx_smooth_residual_workspace_bytes(int64_t n, int W);
+int tdx_smooth_residual_update(const float* x, int F, int64_t n, const double* taps, int W, int h, float* halo, double* acc,
+                               int64_t seen, void* workspace, void* stream);
+size_t tdx_sqdev_workspace_bytes(int64_t n, int C);
+int tdx_sqdev_sum(const float* x, const float* mean, int T, int64_t n, int C, int accumulate, double* out, void* workspace,
+                  void* stream);
+int tdx_fma64_probe(double* out, int blocks, int iters, void* stream);
+
 /* Counter-based N(0,1) generator (Philox4x32-10 + Box-Muller), graph-replay safe: the
  * 64-bit offset is read from device memory and advanced by the kernel itself.
  * Replaces torch.randn_like (ddpm.py:777,801,810,835) inside captured sampling graphs.
