@@ -128,9 +128,9 @@ bool conv3_small_plan(Conv3SmallPlan& p, int C1, int C2, int N, int B, int X, in
 int conv3_small_launch(const Conv3Call& c, const Conv3SmallPlan& p);
 
 // One weight-gradient call: dwp [27][Cin][Cout] (+)= x^T dy, dbias (+)= column sums of dy (nullptr: not wanted).
-// slabs / max_slabs: optional region of max_slabs x 27*Cin*Cout floats; when the launch uses at most max_slabs K-splits
-// every split stores its partial tiles there (no atomics) and *nslab tells the caller how many slabs to add up (0: the
-// result was accumulated into dwp)
+// slabs: region of the plan's max_slabs x 27*Cin*Cout floats (max_slabs = 0: none, slabs is not read); when the plan uses at
+// most max_slabs K-splits every split stores its partial tiles there (no atomics) and the plan's nslab tells the caller how
+// many slabs to add up (0: the result was accumulated into dwp).  The plan functions read the shape (C1, C2, Cout, B, X, Y, Z) only.
 struct Conv3WgradCall {
     const void* x1; int C1;
     const void* x2; int C2;
@@ -139,44 +139,79 @@ struct Conv3WgradCall {
     float* dbias;
     int B, X, Y, Z, Cout;
     hipStream_t st;
-    float* slabs; int max_slabs; int* nslab;
+    float* slabs;
     bool hf;
 };
-// where a launch of nsplit K-splits puts its partial tiles: returns the base (slabs or dwp) and the slab stride (0: atomics
-// into dwp), reports the slab count.  Slab mode: every (tile, split) pair stores its whole partial tile, so the slabs need no
-// zeroing.  TDX_DETERMINISTIC: never the atomic merge -- nsplit is held to the slabs the workspace has (added in order by
-// the unpack kernel)
-static inline float* conv3_wgrad_merge(const Conv3WgradCall& c, int& nsplit, int64_t& slab_stride) {
-    if (tdx_deterministic() && c.slabs != nullptr && nsplit > c.max_slabs) nsplit = c.max_slabs > 0 ? c.max_slabs : 1;
-    const bool use_slabs = c.slabs != nullptr && nsplit <= c.max_slabs;
-    slab_stride = use_slabs ? (int64_t)27 * (c.C1 + c.C2) * c.Cout : 0;
-    if (c.nslab) *c.nslab = use_slabs ? nsplit : 0;
-    return use_slabs ? c.slabs : c.dwp;
+// What a weight-gradient call launches: the ONE decision, made on the host by conv3_wgrad_plan (tdx_conv3_entry.hip) from the
+// per-kernel plan functions below, read by the launchers and reported by tdx_conv3_bwd_weight_plan (include/tdx.h).
+struct Conv3WgradPlan {
+    int kernel;      // TDX_WGRAD_* of include/tdx.h
+    int status;      // TDX_OK, or what tdx_conv3_bwd_weight returns for the call (kernel is then TDX_WGRAD_DIRECT)
+    int nt;          // output tile in units of 32 channels (NT / NTN: 1 or 2); vector-ALU kernel: 0
+    int depth;       // brick depth along the kernel's local x (4 or 2); packed-K and vector-ALU kernels: 0
+    int nsplit;      // K splits launched (vector-ALU kernel: voxel chunks)
+    int nslab;       // slabs the unpack adds up; 0: fp32 atomics into dwp
+    int sum_unpack;  // 1: conv3_unpack_sum_kernel (more slabs than the tiled unpack walks)
+    int max_slabs;   // slabs the call may use (the capacity the plan function was given)
+    int nbricks;     // bricks of the grid (brick kernels)
+    int order;       // brick kernels: the axis order of their view of the grid (WGRAD_ORDERS, tdx_conv3_wgrad.h)
+    // packed-K kernel: samples per row group, x planes per group, x slabs per sample, row groups; bytes of one x image buffer,
+    // dy rows per buffer and the dynamic LDS of the launch
+    int nbg, xs, gx, ngroups, xbytes, grows, lds;
+};
+// The merge rule of the MFMA kernels: a launch of nsplit K-splits stores per-split slabs (every (tile, split) pair stores its
+// whole partial tile, so the slabs need no zeroing) when the workspace holds that many, else merges with atomics into dwp.
+// TDX_DETERMINISTIC: never the atomic merge -- nsplit is held to the slabs the workspace has (added in order by the unpack
+// kernel).
+static inline void conv3_wgrad_plan_merge(Conv3WgradPlan& p, int nsplit, int max_slabs) {
+    if (tdx_deterministic() && nsplit > max_slabs) nsplit = max_slabs > 0 ? max_slabs : 1;
+    p.nsplit = nsplit;
+    p.nslab = nsplit <= max_slabs ? nsplit : 0;
+    p.max_slabs = max_slabs;
 }
-// The six weight-gradient launchers.  16-bit tensors: conv3_wgrad_mfma_launch (tdx_conv3_wgrad_mfma.hip) hands the deep
-// U-Net levels to the packed-K kernel for small grids (tdx_conv3_wgrad_small.hip) and the fine levels to the producer /
-// consumer form (tdx_conv3_wgrad_ring.hip: 8 computing + 4 loader waves per workgroup, 64- and 32-wide output tiles),
-// each of which answers TDX_ESHAPE when the call is not a case for it.  fp32 tensors: split-precision
-// (tdx_conv3_wgrad_mfma_split.hip, which tries its producer / consumer form tdx_conv3_wgrad_split_ring.hip first: 2 x 8 x 8
-// bricks) or fp32-IEEE products (tdx_conv3_wgrad_mfma_f32.hip).
+// where the launch of plan p puts its partial tiles: the base (slabs or dwp) and the slab stride (0: atomics into dwp)
+static inline float* conv3_wgrad_out(const Conv3WgradCall& c, const Conv3WgradPlan& p, int64_t& slab_stride) {
+    slab_stride = p.nslab ? (int64_t)27 * (c.C1 + c.C2) * c.Cout : 0;
+    return p.nslab ? c.slabs : c.dwp;
+}
+// The seven weight-gradient kernels.  16-bit tensors: the packed-K kernel for small grids on the deep U-Net levels
+// (tdx_conv3_wgrad_small.hip), the producer / consumer form on the fine levels (tdx_conv3_wgrad_ring.hip: 8 computing + 4
+// loader waves per workgroup, 64- and 32-wide output tiles), else the brick kernel (tdx_conv3_wgrad_mfma.hip).  fp32
+// tensors: split-precision (tdx_conv3_wgrad_mfma_split.hip, after its producer / consumer form
+// tdx_conv3_wgrad_split_ring.hip: 2 x 8 x 8 bricks) or fp32-IEEE products (tdx_conv3_wgrad_mfma_f32.hip).  Any shape and
+// dtype: the vector ALU (tdx_conv3_direct.hip).
+// *_plan: pure host code (the shape of c, the slab capacity max_slabs, the environment switches, whether an arena is bound):
+// true and p filled when the call is a case for that kernel.  *_launch(c, p): the launch of a plan its own *_plan made; it
+// reads no switch and repeats no decision -- tile width, axis order, K splits, slabs and the packed-K kernel's row groups
+// all come from p.
 // What the brick kernels among them share on the device, and their launch geometry (WgradView, conv3_wgrad_view):
 // tdx_conv3_wgrad.h.
 bool conv3_wgrad_mfma_supported(int C1, int C2, int Cout);
 bool conv3_wgrad_mfma_split_supported(int C1, int C2, int Cout);
 bool conv3_wgrad_mfma_f32_supported(int C1, int C2, int Cout);
-int conv3_wgrad_mfma_launch(const Conv3WgradCall& c);
-int conv3_wgrad_small_launch(const Conv3WgradCall& c);
-int conv3_wgrad_ring_launch(const Conv3WgradCall& c);
-int conv3_wgrad_mfma_split_launch(const Conv3WgradCall& c);
-int conv3_wgrad_split_ring_launch(const Conv3WgradCall& c);
-int conv3_wgrad_mfma_f32_launch(const Conv3WgradCall& c);
+bool conv3_wgrad_mfma_plan(Conv3WgradPlan& p, const Conv3WgradCall& c, int max_slabs);
+bool conv3_wgrad_small_plan(Conv3WgradPlan& p, const Conv3WgradCall& c, int max_slabs);
+bool conv3_wgrad_ring_plan(Conv3WgradPlan& p, const Conv3WgradCall& c, int max_slabs);
+bool conv3_wgrad_mfma_split_plan(Conv3WgradPlan& p, const Conv3WgradCall& c, int max_slabs);
+bool conv3_wgrad_split_ring_plan(Conv3WgradPlan& p, const Conv3WgradCall& c, int max_slabs);
+bool conv3_wgrad_mfma_f32_plan(Conv3WgradPlan& p, const Conv3WgradCall& c, int max_slabs);
+int conv3_wgrad_mfma_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p);
+int conv3_wgrad_small_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p);
+int conv3_wgrad_ring_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p);
+int conv3_wgrad_mfma_split_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p);
+int conv3_wgrad_split_ring_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p);
+int conv3_wgrad_mfma_f32_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p);
 // vector-ALU weight gradient (tdx_conv3_direct.hip), atomics into dwp; max_slabs > 0 (deterministic runs): at most that many
 // voxel chunks, chunk k stores into slab k
-int conv3_wgrad_direct_launch(const Conv3WgradCall& c, int dtype);
-// after the launch of c: dwp [27][Cin][Cout] (or the sum of its *nslab slabs) -> dw (Cout, Cin, 27); the bias-gradient
-// accumulator dbw -> dbias.  The accumulators are left all-zero.  many: the per-tap summing kernel for more slabs than the
-// tiled one walks.
-int conv3_unpack_wgrad_launch(const Conv3WgradCall& c, float* dw, float* dbw, float* dbias, bool many);
+bool conv3_wgrad_direct_plan(Conv3WgradPlan& p, const Conv3WgradCall& c, int max_slabs);
+int conv3_wgrad_direct_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p, int dtype);
+// after the launch of plan p: dwp [27][Cin][Cout] (or the sum of its p.nslab slabs) -> dw (Cout, Cin, 27); the bias-gradient
+// accumulator dbw -> dbias.  The accumulators are left all-zero.  p.sum_unpack: the per-tap summing kernel for more slabs
+// than the tiled one walks.
+int conv3_unpack_wgrad_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p, float* dw, float* dbw, float* dbias);
+// The whole decision for one call of tdx_conv3_bwd_weight (impl: TDX_CONV_*, flag bits above 0xff are ignored): which kernel,
+// its plan, the slab capacity it is given (p.max_slabs), which unpack.
+Conv3WgradPlan conv3_wgrad_plan(int dtype, int impl, int C1, int C2, int Cout, int B, int X, int Y, int Z);
 
 // halo-shell term of the data gradient, added onto dx with atomics (tdx_conv3_shell.hip); mode 0 bf16, 1 fp32 MFMA,
 // 2 split-precision, 3 fp16; wb = the packed data-gradient operand for (K -> N) in that mode's layout

@@ -334,14 +334,15 @@ conv3_unpack_sum_kernel(float* __restrict__ dw, float* __restrict__ dbw, float* 
     }
 }
 
-int conv3_unpack_wgrad_launch(const Conv3WgradCall& c, float* dw, float* dbw, float* dbias, bool many) {
+int conv3_unpack_wgrad_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p, float* dw, float* dbw, float* dbias) {
     const int Cin = c.C1 + c.C2, Cout = c.Cout;
-    if (many)
+    const int nslab = p.nslab;
+    if (p.sum_unpack)
         hipLaunchKernelGGL(conv3_unpack_sum_kernel, dim3(ceil_div(Cin, 8), ceil_div(Cout, 32), 27), dim3(256), 0, c.st, dw, dbw,
-                           dbias, Cin, Cout, c.slabs, *c.nslab);
+                           dbias, Cin, Cout, c.slabs, nslab);
     else
         hipLaunchKernelGGL(conv3_unpack_wgrad_kernel, dim3(ceil_div(Cin, 16), ceil_div(Cout, 16)), dim3(256), 0, c.st, c.dwp, dw,
-                           dbw, dbias, Cin, Cout, c.slabs, *c.nslab);
+                           dbw, dbias, Cin, Cout, c.slabs, nslab);
     return tdx_launch_status();
 }
 
@@ -607,17 +608,25 @@ conv3_wgrad_direct_kernel(const T* __restrict__ x1, int C1, const T* __restrict_
     if (do_bias && tid < D3_BN && co0 + tid < Cout) atomicAdd(&dbias[co0 + tid], bsum);
 }
 
-int conv3_wgrad_direct_launch(const Conv3WgradCall& c, int dtype) {
+// voxels per block: D3W_VOX, or with max_slabs > 0 what leaves at most max_slabs voxel chunks, one slab each
+static int64_t d3w_vpb(int64_t nvox, int max_slabs) {
+    return max_slabs > 0 ? (ceil_div(nvox, max_slabs) + D3_BK - 1) / D3_BK * D3_BK : D3W_VOX;
+}
+bool conv3_wgrad_direct_plan(Conv3WgradPlan& p, const Conv3WgradCall& c, int max_slabs) {
+    const int64_t nvox = (int64_t)c.B * c.X * c.Y * c.Z;
+    p.kernel = TDX_WGRAD_DIRECT; p.nt = 0; p.depth = 0; p.nbricks = 0;
+    p.nsplit = ceil_div(nvox, d3w_vpb(nvox, max_slabs));
+    p.nslab = max_slabs > 0 ? p.nsplit : 0;
+    p.max_slabs = max_slabs;
+    return true;
+}
+
+int conv3_wgrad_direct_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p, int dtype) {
     const int64_t nvox = (int64_t)c.B * c.X * c.Y * c.Z;
     const int Cin = c.C1 + c.C2, nci = ceil_div(Cin, D3_BM), nco = ceil_div(c.Cout, D3_BN);
-    int64_t vpb = D3W_VOX, slab_stride = 0;
-    float* out = c.dwp;
-    if (c.max_slabs > 0) {  // at most max_slabs voxel chunks, one slab each
-        vpb = (ceil_div(nvox, c.max_slabs) + D3_BK - 1) / D3_BK * D3_BK;
-        slab_stride = (int64_t)27 * Cin * c.Cout;
-        out = c.slabs;
-        *c.nslab = ceil_div(nvox, vpb);
-    }
+    const int64_t vpb = d3w_vpb(nvox, p.max_slabs);
+    int64_t slab_stride;
+    float* out = conv3_wgrad_out(c, p, slab_stride);
     dim3 grid(ceil_div(nvox, vpb), 27, nci * nco);
     TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv3_wgrad_direct_kernel<T>), grid, dim3(256), 0, c.st, (const T*)c.x1, c.C1,
                                                   (const T*)c.x2, c.C2, (const T*)c.dy, out, c.dbias, c.B, c.X, c.Y, c.Z, c.Cout,

@@ -214,23 +214,89 @@ extern "C" size_t tdx_conv3_bwd_weight_workspace_bytes(int Cin, int Cout, int im
     return (size_t)(1 + w3_slab_capacity(Cin, Cout)) * 27 * Cin * Cout * sizeof(float) + (size_t)Cout * sizeof(float) + 512;
 }
 
-// which weight-gradient launcher serves a call (nullptr: the vector-ALU kernel); status as tdx_conv3_bwd_weight returns it
-struct Conv3WgradRoute {
-    int (*launch)(const Conv3WgradCall&);
-    bool f32;  // the fp32-tensor kernels: see the slab capacity in tdx_conv3_bwd_weight
-    int status;
-};
-static Conv3WgradRoute conv3_wgrad_route(int dtype, int impl, int C1, int C2, int Cout) {
-    if (dtype == TDX_F32 && impl == TDX_CONV_SPLIT && conv3_wgrad_mfma_split_supported(C1, C2, Cout))
-        return {conv3_wgrad_mfma_split_launch, true, TDX_OK};
-    if (dtype == TDX_F32 && impl != TDX_CONV_DIRECT && conv3_wgrad_mfma_f32_supported(C1, C2, Cout))
-        return {conv3_wgrad_mfma_f32_launch, true, TDX_OK};
-    if (impl == TDX_CONV_MFMA || (impl == TDX_CONV_AUTO && tdx_is_h16(dtype) && conv3_wgrad_mfma_supported(C1, C2, Cout))) {
-        if (!tdx_is_h16(dtype)) return {nullptr, false, TDX_EDTYPE};
-        if (!conv3_wgrad_mfma_supported(C1, C2, Cout)) return {nullptr, false, TDX_ESHAPE};
-        return {conv3_wgrad_mfma_launch, false, TDX_OK};
+// The ONE decision of a weight-gradient call: the kernel family by (dtype, impl, channels), the slab capacity that family is
+// given, then the kernels of the family in the order they are asked (each *_plan says whether the call is a case for it),
+// and the unpack that follows.  Pure host code: reads the environment switches and whether an arena is bound, launches nothing.
+Conv3WgradPlan conv3_wgrad_plan(int dtype, int impl, int C1, int C2, int Cout, int B, int X, int Y, int Z) {
+    Conv3WgradPlan p = {};
+    p.kernel = TDX_WGRAD_DIRECT;
+    auto refuse = [&](int status) { p.status = status; return p; };
+    if (!(B > 0 && X > 0 && Y > 0 && Z > 0 && C1 > 0 && C2 >= 0 && Cout > 0)) return refuse(TDX_EINVAL);
+    if ((C1 % 8) || (C2 % 8) || (Cout % 8)) return refuse(TDX_ESHAPE);
+    impl &= 0xff;
+    const int Cin = C1 + C2;
+    enum { FAM_DIRECT, FAM_H16, FAM_F32, FAM_SPLIT } fam = FAM_DIRECT;
+    if (dtype == TDX_F32 && impl == TDX_CONV_SPLIT && conv3_wgrad_mfma_split_supported(C1, C2, Cout)) {
+        fam = FAM_SPLIT;
+    } else if (dtype == TDX_F32 && impl != TDX_CONV_DIRECT && conv3_wgrad_mfma_f32_supported(C1, C2, Cout)) {
+        fam = FAM_F32;
+    } else if (impl == TDX_CONV_MFMA || (impl == TDX_CONV_AUTO && tdx_is_h16(dtype) && conv3_wgrad_mfma_supported(C1, C2, Cout))) {
+        if (!tdx_is_h16(dtype)) return refuse(TDX_EDTYPE);
+        if (!conv3_wgrad_mfma_supported(C1, C2, Cout)) return refuse(TDX_ESHAPE);
+        fam = FAM_H16;
     }
-    return {nullptr, false, TDX_OK};
+    // TDX_DETERMINISTIC: the launchers hold their K splits to the slab capacity (per-split slabs added in order: their
+    // default for few splits)
+    const bool det = tdx_deterministic();
+    Conv3WgradCall c = {};  // the shape: all a plan function reads of it
+    c.C1 = C1; c.C2 = C2; c.Cout = Cout; c.B = B; c.X = X; c.Y = Y; c.Z = Z;
+    bool ok;
+    if (fam == FAM_DIRECT) {
+        // any shape, the three tensor dtypes (conv3_wgrad_direct_launch dispatches on it)
+        if (dtype != TDX_F32 && dtype != TDX_BF16 && dtype != TDX_F16) return refuse(TDX_EDTYPE);
+        ok = conv3_wgrad_direct_plan(p, c, det ? std::min(w3_slab_capacity(Cin, Cout), 64) : 0);
+    } else {
+        // the fp32-tensor kernels split K 256-fold on the fine levels and merge with atomics by default (8 slabs); deterministic
+        // runs give them the slab capacity the 16-bit kernels use
+        const int ms = (fam != FAM_H16 && !det) ? W3_MAX_SLABS : w3_slab_capacity(Cin, Cout);
+        if (fam == FAM_SPLIT) {
+            // grids that give every workgroup several bricks: the producer / consumer form
+            ok = conv3_wgrad_split_ring_plan(p, c, ms) || conv3_wgrad_mfma_split_plan(p, c, ms);
+        } else if (fam == FAM_F32) {
+            ok = conv3_wgrad_mfma_f32_plan(p, c, ms);
+        } else {
+            // deep U-Net levels: the packed-K kernel; fine levels: the producer / consumer form (8 computing + 4 loader
+            // waves); else the brick kernel
+            ok = conv3_wgrad_small_plan(p, c, ms) || conv3_wgrad_ring_plan(p, c, ms) || conv3_wgrad_mfma_plan(p, c, ms);
+        }
+    }
+    if (!ok) return refuse(TDX_ESHAPE);
+    // more slabs than the 16 x 16 unpack kernel walks (MFMA kernels only): the per-tap summing unpack
+    p.sum_unpack = (p.kernel != TDX_WGRAD_DIRECT && p.nslab > W3_MAX_SLABS) ? 1 : 0;
+    p.status = TDX_OK;
+    return p;
+}
+
+static int conv3_wgrad_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p, int dtype) {
+    switch (p.kernel) {
+        case TDX_WGRAD_BRICK16: return conv3_wgrad_mfma_launch(c, p);
+        case TDX_WGRAD_SMALL: return conv3_wgrad_small_launch(c, p);
+        case TDX_WGRAD_RING: return conv3_wgrad_ring_launch(c, p);
+        case TDX_WGRAD_BRICK_F32: return conv3_wgrad_mfma_f32_launch(c, p);
+        case TDX_WGRAD_SPLIT: return conv3_wgrad_mfma_split_launch(c, p);
+        case TDX_WGRAD_SPLIT_RING: return conv3_wgrad_split_ring_launch(c, p);
+        default: return conv3_wgrad_direct_launch(c, p, dtype);
+    }
+}
+
+extern "C" int tdx_conv3_bwd_weight_plan(int C1, int C2, int Cout, int B, int X, int Y, int Z, int dtype, int impl, int* plan) {
+    TDX_CHECK_ARG(plan);
+    const Conv3WgradPlan p = conv3_wgrad_plan(dtype, impl, C1, C2, Cout, B, X, Y, Z);
+    for (int i = 0; i < TDX_WGRAD_PLAN_INTS; ++i) plan[i] = 0;
+    plan[TDX_WGRAD_PLAN_KERNEL] = p.kernel;
+    plan[TDX_WGRAD_PLAN_TILE] = p.nt;
+    plan[TDX_WGRAD_PLAN_DEPTH] = p.depth;
+    plan[TDX_WGRAD_PLAN_NSPLIT] = p.nsplit;
+    plan[TDX_WGRAD_PLAN_NSLAB] = p.nslab;
+    plan[TDX_WGRAD_PLAN_SUM_UNPACK] = p.sum_unpack;
+    plan[TDX_WGRAD_PLAN_NBG] = p.nbg;
+    plan[TDX_WGRAD_PLAN_XS] = p.xs;
+    plan[TDX_WGRAD_PLAN_GX] = p.gx;
+    plan[TDX_WGRAD_PLAN_NGROUPS] = p.ngroups;
+    plan[TDX_WGRAD_PLAN_MAX_SLABS] = p.max_slabs;
+    plan[TDX_WGRAD_PLAN_NBRICKS] = p.nbricks;
+    plan[TDX_WGRAD_PLAN_ORDER] = p.order;
+    return p.status;
 }
 
 extern "C" int tdx_conv3_bwd_weight(const void* x1, int C1, const void* x2, int C2, const void* dy, float* dw,
@@ -248,12 +314,10 @@ extern "C" int tdx_conv3_bwd_weight(const void* x1, int C1, const void* x2, int 
         int e = tdx_zero_async(dwp, ((size_t)27 * Cin * Cout + Cout) * sizeof(float), st);
         if (e != TDX_OK) return e;
     }
-    const Conv3WgradRoute r = conv3_wgrad_route(dtype, impl & 0xff, C1, C2, Cout);
-    if (r.status != TDX_OK) return r.status;
-    int nslab = 0;
+    const Conv3WgradPlan p = conv3_wgrad_plan(dtype, impl, C1, C2, Cout, B, X, Y, Z);
+    if (p.status != TDX_OK) return p.status;
     // TDX_DETERMINISTIC: no bias-gradient atomics inside the weight-gradient kernels -- the bias gradient is summed from dy in a
-    // fixed order afterwards (partials in the slab region, free again once the unpack kernel has read it); the launchers hold
-    // their K splits to the slab capacity (per-split slabs added in order: their default for few splits)
+    // fixed order afterwards (partials in the slab region, free again once the unpack kernel has read it)
     const bool det = tdx_deterministic();
     float* slab_base = dbw + ((Cout + 63) / 64) * 64;
     auto ordered_bias = [&]() -> int {
@@ -261,18 +325,10 @@ extern "C" int tdx_conv3_bwd_weight(const void* x1, int C1, const void* x2, int 
         return bias_grad_ordered_launch(dy, (int64_t)B * X * Y * Z, Cout, dtype, dbias, slab_base,
                                         (size_t)W3_MAX_SLABS * 27 * Cin * Cout, st);
     };
-    Conv3WgradCall c = {x1, C1, x2, C2, dy, dwp, (dbias && !det) ? dbw : nullptr, B, X, Y, Z, Cout, st, slab_base, 0, &nslab,
-                        dtype == TDX_F16};
-    if (r.launch != nullptr) {
-        // the fp32-tensor kernels split K 256-fold on the fine levels and merge with atomics by default (8 slabs); deterministic
-        // runs give them the slab capacity the 16-bit kernels use
-        c.max_slabs = (r.f32 && !det) ? W3_MAX_SLABS : w3_slab_capacity(Cin, Cout);
-    } else if (det) {
-        c.max_slabs = std::min(w3_slab_capacity(Cin, Cout), 64);
-    }
-    const int rc = r.launch != nullptr ? r.launch(c) : conv3_wgrad_direct_launch(c, dtype);
+    const Conv3WgradCall c = {x1, C1, x2, C2, dy, dwp, (dbias && !det) ? dbw : nullptr, B, X, Y, Z, Cout, st, slab_base,
+                              dtype == TDX_F16};
+    const int rc = conv3_wgrad_launch(c, p, dtype);
     if (rc != TDX_OK) return rc;
-    // more slabs than the 16 x 16 unpack kernel walks (MFMA launchers only): the per-tap summing unpack
-    const int rc_unpack = conv3_unpack_wgrad_launch(c, dw, dbw, dbias, r.launch != nullptr && nslab > W3_MAX_SLABS);
+    const int rc_unpack = conv3_unpack_wgrad_launch(c, p, dw, dbw, dbias);
     return rc_unpack != TDX_OK ? rc_unpack : ordered_bias();
 }

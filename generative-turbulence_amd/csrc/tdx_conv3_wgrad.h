@@ -25,20 +25,27 @@ struct WgradView {
     int batch;    // voxels per sample
 };
 
-// Launch geometry: bricks of bx x by x bz voxels in the kernel's LOCAL axes, the short axis on the grid axis that leaves
-// the fewest bricks (permute false: the grid's own order).  Returns the number of bricks.
-static inline int conv3_wgrad_view(WgradView& g, const Conv3WgradCall& c, int bx, int by, int bz, bool permute = true) {
-    const int E[3] = {c.X, c.Y, c.Z}, gs[3] = {c.Y * c.Z, c.Z, 1}, gw[3] = {9, 3, 1}, bdim[3] = {bx, by, bz};
-    const int cand[3][3] = {{0, 1, 2}, {1, 0, 2}, {2, 0, 1}};
+// Launch geometry: bricks of bx x by x bz voxels in the kernel's LOCAL axes.  The three axis orders a kernel may run in
+// (local axis k = grid axis WGRAD_ORDERS[order][k]):
+static const int WGRAD_ORDERS[3][3] = {{0, 1, 2}, {1, 0, 2}, {2, 0, 1}};
+// the order that puts the short axis on the grid axis that leaves the fewest bricks (the first such; permute false: the
+// grid's own order, 0): decided once, by the kernel's *_plan function
+static inline int conv3_wgrad_view_order(const Conv3WgradCall& c, int bx, int by, int bz, bool permute = true) {
+    const int E[3] = {c.X, c.Y, c.Z};
     int best = 0;
     int64_t best_n = -1;
     for (int k = 0; k < (permute ? 3 : 1); ++k) {
-        const int64_t n = (int64_t)ceil_div(E[cand[k][0]], bx) * ceil_div(E[cand[k][1]], by) * ceil_div(E[cand[k][2]], bz);
+        const int64_t n = (int64_t)ceil_div(E[WGRAD_ORDERS[k][0]], bx) * ceil_div(E[WGRAD_ORDERS[k][1]], by) * ceil_div(E[WGRAD_ORDERS[k][2]], bz);
         if (best_n < 0 || n < best_n) { best_n = n; best = k; }
     }
+    return best;
+}
+// the view of the grid in that order; returns the number of bricks
+static inline int conv3_wgrad_view(WgradView& g, const Conv3WgradCall& c, int bx, int by, int bz, int order) {
+    const int E[3] = {c.X, c.Y, c.Z}, gs[3] = {c.Y * c.Z, c.Z, 1}, gw[3] = {9, 3, 1}, bdim[3] = {bx, by, bz};
     g.B = c.B; g.batch = c.X * c.Y * c.Z;
     for (int k = 0; k < 3; ++k) {
-        const int a = cand[best][k];
+        const int a = WGRAD_ORDERS[order][k];
         g.E[k] = E[a]; g.s[k] = gs[a]; g.ws[k] = gw[a]; g.nb[k] = ceil_div(E[a], bdim[k]);
     }
     return c.B * g.nb[0] * g.nb[1] * g.nb[2];

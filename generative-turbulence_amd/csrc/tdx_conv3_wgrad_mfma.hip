@@ -285,22 +285,15 @@ conv3_wgrad_mfma_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restr
     }
 }
 
-int conv3_wgrad_mfma_launch(const Conv3WgradCall& c) {
-    const int Cout = c.Cout;
-    {   // deep U-Net levels: packed-K kernel (tdx_conv3_wgrad_small.hip); TDX_ESHAPE = not such a case
-        int rs = conv3_wgrad_small_launch(c);
-        if (rs != TDX_ESHAPE) return rs;
-#ifndef W3_STAMPS
-        // fine levels: the producer / consumer form (8 computing + 4 loader waves)
-        rs = conv3_wgrad_ring_launch(c);
-        if (rs != TDX_ESHAPE) return rs;
-#endif
-    }
-    const int Cin = c.C1 + c.C2;
+// The brick kernel takes every supported 16-bit call (the packed-K kernel and the producer / consumer form are asked first:
+// conv3_wgrad_plan).  Local axes: brick 4 x 8 x 8; the short axis goes where it leaves the fewest bricks.
+bool conv3_wgrad_mfma_plan(Conv3WgradPlan& p, const Conv3WgradCall& c, int max_slabs) {
+    if (!conv3_wgrad_mfma_supported(c.C1, c.C2, c.Cout)) return false;
+    const int Cin = c.C1 + c.C2, Cout = c.Cout;
     const int NT = (Cout % 64 == 0) ? 2 : 1;
-    // local axes: brick 4 x 8 x 8; the short axis goes where it leaves the fewest bricks
     WgradView g;
-    const int nbricks = conv3_wgrad_view(g, c, W3::BX, W3::BY, W3::BZ, tdx_switch(SW_CONV3_PERM) != 0);  // A/B switch
+    const int order = conv3_wgrad_view_order(c, W3::BX, W3::BY, W3::BZ, tdx_switch(SW_CONV3_PERM) != 0);  // A/B switch
+    const int nbricks = conv3_wgrad_view(g, c, W3::BX, W3::BY, W3::BZ, order);
     const int n_ci = (Cin + 31) / 32, n_co = Cout / (32 * NT);
     const int ntiles = n_ci * n_co;
     // one workgroup per CU (224 accumulator registers -> one wave per SIMD): aim at 256
@@ -309,8 +302,22 @@ int conv3_wgrad_mfma_launch(const Conv3WgradCall& c) {
     int nsplit = ((NT == 2 ? 256 : 512) + ntiles - 1) / ntiles;
     if (nsplit > nbricks) nsplit = nbricks;
     if (nsplit < 1) nsplit = 1;
+    p.kernel = TDX_WGRAD_BRICK16; p.nt = NT; p.depth = W3::BX; p.nbricks = nbricks; p.order = order;
+    conv3_wgrad_plan_merge(p, nsplit, max_slabs);  // may lower nsplit (TDX_DETERMINISTIC)
+    return true;
+}
+
+int conv3_wgrad_mfma_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p) {
+    const int Cout = c.Cout;
+    const int Cin = c.C1 + c.C2;
+    const int NT = p.nt;
+    WgradView g;
+    conv3_wgrad_view(g, c, W3::BX, W3::BY, W3::BZ, p.order);
+    const int n_ci = (Cin + 31) / 32, n_co = Cout / (32 * NT);
+    const int ntiles = n_ci * n_co;
+    const int nsplit = p.nsplit;
     int64_t slab_stride;
-    float* out = conv3_wgrad_merge(c, nsplit, slab_stride);  // may lower nsplit (TDX_DETERMINISTIC)
+    float* out = conv3_wgrad_out(c, p, slab_stride);
     size_t lds = W3::XBYTES + (size_t)NT * W3::GPLANE;
 #ifdef W3_STAMPS
     lds += 4 * W3_NSTAMP * 8;

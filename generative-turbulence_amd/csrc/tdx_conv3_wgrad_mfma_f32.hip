@@ -203,21 +203,38 @@ conv3_wgrad_mfma_f32_kernel(const float* __restrict__ x1, int C1, const float* _
     }
 }
 
-int conv3_wgrad_mfma_f32_launch(const Conv3WgradCall& c) {
+// local axes: brick 4 x 8 x 8 (NT = 2: 2 x 8 x 8); the short axis goes where it leaves the fewest bricks
+bool conv3_wgrad_mfma_f32_plan(Conv3WgradPlan& p, const Conv3WgradCall& c, int max_slabs) {
+    if (!conv3_wgrad_mfma_f32_supported(c.C1, c.C2, c.Cout)) return false;
     const int Cout = c.Cout;
     const int Cin = c.C1 + c.C2;
     const int NT = (Cout % 64 == 0) ? 2 : 1;
-    // local axes: brick 4 x 8 x 8; the short axis goes where it leaves the fewest bricks
     WgradView g;
-    const int nbricks = conv3_wgrad_view(g, c, NT == 2 ? WF<2>::BX : WF<1>::BX, WF<1>::BY, WF<1>::BZ);
+    const int BX = NT == 2 ? WF<2>::BX : WF<1>::BX;
+    const int order = conv3_wgrad_view_order(c, BX, WF<1>::BY, WF<1>::BZ);
+    const int nbricks = conv3_wgrad_view(g, c, BX, WF<1>::BY, WF<1>::BZ, order);
     const int n_ci = (Cin + 31) / 32, n_co = Cout / (32 * NT);
     const int ntiles = n_ci * n_co;
     // one workgroup per CU (LDS): one resident wave of workgroups, at most one split per brick
     int nsplit = (256 + ntiles - 1) / ntiles;
     if (nsplit > nbricks) nsplit = nbricks;
     if (nsplit < 1) nsplit = 1;
+    p.kernel = TDX_WGRAD_BRICK_F32; p.nt = NT; p.depth = BX; p.nbricks = nbricks; p.order = order;
+    conv3_wgrad_plan_merge(p, nsplit, max_slabs);  // may lower nsplit (TDX_DETERMINISTIC)
+    return true;
+}
+
+int conv3_wgrad_mfma_f32_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p) {
+    const int Cout = c.Cout;
+    const int Cin = c.C1 + c.C2;
+    const int NT = p.nt;
+    WgradView g;
+    conv3_wgrad_view(g, c, p.depth, WF<1>::BY, WF<1>::BZ, p.order);
+    const int n_ci = (Cin + 31) / 32, n_co = Cout / (32 * NT);
+    const int ntiles = n_ci * n_co;
+    const int nsplit = p.nsplit;
     int64_t slab_stride;
-    float* out = conv3_wgrad_merge(c, nsplit, slab_stride);  // may lower nsplit (TDX_DETERMINISTIC)
+    float* out = conv3_wgrad_out(c, p, slab_stride);
     const size_t lds = NT == 2 ? WF<2>::XBYTES + 2 * WF<2>::GPLANE : WF<1>::XBYTES + WF<1>::GPLANE;  // x image + NT dy planes
     dim3 grid((unsigned)(ntiles * nsplit));
 #define WF_LAUNCH(NTV)                                                                                               \

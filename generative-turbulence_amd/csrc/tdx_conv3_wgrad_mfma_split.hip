@@ -222,22 +222,35 @@ conv3_wgrad_mfma_split_kernel(const float* __restrict__ x1, int C1, const float*
     }
 }
 
-int conv3_wgrad_mfma_split_launch(const Conv3WgradCall& c) {
+// The single-role kernel takes every supported call (grids that give every workgroup several bricks go to the producer /
+// consumer form, which is asked first: conv3_wgrad_plan)
+bool conv3_wgrad_mfma_split_plan(Conv3WgradPlan& p, const Conv3WgradCall& c, int max_slabs) {
+    if (!conv3_wgrad_mfma_split_supported(c.C1, c.C2, c.Cout)) return false;
     const int Cout = c.Cout;
-    {   // grids that give every workgroup several bricks: the producer / consumer form
-        const int rs = conv3_wgrad_split_ring_launch(c);
-        if (rs != TDX_ESHAPE) return rs;
-    }
     const int Cin = c.C1 + c.C2;
     WgradView g;
-    const int nbricks = conv3_wgrad_view(g, c, WS::BX, WS::BY, WS::BZ);
+    const int order = conv3_wgrad_view_order(c, WS::BX, WS::BY, WS::BZ);
+    const int nbricks = conv3_wgrad_view(g, c, WS::BX, WS::BY, WS::BZ, order);
     const int n_ci = (Cin + 31) / 32, n_co = Cout / 32;
     const int ntiles = n_ci * n_co;
     int nsplit = (256 + ntiles - 1) / ntiles;  // one workgroup per CU: one resident wave of workgroups
     if (nsplit > nbricks) nsplit = nbricks;
     if (nsplit < 1) nsplit = 1;
+    p.kernel = TDX_WGRAD_SPLIT; p.nt = 1; p.depth = WS::BX; p.nbricks = nbricks; p.order = order;
+    conv3_wgrad_plan_merge(p, nsplit, max_slabs);  // may lower nsplit (TDX_DETERMINISTIC)
+    return true;
+}
+
+int conv3_wgrad_mfma_split_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p) {
+    const int Cout = c.Cout;
+    const int Cin = c.C1 + c.C2;
+    WgradView g;
+    conv3_wgrad_view(g, c, WS::BX, WS::BY, WS::BZ, p.order);
+    const int n_ci = (Cin + 31) / 32, n_co = Cout / 32;
+    const int ntiles = n_ci * n_co;
+    const int nsplit = p.nsplit;
     int64_t slab_stride;
-    float* out = conv3_wgrad_merge(c, nsplit, slab_stride);  // may lower nsplit (TDX_DETERMINISTIC)
+    float* out = conv3_wgrad_out(c, p, slab_stride);
     const size_t lds = (size_t)2 * WS::XBYTES + 2 * WS::GPLANE;
     dim3 grid((unsigned)(ntiles * nsplit));
     auto kern = conv3_wgrad_mfma_split_kernel;

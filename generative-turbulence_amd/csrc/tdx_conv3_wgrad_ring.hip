@@ -271,16 +271,17 @@ bool conv3_wgrad_ring_supported(int C1, int C2, int Cout) {
     return conv3_wgrad_mfma_supported(C1, C2, Cout) && (Cout % 32) == 0 && tdx_scratch_zero() != nullptr;
 }
 
-// same contract as conv3_wgrad_mfma_launch; TDX_ESHAPE = not a case for this kernel
-int conv3_wgrad_ring_launch(const Conv3WgradCall& c) {
+// false = not a case for this kernel (the brick kernel's then)
+bool conv3_wgrad_ring_plan(Conv3WgradPlan& p, const Conv3WgradCall& c, int max_slabs) {
     const int Cout = c.Cout;
-    if (!conv3_wgrad_ring_supported(c.C1, c.C2, Cout)) return TDX_ESHAPE;
+    if (!conv3_wgrad_ring_supported(c.C1, c.C2, Cout)) return false;
     const int Cin = c.C1 + c.C2;
     // local axes: brick 4 x 8 x 8; the short axis goes where it leaves the fewest bricks
     WgradView g;
-    const int nbricks = conv3_wgrad_view(g, c, WR::BX, WR::BY, WR::BZ);
+    const int order = conv3_wgrad_view_order(c, WR::BX, WR::BY, WR::BZ);
+    const int nbricks = conv3_wgrad_view(g, c, WR::BX, WR::BY, WR::BZ, order);
     const int NTN = (Cout % 64) == 0 ? 2 : 1;
-    if (NTN == 1 && tdx_switch(SW_WGRAD_RING) == 2) return TDX_ESHAPE;  // A/B switch: 2 = 64-wide tiles only (round 4's rule)
+    if (NTN == 1 && tdx_switch(SW_WGRAD_RING) == 2) return false;  // A/B switch: 2 = 64-wide tiles only (round 4's rule)
     const int n_ci = (Cin + 31) / 32, n_co = Cout / (32 * NTN);
     const int ntiles = n_ci * n_co;
     const int cus = tdx_persistent_cus();
@@ -288,10 +289,25 @@ int conv3_wgrad_ring_launch(const Conv3WgradCall& c) {
     if (nsplit > nbricks) nsplit = nbricks;
     if (nsplit < 1) nsplit = 1;
     // a workgroup should walk several bricks, or the double buffering has nothing to overlap
-    if (nbricks < 4 * nsplit) return TDX_ESHAPE;
+    if (nbricks < 4 * nsplit) return false;
+    p.kernel = TDX_WGRAD_RING; p.nt = NTN; p.depth = WR::BX; p.nbricks = nbricks; p.order = order;
+    conv3_wgrad_plan_merge(p, nsplit, max_slabs);  // may lower nsplit (TDX_DETERMINISTIC)
+    return true;
+}
+
+int conv3_wgrad_ring_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p) {
+    const int Cout = c.Cout;
+    if (tdx_scratch_zero() == nullptr) return TDX_EINVAL;  // the plan saw an arena: the zero rows come from its zero block
+    const int Cin = c.C1 + c.C2;
+    WgradView g;
+    conv3_wgrad_view(g, c, WR::BX, WR::BY, WR::BZ, p.order);
+    const int NTN = p.nt;
+    const int n_ci = (Cin + 31) / 32, n_co = Cout / (32 * NTN);
+    const int ntiles = n_ci * n_co;
+    const int nsplit = p.nsplit;
     const size_t lds = (size_t)2 * WR_XBUF + (size_t)2 * WR_GBUF(NTN);
     int64_t slab_stride;
-    float* out = conv3_wgrad_merge(c, nsplit, slab_stride);  // may lower nsplit (TDX_DETERMINISTIC)
+    float* out = conv3_wgrad_out(c, p, slab_stride);
     static bool attr_set[2][2] = {{false, false}, {false, false}};
 #define WR_GO(NTNV, HFV)                                                                                                          \
     do {                                                                                                                          \

@@ -224,18 +224,17 @@ conv3_wgrad_small_kernel(const bf16* __restrict__ x1, int C1, const bf16* __rest
     }
 }
 
-// Launch if this is a small-grid case; TDX_ESHAPE otherwise (the caller then takes the brick kernel).
-int conv3_wgrad_small_launch(const Conv3WgradCall& c) {
+// The row groups and the LDS they need, if this is a small-grid case; false otherwise (the brick kernel's case then).
+static bool ws_geom(WsGeom& g, size_t& lds, const Conv3WgradCall& c) {
     const int B = c.B, X = c.X, Y = c.Y, Z = c.Z, Cout = c.Cout;
-    if (tdx_switch(SW_WGRAD_SMALL) == 0) return TDX_ESHAPE;  // A/B switch
+    if (tdx_switch(SW_WGRAD_SMALL) == 0) return false;  // A/B switch
     const int Cin = c.C1 + c.C2;
-    if ((c.C1 % 32) || (c.C2 % 32) || (Cout % 32) || Cin < 128) return TDX_ESHAPE;
+    if ((c.C1 % 32) || (c.C2 % 32) || (Cout % 32) || Cin < 128) return false;
     const int64_t rows_total = (int64_t)B * X * Y * Z;
-    if (rows_total > tdx_switch(SW_WGRAD_SMALL_ROWS)) return TDX_ESHAPE;  // row gate (tests, A/B runs)
-    WsGeom g;
+    if (rows_total > tdx_switch(SW_WGRAD_SMALL_ROWS)) return false;  // row gate (tests, A/B runs)
     g.B = B; g.E[0] = X; g.E[1] = Y; g.E[2] = Z;
     const int plane = Y * Z, V = X * plane;
-    if (plane > WS_MAXROWS) return TDX_ESHAPE;
+    if (plane > WS_MAXROWS) return false;
     if (V <= WS_MAXROWS) { g.nbg = std::min(B, WS_MAXROWS / V); g.xs = X; g.gx = 1; }
     else { g.nbg = 1; g.xs = WS_MAXROWS / plane; g.gx = ceil_div(X, g.xs); }
     g.Ix = g.xs + 2; g.Iy = Y + 2; g.Iz = Z + 2;
@@ -246,18 +245,43 @@ int conv3_wgrad_small_launch(const Conv3WgradCall& c) {
         g.grows = ((g.nbg * g.xs * plane + 15) >> 4) << 4;
         return (size_t)2 * g.xbytes + (size_t)2 * NT * g.grows * 64 + (WS_MAXROWS + (g.xbytes >> 6)) * sizeof(unsigned);
     };
-    size_t lds = sizes();
+    lds = sizes();
     while (lds > 160 * 1024 && (g.nbg > 1 || g.xs > 1)) {  // shrink the group until two buffers fit
         if (g.nbg > 1) --g.nbg; else { --g.xs; g.gx = ceil_div(X, g.xs); g.Ix = g.xs + 2; }
         lds = sizes();
     }
-    if (lds > 160 * 1024) return TDX_ESHAPE;
+    if (lds > 160 * 1024) return false;
     g.ngroups = ceil_div(B, g.nbg) * g.gx;
+    return true;
+}
+
+bool conv3_wgrad_small_plan(Conv3WgradPlan& p, const Conv3WgradCall& c, int max_slabs) {
+    WsGeom g;
+    size_t lds;
+    if (!ws_geom(g, lds, c)) return false;
+    const int NT = (c.Cout % 64 == 0) ? 2 : 1;
+    const int ntiles = ((c.C1 + c.C2) / 32) * (c.Cout / (32 * NT));
+    const int nsplit = std::max(1, std::min(g.ngroups, ceil_div(256, ntiles)));
+    p.kernel = TDX_WGRAD_SMALL; p.nt = NT; p.depth = 0; p.nbricks = 0;
+    p.nbg = g.nbg; p.xs = g.xs; p.gx = g.gx; p.ngroups = g.ngroups; p.xbytes = g.xbytes; p.grows = g.grows; p.lds = (int)lds;
+    conv3_wgrad_plan_merge(p, nsplit, max_slabs);  // may lower nsplit (TDX_DETERMINISTIC)
+    return true;
+}
+
+int conv3_wgrad_small_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p) {
+    const int Cout = c.Cout, Cin = c.C1 + c.C2;
+    WsGeom g;  // the row groups of the plan: nothing is decided again here
+    g.B = c.B; g.E[0] = c.X; g.E[1] = c.Y; g.E[2] = c.Z;
+    g.nbg = p.nbg; g.xs = p.xs; g.gx = p.gx;
+    g.Ix = p.xs + 2; g.Iy = c.Y + 2; g.Iz = c.Z + 2;
+    g.ngroups = p.ngroups; g.xbytes = p.xbytes; g.grows = p.grows;
+    const size_t lds = (size_t)p.lds;
+    const int NT = p.nt;
     const int n_ci = Cin / 32, n_co = Cout / (32 * NT);
     const int ntiles = n_ci * n_co;
-    int nsplit = std::max(1, std::min(g.ngroups, ceil_div(256, ntiles)));
+    const int nsplit = p.nsplit;
     int64_t slab_stride;
-    float* out = conv3_wgrad_merge(c, nsplit, slab_stride);  // may lower nsplit (TDX_DETERMINISTIC)
+    float* out = conv3_wgrad_out(c, p, slab_stride);
     dim3 grid((unsigned)(ntiles * nsplit));
 #define WS_LAUNCH(NTV, HFV)                                                                                           \
     do {                                                                                                              \

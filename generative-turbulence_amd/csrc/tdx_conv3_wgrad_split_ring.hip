@@ -15,7 +15,7 @@
 //     terms of a tap are issued back to back on its accumulator (the SIMD's other computing wave fills the dependent-issue
 //     stall), then the tap's x fragments are re-read for the next step; wave 7's spare slot multiplies ones with dy_hi and
 //     dy_lo: the bias gradient.
-// Same contract as conv3_wgrad_mfma_split_launch; TDX_ESHAPE = not a case for it (too few bricks per workgroup).
+// Same contract as the single-role kernel; conv3_wgrad_split_ring_plan says when a call is a case for it (enough bricks per workgroup).
 #include "tdx_conv3_wgrad.h"
 #include <stdlib.h>
 #include <algorithm>
@@ -213,14 +213,15 @@ conv3_wgrad_split_ring_kernel(const float* __restrict__ x1, int C1, const float*
     }
 }
 
-int conv3_wgrad_split_ring_launch(const Conv3WgradCall& c) {
+bool conv3_wgrad_split_ring_plan(Conv3WgradPlan& p, const Conv3WgradCall& c, int max_slabs) {
     const int Cout = c.Cout;
-    if (tdx_switch(SW_WGRAD_SPLIT_RING) == 0) return TDX_ESHAPE;  // A/B switch
-    if (!conv3_wgrad_mfma_split_supported(c.C1, c.C2, Cout)) return TDX_ESHAPE;
+    if (tdx_switch(SW_WGRAD_SPLIT_RING) == 0) return false;  // A/B switch
+    if (!conv3_wgrad_mfma_split_supported(c.C1, c.C2, Cout)) return false;
     const int Cin = c.C1 + c.C2;
     // local axes: brick 2 x 8 x 8; the short axis goes where it leaves the fewest bricks
     WgradView g;
-    const int nbricks = conv3_wgrad_view(g, c, SR::BX, SR::BY, SR::BZ);
+    const int order = conv3_wgrad_view_order(c, SR::BX, SR::BY, SR::BZ);
+    const int nbricks = conv3_wgrad_view(g, c, SR::BX, SR::BY, SR::BZ, order);
     const int n_ci = (Cin + 31) / 32, n_co = Cout / 32;
     const int ntiles = n_ci * n_co;
     const int cus = tdx_persistent_cus();
@@ -228,10 +229,23 @@ int conv3_wgrad_split_ring_launch(const Conv3WgradCall& c) {
     if (nsplit > nbricks) nsplit = nbricks;
     if (nsplit < 1) nsplit = 1;
     // a workgroup should walk several bricks, or the double buffering has nothing to overlap
-    if (nbricks < 4 * nsplit) return TDX_ESHAPE;
+    if (nbricks < 4 * nsplit) return false;
+    p.kernel = TDX_WGRAD_SPLIT_RING; p.nt = 1; p.depth = SR::BX; p.nbricks = nbricks; p.order = order;
+    conv3_wgrad_plan_merge(p, nsplit, max_slabs);  // may lower nsplit (TDX_DETERMINISTIC)
+    return true;
+}
+
+int conv3_wgrad_split_ring_launch(const Conv3WgradCall& c, const Conv3WgradPlan& p) {
+    const int Cout = c.Cout;
+    const int Cin = c.C1 + c.C2;
+    WgradView g;
+    conv3_wgrad_view(g, c, SR::BX, SR::BY, SR::BZ, p.order);
+    const int n_ci = (Cin + 31) / 32, n_co = Cout / 32;
+    const int ntiles = n_ci * n_co;
+    const int nsplit = p.nsplit;
     const size_t lds = (size_t)2 * SR_SET;
     int64_t slab_stride;
-    float* out = conv3_wgrad_merge(c, nsplit, slab_stride);  // may lower nsplit (TDX_DETERMINISTIC)
+    float* out = conv3_wgrad_out(c, p, slab_stride);
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void*)conv3_wgrad_split_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

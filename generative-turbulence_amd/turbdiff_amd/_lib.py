@@ -54,6 +54,7 @@ SIGNATURES = {
     "tdx_conv3_bwd_data_skip": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "tdx_conv3_bwd_weight_workspace_bytes": (_sz, [_i, _i, _i]),
     "tdx_conv3_bwd_weight": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "tdx_conv3_bwd_weight_plan": (_i, [_i] * 9 + [_vp]),
     "tdx_conv1_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i64, _i, _i, _vp]),
     "tdx_conv1_fwd_gn": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i64, _i, _i, _vp]),
     "tdx_conv1_bwd_weight": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i, _vp]),
@@ -458,6 +459,27 @@ def kernel_sources_fingerprint(pattern: str = "tdx_conv*") -> str | None:
 
 
 KERNEL_DIRECT, KERNEL_BRICK, KERNEL_SMALL, KERNEL_RING = 0, 1, 2, 3  # TDX_KERNEL_* (tdx_conv3_fwd_kernel)
+
+
+# TDX_WGRAD_* (tdx_conv3_bwd_weight_plan)
+WGRAD_DIRECT, WGRAD_BRICK16, WGRAD_SMALL, WGRAD_RING, WGRAD_BRICK_F32, WGRAD_SPLIT, WGRAD_SPLIT_RING = range(7)
+WGRAD_KERNELS = ("direct", "brick16", "small", "ring", "brick_f32", "split", "split_ring")
+WGRAD_PLAN_INTS = 16  # TDX_WGRAD_PLAN_INTS
+# TDX_WGRAD_PLAN_*: index of each field in the plan array
+WGRAD_PLAN_FIELDS = ("kernel", "tile", "depth", "nsplit", "nslab", "sum_unpack", "nbg", "xs", "gx", "ngroups", "max_slabs", "nbricks", "order")
+
+
+def conv3_bwd_weight_plan(C1, C2, Cout, B, X, Y, Z, dtype: int, impl: int) -> dict:
+    """What tdx_conv3_bwd_weight would launch for this call, as the library's own host code plans it: {"status": the code
+    that call would return, "kernel": a name of WGRAD_KERNELS, and the other WGRAD_PLAN_FIELDS}.  Launches nothing; reads the
+    library switches from the environment as it is now and whether an arena is bound (`call` binds the launching stream's
+    before the launch: bind it first -- ensure_scratch -- to ask about a call on this stream)."""
+    buf = (C.c_int * WGRAD_PLAN_INTS)()
+    status = int(load().tdx_conv3_bwd_weight_plan(C1, C2, Cout, B, X, Y, Z, dtype, impl, buf))
+    plan = {k: int(buf[i]) for i, k in enumerate(WGRAD_PLAN_FIELDS)}
+    plan["kernel"] = WGRAD_KERNELS[plan["kernel"]]
+    plan["status"] = status
+    return plan
 
 
 def conv3_fwd_meta(C1, C2, Cout, B, X, Y, Z, dt, real=None):

@@ -223,6 +223,43 @@ int tdx_conv3_bwd_data_skip(const void* dy, const void* wb, void* dx1, int C1, v
 size_t tdx_conv3_bwd_weight_workspace_bytes(int Cin, int Cout, int impl);
 int tdx_conv3_bwd_weight(const void* x1, int C1, const void* x2, int C2, const void* dy, float* dw, float* dbias,
                          int B, int X, int Y, int Z, int Cout, int dtype, int impl, void* workspace, void* stream);
+/* What tdx_conv3_bwd_weight launches for this call -- the same host function decides both; the environment switches are
+ * read as of now and only the presence of a scratch arena (tdx_set_scratch) is looked at.  Nothing is launched.  Returns
+ * the status that call would return for these arguments (impl takes the same bits; TDX_WS_CLEAN changes nothing here) and
+ * fills plan[0 .. TDX_WGRAD_PLAN_INTS):
+ *   KERNEL      TDX_WGRAD_*: vector ALU (tdx_conv3_direct.hip), 16-bit brick kernel (tdx_conv3_wgrad_mfma.hip), packed-K
+ *               small-grid kernel (_small), producer / consumer kernel (_ring), fp32-IEEE brick kernel (_mfma_f32),
+ *               split-precision kernel (_mfma_split) and its producer / consumer form (_split_ring)
+ *   TILE        output-tile width in units of 32 channels (1 or 2; vector ALU: 0)
+ *   DEPTH       brick depth, 4 or 2 (the brick is DEPTH x 8 x 8 voxels; packed-K kernel and vector ALU: 0)
+ *   NSPLIT      K splits launched (vector ALU: voxel chunks)
+ *   NSLAB       per-split slabs the unpack kernel adds up in slab order; 0: the splits merge with fp32 atomics
+ *   SUM_UNPACK  1: the per-tap summing unpack (more than 8 slabs), 0: the tiled unpack
+ *   NBG, XS, GX, NGROUPS   packed-K kernel: samples per row group, x planes per group, x slabs per sample, row groups
+ *   MAX_SLABS   slabs the call's workspace offers the kernel;  NBRICKS  bricks of the grid (brick kernels)
+ *   ORDER       brick kernels: which grid axis carries the brick's short edge -- 0: (x, y, z), 1: (y, x, z), 2: (z, x, y) */
+#define TDX_WGRAD_DIRECT 0
+#define TDX_WGRAD_BRICK16 1
+#define TDX_WGRAD_SMALL 2
+#define TDX_WGRAD_RING 3
+#define TDX_WGRAD_BRICK_F32 4
+#define TDX_WGRAD_SPLIT 5
+#define TDX_WGRAD_SPLIT_RING 6
+#define TDX_WGRAD_PLAN_KERNEL 0
+#define TDX_WGRAD_PLAN_TILE 1
+#define TDX_WGRAD_PLAN_DEPTH 2
+#define TDX_WGRAD_PLAN_NSPLIT 3
+#define TDX_WGRAD_PLAN_NSLAB 4
+#define TDX_WGRAD_PLAN_SUM_UNPACK 5
+#define TDX_WGRAD_PLAN_NBG 6
+#define TDX_WGRAD_PLAN_XS 7
+#define TDX_WGRAD_PLAN_GX 8
+#define TDX_WGRAD_PLAN_NGROUPS 9
+#define TDX_WGRAD_PLAN_MAX_SLABS 10
+#define TDX_WGRAD_PLAN_NBRICKS 11
+#define TDX_WGRAD_PLAN_ORDER 12
+#define TDX_WGRAD_PLAN_INTS 16
+int tdx_conv3_bwd_weight_plan(int C1, int C2, int Cout, int B, int X, int Y, int Z, int dtype, int impl, int* plan);
 
 /* ------------------------------------------------------------------ conv 1x1x1 / linear - */
 /* nn.Conv3d(k=1) (ddpm.py:188,292-293,433,436,459) and nn.Linear seen as a per-row GEMM:

@@ -8,7 +8,6 @@
 #include <vector>
 #include <algorithm>
 bool tdx_deterministic() { return false; }
-int conv3_wgrad_small_launch(const Conv3WgradCall&) { return TDX_ESHAPE; }
 
 __global__ void fill_rand(unsigned* p, size_t n, unsigned seed, unsigned expo) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -35,8 +34,10 @@ int main(int argc, char** argv) {
     (void)hipMalloc(&buf, nrec * 8);
     (void)hipMemset(buf, 0, nrec * 8);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(w3_stamps_dev), &buf, sizeof(buf));
-    const Conv3WgradCall c = {x, Cin, nullptr, 0, dy, dw, db, B, X, Y, Z, Cout, 0, nullptr, 0, nullptr, false};
-    auto go = [&]() { return conv3_wgrad_mfma_launch(c); };
+    const Conv3WgradCall c = {x, Cin, nullptr, 0, dy, dw, db, B, X, Y, Z, Cout, 0, nullptr, false};  // no slabs: atomics
+    Conv3WgradPlan plan = {};
+    if (!conv3_wgrad_mfma_plan(plan, c, 0)) { printf("not a shape of the brick kernel\n"); return 1; }
+    auto go = [&]() { return conv3_wgrad_mfma_launch(c, plan); };
     int rc = go();
     if (rc != 0) { printf("launch failed %d\n", rc); return 1; }
     for (int it = 0; it < 20; ++it) go();
