@@ -8,7 +8,7 @@
 // serve fp32 tensors.  bf16 tensors take the matrix-core kernels of tdx_convg_mfma.hip through the same entry points
 // (TDX_CONVG_MFMA=0 keeps them here: the A/B switch of tools/baseline_conv_bench.py).
 //
-// Three kernels cover forward and both gradients of all three layer types:
+// Three kernels cover forward and both gradients of all three layer types (geometry and index arithmetic: tdx_convg.h):
 //   gather     out[o]  = sum_t W[t] in[src(o, t)],      src = o * stride - pad + t * dilation  (zero or clamped)
 //              = conv forward; = data gradient of the transposed conv
 //   scatter^T  out[i]  = sum_t W[t] in[(i + pad - t * dilation) / stride]   where divisible and in range
@@ -24,14 +24,6 @@
 
 static bool convg_use_mfma(int dtype) { return dtype == TDX_BF16 && tdx_switch(SW_CONVG_MFMA) != 0; }
 
-struct ConvG {
-    int B;
-    int Ei[3], Eo[3];  // grid of `in` and of `out`
-    int k, stride, dil, pad;
-    int clamp;         // gather only: 1 = replicate padding (clamp the source), 0 = zero padding
-    int Cin, Cout;     // channels of `in` and of `out`
-};
-
 template <typename T, bool TRANSPOSED>
 __global__ void __launch_bounds__(256)
 convg_kernel(const T* __restrict__ in, const float* __restrict__ w, const float* __restrict__ bias, T* __restrict__ out, ConvG g) {
@@ -40,12 +32,8 @@ convg_kernel(const T* __restrict__ in, const float* __restrict__ w, const float*
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= nout * groups) return;
     const int cg = (int)(idx % groups);
-    int64_t v = idx / groups;
-    const int o2 = (int)(v % g.Eo[2]); v /= g.Eo[2];
-    const int o1 = (int)(v % g.Eo[1]); v /= g.Eo[1];
-    const int o0 = (int)(v % g.Eo[0]);
-    const int b = (int)(v / g.Eo[0]);
-    const int o[3] = {o0, o1, o2};
+    int o[3];
+    const int b = convg_row_voxel(idx / groups, g.Eo, o);
     float acc[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = bias ? bias[cg * 8 + j] : 0.f;
@@ -55,22 +43,8 @@ convg_kernel(const T* __restrict__ in, const float* __restrict__ w, const float*
             for (int t2 = 0; t2 < k; ++t2) {
                 const int t[3] = {t0, t1, t2};
                 int s[3];
-                bool ok = true;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    if (TRANSPOSED) {
-                        const int num = o[a] + g.pad - t[a] * g.dil;
-                        ok = ok && num >= 0 && (num % g.stride) == 0 && num / g.stride < g.Ei[a];
-                        s[a] = num / g.stride;
-                    } else {
-                        int q = o[a] * g.stride - g.pad + t[a] * g.dil;
-                        if (g.clamp) q = min(max(q, 0), g.Ei[a] - 1);
-                        ok = ok && q >= 0 && q < g.Ei[a];
-                        s[a] = q;
-                    }
-                }
-                if (!ok) continue;
-                const T* src = in + ((((int64_t)b * g.Ei[0] + s[0]) * g.Ei[1] + s[1]) * g.Ei[2] + s[2]) * g.Cin;
+                if (!(TRANSPOSED ? convg_scatter_src<false>(g, o, t, s) : convg_gather_src(g, o, t, s))) continue;
+                const T* src = in + convg_row(b, s, g.Ei) * g.Cin;
                 const float* wt = w + ((int64_t)((t0 * k + t1) * k + t2) * g.Cin) * g.Cout + cg * 8;
                 for (int ci = 0; ci < g.Cin; ci += 8) {
                     Vec8<T> xv;
@@ -90,51 +64,15 @@ convg_kernel(const T* __restrict__ in, const float* __restrict__ w, const float*
     r.store(out + (idx / groups) * g.Cout + cg * 8);
 }
 
-// dx[i] = sum of dpad[q] over the padded positions q (grid E + 2 pad) that clamp onto i.  Interior voxels have one.
-template <typename T>
-__global__ void __launch_bounds__(256)
-convg_fold_clamp_kernel(const T* __restrict__ dpad, T* __restrict__ dx, int B, int E0, int E1, int E2, int pad, int C) {
-    const int groups = C >> 3;
-    const int64_t n = (int64_t)B * E0 * E1 * E2;
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n * groups) return;
-    const int cg = (int)(idx % groups);
-    int64_t v = idx / groups;
-    const int i2 = (int)(v % E2); v /= E2;
-    const int i1 = (int)(v % E1); v /= E1;
-    const int i0 = (int)(v % E0);
-    const int b = (int)(v / E0);
-    const int E[3] = {E0, E1, E2}, i[3] = {i0, i1, i2};
-    int lo[3], hi[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = i[a] == 0 ? 0 : i[a] + pad;                    // padded coordinates q = i + pad; q <= pad clamps to 0
-        hi[a] = i[a] == E[a] - 1 ? E[a] - 1 + 2 * pad : i[a] + pad;
-    }
-    const int P1 = E1 + 2 * pad, P2 = E2 + 2 * pad;
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int q0 = lo[0]; q0 <= hi[0]; ++q0)
-        for (int q1 = lo[1]; q1 <= hi[1]; ++q1)
-            for (int q2 = lo[2]; q2 <= hi[2]; ++q2) {
-                Vec8<T> t;
-                t.load(dpad + ((((int64_t)b * (E0 + 2 * pad) + q0) * P1 + q1) * P2 + q2) * C + cg * 8);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[j] += t.v[j];
-            }
-    Vec8<T> r;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r.v[j] = acc[j];
-    r.store(dx + (idx / groups) * C + cg * 8);
-}
-
 // dW[t][ci][co]: one workgroup per (tap, 8-channel ci group, chunk of output voxels); thread = (ci lane, co group)
 #define CGW_VOX 4096
 template <typename T>
 __global__ void __launch_bounds__(256)
 convg_wgrad_kernel(const T* __restrict__ in, const T* __restrict__ dy, float* __restrict__ dw, float* __restrict__ dbias, ConvG g) {
     // g.Cin = channels of `in` (the conv's input), g.Cout = channels of dy; g.Eo = dy grid
-    const int tap = blockIdx.y, k = g.k;
-    const int t[3] = {tap / (k * k), (tap / k) % k, tap % k};
+    const int tap = blockIdx.y;
+    int t[3];
+    convg_tap(tap, g.k, t);
     const int ci0 = blockIdx.z * 8;
     const int64_t nvox = (int64_t)g.B * g.Eo[0] * g.Eo[1] * g.Eo[2];
     const int64_t v0 = (int64_t)blockIdx.x * CGW_VOX, v1 = min(nvox, v0 + CGW_VOX);
@@ -152,12 +90,8 @@ convg_wgrad_kernel(const T* __restrict__ in, const T* __restrict__ dy, float* __
     const bool do_bias = dbias != nullptr && tap == 0 && blockIdx.z == 0;
     if (vl < lanes) {
         for (int64_t v = v0 + vl; v < v1; v += lanes) {
-            int64_t r = v;
-            const int o2 = (int)(r % g.Eo[2]); r /= g.Eo[2];
-            const int o1 = (int)(r % g.Eo[1]); r /= g.Eo[1];
-            const int o0 = (int)(r % g.Eo[0]);
-            const int b = (int)(r / g.Eo[0]);
-            const int o[3] = {o0, o1, o2};
+            int o[3];
+            const int b = convg_row_voxel(v, g.Eo, o);
             Vec8<T> gy;
             gy.load(dy + v * g.Cout + cg * 8);
             if (do_bias) {
@@ -165,17 +99,9 @@ convg_wgrad_kernel(const T* __restrict__ in, const T* __restrict__ dy, float* __
                 for (int c = 0; c < 8; ++c) bsum[c] += gy.v[c];
             }
             int s[3];
-            bool ok = true;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                int q = o[a] * g.stride - g.pad + t[a] * g.dil;
-                if (g.clamp) q = min(max(q, 0), g.Ei[a] - 1);
-                ok = ok && q >= 0 && q < g.Ei[a];
-                s[a] = q;
-            }
-            if (!ok) continue;
+            if (!convg_gather_src(g, o, t, s)) continue;
             Vec8<T> xv;
-            xv.load(in + ((((int64_t)b * g.Ei[0] + s[0]) * g.Ei[1] + s[1]) * g.Ei[2] + s[2]) * g.Cin + ci0);
+            xv.load(in + convg_row(b, s, g.Ei) * g.Cin + ci0);
 #pragma unroll
             for (int a = 0; a < 8; ++a)
 #pragma unroll
@@ -210,26 +136,16 @@ convg_wgrad_kernel(const T* __restrict__ in, const T* __restrict__ dy, float* __
     }
 }
 
-static int convg_check(int B, const int* Ei, const int* Eo, int k, int stride, int dil, int pad, int Cin, int Cout) {
-    if (B <= 0 || k < 1 || k > 7 || stride < 1 || dil < 1 || pad < 0) return TDX_EINVAL;
-    for (int a = 0; a < 3; ++a)
-        if (Ei[a] <= 0 || Eo[a] <= 0) return TDX_EINVAL;
-    if ((Cin % 8) || (Cout % 8) || Cin <= 0 || Cout <= 0) return TDX_ESHAPE;
-    return TDX_OK;
-}
-
 // out = gather (transposed == 0) or scatter^T (transposed != 0) of `in` with w [k^3][Cin][Cout] (+ bias)
 extern "C" int tdx_convg_apply(const void* in, const float* w, const float* bias, void* out, int B, int Xi, int Yi, int Zi,
                                int Cin, int Xo, int Yo, int Zo, int Cout, int k, int stride, int dilation, int pad,
                                int replicate, int transposed, int dtype, void* stream) {
     TDX_CHECK_ARG(in && w && out);
-    ConvG g = {B, {Xi, Yi, Zi}, {Xo, Yo, Zo}, k, stride, dilation, pad, replicate, Cin, Cout};
-    int rc = convg_check(B, g.Ei, g.Eo, k, stride, dilation, pad, Cin, Cout);
+    const ConvG g = convg_geometry(B, Xi, Yi, Zi, Cin, Xo, Yo, Zo, Cout, k, stride, dilation, pad, replicate, transposed);
+    int rc = convg_check(g);
     if (rc != TDX_OK) return rc;
     if (transposed && replicate) return TDX_EINVAL;
-    if (convg_use_mfma(dtype))
-        return convg_mfma_apply(in, w, bias, out, B, g.Ei, g.Eo, Cin, Cout, k, stride, dilation, pad, replicate, transposed,
-                                as_stream(stream));
+    if (convg_use_mfma(dtype)) return convg_mfma_apply(g, in, w, bias, out, transposed != 0, nullptr, as_stream(stream));
     const int64_t total = (int64_t)B * Xo * Yo * Zo * (Cout / 8);
     if (transposed)
         TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((convg_kernel<T, true>), dim3(ceil_div(total, 256)), dim3(256), 0,
@@ -246,8 +162,9 @@ extern "C" int tdx_convg_fold_clamp(const void* dpad, void* dx, int B, int X, in
     TDX_CHECK_ARG(dpad && dx && B > 0 && X > 0 && Y > 0 && Z > 0 && pad >= 0 && C > 0);
     if (C % 8) return TDX_ESHAPE;
     const int64_t total = (int64_t)B * X * Y * Z * (C / 8);
-    TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((convg_fold_clamp_kernel<T>), dim3(ceil_div(total, 256)), dim3(256), 0,
-                                                  as_stream(stream), (const T*)dpad, (T*)dx, B, X, Y, Z, pad, C));
+    TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((convg_fold_kernel<T, false>), dim3(ceil_div(total, 256)), dim3(256), 0,
+                                                  as_stream(stream), (const T*)dpad, (const T*)nullptr, (const T*)nullptr,
+                                                  (T*)dx, (T*)nullptr, (float*)nullptr, B, 1, X, Y, Z, pad, C));
     return tdx_launch_status();
 }
 
@@ -257,12 +174,10 @@ extern "C" int tdx_convg_bwd_weight(const void* in, const void* dy, float* dw, f
                                     int Cin, int Xo, int Yo, int Zo, int Cout, int k, int stride, int dilation, int pad,
                                     int replicate, int dtype, void* stream) {
     TDX_CHECK_ARG(in && dy && dw);
-    ConvG g = {B, {Xi, Yi, Zi}, {Xo, Yo, Zo}, k, stride, dilation, pad, replicate, Cin, Cout};
-    int rc = convg_check(B, g.Ei, g.Eo, k, stride, dilation, pad, Cin, Cout);
+    const ConvG g = convg_geometry(B, Xi, Yi, Zi, Cin, Xo, Yo, Zo, Cout, k, stride, dilation, pad, replicate, 0);
+    int rc = convg_check(g);
     if (rc != TDX_OK) return rc;
-    if (convg_use_mfma(dtype))
-        return convg_mfma_bwd_weight(in, dy, dw, dbias, B, g.Ei, g.Eo, Cin, Cout, k, stride, dilation, pad, replicate,
-                                     as_stream(stream));
+    if (convg_use_mfma(dtype)) return convg_mfma_bwd_weight(g, in, dy, dw, dbias, as_stream(stream));
     if (Cout > 512) return TDX_ESHAPE;  // co groups of 8 must fit one workgroup
     const int64_t nvox = (int64_t)B * Xo * Yo * Zo;
     dim3 grid(ceil_div(nvox, CGW_VOX), k * k * k, Cin / 8);

@@ -1,6 +1,6 @@
 // Matrix-core kernels of the general 3-D convolution family (the vector-ALU kernels and the layer list
 // are in tdx_convg.hip), gfx950, bf16 tensors with fp32 accumulation:
-//   convg_mfma_kernel<TRANSPOSED, NT>    gather / scatter^T   = forward and data gradient of the dilated (dilresnet.py:22-38),
+//   convg_mfma_kernel<TRANSPOSED, NT, EPI>  gather / scatter^T   = forward and data gradient of the dilated (dilresnet.py:22-38),
 //                                        strided (tfnet.py:185-199) and transposed (tfnet.py:201-208) convolutions
 //   convg_wgrad_mfma_kernel              their weight gradients
 // Same entry points, same operands as the vector-ALU kernels (weights [taps][Cin][Cout] fp32): tdx_convg_apply and
@@ -20,18 +20,7 @@
 #include "tdx_convg.h"
 #include "tdx_mfma.h"
 
-struct ConvGM {
-    int B;
-    int Ei[3], Eo[3];  // grid of `in` and of `out`
-    int k, stride, dil, pad;
-    int clamp;         // gather only: replicate padding
-    int Cin, Cout;     // channels of `in` and of `out`
-    int cs;            // residue classes per axis (= stride for scatter^T, else 1)
-    int cls_blocks;    // workgroups per residue class
-};
-
 #define CGM_KCH 128   // channels per weight stage
-#define CGM_ROWS 256  // output voxels per workgroup
 
 // the accumulator row rho = 8 j + 4 hh + i (register 4 j + i of lane half hh) holds channel 16 hh + 4 j + i
 __device__ __forceinline__ int cgm_row_channel(int rho) { return 16 * ((rho >> 2) & 1) + 4 * (rho >> 3) + (rho & 3); }
@@ -41,7 +30,7 @@ __device__ __forceinline__ int cgm_row_channel(int rho) { return 16 * ((rho >> 2
 template <bool TRANSPOSED, int NT, bool EPI>
 __global__ void __launch_bounds__(256, 2)
 convg_mfma_kernel(const bf16* __restrict__ in, const float* __restrict__ w, const float* __restrict__ bias, bf16* __restrict__ out,
-                  ConvGM g, TdxConvgEpilogue e) {
+                  ConvG g, TdxConvgEpilogue e) {
     constexpr int BN = 32 * NT;
     constexpr int WBUF = (CGM_KCH / 8) * BN * 16;  // one weight stage: [k group][channel][8] bf16
     __shared__ __attribute__((aligned(16))) unsigned char sW[2 * WBUF];
@@ -51,10 +40,9 @@ convg_mfma_kernel(const bf16* __restrict__ in, const float* __restrict__ w, cons
     const int cls = blockIdx.x / g.cls_blocks, blk = blockIdx.x - cls * g.cls_blocks;
     const int n0 = blockIdx.y * BN;
     const int cs = g.cs;
-    const int c[3] = {cls / (cs * cs), (cls / cs) % cs, cls % cs};
-    int Ec[3];  // voxels of this class per axis
-#pragma unroll
-    for (int a = 0; a < 3; ++a) Ec[a] = g.Eo[a] > c[a] ? (g.Eo[a] - c[a] + cs - 1) / cs : 0;
+    int c[3], Ec[3];  // the residue class, and its voxels per axis
+    convg_tap(cls, cs, c);
+    convg_class_grid(g.Eo, c, cs, Ec);
     const int64_t Mc = (int64_t)g.B * Ec[0] * Ec[1] * Ec[2];
     if ((int64_t)blk * CGM_ROWS >= Mc) return;  // uniform
 
@@ -67,12 +55,8 @@ convg_mfma_kernel(const bf16* __restrict__ in, const float* __restrict__ w, cons
         int64_t m = (int64_t)blk * CGM_ROWS + wave * 64 + mt * 32 + r;
         live[mt] = m < Mc;
         if (!live[mt]) m = 0;
-        const int z = (int)(m % Ec[2]); m /= Ec[2];
-        const int y = (int)(m % Ec[1]); m /= Ec[1];
-        const int x = (int)(m % Ec[0]);
-        ob[mt] = (int)(m / Ec[0]);
-        o[mt][0] = c[0] + cs * x; o[mt][1] = c[1] + cs * y; o[mt][2] = c[2] + cs * z;
-        orow[mt] = (((int64_t)ob[mt] * g.Eo[0] + o[mt][0]) * g.Eo[1] + o[mt][1]) * g.Eo[2] + o[mt][2];
+        ob[mt] = convg_class_row_voxel(m, Ec, c, cs, o[mt]);
+        orow[mt] = convg_row(ob[mt], o[mt], g.Eo);
     }
 
     f32x16 acc[NT][2];
@@ -88,14 +72,9 @@ convg_mfma_kernel(const bf16* __restrict__ in, const float* __restrict__ w, cons
     // scatter^T: a tap is live for this residue class iff (c + pad - t dil) is divisible by the stride along every axis
     auto tap_live = [&](int t) -> bool {
         if (!TRANSPOSED || cs == 1) return true;
-        const int tt[3] = {t / (k * k), (t / k) % k, t % k};
-        bool ok = true;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const int num = c[a] + g.pad - tt[a] * g.dil;
-            ok = ok && (((num % cs) + cs) % cs) == 0;
-        }
-        return ok;
+        int tt[3];
+        convg_tap(t, k, tt);
+        return convg_tap_live(g, c, tt);
     };
     // stage = (tap, channel slice); stages are walked in order, dead taps skipped
     auto next_stage = [&](int& t, int& kc) {
@@ -141,25 +120,14 @@ convg_mfma_kernel(const bf16* __restrict__ in, const float* __restrict__ w, cons
         next_stage(tn, kn);
         if (tn < ntaps) stage_load(tn, kn);
         // source voxel of this tap for the lane's two rows
-        const int tt[3] = {t / (k * k), (t / k) % k, t % k};
+        int tt[3];
+        convg_tap(t, k, tt);
         const bf16* src[2];
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
-            bool ok = live[mt];
             int q[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                if (TRANSPOSED) {
-                    const int num = o[mt][a] + g.pad - tt[a] * g.dil;  // divisible by the stride (tap_live), or cs == 1
-                    q[a] = cs == 1 ? num : (num >= 0 ? num / cs : -1);
-                } else {
-                    q[a] = o[mt][a] * g.stride - g.pad + tt[a] * g.dil;
-                    if (g.clamp) q[a] = min(max(q[a], 0), g.Ei[a] - 1);
-                }
-                ok = ok && q[a] >= 0 && q[a] < g.Ei[a];
-            }
-            src[mt] = ok ? in + ((((int64_t)ob[mt] * g.Ei[0] + q[0]) * g.Ei[1] + q[1]) * g.Ei[2] + q[2]) * g.Cin + kc * CGM_KCH + 8 * hh
-                         : nullptr;
+            const bool ok = live[mt] && (TRANSPOSED ? convg_scatter_src<true>(g, o[mt], tt, q) : convg_gather_src(g, o[mt], tt, q));
+            src[mt] = ok ? in + convg_row(ob[mt], q, g.Ei) * g.Cin + kc * CGM_KCH + 8 * hh : nullptr;
         }
         const int kcs = min(CGM_KCH, g.Cin - kc * CGM_KCH);  // channels of this slice
         const unsigned char* wb = sW + buf * WBUF + hh * (BN * 16) + wslot;
@@ -186,57 +154,64 @@ convg_mfma_kernel(const bf16* __restrict__ in, const float* __restrict__ w, cons
     }
 
     // ---- epilogue: lane (r, hh) holds channels n0 + 32 nt + 16 hh + (0..15) of its voxel in registers 0..15
-    if constexpr (EPI) {
-        const int64_t V = (int64_t)g.Eo[0] * g.Eo[1] * g.Eo[2];
+    const int64_t V = (int64_t)g.Eo[0] * g.Eo[1] * g.Eo[2];
+    // the rollout update of the decode conv (e.x != nullptr; the host guarantees Cout <= 16, so the lane with ch == 0 holds every
+    // channel of its voxel): x_next = inside ? x + dx_mean + dx_std (acc + bias) : x in fp32 for the F state channels, and its bf16
+    // copy in `out`, padded with zeros to Cout.  (A lambda like the staging steps above: as a free function taking `e` the
+    // compiler keeps both EPI kernels at 256 VGPRs with scratch.)
+    auto rollout_update = [&](const f32x16& a, const float* bv, int64_t vox) {
+        const bool upd = e.inside[vox % V] != 0;
+        const float* xs = e.x + vox * e.F;
+        float* xn = e.x_next + vox * e.F;
+        float nx[16];
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int ch = n0 + 32 * nt + 16 * hh;
-            if (ch >= g.Cout) continue;
-            float bv[16];
+        for (int i = 0; i < 16; ++i) {
+            nx[i] = 0.f;
+            if (i < e.F) {
+                const float xv = xs[i];
+                nx[i] = upd ? xv + (e.dx_mean[i] + e.dx_std[i] * (a[i] + bv[i])) : xv;
+                xn[i] = nx[i];
+            }
+        }
 #pragma unroll
-            for (int i = 0; i < 16; ++i) bv[i] = (bias != nullptr && ch + i < g.Cout) ? bias[ch + i] : 0.f;
+        for (int h8 = 0; h8 < 2; ++h8) {
+            if (8 * h8 >= g.Cout) continue;
+            Vec8<bf16> v;
 #pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                if (!live[mt]) continue;
-                const int64_t vox = orow[mt];
+            for (int i = 0; i < 8; ++i) v.v[i] = nx[8 * h8 + i];
+            v.store(out + vox * g.Cout + 8 * h8);
+        }
+    };
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int ch = n0 + 32 * nt + 16 * hh;
+        if (ch >= g.Cout) continue;
+        float bv[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) bv[i] = (bias != nullptr && ch + i < g.Cout) ? bias[ch + i] : 0.f;
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            if (!live[mt]) continue;
+            const int64_t vox = orow[mt];
+            if constexpr (EPI) {
                 if (e.x != nullptr) {
-                    // rollout update (the host guarantees Cout <= 16, so channels 0..15 sit in the lanes with ch == 0):
-                    // x_next = inside ? x + dx_mean + dx_std (acc + bias) : x in fp32, and its bf16 copy padded with zeros
-                    if (ch != 0) continue;
-                    const bool upd = e.inside[vox % V] != 0;
-                    const float* xs = e.x + vox * e.F;
-                    float* xn = e.x_next + vox * e.F;
-                    float nx[16];
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        nx[i] = 0.f;
-                        if (i < e.F) {
-                            const float xv = xs[i];
-                            nx[i] = upd ? xv + (e.dx_mean[i] + e.dx_std[i] * (acc[nt][mt][i] + bv[i])) : xv;
-                            xn[i] = nx[i];
-                        }
-                    }
-#pragma unroll
-                    for (int h8 = 0; h8 < 2; ++h8) {
-                        if (8 * h8 >= g.Cout) continue;
-                        Vec8<bf16> v;
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) v.v[i] = nx[8 * h8 + i];
-                        v.store(out + vox * g.Cout + 8 * h8);
-                    }
+                    if (ch == 0) rollout_update(acc[nt][mt], bv, vox);
                     continue;
                 }
+            }
 #pragma unroll
-                for (int h8 = 0; h8 < 2; ++h8) {
-                    if (ch + 8 * h8 >= g.Cout) continue;
-                    const int64_t off = vox * g.Cout + ch + 8 * h8;
-                    float v[8];
+            for (int h8 = 0; h8 < 2; ++h8) {
+                if (ch + 8 * h8 >= g.Cout) continue;
+                const int64_t off = vox * g.Cout + ch + 8 * h8;
+                float v[8];
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        v[i] = acc[nt][mt][8 * h8 + i] + bv[8 * h8 + i];
-                        if (e.relu) v[i] = fmaxf(v[i], 0.f);
+                for (int i = 0; i < 8; ++i) v[i] = acc[nt][mt][8 * h8 + i] + bv[8 * h8 + i];
+                if constexpr (EPI) {
+                    if (e.relu) {
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) v[i] = fmaxf(v[i], 0.f);
                     }
-                    if (e.h != nullptr) {
+                    if (e.h != nullptr) {  // the pre-add activation
                         Vec8<bf16> hv;
 #pragma unroll
                         for (int i = 0; i < 8; ++i) hv.v[i] = v[i];
@@ -252,77 +227,36 @@ convg_mfma_kernel(const bf16* __restrict__ in, const float* __restrict__ w, cons
 #pragma unroll
                         for (int i = 0; i < 8; ++i) v[i] += av.v[i];
                     }
-                    if (e.out_f32) {
-                        Vec8<float> ov;
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) ov.v[i] = v[i];
-                        ov.store(reinterpret_cast<float*>(out) + off);
-                    } else {
-                        Vec8<bf16> ov;
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) ov.v[i] = v[i];
-                        ov.store(out + off);
-                    }
                 }
-            }
-        }
-        return;
-    }
+                if (EPI && e.out_f32) {
+                    Vec8<float> ov;
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int ch = n0 + 32 * nt + 16 * hh;
-        float bv[16];
+                    for (int i = 0; i < 8; ++i) ov.v[i] = v[i];
+                    ov.store(reinterpret_cast<float*>(out) + off);
+                } else {
+                    Vec8<bf16> ov;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) bv[i] = (bias != nullptr && ch + i < g.Cout) ? bias[ch + i] : 0.f;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            if (!live[mt]) continue;
-            bf16* dst = out + orow[mt] * g.Cout + ch;
-#pragma unroll
-            for (int h8 = 0; h8 < 2; ++h8) {
-                if (ch + 8 * h8 >= g.Cout) continue;
-                Vec8<bf16> v;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v.v[i] = acc[nt][mt][8 * h8 + i] + bv[8 * h8 + i];
-                v.store(dst + 8 * h8);
+                    for (int i = 0; i < 8; ++i) ov.v[i] = v[i];
+                    ov.store(out + off);
+                }
             }
         }
     }
 }
 
-static int convg_mfma_launch(const void* in, const float* w, const float* bias, void* out, int B, const int* Ei, const int* Eo,
-                             int Cin, int Cout, int k, int stride, int dil, int pad, int replicate, int transposed,
-                             const TdxConvgEpilogue* ep, hipStream_t st) {
-    ConvGM g;
-    g.B = B;
-    for (int a = 0; a < 3; ++a) { g.Ei[a] = Ei[a]; g.Eo[a] = Eo[a]; }
-    g.k = k; g.stride = stride; g.dil = dil; g.pad = pad; g.clamp = replicate; g.Cin = Cin; g.Cout = Cout;
-    g.cs = transposed ? stride : 1;
-    int64_t mc = B;  // class 0 has the most voxels
-    for (int a = 0; a < 3; ++a) mc *= (Eo[a] + g.cs - 1) / g.cs;
-    g.cls_blocks = ceil_div(mc, CGM_ROWS);
-    const int nt = Cout > 32 ? 2 : 1;
-    dim3 grid((unsigned)(g.cls_blocks * g.cs * g.cs * g.cs), (unsigned)ceil_div(Cout, 32 * nt));
+int convg_mfma_apply(const ConvG& g, const void* in, const float* w, const float* bias, void* out, bool transposed,
+                     const TdxConvgEpilogue* ep, hipStream_t st) {
+    const int nt = g.Cout > 32 ? 2 : 1;
+    dim3 grid((unsigned)(g.cls_blocks * g.cs * g.cs * g.cs), (unsigned)ceil_div(g.Cout, 32 * nt));
     TdxConvgEpilogue e = {};
     if (ep != nullptr) e = *ep;
 #define CGM_GO(TR, NTV, EP) \
     hipLaunchKernelGGL((convg_mfma_kernel<TR, NTV, EP>), grid, dim3(256), 0, st, (const bf16*)in, w, bias, (bf16*)out, g, e)
     if (ep != nullptr) { if (nt == 2) CGM_GO(false, 2, true); else CGM_GO(false, 1, true); }
-    else if (transposed) { if (nt == 2) CGM_GO(true, 2, false); else CGM_GO(true, 1, false); }
-    else                 { if (nt == 2) CGM_GO(false, 2, false); else CGM_GO(false, 1, false); }
+    else if (transposed)   { if (nt == 2) CGM_GO(true, 2, false); else CGM_GO(true, 1, false); }
+    else                   { if (nt == 2) CGM_GO(false, 2, false); else CGM_GO(false, 1, false); }
 #undef CGM_GO
     return tdx_launch_status();
-}
-
-int convg_mfma_apply(const void* in, const float* w, const float* bias, void* out, int B, const int* Ei, const int* Eo, int Cin,
-                     int Cout, int k, int stride, int dil, int pad, int replicate, int transposed, hipStream_t st) {
-    return convg_mfma_launch(in, w, bias, out, B, Ei, Eo, Cin, Cout, k, stride, dil, pad, replicate, transposed, nullptr, st);
-}
-
-// gather form (stride 1) with a fused epilogue: the caller (tdx_convg_apply_fused) has checked the options
-int convg_mfma_apply_epilogue(const void* in, const float* w, const float* bias, void* out, int B, const int* Ei, const int* Eo,
-                              int Cin, int Cout, int k, int dil, int pad, int replicate, const TdxConvgEpilogue* ep, hipStream_t st) {
-    return convg_mfma_launch(in, w, bias, out, B, Ei, Eo, Cin, Cout, k, 1, dil, pad, replicate, 0, ep, st);
 }
 
 // ------------------------------------------------------------------------------------------ weight gradient
@@ -335,15 +269,16 @@ int convg_mfma_apply_epilogue(const void* in, const float* w, const float* bias,
 
 __global__ void __launch_bounds__(256, 2)
 convg_wgrad_mfma_kernel(const bf16* __restrict__ in, const bf16* __restrict__ dy, float* __restrict__ dw, float* __restrict__ dbias,
-                        ConvGM g, int nsplit, int n_ci_tiles) {
+                        ConvG g, int nsplit, int n_ci_tiles) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[4 * CGW_PLANE];
     unsigned char* sX = smem;
     unsigned char* sG = smem + 2 * CGW_PLANE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tile = blockIdx.x / nsplit, split = blockIdx.x - tile * nsplit;
     const int ci0 = (tile % n_ci_tiles) * 64, co0 = (tile / n_ci_tiles) * 64;
-    const int tap = blockIdx.y, k = g.k;
-    const int tt[3] = {tap / (k * k), (tap / k) % k, tap % k};
+    const int tap = blockIdx.y;
+    int tt[3];
+    convg_tap(tap, g.k, tt);
     const int grp = lane >> 4, i16 = lane & 15, q4 = i16 >> 2, p4 = i16 & 3;
     const int col_off = (16 * (grp & 1) + 4 * p4) * 2;
     const int kh = grp >> 1;
@@ -364,20 +299,10 @@ convg_wgrad_mfma_kernel(const bf16* __restrict__ in, const bf16* __restrict__ dy
         const bool live = m < rows;
         const bf16* gp = dy + m * g.Cout + co0;
         if (!live) m = 0;
-        const int z = (int)(m % g.Eo[2]); m /= g.Eo[2];
-        const int y = (int)(m % g.Eo[1]); m /= g.Eo[1];
-        const int x = (int)(m % g.Eo[0]);
-        const int b = (int)(m / g.Eo[0]);
-        const int oo[3] = {x, y, z};
-        int qq[3];
-        bool ok = live;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            qq[a] = oo[a] * g.stride - g.pad + tt[a] * g.dil;
-            if (g.clamp) qq[a] = min(max(qq[a], 0), g.Ei[a] - 1);
-            ok = ok && qq[a] >= 0 && qq[a] < g.Ei[a];
-        }
-        const bf16* xp = in + ((((int64_t)b * g.Ei[0] + qq[0]) * g.Ei[1] + qq[1]) * g.Ei[2] + qq[2]) * g.Cin + ci0;
+        int oo[3], qq[3];
+        const int b = convg_row_voxel(m, g.Eo, oo);
+        const bool ok = convg_gather_src(g, oo, tt, qq) && live;
+        const bf16* xp = in + convg_row(b, qq, g.Ei) * g.Cin + ci0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             xr[i] = gr[i] = make_uint4(0, 0, 0, 0);
@@ -437,15 +362,9 @@ convg_wgrad_mfma_kernel(const bf16* __restrict__ in, const bf16* __restrict__ dy
     }
 }
 
-int convg_mfma_bwd_weight(const void* in, const void* dy, float* dw, float* dbias, int B, const int* Ei, const int* Eo, int Cin,
-                          int Cout, int k, int stride, int dil, int pad, int replicate, hipStream_t st) {
-    ConvGM g;
-    g.B = B;
-    for (int a = 0; a < 3; ++a) { g.Ei[a] = Ei[a]; g.Eo[a] = Eo[a]; }
-    g.k = k; g.stride = stride; g.dil = dil; g.pad = pad; g.clamp = replicate; g.Cin = Cin; g.Cout = Cout;
-    g.cs = 1; g.cls_blocks = 0;
-    const int n_ci = ceil_div(Cin, 64), n_co = ceil_div(Cout, 64);
-    const int64_t rows = (int64_t)B * Eo[0] * Eo[1] * Eo[2];
+int convg_mfma_bwd_weight(const ConvG& g, const void* in, const void* dy, float* dw, float* dbias, hipStream_t st) {
+    const int k = g.k, n_ci = ceil_div(g.Cin, 64), n_co = ceil_div(g.Cout, 64);
+    const int64_t rows = (int64_t)g.B * g.Eo[0] * g.Eo[1] * g.Eo[2];
     const int64_t nchunks = (rows + CGM_ROWS - 1) / CGM_ROWS;
     // enough workgroups for four rounds of the chip, at least four chunks per workgroup
     const int64_t base = (int64_t)k * k * k * n_ci * n_co;

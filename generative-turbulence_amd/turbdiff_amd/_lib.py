@@ -166,6 +166,11 @@ class FilmGrad(C.Structure):  # TdxFilmGrad
     _fields_ = [("weight", _vp), ("grad_out", _vp), ("grad_weight", _vp), ("grad_bias", _vp), ("channels", _i)]
 
 
+class ConvgEpilogue(C.Structure):  # TdxConvgEpilogue
+    _fields_ = [("relu", _i), ("add0", _vp), ("add1", _vp), ("add_bcast", _i), ("h", _vp), ("out_f32", _i), ("x", _vp),
+                ("x_next", _vp), ("inside", _vp), ("dx_mean", _vp), ("dx_std", _vp), ("F", _i)]
+
+
 _lib = None
 
 

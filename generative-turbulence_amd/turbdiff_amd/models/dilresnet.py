@@ -48,14 +48,6 @@ def _to_nvc_padded(x: torch.Tensor, channels: int, dtype) -> torch.Tensor:
     return F.pad(x, (0, channels - x.shape[-1])).to(dtype).contiguous()
 
 
-class TdxConvgEpilogue(_C.Structure):
-    """include/tdx.h TdxConvgEpilogue."""
-
-    _fields_ = [("relu", _C.c_int), ("add0", _C.c_void_p), ("add1", _C.c_void_p), ("add_bcast", _C.c_int),
-                ("h", _C.c_void_p), ("out_f32", _C.c_int), ("x", _C.c_void_p), ("x_next", _C.c_void_p),
-                ("inside", _C.c_void_p), ("dx_mean", _C.c_void_p), ("dx_std", _C.c_void_p), ("F", _C.c_int)]
-
-
 def conv_fused(x, w_t, bias, Cout, dilation, *, relu=False, add0=None, add1=None, h=None, out=None, out_f32=False,
                rollout=None):
     """One replicate-padded 3x3x3 conv (stride 1, padding = dilation) of a bf16 NDHWC tensor with a fused epilogue
@@ -65,7 +57,7 @@ def conv_fused(x, w_t, bias, Cout, dilation, *, relu=False, add0=None, add1=None
     B, X, Y, Z, Cin = x.shape
     if out is None:
         out = torch.empty((B, X, Y, Z, Cout), dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
-    ep = TdxConvgEpilogue()
+    ep = L.ConvgEpilogue()
     ep.relu, ep.out_f32 = int(relu), int(out_f32)
     bcast = 0
     for a, t in enumerate((add0, add1)):
@@ -99,13 +91,7 @@ def _adjoint_padded(gz, w_b, Cin, dilation):
 
 
 def _wgrad(inp, gz, dilation):
-    B, X, Y, Z, Cin = inp.shape
-    Cout = gz.shape[-1]
-    dw = torch.zeros((27, Cin, Cout), dtype=torch.float32, device=inp.device)
-    db = torch.zeros(Cout, dtype=torch.float32, device=inp.device)
-    L.call("tdx_convg_bwd_weight", L.ptr(inp), L.ptr(gz), L.ptr(dw), L.ptr(db), B, X, Y, Z, Cin, X, Y, Z, Cout, 3, 1, dilation,
-           dilation, 1, L.dtype_code(inp.dtype), L.stream())
-    return dw.reshape(3, 3, 3, Cin, Cout).permute(4, 3, 0, 1, 2).contiguous(), db
+    return ops._convg_bwd_weight(inp, gz, 3, 1, dilation, dilation, True, True)
 
 
 class _Chain(torch.autograd.Function):

@@ -1530,6 +1530,18 @@ def _convg_apply(x, w_t, bias, out_grid, Cout, k, stride, dilation, pad, replica
     return y
 
 
+def _convg_bwd_weight(x, gy, k, stride, dilation, pad, replicate, with_bias):
+    """(dw, db) of y = conv(x, w) given gy, dw in nn.Conv3d's layout (channels of gy, channels of x, k, k, k); db None without
+    bias.  A transposed conv passes its output gradient as `x` and its input as `gy` (the roles swap) and gets its own layout."""
+    B, Xi, Yi, Zi, Cin = _grid(x)
+    _, Xo, Yo, Zo, Cout = _grid(gy)
+    dw = torch.zeros((k**3, Cin, Cout), dtype=torch.float32, device=x.device)
+    db = torch.zeros(Cout, dtype=torch.float32, device=x.device) if with_bias else None
+    L.call("tdx_convg_bwd_weight", L.ptr(x), L.ptr(gy), L.ptr(dw), L.ptr(db), B, Xi, Yi, Zi, Cin, Xo, Yo, Zo, Cout, k, stride,
+           dilation, pad, int(replicate), L.dtype_code(x.dtype), L.stream())
+    return dw.reshape(k, k, k, Cin, Cout).permute(4, 3, 0, 1, 2).contiguous(), db
+
+
 class _ConvG(torch.autograd.Function):
     """nn.Conv3d(k, stride, dilation, padding, padding_mode in {"zeros", "replicate"}) on NDHWC tensors: the dilated
     convs of DilatedCNNBlock (dilresnet.py:28-35) and the strided convs of tfnet's conv() (tfnet.py:187-193)."""
@@ -1553,25 +1565,19 @@ class _ConvG(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         stride, dilation, pad, replicate, has_bias = ctx.cfg
         B, Xi, Yi, Zi, Cin = _grid(x)
-        Cout, k = weight.shape[0], weight.shape[-1]
+        k = weight.shape[-1]
         gy = gy.contiguous()
-        Xo, Yo, Zo = gy.shape[1:4]
-        code, st = L.dtype_code(x.dtype), L.stream()
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             w_b = _taps_first(weight, 0, 1)  # [k^3][Cout][Cin]
             if replicate:  # adjoint on the padded grid, then every padded position onto the voxel it clamps to
                 dpad = _convg_apply(gy, w_b, None, (Xi + 2 * pad, Yi + 2 * pad, Zi + 2 * pad), Cin, k, stride, dilation, 0, False, True)
                 gx = torch.empty_like(x)
-                L.call("tdx_convg_fold_clamp", L.ptr(dpad), L.ptr(gx), B, Xi, Yi, Zi, pad, Cin, code, st)
+                L.call("tdx_convg_fold_clamp", L.ptr(dpad), L.ptr(gx), B, Xi, Yi, Zi, pad, Cin, L.dtype_code(x.dtype), L.stream())
             else:
                 gx = _convg_apply(gy, w_b, None, (Xi, Yi, Zi), Cin, k, stride, dilation, pad, False, True)
         if ctx.needs_input_grad[1]:
-            dw = torch.zeros((k**3, Cin, Cout), dtype=torch.float32, device=x.device)
-            gb = torch.zeros(Cout, dtype=torch.float32, device=x.device) if has_bias else None
-            L.call("tdx_convg_bwd_weight", L.ptr(x), L.ptr(gy), L.ptr(dw), L.ptr(gb), B, Xi, Yi, Zi, Cin, Xo, Yo, Zo, Cout, k,
-                   stride, dilation, pad, int(replicate), code, st)
-            gw = dw.reshape(k, k, k, Cin, Cout).permute(4, 3, 0, 1, 2).contiguous()
+            gw, gb = _convg_bwd_weight(x, gy, k, stride, dilation, pad, replicate, has_bias)
         return gx, gw, gb, None, None, None, None
 
 
@@ -1606,20 +1612,15 @@ class _ConvTransposeG(torch.autograd.Function):
     def backward(ctx, gy):
         x, weight = ctx.saved_tensors
         stride, pad, has_bias = ctx.cfg
-        B, Xi, Yi, Zi, Cin = _grid(x)
-        Cout, k = weight.shape[1], weight.shape[-1]
+        _, Xi, Yi, Zi, Cin = _grid(x)
+        k = weight.shape[-1]
         gy = gy.contiguous()
-        Xo, Yo, Zo = gy.shape[1:4]
-        code, st = L.dtype_code(x.dtype), L.stream()
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:  # a strided conv of dy
             gx = _convg_apply(gy, _taps_first(weight, 1, 0), None, (Xi, Yi, Zi), Cin, k, stride, 1, pad, False, False)
         if ctx.needs_input_grad[1]:
             # dW[ci][co][t] = sum_i x[i][ci] dy[i*s - p + t][co]: the weight gradient of that strided conv, roles swapped
-            dw = torch.zeros((k**3, Cout, Cin), dtype=torch.float32, device=x.device)
-            L.call("tdx_convg_bwd_weight", L.ptr(gy), L.ptr(x), L.ptr(dw), None, B, Xo, Yo, Zo, Cout, Xi, Yi, Zi, Cin, k, stride,
-                   1, pad, 0, code, st)
-            gw = dw.reshape(k, k, k, Cout, Cin).permute(4, 3, 0, 1, 2).contiguous()
+            gw, _ = _convg_bwd_weight(gy, x, k, stride, 1, pad, False, False)
             if has_bias:
                 gb = gy.float().sum(dim=(0, 1, 2, 3))
         return gx, gw, gb, None, None

@@ -7,7 +7,7 @@ the operators then run forward and backward on small CPU tensors and every call 
     {"call": name, "args": [...], "work": w, "meta": {...} or null}      {"query": name, "args": [...], "ret": n}
 
 An argument whose ctypes type (`_lib.SIGNATURES`) is a pointer is written as null, "stream", a list of structs (job
-tables) or `[label, byte offset]`.  The label names the allocation the address lies in: `t<k> <dtype> <shape>`, k = order
+tables), one struct (passed with `ctypes.byref`: the conv epilogue) or `[label, byte offset]`.  The label names the allocation the address lies in: `t<k> <dtype> <shape>`, k = order
 of first appearance in the case's calls, dtype / shape those of the tensor first seen at it.  Addresses that ops.py
 computes itself (`w2.data_ptr() + 4 * C1`) resolve the same way: `Tensor.data_ptr` is wrapped while recording, so every
 tensor whose address was taken is known -- and kept alive, so that no two labels can share an address.
@@ -43,7 +43,9 @@ class Recorder:
         if p == STREAM:
             return "stream"
         if isinstance(p, C.Array):
-            return [{f: (self.pointer(getattr(s, f)) if ty is C.c_void_p else getattr(s, f)) for f, ty in s._fields_} for s in p]
+            return [self.struct(s) for s in p]
+        if isinstance(getattr(p, "_obj", None), C.Structure):  # ctypes.byref(struct)
+            return self.struct(p._obj)
         for base, (nbytes, first) in self.spans.items():
             if base <= p < base + max(nbytes, 1):
                 if base not in self.labels:
@@ -51,6 +53,9 @@ class Recorder:
                     self.labels[base] = f"t{len(self.labels)} {str(dtype)[6:]} {list(shape)}"
                 return [self.labels[base], p - base]
         raise AssertionError(f"pointer argument {p:#x} belongs to no tensor whose address was taken")
+
+    def struct(self, s):
+        return {f: (self.pointer(getattr(s, f)) if ty is C.c_void_p else getattr(s, f)) for f, ty in s._fields_}
 
     def args(self, name, args):
         types = self.sig[name][1]
@@ -315,6 +320,24 @@ def _randn(ops):
     ops.randn_philox_batched(state(), 1234, i64(B), i64(1))
 
 
+# the general convolution family (csrc/tdx_convg*.hip): forward and backward with bias
+def _convg(ops, **kw):
+    back(ops.conv3d(act(16, bf16), par(24, 16, 3, 3, 3), par(24), **kw))
+
+
+def _conv_transpose(ops):
+    back(ops.conv_transpose3d(act(16, bf16), par(16, 8, 4, 4, 4), par(8), stride=2, padding=1))
+
+
+def _dilresnet_chain(ops):
+    from turbdiff_amd.models.dilresnet import _Chain
+
+    H, Fp, n_blocks, dil = 16, 8, 2, (1, 2)  # two blocks of two layers between encode and decode
+    shapes = [(H, Fp)] + [(H, H)] * (n_blocks * len(dil)) + [(Fp, H)]
+    wb = [t for co, ci in shapes for t in (par(co, ci, 3, 3, 3), par(co))]
+    back(_Chain.apply(act(Fp, bf16), act(H, bf16, b=1), n_blocks, [1, *dil * n_blocks, 1], *wb))
+
+
 CASES = {
     "block_two_inputs_bf16_fused_tail": lambda ops: block(ops, bf16, 32, 32, 64, True),
     "block_two_inputs_f32_scale_shift": lambda ops: block(ops, f32, 32, 32, 64, True, film=False),
@@ -359,6 +382,10 @@ CASES = {
     "elbo_loss_int_n_cells": lambda ops: _elbo_loss(ops, 40),
     "elbo_loss_device_n_cells": lambda ops: _elbo_loss(ops, dev_scalar()),
     "randn_philox": _randn,
+    "conv3d_zeros_stride2": lambda ops: _convg(ops, stride=2, padding=1),
+    "conv3d_replicate_dilated": lambda ops: _convg(ops, dilation=2, padding=2, padding_mode="replicate"),
+    "conv_transpose3d": _conv_transpose,
+    "dilresnet_chain": _dilresnet_chain,
 }
 
 
