@@ -3,15 +3,12 @@
 // 64 rows x 64 cols per 256-thread block, 4x4 register tile per thread, K staged through
 // LDS in 32-deep slices (x slice stored k-major so the inner loop reads conflict-free
 // float4 rows).  f32 accumulation.  These layers are HBM-bound at the U-Net's channel
-// counts (4-174 FLOP/B); the MFMA versions live in tdx_conv1_mfma.hip and tdx_conv1_mfma_f32.hip (launchers: tdx_conv1.h;
-// TDX_CONV1_IMPL=direct forces the kernels of this file).
+// counts (4-174 FLOP/B); the MFMA versions live in tdx_conv1_mfma.hip and tdx_conv1_mfma_f32.hip.  Also here: the family's
+// host side -- conv1_route (TDX_CONV1_IMPL=direct forces the kernels of this file), conv1_wgrad_plan, the entry points.
 #include "tdx_common.h"
 #include "tdx_conv1.h"
 #include "tdx_runtime.h"
-#include <stdlib.h>
 #include <algorithm>
-
-static bool conv1_force_direct() { return tdx_switch(SW_CONV1_IMPL) != 0; }
 
 #define C1_BM 64
 #define C1_BN 64
@@ -86,21 +83,48 @@ conv1_fwd_kernel(const T* __restrict__ x1, int C1, const T* __restrict__ x2, int
     }
 }
 
+Conv1Route conv1_route(int dtype, int C1, int C2, int Cout, int ldw, unsigned w_mod16, bool gn_tail) {
+    const bool mfma = tdx_switch(SW_CONV1_IMPL) == 0;  // TDX_CONV1_IMPL=direct: the vector-ALU kernels of this file
+    const int nt = (Cout % 64 == 0) ? 2 : 1;  // NT = 4 needs 270 registers on the 16-bit kernel: 1 wave/SIMD, too few loads in flight
+    if (!tdx_is_h16(dtype) && (dtype != TDX_F32 || gn_tail)) return {TDX_CONV1_VECTOR, 0, TDX_EDTYPE};
+    if (tdx_is_h16(dtype) && mfma && conv1_mfma_supported(C1, C2, Cout)) return {TDX_CONV1_H16, nt, TDX_OK};
+    if (gn_tail) return {TDX_CONV1_VECTOR, 0, TDX_ESHAPE};
+    if (dtype == TDX_F32 && mfma && conv1_mfma_f32_supported(C1, C2, Cout, ldw, w_mod16)) return {TDX_CONV1_F32, nt, TDX_OK};
+    return {TDX_CONV1_VECTOR, 0, TDX_OK};
+}
+
+int conv1_vector_fwd_launch(const Conv1Call& c, const Conv1Route& r) {
+    if (r.status != TDX_OK || r.family != TDX_CONV1_VECTOR) return TDX_EINVAL;
+    dim3 grid(ceil_div(c.rows, C1_BM), ceil_div(c.Cout, C1_BN));
+    TDX_DISPATCH_DTYPE(c.fmt, hipLaunchKernelGGL((conv1_fwd_kernel<T>), grid, dim3(256), 0, c.st, (const T*)c.x1, c.C1,
+                                                 (const T*)c.x2, c.C2, c.w, c.ldw, c.bias, (const T*)c.add, (T*)c.y, c.rows, c.Cout));
+    return tdx_launch_status();
+}
+
+static int conv1_fwd_impl(const Conv1Call& c) {
+    const Conv1Route r = conv1_route(c.fmt, c.C1, c.C2, c.Cout, c.ldw, (unsigned)((uintptr_t)c.w % 16), c.gn.stats != nullptr);
+    if (r.status != TDX_OK) return r.status;
+    if (r.family == TDX_CONV1_H16) return conv1_mfma_fwd_launch(c, r);
+    return r.family == TDX_CONV1_F32 ? conv1_mfma_f32_fwd_launch(c, r) : conv1_vector_fwd_launch(c, r);
+}
+
 extern "C" int tdx_conv1_fwd(const void* x1, int C1, const void* x2, int C2, const float* w, int ldw,
                              const float* bias, const void* add, void* y, int64_t rows, int Cout, int dtype,
                              void* stream) {
     TDX_CHECK_ARG(x1 && w && y && rows > 0 && C1 > 0 && C2 >= 0 && Cout > 0 && ldw >= Cout);
     TDX_CHECK_ARG(C2 == 0 || x2);
-    if (tdx_is_h16(dtype) && !conv1_force_direct() && conv1_mfma_supported(C1, C2, Cout))
-        return conv1_mfma_fwd_launch(x1, C1, x2, C2, w, ldw, bias, add, y, rows, Cout, as_stream(stream), nullptr, nullptr, nullptr, 1,
-                                     1, dtype == TDX_F16);
-    if (dtype == TDX_F32 && !conv1_force_direct() && conv1_mfma_f32_supported(C1, C2, Cout, w, ldw))
-        return conv1_mfma_f32_fwd_launch(x1, C1, x2, C2, w, ldw, bias, add, y, rows, Cout, as_stream(stream));
-    dim3 grid(ceil_div(rows, C1_BM), ceil_div(Cout, C1_BN));
-    TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_fwd_kernel<T>), grid, dim3(256), 0, as_stream(stream),
-                                                  (const T*)x1, C1, (const T*)x2, C2, w, ldw, bias, (const T*)add,
-                                                  (T*)y, rows, Cout));
-    return tdx_launch_status();
+    return conv1_fwd_impl({x1, C1, x2, C2, w, ldw, bias, add, y, rows, Cout, dtype, as_stream(stream), {nullptr, nullptr, nullptr, 1, 1}});
+}
+
+extern "C" int tdx_conv1_fwd_plan(int C1, int C2, int Cout, int ldw, int w_mod16, int has_add, int gn_tail, int dtype, int* plan) {
+    TDX_CHECK_ARG(plan && C1 > 0 && C2 >= 0 && Cout > 0 && ldw >= Cout && (!gn_tail || has_add));
+    const Conv1Route r = conv1_route(dtype, C1, C2, Cout, ldw, (unsigned)w_mod16 % 16, gn_tail != 0);
+    static const int tile_rows[] = {C1_BM, C1M_ROWS, F1_ROWS};  // by TDX_CONV1_*
+    for (int i = 0; i < TDX_CONV1_PLAN_INTS; ++i) plan[i] = 0;
+    plan[TDX_CONV1_PLAN_KERNEL] = r.family;
+    plan[TDX_CONV1_PLAN_NT] = r.nt;
+    plan[TDX_CONV1_PLAN_TILE_ROWS] = tile_rows[r.family];
+    return r.status;
 }
 
 // y = silu(GroupNorm(h)) + bias + [x1|x2] @ w: the tail of a ResnetBlock with a projected skip in one pass (bf16 / fp16 tensors on
@@ -110,10 +134,7 @@ extern "C" int tdx_conv1_fwd_gn(const void* x1, int C1, const void* x2, int C2, 
                                 void* y, int B, int64_t V, int Cout, int dtype, void* stream) {
     TDX_CHECK_ARG(x1 && w && y && h && stats && gamma && beta && B > 0 && V > 0 && C1 > 0 && C2 >= 0 && Cout > 0 && ldw >= Cout);
     TDX_CHECK_ARG((C2 == 0 || x2) && groups > 0 && (Cout % groups) == 0);
-    if (!tdx_is_h16(dtype)) return TDX_EDTYPE;
-    if (conv1_force_direct() || !conv1_mfma_supported(C1, C2, Cout)) return TDX_ESHAPE;
-    return conv1_mfma_fwd_launch(x1, C1, x2, C2, w, ldw, bias, h, y, (int64_t)B * V, Cout, as_stream(stream), stats, gamma,
-                                 beta, groups, V, dtype == TDX_F16);
+    return conv1_fwd_impl({x1, C1, x2, C2, w, ldw, bias, h, y, (int64_t)B * V, Cout, dtype, as_stream(stream), {stats, gamma, beta, groups, V}});
 }
 
 // dw[ci][co] = sum_r x[r,ci] dy[r,co]; each block reduces a chunk of rows for one
@@ -181,78 +202,97 @@ conv1_wgrad_kernel(const T* __restrict__ x, int Cin, const T* __restrict__ dy, i
     if (dbias && blockIdx.y == 0 && tid < C1_BN && co0 + tid < Cout) atomicAdd(&dbias[co0 + tid], bsum);
 }
 
-// One launch of whichever weight-gradient kernel serves (dtype, Cin, Cout).  max_split / split_stride: see above.
-static int conv1_wgrad_dispatch(const void* x, int Cin, const void* dy, int Cout, float* dw, int ldw, float* dbias, int64_t rows,
-                                int dtype, bool transposed, hipStream_t st, int max_split, int64_t split_stride, int* nsplit_out,
-                                bool plan_only = false) {
-    if (tdx_is_h16(dtype) && !conv1_force_direct() && conv1_wgrad_mfma_supported(Cin, Cout))
-        return conv1_wgrad_mfma_launch(x, Cin, dy, Cout, dw, ldw, dbias, rows, transposed, st, dtype == TDX_F16, max_split,
-                                       split_stride, nsplit_out, plan_only);
-    if (dtype == TDX_F32 && !conv1_force_direct() && conv1_wgrad_mfma_f32_supported(Cin, Cout))
-        return conv1_wgrad_mfma_f32_launch(x, Cin, dy, Cout, dw, ldw, dbias, rows, transposed, st, max_split, split_stride,
-                                           nsplit_out, plan_only);
+void conv1_wgrad_vector_plan(Conv1WgradPlan& p, int64_t rows, int max_split) {
     int64_t rpb = C1W_ROWS;
     if (max_split > 0 && ceil_div(rows, rpb) > max_split) rpb = (ceil_div(rows, max_split) + C1_BK - 1) / C1_BK * C1_BK;
-    dim3 grid(ceil_div(rows, rpb), ceil_div(Cin, C1_BM), ceil_div(Cout, C1_BN));
-    if (nsplit_out) *nsplit_out = (int)grid.x;
-    if (plan_only) return TDX_OK;
-    TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_wgrad_kernel<T>), grid, dim3(256), 0, st, (const T*)x, Cin,
-                                                  (const T*)dy, Cout, dw, ldw, dbias, rows, transposed ? 1 : 0, rpb, split_stride));
+    p.kernel = TDX_CONV1_VECTOR;
+    p.mt = p.nt = 0;
+    p.nsplit = ceil_div(rows, rpb);
+    p.step_rows = C1_BK;
+    p.rows_per_split = rpb;
+}
+
+int conv1_wgrad_vector_launch(const Conv1WgradCall& c, const Conv1WgradPlan& p) {
+    if (p.status != TDX_OK || p.kernel != TDX_CONV1_VECTOR) return TDX_EINVAL;
+    dim3 grid(p.nsplit, ceil_div(c.Cin, C1_BM), ceil_div(c.Cout, C1_BN));
+    TDX_DISPATCH_DTYPE(c.fmt, hipLaunchKernelGGL((conv1_wgrad_kernel<T>), grid, dim3(256), 0, c.st, (const T*)c.x, c.Cin,
+                                                 (const T*)c.dy, c.Cout, c.dw, c.ldw, c.dbias, c.rows, c.transposed ? 1 : 0,
+                                                 p.rows_per_split, p.slab_stride));
     return tdx_launch_status();
 }
 
-static int conv1_bwd_weight_impl(const void* x, int Cin, const void* dy, int Cout, float* dw, int ldw, float* dbias,
-                                 int64_t rows, int dtype, bool transposed, bool accumulate, hipStream_t st) {
-    const int nrow = transposed ? Cout : Cin, ncol = transposed ? Cin : Cout;
+Conv1WgradPlan conv1_wgrad_plan(int dtype, int Cin, int Cout, int64_t rows) {
+    Conv1WgradPlan p = {};
+    int max_split = 0;  // the kernel's own choice
+    int64_t slab = 0;
     if (tdx_deterministic()) {
-        // K split k adds its tile into slab k of the scratch arena (zeroed; one contributor per element, so the f32 atomics
-        // are plain stores in effect), then the slabs are added in order into dw / dbias.  Without an arena: one split.
-        const int64_t slab = ((int64_t)nrow * ncol + Cout + 63) / 64 * 64;  // [nrow][ncol] compact, then the bias gradient
+        slab = ((int64_t)Cin * Cout + Cout + 63) / 64 * 64;  // [nrow][ncol] compact, then the bias gradient
         const int64_t room =
             tdx_scratch_ptr() ? ((int64_t)tdx_scratch_bytes() - TDX_SCRATCH_SLAB_OFFSET) / (int64_t)sizeof(float) / slab : 0;
-        int max_split = (int)std::min<int64_t>(room, 256);
-        float* slabs = max_split >= 2 ? reinterpret_cast<float*>(tdx_scratch_region(
-                                            TDX_SCRATCH_SLAB_OFFSET, (size_t)max_split * slab * sizeof(float)))
-                                      : nullptr;
-        if (slabs != nullptr) {
-            float* bias_slab = dbias ? slabs + (int64_t)nrow * ncol : nullptr;
-            int nsplit = 0;  // what the launcher will use (often far fewer than allowed): only those slabs are zeroed and summed
-            int rc = conv1_wgrad_dispatch(x, Cin, dy, Cout, slabs, ncol, bias_slab, rows, dtype, transposed, st, max_split, slab,
-                                          &nsplit, true);
-            if (rc != TDX_OK) return rc;
-            if (nsplit < 1 || nsplit > max_split) return TDX_EINVAL;
-            rc = tdx_zero_async(slabs, (size_t)nsplit * slab * sizeof(float), st);
-            if (rc != TDX_OK) return rc;
-            int launched = 0;
-            rc = conv1_wgrad_dispatch(x, Cin, dy, Cout, slabs, ncol, bias_slab, rows, dtype, transposed, st, max_split, slab, &launched);
-            if (rc != TDX_OK) return rc;
-            if (launched != nsplit) return TDX_EINVAL;
-            rc = ordered_sum_launch(slabs, nsplit, slab, dw, nrow, ncol, ldw, accumulate, st);
-            if (rc != TDX_OK || !dbias) return rc;
-            return ordered_sum_launch(slabs + (int64_t)nrow * ncol, nsplit, slab, dbias, 1, Cout, Cout, accumulate, st);
-        }
+        max_split = (int)std::min<int64_t>(room, 256);
+        if (max_split < 2) max_split = 1, slab = 0;  // fewer than two slabs: one split straight into dw
     }
-    const int one_split = tdx_deterministic() ? 1 : 0;
-    if (!accumulate) {
+    // the family the forward of these channels takes (no weight matrix is read: ldw = 0 at address 0 passes the fp32
+    // kernel's clauses on it), where the weight-gradient kernel of that family takes them too
+    const Conv1Route r = conv1_route(dtype, Cin, 0, Cout, 0, 0, false);
+    p.status = r.status;
+    if (r.family == TDX_CONV1_H16 && conv1_wgrad_mfma_supported(Cin, Cout)) conv1_wgrad_mfma_plan(p, Cin, Cout, rows, max_split);
+    else if (r.family == TDX_CONV1_F32 && conv1_wgrad_mfma_f32_supported(Cin, Cout)) conv1_wgrad_mfma_f32_plan(p, Cin, Cout, rows, max_split);
+    else conv1_wgrad_vector_plan(p, rows, max_split);
+    p.nslab = slab ? p.nsplit : 0;  // often far fewer than allowed: only those slabs are zeroed and summed
+    p.slab_stride = slab;
+    return p;
+}
+
+static int conv1_bwd_weight_impl(const Conv1WgradCall& c) {
+    const Conv1WgradPlan p = conv1_wgrad_plan(c.fmt, c.Cin, c.Cout, c.rows);
+    if (p.status != TDX_OK) return p.status;
+    const int nrow = c.transposed ? c.Cout : c.Cin, ncol = c.transposed ? c.Cin : c.Cout;
+    Conv1WgradCall k = c;  // where the kernel adds: the block itself, or the slabs
+    int rc = TDX_OK;
+    if (p.nslab > 0) {
+        float* slabs = reinterpret_cast<float*>(tdx_scratch_region(TDX_SCRATCH_SLAB_OFFSET, (size_t)p.nslab * p.slab_stride * sizeof(float)));
+        if (slabs == nullptr) return TDX_EINVAL;
+        k.dw = slabs, k.ldw = ncol, k.dbias = c.dbias ? slabs + (int64_t)nrow * ncol : nullptr;
+        rc = tdx_zero_async(slabs, (size_t)p.nslab * p.slab_stride * sizeof(float), c.st);
+    } else if (!c.accumulate) {
         // zero the block that is written (ldw may exceed the row length for sub-blocks)
-        int e = tdx_zero2d_async(dw, (size_t)ldw * sizeof(float), (size_t)ncol * sizeof(float), (size_t)nrow, st);
-        if (e != TDX_OK) return e;
-        if (dbias) {
-            e = tdx_zero_async(dbias, (size_t)Cout * sizeof(float), st);
-            if (e != TDX_OK) return e;
-        }
+        rc = tdx_zero2d_async(c.dw, (size_t)c.ldw * sizeof(float), (size_t)ncol * sizeof(float), (size_t)nrow, c.st);
+        if (rc == TDX_OK && c.dbias) rc = tdx_zero_async(c.dbias, (size_t)c.Cout * sizeof(float), c.st);
     }
-    return conv1_wgrad_dispatch(x, Cin, dy, Cout, dw, ldw, dbias, rows, dtype, transposed, st, one_split, 0, nullptr);
+    if (rc != TDX_OK) return rc;
+    rc = p.kernel == TDX_CONV1_H16   ? conv1_wgrad_mfma_launch(k, p)
+         : p.kernel == TDX_CONV1_F32 ? conv1_wgrad_mfma_f32_launch(k, p)
+                                     : conv1_wgrad_vector_launch(k, p);
+    if (rc != TDX_OK || p.nslab == 0) return rc;
+    rc = ordered_sum_launch(k.dw, p.nslab, p.slab_stride, c.dw, nrow, ncol, c.ldw, c.accumulate, c.st);
+    if (rc != TDX_OK || !c.dbias) return rc;
+    return ordered_sum_launch(k.dbias, p.nslab, p.slab_stride, c.dbias, 1, c.Cout, c.Cout, c.accumulate, c.st);
+}
+
+extern "C" int tdx_conv1_bwd_weight_plan(int Cin, int Cout, int64_t rows, int transposed, int dtype, int* plan) {
+    TDX_CHECK_ARG(plan && rows > 0 && Cin > 0 && Cout > 0);
+    (void)transposed;  // the layout of dw changes the kernel's TR argument and nothing of the plan
+    const Conv1WgradPlan p = conv1_wgrad_plan(dtype, Cin, Cout, rows);
+    for (int i = 0; i < TDX_CONV1_PLAN_INTS; ++i) plan[i] = 0;
+    plan[TDX_CONV1_PLAN_KERNEL] = p.kernel;
+    plan[TDX_CONV1_PLAN_NT] = p.nt;
+    plan[TDX_CONV1_PLAN_MT] = p.mt;
+    plan[TDX_CONV1_PLAN_NSPLIT] = p.nsplit;
+    plan[TDX_CONV1_PLAN_NSLAB] = p.nslab;
+    plan[TDX_CONV1_PLAN_STEP_ROWS] = p.step_rows;
+    plan[TDX_CONV1_PLAN_ROWS_PER_SPLIT] = (int)std::min<int64_t>(p.rows_per_split, INT32_MAX);
+    return p.status;
 }
 
 extern "C" int tdx_conv1_bwd_weight(const void* x, int Cin, const void* dy, int Cout, float* dw, int ldw,
                                     float* dbias, int64_t rows, int dtype, void* stream) {
     TDX_CHECK_ARG(x && dy && dw && rows > 0 && Cin > 0 && Cout > 0 && ldw >= Cout);
-    return conv1_bwd_weight_impl(x, Cin, dy, Cout, dw, ldw, dbias, rows, dtype, false, false, as_stream(stream));
+    return conv1_bwd_weight_impl({x, Cin, dy, Cout, dw, ldw, dbias, rows, false, false, dtype, as_stream(stream)});
 }
 
 extern "C" int tdx_conv1_bwd_weight_oc(const void* x, int Cin, const void* dy, int Cout, float* dw, int ldw,
                                        float* dbias, int accumulate, int64_t rows, int dtype, void* stream) {
     TDX_CHECK_ARG(x && dy && dw && rows > 0 && Cin > 0 && Cout > 0 && ldw >= Cin);
-    return conv1_bwd_weight_impl(x, Cin, dy, Cout, dw, ldw, dbias, rows, dtype, true, accumulate != 0, as_stream(stream));
+    return conv1_bwd_weight_impl({x, Cin, dy, Cout, dw, ldw, dbias, rows, true, accumulate != 0, dtype, as_stream(stream)});
 }

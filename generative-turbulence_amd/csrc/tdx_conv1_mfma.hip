@@ -23,23 +23,11 @@
 #include "tdx_conv1.h"
 #include "tdx_mfma.h"
 
-#define C1M_ROWS 256
 #define C1M_KC 32
 
 bool conv1_mfma_supported(int C1, int C2, int Cout) {
     return C1 > 0 && (C1 % C1M_KC) == 0 && (C2 % C1M_KC) == 0 && (Cout % 32) == 0;
 }
-
-// `add` through a normalisation: with gn.stats != nullptr the addend is silu(GroupNorm(add)) -- the tail of a ResnetBlock
-// with a projected skip, y = silu(GN(h2)) + conv1x1(x) (reference ddpm.py:176,197), in ONE pass: the skip tensor is never
-// written or re-read.  Same arithmetic as gn_apply_kernel (tdx_groupnorm.hip): n = fma(h, rstd gamma, beta - mean rstd gamma).
-struct Conv1GnAdd {
-    const float* stats;   // [B][G][2] (mean, rstd), or nullptr: plain addend
-    const float* gamma;   // [Cout]
-    const float* beta;    // [Cout]
-    int G;
-    int64_t V;            // voxels per sample (rows = B V)
-};
 
 // HF: format of the 16-bit tensors (H16<HF>: bf16 or fp16 words behind the bf16-typed pointers); the fp32 weights are
 // rounded to it while staging
@@ -218,18 +206,12 @@ conv1_mfma_fwd_kernel(const bf16* __restrict__ x1, int C1, const bf16* __restric
     }
 }
 
-int conv1_mfma_fwd_launch(const void* x1, int C1, const void* x2, int C2, const float* w, int ldw, const float* bias,
-                          const void* add, void* y, int64_t rows, int Cout, hipStream_t st, const float* gn_stats,
-                          const float* gn_gamma, const float* gn_beta, int gn_groups, int64_t gn_voxels, bool hf) {
-    const int NT = (Cout % 64 == 0) ? 2 : 1;  // NT = 4 needs 270 registers: 1 wave/SIMD, too few loads in flight
-    dim3 grid(ceil_div(rows, C1M_ROWS), Cout / (32 * NT));
-    const Conv1GnAdd gn = {gn_stats, gn_gamma, gn_beta, gn_groups, gn_voxels};
-#define C1M_LAUNCH(NTV, HFV)                                                                                             \
-    hipLaunchKernelGGL((conv1_mfma_fwd_kernel<NTV, HFV>), grid, dim3(256), 0, st, (const bf16*)x1, C1, (const bf16*)x2, \
-                       C2, w, ldw, bias, (const bf16*)add, (bf16*)y, rows, Cout, gn)
-    if (NT == 2) { if (hf) C1M_LAUNCH(2, true); else C1M_LAUNCH(2, false); }
-    else { if (hf) C1M_LAUNCH(1, true); else C1M_LAUNCH(1, false); }
-#undef C1M_LAUNCH
+int conv1_mfma_fwd_launch(const Conv1Call& c, const Conv1Route& r) {
+    if (r.status != TDX_OK || r.family != TDX_CONV1_H16 || !tdx_is_h16(c.fmt)) return TDX_EINVAL;
+    dim3 grid(ceil_div(c.rows, C1M_ROWS), c.Cout / (32 * r.nt));
+    TDX_DISPATCH_BOOL(r.nt == 2, WIDE, TDX_DISPATCH_H16(c.fmt == TDX_F16,
+        hipLaunchKernelGGL((conv1_mfma_fwd_kernel<WIDE ? 2 : 1, HF>), grid, dim3(256), 0, c.st, (const bf16*)c.x1, c.C1,
+                           (const bf16*)c.x2, c.C2, c.w, c.ldw, c.bias, (const bf16*)c.add, (bf16*)c.y, c.rows, c.Cout, c.gn)));
     return tdx_launch_status();
 }
 
@@ -385,12 +367,9 @@ conv1_wgrad_mfma_kernel(const bf16* __restrict__ x, int Cin, const bf16* __restr
     }
 }
 
-int conv1_wgrad_mfma_launch(const void* x, int Cin, const void* dy, int Cout, float* dw, int ldw, float* dbias,
-                            int64_t rows, bool transposed, hipStream_t st, bool hf, int max_split, int64_t split_stride,
-                            int* nsplit_out, bool plan_only) {
+void conv1_wgrad_mfma_plan(Conv1WgradPlan& p, int Cin, int Cout, int64_t rows, int max_split) {
     const int MT = (Cin % 64 == 0) ? 2 : 1, NT = (Cout % 64 == 0) ? 2 : 1;
-    const int n_ci = Cin / (32 * MT), n_co = Cout / (32 * NT);
-    const int ntiles = n_ci * n_co;
+    const int ntiles = (Cin / (32 * MT)) * (Cout / (32 * NT));
     const int64_t nchunks = (rows + C1M_ROWS - 1) / C1M_ROWS;
     // one full wave of resident workgroups (LDS-limited occupancy), so that no partial second round trails
     const int per_cu = 160 / ((MT + NT) * 16);
@@ -398,25 +377,19 @@ int conv1_wgrad_mfma_launch(const void* x, int Cin, const void* dy, int Cout, fl
     if (nsplit > nchunks) nsplit = (int)nchunks;
     if (nsplit < 1) nsplit = 1;
     if (max_split > 0 && nsplit > max_split) nsplit = max_split;
-    if (nsplit_out) *nsplit_out = nsplit;
-    if (plan_only) return TDX_OK;
-    dim3 grid((unsigned)(ntiles * nsplit));
-#define C1W_LAUNCH(M, N, T)                                                                                                 \
-    do {                                                                                                                    \
-        if (hf)                                                                                                            \
-            hipLaunchKernelGGL((conv1_wgrad_mfma_kernel<M, N, T, true>), grid, dim3(256), 0, st, (const bf16*)x, Cin,       \
-                               (const bf16*)dy, Cout, dw, ldw, dbias, rows, nsplit, n_ci, split_stride);                    \
-        else                                                                                                                \
-            hipLaunchKernelGGL((conv1_wgrad_mfma_kernel<M, N, T, false>), grid, dim3(256), 0, st, (const bf16*)x, Cin,      \
-                               (const bf16*)dy, Cout, dw, ldw, dbias, rows, nsplit, n_ci, split_stride);                    \
-    } while (0)
-#define C1W_PICK(T)                           \
-    if (MT == 2 && NT == 2) C1W_LAUNCH(2, 2, T); \
-    else if (MT == 2) C1W_LAUNCH(2, 1, T);       \
-    else if (NT == 2) C1W_LAUNCH(1, 2, T);       \
-    else C1W_LAUNCH(1, 1, T)
-    if (transposed) { C1W_PICK(true); } else { C1W_PICK(false); }
-#undef C1W_PICK
-#undef C1W_LAUNCH
+    p.kernel = TDX_CONV1_H16;
+    p.mt = MT, p.nt = NT;
+    p.nsplit = nsplit;
+    p.step_rows = C1M_ROWS;
+    p.rows_per_split = 0;  // split s takes the chunks s, s + nsplit, ...
+}
+
+int conv1_wgrad_mfma_launch(const Conv1WgradCall& c, const Conv1WgradPlan& p) {
+    if (p.status != TDX_OK || p.kernel != TDX_CONV1_H16 || !tdx_is_h16(c.fmt)) return TDX_EINVAL;
+    const int n_ci = c.Cin / (32 * p.mt), n_co = c.Cout / (32 * p.nt);
+    dim3 grid((unsigned)(n_ci * n_co * p.nsplit));
+    TDX_DISPATCH_BOOL(p.mt == 2, M2, TDX_DISPATCH_BOOL(p.nt == 2, N2, TDX_DISPATCH_BOOL(c.transposed, TR, TDX_DISPATCH_H16(c.fmt == TDX_F16,
+        hipLaunchKernelGGL((conv1_wgrad_mfma_kernel<M2 ? 2 : 1, N2 ? 2 : 1, TR, HF>), grid, dim3(256), 0, c.st, (const bf16*)c.x,
+                           c.Cin, (const bf16*)c.dy, c.Cout, c.dw, c.ldw, c.dbias, c.rows, p.nsplit, n_ci, p.slab_stride)))));
     return tdx_launch_status();
 }

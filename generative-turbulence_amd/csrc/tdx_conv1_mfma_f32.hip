@@ -17,12 +17,11 @@
 #include "tdx_conv1.h"
 #include "tdx_mfma.h"
 
-#define F1_ROWS 128
 #define F1_BK 32
 #define F1_XP (F1_BK + 1)
 
-bool conv1_mfma_f32_supported(int C1, int C2, int Cout, const float* w, int ldw) {
-    return C1 > 0 && (C1 % F1_BK) == 0 && (C2 % F1_BK) == 0 && (Cout % 32) == 0 && (ldw % 4) == 0 && ((uintptr_t)w % 16) == 0;
+bool conv1_mfma_f32_supported(int C1, int C2, int Cout, int ldw, unsigned w_mod16) {
+    return C1 > 0 && (C1 % F1_BK) == 0 && (C2 % F1_BK) == 0 && (Cout % 32) == 0 && (ldw % 4) == 0 && w_mod16 == 0;
 }
 
 template <int NT, bool HAS_ADD>
@@ -112,16 +111,12 @@ conv1_f32_mfma_fwd_kernel(const float* __restrict__ x1, int C1, const float* __r
     }
 }
 
-int conv1_mfma_f32_fwd_launch(const void* x1, int C1, const void* x2, int C2, const float* w, int ldw, const float* bias,
-                              const void* add, void* y, int64_t rows, int Cout, hipStream_t st) {
-    const int NT = (Cout % 64 == 0) ? 2 : 1;
-    dim3 grid((unsigned)ceil_div(rows, (int64_t)F1_ROWS), Cout / (32 * NT));
-#define F1_GO(NTV, ADD)                                                                                                    \
-    hipLaunchKernelGGL((conv1_f32_mfma_fwd_kernel<NTV, ADD>), grid, dim3(256), 0, st, (const float*)x1, C1, (const float*)x2, \
-                       C2, w, ldw, bias, (const float*)add, (float*)y, rows, Cout)
-    if (NT == 2) { if (add) F1_GO(2, true); else F1_GO(2, false); }
-    else { if (add) F1_GO(1, true); else F1_GO(1, false); }
-#undef F1_GO
+int conv1_mfma_f32_fwd_launch(const Conv1Call& c, const Conv1Route& r) {
+    if (r.status != TDX_OK || r.family != TDX_CONV1_F32 || c.fmt != TDX_F32 || c.gn.stats != nullptr) return TDX_EINVAL;
+    dim3 grid((unsigned)ceil_div(c.rows, (int64_t)F1_ROWS), c.Cout / (32 * r.nt));
+    TDX_DISPATCH_BOOL(r.nt == 2, WIDE, TDX_DISPATCH_BOOL(c.add != nullptr, ADD,
+        hipLaunchKernelGGL((conv1_f32_mfma_fwd_kernel<WIDE ? 2 : 1, ADD>), grid, dim3(256), 0, c.st, (const float*)c.x1, c.C1,
+                           (const float*)c.x2, c.C2, c.w, c.ldw, c.bias, (const float*)c.add, (float*)c.y, c.rows, c.Cout)));
     return tdx_launch_status();
 }
 
@@ -237,9 +232,7 @@ conv1_f32_mfma_wgrad_kernel(const float* __restrict__ x, int Cin, const float* _
     }
 }
 
-int conv1_wgrad_mfma_f32_launch(const void* x, int Cin, const void* dy, int Cout, float* dw, int ldw, float* dbias,
-                                int64_t rows, bool transposed, hipStream_t st, int max_split_arg, int64_t split_stride,
-                                int* nsplit_out, bool plan_only) {
+void conv1_wgrad_mfma_f32_plan(Conv1WgradPlan& p, int Cin, int Cout, int64_t rows, int max_split_arg) {
     const int NT = (Cout % 64 == 0) ? 2 : 1;
     const int nblk = ceil_div(Cin, F1W_CI), nco = Cout / (32 * NT);
     // ~1024 workgroups overall (two per CU resident), each at least 8 slices long
@@ -250,17 +243,18 @@ int conv1_wgrad_mfma_f32_launch(const void* x, int Cin, const void* dy, int Cout
     if (nsplit < 1) nsplit = 1;
     int64_t rps = ceil_div(rows, nsplit);
     rps = ceil_div(rps, (int64_t)F1W_RS) * F1W_RS;
-    nsplit = ceil_div(rows, rps);
-    if (nsplit_out) *nsplit_out = (int)nsplit;
-    if (plan_only) return TDX_OK;
-    dim3 grid((unsigned)nsplit, nblk, nco);
-#define F1W_LAUNCH(N, T)                                                                                                  \
-    hipLaunchKernelGGL((conv1_f32_mfma_wgrad_kernel<N, T>), grid, dim3(256), 0, st, (const float*)x, Cin, (const float*)dy, \
-                       Cout, dw, ldw, dbias, rows, rps, split_stride)
-    if (NT == 2 && transposed) F1W_LAUNCH(2, true);
-    else if (NT == 2) F1W_LAUNCH(2, false);
-    else if (transposed) F1W_LAUNCH(1, true);
-    else F1W_LAUNCH(1, false);
-#undef F1W_LAUNCH
+    p.kernel = TDX_CONV1_F32;
+    p.mt = 0, p.nt = NT;
+    p.nsplit = ceil_div(rows, rps);
+    p.step_rows = F1W_RS;
+    p.rows_per_split = rps;
+}
+
+int conv1_wgrad_mfma_f32_launch(const Conv1WgradCall& c, const Conv1WgradPlan& p) {
+    if (p.status != TDX_OK || p.kernel != TDX_CONV1_F32 || c.fmt != TDX_F32) return TDX_EINVAL;
+    dim3 grid((unsigned)p.nsplit, ceil_div(c.Cin, F1W_CI), c.Cout / (32 * p.nt));
+    TDX_DISPATCH_BOOL(p.nt == 2, WIDE, TDX_DISPATCH_BOOL(c.transposed, TR,
+        hipLaunchKernelGGL((conv1_f32_mfma_wgrad_kernel<WIDE ? 2 : 1, TR>), grid, dim3(256), 0, c.st, (const float*)c.x, c.Cin,
+                           (const float*)c.dy, c.Cout, c.dw, c.ldw, c.dbias, c.rows, p.rows_per_split, p.slab_stride)));
     return tdx_launch_status();
 }

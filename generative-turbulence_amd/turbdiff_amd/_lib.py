@@ -59,6 +59,8 @@ SIGNATURES = {
     "tdx_conv1_fwd_gn": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i64, _i, _i, _vp]),
     "tdx_conv1_bwd_weight": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i, _vp]),
     "tdx_conv1_bwd_weight_oc": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i64, _i, _vp]),
+    "tdx_conv1_fwd_plan": (_i, [_i] * 8 + [_vp]),
+    "tdx_conv1_bwd_weight_plan": (_i, [_i, _i, _i64, _i, _i, _vp]),
     "tdx_encode_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _vp]),
     "tdx_encode_bwd": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp]),
     "tdx_decode_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp]),
@@ -485,6 +487,36 @@ def conv3_bwd_weight_plan(C1, C2, Cout, B, X, Y, Z, dtype: int, impl: int) -> di
     plan["kernel"] = WGRAD_KERNELS[plan["kernel"]]
     plan["status"] = status
     return plan
+
+
+CONV1_KERNELS = ("vector", "h16", "f32")  # TDX_CONV1_*
+CONV1_PLAN_INTS = 8  # TDX_CONV1_PLAN_INTS
+CONV1_PLAN_FIELDS = ("kernel", "nt", "tile_rows", "mt", "nsplit", "nslab", "step_rows", "rows_per_split")  # TDX_CONV1_PLAN_*
+
+
+def _conv1_plan(entry, fields, *args) -> dict:
+    buf = (C.c_int * CONV1_PLAN_INTS)()
+    status = int(getattr(load(), entry)(*args, buf))
+    plan = {k: int(buf[CONV1_PLAN_FIELDS.index(k)]) for k in fields}
+    plan["kernel"] = CONV1_KERNELS[plan["kernel"]]
+    plan["status"] = status
+    return plan
+
+
+def conv1_fwd_plan(C1, C2, Cout, ldw, w_mod16, has_add, gn_tail, dtype: int) -> dict:
+    """What tdx_conv1_fwd (gn_tail: tdx_conv1_fwd_gn) would launch for this call, as the library's own route decides it:
+    {"status": the code that call would return, "kernel": a name of CONV1_KERNELS, "nt", "tile_rows"}.  w_mod16: the address
+    of w modulo 16.  Launches nothing; reads the library switches from the environment as it is now."""
+    return _conv1_plan("tdx_conv1_fwd_plan", CONV1_PLAN_FIELDS[:3], C1, C2, Cout, ldw, w_mod16, int(has_add), int(gn_tail), dtype)
+
+
+def conv1_bwd_weight_plan(Cin, Cout, rows, transposed, dtype: int) -> dict:
+    """What tdx_conv1_bwd_weight (transposed: tdx_conv1_bwd_weight_oc) would launch, as the library's own host code plans it:
+    {"status", "kernel", and the other CONV1_PLAN_FIELDS but "tile_rows"}.  Launches nothing; reads the library switches as of
+    now and the bound arena's size (under TDX_DETERMINISTIC `call` binds the launching stream's before the launch: bind it
+    first -- ensure_scratch -- to ask about a call on this stream)."""
+    fields = CONV1_PLAN_FIELDS[:2] + CONV1_PLAN_FIELDS[3:]
+    return _conv1_plan("tdx_conv1_bwd_weight_plan", fields, Cin, Cout, rows, int(transposed), dtype)
 
 
 def conv3_fwd_meta(C1, C2, Cout, B, X, Y, Z, dt, real=None):

@@ -286,6 +286,40 @@ int tdx_conv1_bwd_weight(const void* x, int Cin, const void* dy, int Cout, float
  * dw / dbias as they are (the caller zeroed them, e.g. as one allocation) instead of zeroing inside. */
 int tdx_conv1_bwd_weight_oc(const void* x, int Cin, const void* dy, int Cout, float* dw, int ldw, float* dbias,
                             int accumulate, int64_t rows, int dtype, void* stream);
+/* What tdx_conv1_fwd (gn_tail != 0: tdx_conv1_fwd_gn) launches for this call -- the same host function routes both; the
+ * environment switches (TDX_CONV1_IMPL) are read as of now.  Nothing is launched.  w_mod16: the address of w modulo 16, the
+ * only thing the routing looks at a pointer for (the fp32 matrix-core kernel stages w with 16-byte loads); has_add: whether
+ * the call has an addend (the fused tail always has: h).  Returns the status that call would return for these arguments and
+ * fills plan[0 .. TDX_CONV1_PLAN_INTS):
+ *   KERNEL      TDX_CONV1_*: vector ALU (tdx_conv1.hip), 16-bit matrix-core kernel (tdx_conv1_mfma.hip), fp32-IEEE
+ *               matrix-core kernel (tdx_conv1_mfma_f32.hip)
+ *   NT          output-tile width in units of 32 channels (1 or 2; vector ALU: 0)
+ *   TILE_ROWS   rows of y per workgroup: 64, 256, 128 */
+#define TDX_CONV1_VECTOR 0
+#define TDX_CONV1_H16 1
+#define TDX_CONV1_F32 2
+#define TDX_CONV1_PLAN_KERNEL 0
+#define TDX_CONV1_PLAN_NT 1
+#define TDX_CONV1_PLAN_TILE_ROWS 2
+#define TDX_CONV1_PLAN_MT 3
+#define TDX_CONV1_PLAN_NSPLIT 4
+#define TDX_CONV1_PLAN_NSLAB 5
+#define TDX_CONV1_PLAN_STEP_ROWS 6
+#define TDX_CONV1_PLAN_ROWS_PER_SPLIT 7
+#define TDX_CONV1_PLAN_INTS 8
+int tdx_conv1_fwd_plan(int C1, int C2, int Cout, int ldw, int w_mod16, int has_add, int gn_tail, int dtype, int* plan);
+/* What tdx_conv1_bwd_weight (transposed != 0: tdx_conv1_bwd_weight_oc) launches for this call -- the same host function
+ * plans both; TDX_CONV1_IMPL and TDX_DETERMINISTIC are read as of now, and of the scratch arena (tdx_set_scratch) only
+ * whether one is bound and how large it claims to be.  Nothing is launched.  Returns the status that call would return
+ * (plan == NULL: TDX_EINVAL) and fills plan[0 .. TDX_CONV1_PLAN_INTS):
+ *   KERNEL, NT      as above;  MT  input-channel tile in units of 32 (16-bit kernel: 1 or 2, else 0).  With `transposed` and
+ *                   dtype they name the template instantiation; the layout of dw changes nothing else of the plan
+ *   NSPLIT          splits of the rows, each one contributor to the elements of its tiles
+ *   NSLAB           TDX_DETERMINISTIC with an arena of two slabs or more: = NSPLIT, split s adds into its own zeroed slab and
+ *                   the slabs are added in slab order; 0: the splits merge with fp32 atomics (TDX_DETERMINISTIC: one split)
+ *   STEP_ROWS       rows per loop trip of a split: 256 (16-bit kernel), 32 (fp32 kernel, vector ALU)
+ *   ROWS_PER_SPLIT  split s reduces the rows [s, s + 1) * ROWS_PER_SPLIT; 0: the STEP_ROWS-row chunks s, s + NSPLIT, ... */
+int tdx_conv1_bwd_weight_plan(int Cin, int Cout, int64_t rows, int transposed, int dtype, int* plan);
 
 /* ------------------------------------------------------------------ model boundary ------ */
 /* encode_x / encode_c_local (ddpm.py:433,436,495-501) fused with NCDHW -> NDHWC and the

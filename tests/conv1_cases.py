@@ -1,9 +1,10 @@
 """The host side of the 1x1 convolution family restated in Python, and the table of shapes tests/test_conv1_reference.py runs.
 
-`fwd_route`, `gn_route` and `wgrad_route` repeat what tdx_conv1_fwd, tdx_conv1_fwd_gn and conv1_wgrad_dispatch (csrc/tdx_conv1.hip)
-decide before they launch; `plan_h`, `plan_f`, `plan_v` repeat the split planning of the three weight-gradient launchers
-(conv1_wgrad_mfma_launch, conv1_wgrad_mfma_f32_launch, the vector-ALU branch of conv1_wgrad_dispatch) and `det_plan` what
-conv1_bwd_weight_impl does with them under TDX_DETERMINISTIC.  Pure functions: no GPU, no library.
+`fwd_route`, `gn_route` and `wgrad_route` repeat what conv1_route and conv1_wgrad_plan (csrc/tdx_conv1.hip) decide for tdx_conv1_fwd,
+tdx_conv1_fwd_gn and the two weight-gradient entries; `plan_h`, `plan_f`, `plan_v` repeat the split rules of the three weight-gradient
+kernels (conv1_wgrad_mfma_plan, conv1_wgrad_mfma_f32_plan, conv1_wgrad_vector_plan) and `det_plan` what conv1_wgrad_plan does with them
+under TDX_DETERMINISTIC.  Pure functions: no GPU, no library -- the independent statement of the rules, which the library's own
+answers (tdx_conv1_fwd_plan, tdx_conv1_bwd_weight_plan) are held against.
 
 Routes: V = the vector-ALU kernels conv1_fwd_kernel<T> / conv1_wgrad_kernel<T> (64 x 64 tiles, any channel count, any T),
 H = the 16-bit matrix-core kernels of tdx_conv1_mfma.hip (256-row tiles), F = the fp32 matrix-core kernels of
@@ -19,7 +20,7 @@ from collections import namedtuple
 V, H, F = "V", "H", "F"
 TILE_ROWS = {V: 64, F: 128, H: 256}  # forward tile heights: C1_BM, F1_ROWS, C1M_ROWS
 H16 = ("bf16", "f16")
-ARENA_HEAD, MAX_SLABS = 256, 256  # conv1_bwd_weight_impl: bytes skipped at the arena's head, most slabs
+ARENA_HEAD, MAX_SLABS = 256, 256  # conv1_wgrad_plan: bytes skipped at the arena's head, most slabs
 ARENA = 96 << 20  # the default TDX_SCRATCH_MB
 
 Route = namedtuple("Route", "route kernel")
@@ -37,7 +38,7 @@ def _mfma_ok(C1, C2, Cout):
 
 
 def fwd_route(dtype, C1, C2, Cout, ldw, col, add, direct=False):
-    """tdx_conv1_fwd.  col: the first column of the weight block inside a 16-byte aligned matrix with rows of ldw floats (the
+    """conv1_route for tdx_conv1_fwd.  col: the first column of the weight block inside a 16-byte aligned matrix with rows of ldw floats (the
     pointer handed over is w + col: conv1_mfma_f32_supported wants it 16-byte aligned and ldw a multiple of 4)."""
     nt = 2 if Cout % 64 == 0 else 1
     if dtype in H16 and not direct and _mfma_ok(C1, C2, Cout):
@@ -57,7 +58,7 @@ def gn_route(dtype, C1, C2, Cout, direct=False):
 
 
 def wgrad_route(dtype, Cin, Cout, transposed, direct=False):
-    """conv1_wgrad_dispatch"""
+    """conv1_wgrad_plan: the kernel"""
     ok = Cin % 32 == 0 and Cout % 32 == 0 and not direct
     tr, nt = int(bool(transposed)), 2 if Cout % 64 == 0 else 1
     if dtype in H16 and ok:
@@ -73,7 +74,7 @@ Plan = namedtuple("Plan", "nsplit steps")  # steps: loop trips (256-row chunks o
 
 
 def plan_h(Cin, Cout, rows, max_split=0):
-    """conv1_wgrad_mfma_launch: split s reduces the 256-row chunks s, s + nsplit, ..."""
+    """conv1_wgrad_mfma_plan: split s reduces the 256-row chunks s, s + nsplit, ..."""
     mt, nt = (2 if Cin % 64 == 0 else 1), (2 if Cout % 64 == 0 else 1)
     ntiles = (Cin // (32 * mt)) * (Cout // (32 * nt))
     nchunks = ceil_div(rows, 256)
@@ -89,7 +90,7 @@ def _row_blocks(rows, per, nsplit):
 
 
 def plan_f(Cin, Cout, rows, max_split=0):
-    """conv1_wgrad_mfma_f32_launch: split s reduces rows [s rps, (s + 1) rps) in 32-row slices"""
+    """conv1_wgrad_mfma_f32_plan: split s reduces rows [s rps, (s + 1) rps) in 32-row slices"""
     nt = 2 if Cout % 64 == 0 else 1
     nsplit = min(ceil_div(1024, ceil_div(Cin, 128) * (Cout // (32 * nt))), ceil_div(rows, 256))
     if max_split > 0:
@@ -100,7 +101,7 @@ def plan_f(Cin, Cout, rows, max_split=0):
 
 
 def plan_v(rows, max_split=0):
-    """the vector-ALU branch: 4096 rows per block, or ceil(rows / max_split) rounded up to the 32-row slice"""
+    """conv1_wgrad_vector_plan: 4096 rows per block, or ceil(rows / max_split) rounded up to the 32-row slice"""
     rpb = 4096
     if max_split > 0 and ceil_div(rows, rpb) > max_split:
         rpb = ceil_div(ceil_div(rows, max_split), 32) * 32
@@ -112,7 +113,7 @@ def plan(route, Cin, Cout, rows, max_split=0):
 
 
 def det_plan(route, Cin, Cout, rows, arena_bytes):
-    """conv1_bwd_weight_impl under TDX_DETERMINISTIC: ("slabs", plan) when the arena holds two slabs or more, else
+    """conv1_wgrad_plan under TDX_DETERMINISTIC: ("slabs", plan) when the arena holds two slabs or more, else
     ("single", plan with max_split = 1): one contributor per element straight into dw."""
     slab = ceil_div(Cin * Cout + Cout, 64) * 64
     room = (arena_bytes - ARENA_HEAD) // 4 // slab if arena_bytes > 0 else 0

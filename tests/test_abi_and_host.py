@@ -65,6 +65,9 @@ def test_header_symbols_are_bound_and_exported():
         assert hasattr(lib, s), f"{s} not exported by libtdx_hip.so"
     assert lib.tdx_arch() == b"gfx950"
     assert lib.tdx_version() >= 1
+    assert {"tdx_conv1_fwd_plan", "tdx_conv1_bwd_weight_plan"} <= set(syms)
+    assert protos["tdx_conv1_fwd_plan"] == ("int", ["int"] * 8 + ["ptr"])
+    assert protos["tdx_conv1_bwd_weight_plan"] == ("int", ["int", "int", "int64_t", "int", "int", "ptr"])
 
 
 def test_product_refuses_cpu_tensors():

@@ -4,10 +4,12 @@ rounded at the route's rounding points is THE answer (torch.equal); elsewhere ev
 docstring of conv1_reference.py.  No tolerance is a measured number and no element is left out.
 
 Without a GPU: the reference against float64 F.conv3d and its autograd, the route and split plan every row is listed for
-(against the restated host code of conv1_cases), the exactness preconditions of every exact row, where the two rounding forms
-differ, and what the table reaches.
+(against the restated host code of conv1_cases, and that restatement against the library's own answers: tdx_conv1_fwd_plan,
+tdx_conv1_bwd_weight_plan), the exactness preconditions of every exact row, where the two rounding forms differ, and what the
+table reaches.  On the GPU every call that a row's route is asserted for asks the library first, immediately before the launch.
 """
 
+import ctypes
 import functools
 import itertools
 
@@ -20,6 +22,7 @@ import conv1_reference as R
 import gn_reference as G
 
 DT = R.DTYPES
+DNAME = {dt: name for name, dt in DT.items()}
 MARGIN = 1024   # elements behind every forward output
 SENTINEL = -768.0  # exact in bf16 and fp16
 OFF, PAD_C, PAD_R = 6, 3, 2  # the gradient block starts at column OFF of a buffer PAD_C columns and PAD_R rows larger
@@ -270,6 +273,121 @@ def test_layers_are_exact(layer):
     R.assert_exact(R.exact_inputs(rows, C1, C2, Cout), bias, False)
 
 
+# ------------------------------------------------------------------------ the library's own answers (no GPU: nothing launches)
+
+KIND = {"vector": "V", "h16": "H", "f32": "F"}  # _lib.CONV1_KERNELS -> the routes of conv1_cases
+STATUS = {"TDX_ESHAPE": -2, "TDX_EDTYPE": -3}
+DIRECT = {False: None, True: "direct"}  # TDX_CONV1_IMPL
+
+
+def _code(L, dname):
+    return L.dtype_code(DT[dname])
+
+
+def _ask_forward(L, c, dname, w_mod16, direct):
+    """tdx_conv1_fwd_plan answers what conv1_cases.fwd_route restates; the template instantiation follows from its ints"""
+    q = L.conv1_fwd_plan(c.C1, c.C2, c.Cout, c.ldw, w_mod16, c.add, False, _code(L, dname))
+    want = cases.fwd_route(dname, c.C1, c.C2, c.Cout, c.ldw, w_mod16 // 4, c.add, direct)  # col: w is a float pointer
+    name = {"V": f"conv1_fwd_kernel<{dname}>", "H": f"conv1_mfma_fwd_kernel<{q['nt']},{dname}>",
+            "F": f"conv1_f32_mfma_fwd_kernel<{q['nt']},{int(bool(c.add))}>"}[KIND[q["kernel"]]]
+    assert (q["status"], KIND[q["kernel"]], name) == (0, want.route, want.kernel), (c.name, dname, q)
+    assert q["tile_rows"] == cases.TILE_ROWS[want.route] and (q["nt"] == 0) == (want.route == "V")
+    return want.route
+
+
+def _ask_tail(L, C1, C2, Cout, dname, direct):
+    """tdx_conv1_fwd_plan(gn_tail) answers what conv1_cases.gn_route restates: the kernel, or the error of tdx_conv1_fwd_gn"""
+    q = L.conv1_fwd_plan(C1, C2, Cout, Cout, 0, True, True, _code(L, dname))
+    want = cases.gn_route(dname, C1, C2, Cout, direct)
+    if isinstance(want, str):
+        assert q["status"] == STATUS[want], (C1, C2, Cout, dname, q)
+    else:
+        assert (q["status"], KIND[q["kernel"]], f"conv1_mfma_fwd_kernel<{q['nt']},{dname}>", q["tile_rows"]) == (0, "H", want.kernel, 256)
+    return want
+
+
+def _steps(q, rows):
+    """the loop trips of every split, from the ints of the library's plan"""
+    n, step, per = q["nsplit"], q["step_rows"], q["rows_per_split"]
+    if per == 0:  # split s takes the chunks s, s + n, ...
+        return tuple(cases.ceil_div(cases.ceil_div(rows, step) - s, n) for s in range(n))
+    return tuple(cases.ceil_div(min(rows, (s + 1) * per) - s * per, step) for s in range(n))
+
+
+def _ask_wgrad(L, c, dname, tr, direct, det, arena_bytes):
+    """tdx_conv1_bwd_weight_plan answers what conv1_cases restates: wgrad_route, and plan / det_plan for the splits.  Returns
+    (route, how the splits merge, steps)."""
+    q = L.conv1_bwd_weight_plan(c.Cin, c.Cout, c.rows, tr, _code(L, dname))
+    want = cases.wgrad_route(dname, c.Cin, c.Cout, tr, direct)
+    merge, plan = cases.det_plan(want.route, c.Cin, c.Cout, c.rows, arena_bytes) if det else ("atomics", cases.plan(want.route, c.Cin, c.Cout, c.rows))
+    name = {"V": f"conv1_wgrad_kernel<{dname}>", "H": f"conv1_wgrad_mfma_kernel<{q['mt']},{q['nt']},{int(tr)},{dname}>",
+            "F": f"conv1_f32_mfma_wgrad_kernel<{q['nt']},{int(tr)}>"}[KIND[q["kernel"]]]
+    what = (c.name, dname, tr, direct, det, arena_bytes, q)
+    assert (q["status"], KIND[q["kernel"]], name) == (0, want.route, want.kernel), what
+    assert (q["nsplit"], _steps(q, c.rows)) == plan, what
+    assert q["nslab"] == (plan.nsplit if merge == "slabs" else 0) and (merge != "single" or plan.nsplit == 1), what
+    assert q["step_rows"] == (256 if want.route == "H" else 32) and (q["rows_per_split"] == 0) == (want.route == "H"), what
+    return want.route, merge, plan.steps
+
+
+@pytest.mark.parametrize("arena", (True, False), ids=("arena", "no_arena"))
+@pytest.mark.parametrize("det", (0, 1))
+@pytest.mark.parametrize("direct", (False, True))
+def test_library_routes_every_forward_and_tail_row_as_restated(direct, det, arena, monkeypatch):
+    """(neither TDX_DETERMINISTIC nor the arena may move a forward route)"""
+    from test_conv3_wgrad_reference import _fake_arena
+    from turbdiff_amd import _lib as L
+
+    _set_env(monkeypatch, "TDX_CONV1_IMPL", DIRECT[direct])
+    _set_env(monkeypatch, "TDX_DETERMINISTIC", "1" if det else None)
+    with _fake_arena(L, arena):
+        _forward_and_tail_rows(L, direct)
+
+
+def _forward_and_tail_rows(L, direct):
+    for c in cases.FWD:
+        for dname in cases.ALL:
+            for mod in sorted({4 * c.col % 16, 0, 4, 8}):  # the row's own alignment of w, and others
+                route = _ask_forward(L, c, dname, mod, direct)
+                if dname in c.dtypes and direct == c.direct and mod == 4 * c.col % 16:
+                    assert route == c.route, (c.name, dname)
+    for c in cases.TAIL:
+        for dname in cases.ALL:
+            want = _ask_tail(L, c.C1, c.C2, c.Cout, dname, direct)
+            assert (want if isinstance(want, str) else want.route) == ("TDX_EDTYPE" if dname == "f32" else "TDX_ESHAPE" if direct else "H")
+    assert _ask_tail(L, 40, 0, 64, "bf16", direct) == "TDX_ESHAPE" and _ask_tail(L, 64, 0, 48, "f16", direct) == "TDX_ESHAPE"
+    plan = (ctypes.c_int * L.CONV1_PLAN_INTS)()
+    assert L.load().tdx_conv1_fwd_plan(32, 0, 32, 32, 0, 0, 0, L.BF16, None) == -1
+    assert L.load().tdx_conv1_fwd_plan(32, 0, 32, 32, 0, 0, 0, 2, plan) == -3  # TDX_F32_SPLIT is a pack code, no tensor format
+
+
+@pytest.mark.parametrize("arena", (True, False), ids=("arena", "no_arena"))
+@pytest.mark.parametrize("det", (0, 1))
+@pytest.mark.parametrize("direct", (False, True))
+def test_library_plans_every_weight_gradient_row_as_restated(direct, det, arena, monkeypatch):
+    from test_conv3_wgrad_reference import _fake_arena
+    from turbdiff_amd import _lib as L
+
+    _set_env(monkeypatch, "TDX_CONV1_IMPL", DIRECT[direct])
+    _set_env(monkeypatch, "TDX_DETERMINISTIC", "1" if det else None)
+    with _fake_arena(L, arena):  # 96 MiB claimed, as cases.ARENA
+        for c in cases.WGRAD:
+            for dname in cases.ALL:
+                for tr in (0, 1):
+                    route, merge, steps = _ask_wgrad(L, c, dname, tr, direct, det, cases.ARENA if arena else 0)
+                    if dname not in c.dtypes or direct != c.direct:
+                        continue
+                    assert route == c.route and merge == ("atomics" if not det else "slabs" if arena else "single")
+                    if arena or not det:
+                        assert steps == c.steps
+                    elif c.name in cases.NO_ARENA:
+                        assert steps == cases.NO_ARENA_STEPS[c.name]
+        plan = (ctypes.c_int * L.CONV1_PLAN_INTS)()
+        assert L.load().tdx_conv1_bwd_weight_plan(32, 32, 1, 0, L.BF16, None) == -1
+        assert L.load().tdx_conv1_bwd_weight_plan(32, 32, 0, 0, L.BF16, plan) == -1
+        assert L.load().tdx_conv1_bwd_weight_plan(32, 32, 1, 0, 2, plan) == -3
+
+
 # ---------------------------------------------------------------------------------------------------------------- on the GPU
 
 
@@ -304,14 +422,18 @@ def _as(t, dt):
     return None if t is None else t.to(dt).contiguous()
 
 
-def _forward(L, c, p, dt, bias, add):
+def _forward(L, c, p, dt, bias, add, ask=True):
     """tdx_conv1_fwd into a buffer with a sentinel margin; the weight block sits at column c.col of a (Cin, ldw) matrix whose
-    other columns hold 3.0 (a kernel that strays into them misses the reference)."""
+    other columns hold 3.0 (a kernel that strays into them misses the reference).  ask: the library's own route for this very
+    call, pointer included, must be the row's (False: a library from before the query, as the recorder of the pinned bits runs)."""
     d = _dev()
     wm = torch.full((c.C1 + c.C2, c.ldw), 3.0, device=d)
     wm[:, c.col:c.col + c.Cout] = p["w"]
     buf = torch.full((c.rows * c.Cout + MARGIN,), SENTINEL, dtype=dt, device=d)
     x1, x2 = _as(p["x1"], dt), _as(p["x2"], dt)
+    if ask:
+        assert bool(c.add) == (add is not None)
+        assert _ask_forward(L, c, DNAME[dt], (L.ptr(wm) + 4 * c.col) % 16, c.direct) == c.route
     L.call("tdx_conv1_fwd", L.ptr(x1), c.C1, L.ptr(x2), c.C2, L.ptr(wm) + 4 * c.col, c.ldw, L.ptr(bias), L.ptr(_as(add, dt)),
            L.ptr(buf), c.rows, c.Cout, L.dtype_code(dt), L.stream())
     assert bool((buf[c.rows * c.Cout:] == SENTINEL).all()), "the margin behind y was written"
@@ -391,7 +513,10 @@ def test_layer_through_autograd_is_exact(layer, dname, monkeypatch):
     dt = DT[dname]
     p = _exact(rows, C1, C2, Cout)
     bias = p["bias"] if has_bias else None
+    from turbdiff_amd import _lib as L
+
     fr = cases.fwd_route(dname, C1, C2, Cout, Cout, 0, False).route
+    assert _ask_forward(L, cases._fwd(str(layer), fr, (dname,), C1, C2, Cout, rows, has_bias, False, "ops.conv1"), dname, 0, False) == fr
     y0, _ = R.forward(p["x1"], p["x2"], p["w"], bias, None)
     w2 = p["w"].t().contiguous()
     dW, db = R.wgrad(R._cat(p["x1"], p["x2"]), p["dy"])
@@ -450,6 +575,7 @@ def test_fused_tail_on_exact_inputs(case, dname):
     n, s = R.tail(t["h"], t["stats"], t["gamma"], t["beta"], c.G)
     assert n.abs().max().item() <= R.N_MAX and torch.equal(n.float().double(), n)
     y = y0 + s
+    assert _ask_tail(L, c.C1, c.C2, c.Cout, dname, False).route == "H"
     fused, two, res = _tail_calls(L, c, p, t, dt)
     _assert_equal(res, y0.to(dt).view(rows, c.Cout), f"{c.name} {dname}: the two-launch form's residual")
     _assert_within(fused, y, R.tail_bound(t["h"], t["stats"], t["gamma"], t["beta"], n, 0.0, y0, y, dt), f"{c.name} {dname} fused")
@@ -473,6 +599,7 @@ def test_fused_tail_on_gaussian_inputs_within_the_derived_bound(name, dname):
     n, s = R.tail(t["h"], t["stats"], t["gamma"], t["beta"], c.G)
     assert n.abs().max().item() <= R.N_MAX
     y = y0 + s
+    assert _ask_tail(L, c.C1, c.C2, c.Cout, dname, False).route == "H"
     fused, _, _ = _tail_calls(L, c, p, t, dt)
     _assert_within(fused, y, R.tail_bound(t["h"], t["stats"], t["gamma"], t["beta"], n, y0_bound, y0, y, dt), f"{c.name} {dname}")
 
@@ -488,6 +615,7 @@ def test_fused_tail_refuses_fp32_and_ineligible_shapes(monkeypatch):
         dt = DT[dname]
         assert cases.gn_route(dname, C1, 0, Cout, direct) == {-3: "TDX_EDTYPE", -2: "TDX_ESHAPE"}[want]
         _set_env(monkeypatch, "TDX_CONV1_IMPL", "direct" if direct else None)
+        assert STATUS[_ask_tail(L, C1, 0, Cout, dname, direct)] == want
         x, h = torch.zeros(B, V, C1, dtype=dt, device=d), torch.zeros(B, V, Cout, dtype=dt, device=d)
         w, bias, stats = torch.zeros(C1, Cout, device=d), torch.zeros(Cout, device=d), torch.ones(B, G_, 2, device=d)
         y = torch.full((B, V, Cout), SENTINEL, dtype=dt, device=d)
@@ -533,6 +661,15 @@ def _prefills(Cin, Cout, tr, exact=True):
     return R.prefill((nrow + PAD_R, OFF + ncol + PAD_C), tr, exact).to(d), R.prefill((Cout + 8,), 2 + tr, exact).to(d)
 
 
+def _ask_wgrad_row(L, c, dname, tr, det):
+    """the library's own plan for the call about to be made on this stream, with the arena that call will see: the row's route,
+    its way of merging and its steps"""
+    L.ensure_scratch()
+    route, merge, steps = _ask_wgrad(L, c, dname, tr, c.direct, det, L.SCRATCH_BYTES)
+    assert (route, merge) == (c.route, "atomics" if not det else "slabs" if L.SCRATCH_BYTES else "single")
+    assert steps == (cases.NO_ARENA_STEPS[c.name] if merge == "single" else c.steps)
+
+
 def _run_exact_wgrad(L, c, monkeypatch, dets):
     p = _exact(c.rows, c.Cin, 0, c.Cout)
     dW, db = R.wgrad(p["x1"], p["dy"])
@@ -547,6 +684,7 @@ def _run_exact_wgrad(L, c, monkeypatch, dets):
                 ew, eb = _wgrad_expected(tr, acc, dW, db, pre_w, pre_b if with_bias else None)
                 for det in dets:
                     _set_deterministic(monkeypatch, det)
+                    _ask_wgrad_row(L, c, dname, tr, det)
                     bw, bb = _wgrad_call(L, entry, tr, acc, x, dy, c.Cin, c.Cout, c.rows, dt, pre_w, pre_b if with_bias else None)
                     what = f"{c.name} {dname} {entry} accumulate={acc} dbias={with_bias} deterministic={det}"
                     _assert_equal(bw, ew.float(), what + ": dW and the buffer around it")
@@ -613,6 +751,7 @@ def test_weight_gradient_on_gaussian_inputs_within_the_derived_bound(name, monke
             runs = []
             for det in (0, 1, 1):
                 _set_deterministic(monkeypatch, det)
+                _ask_wgrad_row(L, c, dname, tr, det)
                 bw, bb = _wgrad_call(L, entry, tr, acc, x, dy, c.Cin, c.Cout, c.rows, dt, pre_w, pre_b)
                 what = f"{c.name} {dname} {entry} accumulate={acc} deterministic={det}"
                 _assert_within(bw, ew, bound_w, what + " dW")

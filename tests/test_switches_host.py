@@ -133,6 +133,33 @@ def test_formerly_frozen_switches_are_read_per_call(L, monkeypatch):
         L._ACTIVE = None  # a later GPU test in this process binds its real arena again
 
 
+def test_conv1_queries_follow_the_switches_between_two_calls(L, monkeypatch):
+    """TDX_CONV1_IMPL has ONE reader, conv1_route, asked per call by the forward, the fused tail and the weight gradient's plan;
+    TDX_DETERMINISTIC and the arena's size are read by that plan per call: the same queries again after each change."""
+    uses = [(f.name, n) for f in sorted(CSRC.glob("tdx_conv*")) if (n := len(re.findall(r"\bSW_CONV1_IMPL\b", f.read_text())))]
+    assert uses == [("tdx_conv1.hip", 1)], uses
+    lib = L.load()
+    fake = ctypes.create_string_buffer(256)  # never dereferenced: the plan looks at the claimed size only
+    fwd = lambda: L.conv1_fwd_plan(64, 64, 64, 64, 0, True, False, L.BF16)["kernel"]
+    tail = lambda: L.conv1_fwd_plan(64, 64, 64, 64, 0, True, True, L.BF16)["status"]
+    wgrad = lambda: L.conv1_bwd_weight_plan(32, 32, 2305, 0, L.BF16)  # one tile, ten 256-row chunks
+    try:
+        assert lib.tdx_set_scratch(ctypes.addressof(fake), 96 << 20) == 0
+        for value, kernel, status in ((None, "h16", 0), ("direct", "vector", -2), ("0", "h16", 0), ("1", "vector", -2), (None, "h16", 0)):
+            monkeypatch.delenv("TDX_CONV1_IMPL", raising=False) if value is None else monkeypatch.setenv("TDX_CONV1_IMPL", value)
+            assert (fwd(), tail(), wgrad()["kernel"]) == (kernel, status, kernel), value
+        for value, nslab in ((None, 0), ("1", 10), ("0", 0), ("1", 10)):
+            monkeypatch.delenv("TDX_DETERMINISTIC", raising=False) if value is None else monkeypatch.setenv("TDX_DETERMINISTIC", value)
+            assert (wgrad()["nsplit"], wgrad()["nslab"]) == (10, nslab), value
+        assert lib.tdx_set_scratch(ctypes.addressof(fake), 256 + 4 * 1088 * 3) == 0  # room for three slabs of 32 * 32 + 32 floats, rounded up to 64
+        assert (wgrad()["nsplit"], wgrad()["nslab"]) == (3, 3)
+        assert lib.tdx_set_scratch(None, 0) == 0
+        assert (wgrad()["nsplit"], wgrad()["nslab"]) == (1, 0)
+    finally:
+        lib.tdx_set_scratch(None, 0)
+        L._ACTIVE = None  # a later GPU test in this process binds its real arena again
+
+
 def test_python_and_library_agree_on_deterministic(L, monkeypatch):
     assert L.deterministic() is False
     for s, want in (("", False), ("0", False), ("1", True), ("2", False), ("off", False)):
