@@ -5,8 +5,11 @@
 // gathered voxel ~17x from L2); all loads of a thread are issued before the arithmetic.
 // Index arithmetic follows ATen's upsample_trilinear3d exactly (float scale, float source
 // index, truncation, clamped second tap) so that tap selection matches the reference.
+//
+// Host side: resize_plan decides, once per call, everything a launch depends on; tdx_resize_fwd, tdx_resize_bwd and the
+// query tdx_resize_plan read that plan and hold no condition of their own.  The forward evaluates only the forward half
+// of the plan (no spans) and the adjoint only the adjoint half (no pair windows); the query evaluates both.
 #include "tdx_common.h"
-#include <stdlib.h>
 
 struct AxisMap {
     int in, out;
@@ -43,6 +46,41 @@ __device__ __forceinline__ void tile_origin(const TileGrid& tg, int& b, int& x0,
     x0 = (t % tg.nx) * tg.tx;
     b = t / tg.nx;
 }
+// the map of axis a (0: x, 1: y, 2: z) and the tile's origin along it, for the few threads that fill the LDS tables
+__device__ __forceinline__ const AxisMap& tile_axis(int a, const AxisMap& ax, const AxisMap& ay, const AxisMap& az, int x0,
+                                                    int y0, int z0, int& origin) {
+    origin = a == 0 ? x0 : (a == 1 ? y0 : z0);
+    return a == 0 ? ax : (a == 1 ? ay : az);
+}
+// lane split of a workgroup: lane lc of C / 8 owns 8 channels of slot0, slot0 + per_pass, ...; false for the idle lanes
+// past the last whole slot of a pass
+__device__ __forceinline__ bool lane_split(int C, int& lc, int& per_pass, int& slot0) {
+    const int L = C >> 3;
+    per_pass = 256 / L; lc = (int)threadIdx.x % L; slot0 = (int)threadIdx.x / L;
+    return (int)threadIdx.x < per_pass * L;
+}
+// slot -> voxel of the tile, z fastest (the pair kernel's slots are 2 x 2 x 2 blocks: it divides by its half extents)
+__device__ __forceinline__ void slot_voxel(const TileGrid& tg, int slot, int& kx, int& ky, int& kz) {
+    kz = slot & (tg.tz - 1); ky = (slot >> tg.sz) & (tg.ty - 1); kx = slot >> (tg.sz + tg.sy);
+}
+template <typename T>
+__device__ __forceinline__ void store_acc(const float (&acc)[8], T* p) {
+    Vec8<T> o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o.v[j] = acc[j];
+    o.store(p);
+}
+// the adjoints' tail: dx = acc (+ add, a second gradient of the resampled tensor -- its use as a U-Net skip), one store
+template <typename T>
+__device__ __forceinline__ void store_adjoint(float (&acc)[8], const T* add, T* dx, int64_t di) {
+    if (add != nullptr) {
+        Vec8<T> a;
+        a.load(add + di);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] += a.v[j];
+    }
+    store_acc(acc, dx + di);
+}
 
 // Per-axis interpolation tables of the tile live in LDS: they are computed once per workgroup by a
 // few threads instead of once per lane (the index arithmetic, not the gather, was the bottleneck).
@@ -55,21 +93,19 @@ resize_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, AxisMap ax, AxisMa
     tile_origin(tg, b, ox0, oy0, oz0);
     if (threadIdx.x < 3 * RS_MAXT) {
         const int a = threadIdx.x / RS_MAXT, k = threadIdx.x % RS_MAXT;
-        const AxisMap& m = a == 0 ? ax : (a == 1 ? ay : az);
-        const int o = min((a == 0 ? ox0 : (a == 1 ? oy0 : oz0)) + k, m.out - 1);
-        int i0, i1;
+        int o0, i0, i1;
+        const AxisMap& m = tile_axis(a, ax, ay, az, ox0, oy0, oz0, o0);
+        const int o = min(o0 + k, m.out - 1);
         float w1;
         axis_taps(m, o, i0, i1, w1);
         s_i0[a][k] = i0; s_i1[a][k] = i1; s_w[a][k] = w1;
     }
     __syncthreads();
-    const int L = C >> 3;
-    const int per_pass = 256 / L;
-    const int lc = (int)threadIdx.x % L;
     const int nvox = tg.tx * tg.ty * tg.tz;
-    if ((int)threadIdx.x >= per_pass * L) return;
-    for (int slot = (int)threadIdx.x / L; slot < nvox; slot += per_pass) {
-        const int kz = slot & (tg.tz - 1), ky = (slot >> tg.sz) & (tg.ty - 1), kx = slot >> (tg.sz + tg.sy);
+    int lc, per_pass, slot0, kx, ky, kz;
+    if (!lane_split(C, lc, per_pass, slot0)) return;
+    for (int slot = slot0; slot < nvox; slot += per_pass) {
+        slot_voxel(tg, slot, kx, ky, kz);
         const int ox = ox0 + kx, oy = oy0 + ky, oz = oz0 + kz;
         if (ox >= ax.out || oy >= ay.out || oz >= az.out) continue;
         const float wx = s_w[0][kx], wy = s_w[1][ky], wz = s_w[2][kz];
@@ -81,9 +117,7 @@ resize_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, AxisMap ax, AxisMa
         for (int k = 0; k < 8; ++k)
             t[k].load(xb + (((int64_t)xs[k >> 2] * ay.in + ys[(k >> 1) & 1]) * az.in + zs[k & 1]) * C);
         __builtin_amdgcn_sched_barrier(0);
-        float acc[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+        float acc[8] = {};
 #pragma unroll
         for (int k = 0; k < 8; ++k) {  // x outer, y, z inner
             const float w = wxs[k >> 2] * wys[(k >> 1) & 1] * wzs[k & 1];
@@ -91,10 +125,7 @@ resize_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, AxisMap ax, AxisMa
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc[j] += w * v.v[j];
         }
-        Vec8<T> o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o.v[j] = acc[j];
-        o.store(y + ((((int64_t)b * ax.out + ox) * ay.out + oy) * az.out + oz) * C + lc * 8);
+        store_acc(acc, y + ((((int64_t)b * ax.out + ox) * ay.out + oy) * az.out + oz) * C + lc * 8);
     }
 }
 
@@ -151,19 +182,18 @@ resize_up_pairs_kernel(const T* __restrict__ x, T* __restrict__ y, AxisMap ax, A
     tile_origin(tg, b, ox0, oy0, oz0);  // tile extents are even (host-checked), so pairs never straddle tiles
     if (threadIdx.x < 3 * (RS_MAXT / 2)) {
         const int a = threadIdx.x / (RS_MAXT / 2), k = threadIdx.x % (RS_MAXT / 2);
-        const AxisMap& m = a == 0 ? ax : (a == 1 ? ay : az);
+        int o0;
+        const AxisMap& m = tile_axis(a, ax, ay, az, ox0, oy0, oz0, o0);
         PairTaps p;
-        pair_taps(m, (a == 0 ? ox0 : (a == 1 ? oy0 : oz0)) + 2 * k, p);
+        pair_taps(m, o0 + 2 * k, p);
         s_p[a][k] = p;
     }
     __syncthreads();
-    const int L = C >> 3;
-    const int per_pass = 256 / L;
-    const int lc = (int)threadIdx.x % L;
+    int lc, per_pass, slot0;
+    if (!lane_split(C, lc, per_pass, slot0)) return;
     const int px = tg.tx >> 1, py = tg.ty >> 1, pz = tg.tz >> 1;
     const int nblk = px * py * pz;
-    if ((int)threadIdx.x >= per_pass * L) return;
-    for (int slot = (int)threadIdx.x / L; slot < nblk; slot += per_pass) {
+    for (int slot = slot0; slot < nblk; slot += per_pass) {
         const int kz = slot % pz, ky = (slot / pz) % py, kx = slot / (pz * py);
         const int ox = ox0 + 2 * kx, oy = oy0 + 2 * ky, oz = oz0 + 2 * kz;
         if (ox >= ax.out || oy >= ay.out || oz >= az.out) continue;
@@ -216,10 +246,7 @@ resize_up_pairs_kernel(const T* __restrict__ x, T* __restrict__ y, AxisMap ax, A
 #pragma unroll
                 for (int qz = 0; qz < 2; ++qz) {
                     if (ox + qx >= ax.out || oy + qy >= ay.out || oz + qz >= az.out) continue;
-                    Vec8<T> o;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) o.v[j] = acc[qx][qy][qz][j];
-                    o.store(y + ((((int64_t)b * ax.out + ox + qx) * ay.out + oy + qy) * az.out + oz + qz) * C + lc * 8);
+                    store_acc(acc[qx][qy][qz], y + ((((int64_t)b * ax.out + ox + qx) * ay.out + oy + qy) * az.out + oz + qz) * C + lc * 8);
                 }
     }
 }
@@ -272,21 +299,19 @@ resize_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ add, T* __rest
     tile_origin(tg, b, ix0, iy0, iz0);
     if (threadIdx.x < 3 * RS_MAXT) {
         const int a = threadIdx.x / RS_MAXT, k = threadIdx.x % RS_MAXT;
-        const AxisMap& m = a == 0 ? ax : (a == 1 ? ay : az);
-        const int i = min((a == 0 ? ix0 : (a == 1 ? iy0 : iz0)) + k, m.in - 1);
-        int f, c;
+        int i0, f, c;
+        const AxisMap& m = tile_axis(a, ax, ay, az, ix0, iy0, iz0, i0);
+        const int i = min(i0 + k, m.in - 1);
         axis_span(m, i, f, c);
         s_first[a][k] = f; s_cnt[a][k] = c;
         for (int j = 0; j < RS_KMAX; ++j) s_w[a][k][j] = j < c ? axis_weight(m, f + j, i) : 0.f;
     }
     __syncthreads();
-    const int L = C >> 3;
-    const int per_pass = 256 / L;
-    const int lc = (int)threadIdx.x % L;
     const int nvox = tg.tx * tg.ty * tg.tz;
-    if ((int)threadIdx.x >= per_pass * L) return;
-    for (int slot = (int)threadIdx.x / L; slot < nvox; slot += per_pass) {
-        const int kz = slot & (tg.tz - 1), ky = (slot >> tg.sz) & (tg.ty - 1), kx = slot >> (tg.sz + tg.sy);
+    int lc, per_pass, slot0, kx, ky, kz;
+    if (!lane_split(C, lc, per_pass, slot0)) return;
+    for (int slot = slot0; slot < nvox; slot += per_pass) {
+        slot_voxel(tg, slot, kx, ky, kz);
         const int ix = ix0 + kx, iy = iy0 + ky, iz = iz0 + kz;
         if (ix >= ax.in || iy >= ay.in || iz >= az.in) continue;
         const int fx = s_first[0][kx], cx = s_cnt[0][kx], fy = s_first[1][ky], cy = s_cnt[1][ky], fz = s_first[2][kz];
@@ -298,9 +323,7 @@ resize_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ add, T* __rest
             wz[k] = s_w[2][kz][k];
         }
         const T* gb = dy + ((int64_t)b * ax.out * ay.out * az.out) * C + lc * 8;
-        float acc[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+        float acc[8] = {};
         for (int a = 0; a < cx; ++a) {
             const float wx = s_w[0][kx][a];
             for (int bb = 0; bb < cy; ++bb) {
@@ -319,17 +342,7 @@ resize_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ add, T* __rest
                 }
             }
         }
-        const int64_t di = ((((int64_t)b * ax.in + ix) * ay.in + iy) * az.in + iz) * C + lc * 8;
-        if (add != nullptr) {  // second gradient of the resampled tensor (its use as a U-Net skip), fused add
-            Vec8<T> a;
-            a.load(add + di);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[j] += a.v[j];
-        }
-        Vec8<T> o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o.v[j] = acc[j];
-        o.store(dx + di);
+        store_adjoint(acc, add, dx, ((((int64_t)b * ax.in + ix) * ay.in + iy) * az.in + iz) * C + lc * 8);
     }
 }
 
@@ -353,9 +366,7 @@ resize_bwd_generic_kernel(const T* __restrict__ dy, const T* __restrict__ add, T
     axis_range(ay, iy, y0, y1);
     axis_range(az, iz, z0, z1);
     const T* gb = dy + ((int64_t)b * ax.out * ay.out * az.out) * C + lc * 8;
-    float acc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+    float acc[8] = {};
     for (int ox = x0; ox <= x1; ++ox) {
         const float wx = axis_weight(ax, ox, ix);
         if (wx == 0.f) continue;
@@ -373,30 +384,18 @@ resize_bwd_generic_kernel(const T* __restrict__ dy, const T* __restrict__ add, T
             }
         }
     }
-    const int64_t di = ((((int64_t)b * ax.in + ix) * ay.in + iy) * az.in + iz) * C + lc * 8;
-    if (add != nullptr) {
-        Vec8<T> a;
-        a.load(add + di);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] += a.v[j];
-    }
-    Vec8<T> o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o.v[j] = acc[j];
-    o.store(dx + di);
+    store_adjoint(acc, add, dx, ((((int64_t)b * ax.in + ix) * ay.in + iy) * az.in + iz) * C + lc * 8);
 }
 
-static int resize_args_ok(int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int C) {
-    return B > 0 && Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0 && C > 0;
-}
+// ---- host side: one plan per call --------------------------------------------------------------------------------------
 static TileGrid make_tiles(int X, int Y, int Z, int C, int64_t samples = 0) {
     // ~8 passes of (256 / L) voxels: 256 voxels up to 64 channels, halved for every doubling beyond
     const int L = C >> 3;
     int vox = 256;
     while (vox > 8 && vox * L > 8 * 256) vox >>= 1;
-    // samples > 0 (the adjoint): small tensors get smaller tiles, down to one pass per workgroup, until ~1024 workgroups
-    // exist -- a tile's passes are chains of dependent gathers, and the 48x16x12 / 24x8x6 levels left 576 / 144 / 72
-    // eight-pass workgroups on 256 CUs (100 / 68 / 30 us for 141 / 35 / 8 MB)
+    // samples > 0 (both callers pass the batch size): small tensors get smaller tiles, down to one pass per workgroup, until
+    // ~1024 workgroups exist -- a tile's passes are chains of dependent gathers, and the 48x16x12 / 24x8x6 levels left 576 /
+    // 144 / 72 eight-pass workgroups on 256 CUs (100 / 68 / 30 us for 141 / 35 / 8 MB)
     const int one_pass = 256 / L > 8 ? 256 / L : 8;
     while (samples > 0 && vox > one_pass && samples * X * Y * Z / vox < 1024) vox >>= 1;
     TileGrid t;
@@ -410,26 +409,6 @@ static TileGrid make_tiles(int X, int Y, int Z, int C, int64_t samples = 0) {
     t.nx = ceil_div(X, t.tx); t.ny = ceil_div(Y, t.ty); t.nz = ceil_div(Z, t.tz);
     return t;
 }
-extern "C" int tdx_resize_fwd(const void* x, void* y, int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int C,
-                              int dtype, void* stream) {
-    TDX_CHECK_ARG(x && y && resize_args_ok(B, Xi, Yi, Zi, Xo, Yo, Zo, C));
-    if (C % 8 || C / 8 > 256) return TDX_ESHAPE;
-    const TileGrid tg = make_tiles(Xo, Yo, Zo, C, B);
-    const int64_t blocks = (int64_t)B * tg.nx * tg.ny * tg.nz;
-    const AxisMap mx = make_axis(Xi, Xo), my = make_axis(Yi, Yo), mz = make_axis(Zi, Zo);
-    // measured (tools/micro/resize_bench.py, B = 8): 64 channels 281 -> 256 us, 128 channels 65 -> 69 us: narrow rows only
-    if (C <= 64 && !((tg.tx | tg.ty | tg.tz) & 1) && Xo > Xi && Yo > Yi && Zo > Zi && pair_window_ok(mx) &&
-        pair_window_ok(my) && pair_window_ok(mz)) {
-        TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((resize_up_pairs_kernel<T>), dim3((unsigned)blocks), dim3(256), 0,
-                                                      as_stream(stream), (const T*)x, (T*)y, mx, my, mz, C, tg));
-        return tdx_launch_status();
-    }
-    TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((resize_fwd_kernel<T>), dim3((unsigned)blocks), dim3(256), 0,
-                                                  as_stream(stream), (const T*)x, (T*)y, make_axis(Xi, Xo),
-                                                  make_axis(Yi, Yo), make_axis(Zi, Zo), C, tg));
-    return tdx_launch_status();
-}
-
 // largest number of outputs that read one input along an axis (exact, same float arithmetic)
 static int axis_max_span(const AxisMap& a) {
     int m = 0;
@@ -440,28 +419,98 @@ static int axis_max_span(const AxisMap& a) {
     }
     return m;
 }
+static int dtype_status(int dtype) {
+    TDX_DISPATCH_DTYPE(dtype, (void)sizeof(T));
+    return TDX_OK;
+}
 
+struct ResizePlan {
+    int status;  // what tdx_resize_fwd / tdx_resize_bwd return for these arguments; the rest is set when it is TDX_OK
+    int B, C;
+    AxisMap ax, ay, az;
+    int fwd_kernel;      // TDX_RESIZE_PAIRS / TDX_RESIZE_GATHER
+    TileGrid fwd_tiles;  // of the output grid
+    int bwd_kernel, bwd_k;  // TDX_RESIZE_TILED with K = 2 / 4 / 6 / 12; TDX_RESIZE_GENERIC with K = 0
+    TileGrid bwd_tiles;     // of the input grid; zeros for the generic kernel
+    int span[3];            // axis_max_span of x, y, z
+};
+enum { RS_FWD = 1, RS_BWD = 2 };  // the halves of a plan
+static ResizePlan resize_plan(int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int C, int dtype, int halves = RS_FWD | RS_BWD) {
+    ResizePlan p = {};
+    p.status = !(B > 0 && Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0 && C > 0) ? TDX_EINVAL
+               : (C % 8 || C / 8 > 256)                                                        ? TDX_ESHAPE
+                                                                                               : dtype_status(dtype);
+    if (p.status != TDX_OK) return p;
+    p.B = B; p.C = C;
+    p.ax = make_axis(Xi, Xo); p.ay = make_axis(Yi, Yo); p.az = make_axis(Zi, Zo);
+    if (halves & RS_FWD) {
+        const TileGrid t = p.fwd_tiles = make_tiles(Xo, Yo, Zo, C, B);
+        // measured (tools/micro/resize_bench.py, B = 8): 64 channels 281 -> 256 us, 128 channels 65 -> 69 us: narrow rows only
+        const bool pairs = C <= 64 && !((t.tx | t.ty | t.tz) & 1) && Xo > Xi && Yo > Yi && Zo > Zi && pair_window_ok(p.ax) &&
+                           pair_window_ok(p.ay) && pair_window_ok(p.az);
+        p.fwd_kernel = pairs ? TDX_RESIZE_PAIRS : TDX_RESIZE_GATHER;
+    }
+    if (halves & RS_BWD) {
+        const int kx = p.span[0] = axis_max_span(p.ax), ky = p.span[1] = axis_max_span(p.ay), kz = p.span[2] = axis_max_span(p.az);
+        p.bwd_kernel = TDX_RESIZE_GENERIC;  // more than ~6x upsampling along an axis: general kernel
+        if (kx <= RS_KMAX && ky <= RS_KMAX && kz <= RS_KMAX) {
+            p.bwd_kernel = TDX_RESIZE_TILED;
+            p.bwd_k = kz <= 2 ? 2 : kz <= 4 ? 4 : kz <= 6 ? 6 : RS_KMAX;
+            p.bwd_tiles = make_tiles(Xi, Yi, Zi, C, B);
+        }
+    }
+    return p;
+}
+
+static dim3 tile_blocks(int B, const TileGrid& tg) { return dim3((unsigned)((int64_t)B * tg.nx * tg.ny * tg.nz)); }
+template <typename T>
+static void launch_fwd(const ResizePlan& p, const T* x, T* y, hipStream_t st) {
+    auto kernel = p.fwd_kernel == TDX_RESIZE_PAIRS ? resize_up_pairs_kernel<T> : resize_fwd_kernel<T>;
+    hipLaunchKernelGGL(kernel, tile_blocks(p.B, p.fwd_tiles), dim3(256), 0, st, x, y, p.ax, p.ay, p.az, p.C, p.fwd_tiles);
+}
+template <typename T>
+static void launch_bwd(const ResizePlan& p, const T* dy, const T* add, T* dx, hipStream_t st) {
+    if (p.bwd_kernel == TDX_RESIZE_GENERIC) {
+        const int64_t total = (int64_t)p.B * p.ax.in * p.ay.in * p.az.in * (p.C / 8);
+        hipLaunchKernelGGL((resize_bwd_generic_kernel<T>), dim3(ceil_div(total, 256)), dim3(256), 0, st, dy, add, dx, p.ax, p.ay, p.az,
+                           p.C, total);
+        return;
+    }
+    auto kernel = p.bwd_k == 2 ? resize_bwd_kernel<T, 2> : p.bwd_k == 4 ? resize_bwd_kernel<T, 4>
+                : p.bwd_k == 6 ? resize_bwd_kernel<T, 6> : resize_bwd_kernel<T, RS_KMAX>;
+    hipLaunchKernelGGL(kernel, tile_blocks(p.B, p.bwd_tiles), dim3(256), 0, st, dy, add, dx, p.ax, p.ay, p.az, p.C, p.bwd_tiles);
+}
+
+extern "C" int tdx_resize_fwd(const void* x, void* y, int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int C,
+                              int dtype, void* stream) {
+    TDX_CHECK_ARG(x && y);
+    const ResizePlan p = resize_plan(B, Xi, Yi, Zi, Xo, Yo, Zo, C, dtype, RS_FWD);
+    if (p.status != TDX_OK) return p.status;
+    TDX_DISPATCH_DTYPE(dtype, launch_fwd<T>(p, (const T*)x, (T*)y, as_stream(stream)));
+    return tdx_launch_status();
+}
 extern "C" int tdx_resize_bwd(const void* dy, const void* add, void* dx, int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int C,
                               int dtype, void* stream) {
-    TDX_CHECK_ARG(dy && dx && resize_args_ok(B, Xi, Yi, Zi, Xo, Yo, Zo, C));
-    if (C % 8 || C / 8 > 256) return TDX_ESHAPE;
-    const AxisMap ax = make_axis(Xi, Xo), ay = make_axis(Yi, Yo), az = make_axis(Zi, Zo);
-    const int kx = axis_max_span(ax), ky = axis_max_span(ay), kz = axis_max_span(az);
-    if (kx > RS_KMAX || ky > RS_KMAX || kz > RS_KMAX) {  // more than ~6x upsampling along an axis: general kernel
-        const int64_t total = (int64_t)B * Xi * Yi * Zi * (C / 8);
-        TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((resize_bwd_generic_kernel<T>), dim3(ceil_div(total, 256)), dim3(256), 0,
-                                                      as_stream(stream), (const T*)dy, (const T*)add, (T*)dx, ax, ay, az, C, total));
-        return tdx_launch_status();
-    }
-    const TileGrid tg = make_tiles(Xi, Yi, Zi, C, B);
-    const dim3 grid((unsigned)((int64_t)B * tg.nx * tg.ny * tg.nz));
-#define RS_BWD(KV)                                                                                                     \
-    TDX_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((resize_bwd_kernel<T, KV>), grid, dim3(256), 0, as_stream(stream),     \
-                                                  (const T*)dy, (const T*)add, (T*)dx, ax, ay, az, C, tg))
-    if (kz <= 2) RS_BWD(2);
-    else if (kz <= 4) RS_BWD(4);
-    else if (kz <= 6) RS_BWD(6);
-    else RS_BWD(RS_KMAX);
-#undef RS_BWD
+    TDX_CHECK_ARG(dy && dx);
+    const ResizePlan p = resize_plan(B, Xi, Yi, Zi, Xo, Yo, Zo, C, dtype, RS_BWD);
+    if (p.status != TDX_OK) return p.status;
+    TDX_DISPATCH_DTYPE(dtype, launch_bwd<T>(p, (const T*)dy, (const T*)add, (T*)dx, as_stream(stream)));
     return tdx_launch_status();
+}
+
+// the plan query (include/tdx.h): the whole plan as integers, nothing launched
+extern "C" int tdx_resize_plan(int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int C, int dtype, int* plan) {
+    TDX_CHECK_ARG(plan);
+    const ResizePlan p = resize_plan(B, Xi, Yi, Zi, Xo, Yo, Zo, C, dtype);
+    const TileGrid tiles[2] = {p.fwd_tiles, p.bwd_tiles};  // all zeros unless the status is TDX_OK (and the adjoint tiled)
+    const int first[2] = {TDX_RESIZE_PLAN_FWD_TX, TDX_RESIZE_PLAN_BWD_TX};
+    for (int h = 0; h < 2; ++h) {
+        const int v[6] = {tiles[h].tx, tiles[h].ty, tiles[h].tz, tiles[h].nx, tiles[h].ny, tiles[h].nz};
+        for (int i = 0; i < 6; ++i) plan[first[h] + i] = v[i];  // TX, TY, TZ, NX, NY, NZ are consecutive (include/tdx.h)
+    }
+    plan[TDX_RESIZE_PLAN_FWD_KERNEL] = p.fwd_kernel;
+    plan[TDX_RESIZE_PLAN_BWD_KERNEL] = p.bwd_kernel;
+    plan[TDX_RESIZE_PLAN_BWD_K] = p.bwd_k;
+    for (int a = 0; a < 3; ++a) plan[TDX_RESIZE_PLAN_SPAN_X + a] = p.span[a];
+    return p.status;
 }

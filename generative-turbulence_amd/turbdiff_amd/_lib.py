@@ -82,6 +82,7 @@ SIGNATURES = {
     "tdx_flow_decompose_bwd": (_i, [_vp] * 9 + [_i] * 8 + [_vp, _vp]),
     "tdx_resize_fwd": (_i, [_vp, _vp] + [_i] * 9 + [_vp]),
     "tdx_resize_bwd": (_i, [_vp, _vp, _vp] + [_i] * 9 + [_vp]),
+    "tdx_resize_plan": (_i, [_i] * 9 + [_vp]),
     "tdx_attn_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tdx_attn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "tdx_attn_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
@@ -517,6 +518,26 @@ def conv1_bwd_weight_plan(Cin, Cout, rows, transposed, dtype: int) -> dict:
     first -- ensure_scratch -- to ask about a call on this stream)."""
     fields = CONV1_PLAN_FIELDS[:2] + CONV1_PLAN_FIELDS[3:]
     return _conv1_plan("tdx_conv1_bwd_weight_plan", fields, Cin, Cout, rows, int(transposed), dtype)
+
+
+RESIZE_FWD_KERNELS = ("gather", "pairs")  # TDX_RESIZE_GATHER, TDX_RESIZE_PAIRS
+RESIZE_BWD_KERNELS = ("tiled", "generic")  # TDX_RESIZE_TILED, TDX_RESIZE_GENERIC
+RESIZE_PLAN_INTS = 18  # TDX_RESIZE_PLAN_INTS
+RESIZE_PLAN_FIELDS = ("fwd_kernel", "fwd_tx", "fwd_ty", "fwd_tz", "fwd_nx", "fwd_ny", "fwd_nz", "bwd_kernel", "bwd_k", "bwd_tx",
+                      "bwd_ty", "bwd_tz", "bwd_nx", "bwd_ny", "bwd_nz", "span_x", "span_y", "span_z")  # TDX_RESIZE_PLAN_*
+
+
+def resize_plan(B, C, src, dst, dtype: int) -> dict:
+    """What tdx_resize_fwd and tdx_resize_bwd would launch for x (B, *src, C) -> y (B, *dst, C), as the library's own host
+    function plans both: {"status": the code those calls would return, "fwd_kernel": a name of RESIZE_FWD_KERNELS,
+    "bwd_kernel": a name of RESIZE_BWD_KERNELS, and the other RESIZE_PLAN_FIELDS}.  Launches nothing."""
+    buf = (_i * RESIZE_PLAN_INTS)()  # `C` is the channel count here, not ctypes
+    status = int(load().tdx_resize_plan(B, *src, *dst, C, dtype, buf))
+    plan = {k: int(buf[i]) for i, k in enumerate(RESIZE_PLAN_FIELDS)}
+    plan["fwd_kernel"] = RESIZE_FWD_KERNELS[plan["fwd_kernel"]]
+    plan["bwd_kernel"] = RESIZE_BWD_KERNELS[plan["bwd_kernel"]]
+    plan["status"] = status
+    return plan
 
 
 def conv3_fwd_meta(C1, C2, Cout, B, X, Y, Z, dt, real=None):

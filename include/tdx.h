@@ -445,6 +445,39 @@ int tdx_resize_fwd(const void* x, void* y, int B, int Xi, int Yi, int Zi, int Xo
  * separate three-pass add. */
 int tdx_resize_bwd(const void* dy, const void* add, void* dx, int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int C,
                    int dtype, void* stream);
+/* What tdx_resize_fwd and tdx_resize_bwd launch for these arguments, from the host function that plans both.  Nothing is
+ * launched.  Returns the status those calls would return (plan == NULL: TDX_EINVAL) and fills plan[0 .. TDX_RESIZE_PLAN_INTS)
+ * (zeros unless the status is TDX_OK):
+ *   FWD_KERNEL           TDX_RESIZE_PAIRS (2 x 2 x 2 outputs per lane) or TDX_RESIZE_GATHER (one output per lane)
+ *   FWD_TX/TY/TZ         the forward's tile of the output grid;  FWD_NX/NY/NZ  tiles per axis
+ *   BWD_KERNEL, BWD_K    TDX_RESIZE_TILED and its compile-time number of z candidates (2, 4, 6 or 12), or
+ *                        TDX_RESIZE_GENERIC (any resampling factor) and 0
+ *   BWD_TX/TY/TZ         the adjoint's tile of the input grid;  BWD_NX/NY/NZ  tiles per axis (all 0 for TDX_RESIZE_GENERIC)
+ *   SPAN_X/Y/Z           the largest number of outputs that read one input along each axis */
+#define TDX_RESIZE_GATHER 0
+#define TDX_RESIZE_PAIRS 1
+#define TDX_RESIZE_TILED 0
+#define TDX_RESIZE_GENERIC 1
+#define TDX_RESIZE_PLAN_FWD_KERNEL 0
+#define TDX_RESIZE_PLAN_FWD_TX 1
+#define TDX_RESIZE_PLAN_FWD_TY 2
+#define TDX_RESIZE_PLAN_FWD_TZ 3
+#define TDX_RESIZE_PLAN_FWD_NX 4
+#define TDX_RESIZE_PLAN_FWD_NY 5
+#define TDX_RESIZE_PLAN_FWD_NZ 6
+#define TDX_RESIZE_PLAN_BWD_KERNEL 7
+#define TDX_RESIZE_PLAN_BWD_K 8
+#define TDX_RESIZE_PLAN_BWD_TX 9
+#define TDX_RESIZE_PLAN_BWD_TY 10
+#define TDX_RESIZE_PLAN_BWD_TZ 11
+#define TDX_RESIZE_PLAN_BWD_NX 12
+#define TDX_RESIZE_PLAN_BWD_NY 13
+#define TDX_RESIZE_PLAN_BWD_NZ 14
+#define TDX_RESIZE_PLAN_SPAN_X 15
+#define TDX_RESIZE_PLAN_SPAN_Y 16
+#define TDX_RESIZE_PLAN_SPAN_Z 17
+#define TDX_RESIZE_PLAN_INTS 18
+int tdx_resize_plan(int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int C, int dtype, int* plan);
 
 /* ------------------------------------------------------------------ attention ---------- */
 /* F.scaled_dot_product_attention on the to_qkv output (attention.py:9-15, ddpm.py:295-308).

@@ -1,13 +1,16 @@
 """The host routing of csrc/tdx_resize.hip restated in Python, and the table of shapes that tests/test_resize_reference.py runs.
 
-`route(B, C, src, dst)` repeats what tdx_resize_fwd / tdx_resize_bwd decide before they launch: make_axis, axis_taps,
-pair_taps / pair_window_ok, axis_range, axis_weight, axis_span / axis_max_span, make_tiles and the choice of K.  The arithmetic
-is float32 through numpy scalars and arrays, operation for operation as in the C code (one float32 division for the scale, one
-float32 product for the source index, truncation, the clamped second tap).  It is a pure function; no GPU, no library.
+`route(B, C, src, dst)` repeats what resize_plan decides for tdx_resize_fwd / tdx_resize_bwd before they launch: make_axis,
+axis_taps, pair_taps / pair_window_ok, axis_range, axis_weight, axis_span / axis_max_span, make_tiles and the choice of K.  The
+arithmetic is float32 through numpy scalars and arrays, operation for operation as in the C code (one float32 division for the
+scale, one float32 product for the source index, truncation, the clamped second tap).  It is a pure function; no GPU, no
+library: the independent model the error bounds of resize_reference.py are derived from.
 
-Every row of CASES names the route it was written for.  test_resize_reference.py holds each row against `route` without a GPU,
-and every GPU test asserts the row's route again before it calls the library: a later change of the routing makes the row fail
-instead of quietly testing another kernel.
+The library is held against it by a test: test_resize_reference.py requires the library's plan query (tdx_resize_plan, which
+calls the same resize_plan as the two entries) to equal `route` / `make_tiles` on every row of CASES, every shape of EARLIER and
+300 generated shapes, without a GPU.  Every row of CASES names the route it was written for; the same module holds each row
+against `route`, and every GPU test asserts the row's route and the library's plan again before it calls the library: a later
+change of the routing, here or in the library, makes the row fail instead of quietly testing another kernel.
 """
 
 from collections import namedtuple

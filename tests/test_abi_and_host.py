@@ -68,6 +68,14 @@ def test_header_symbols_are_bound_and_exported():
     assert {"tdx_conv1_fwd_plan", "tdx_conv1_bwd_weight_plan"} <= set(syms)
     assert protos["tdx_conv1_fwd_plan"] == ("int", ["int"] * 8 + ["ptr"])
     assert protos["tdx_conv1_bwd_weight_plan"] == ("int", ["int", "int", "int64_t", "int", "int", "ptr"])
+    assert protos["tdx_resize_plan"] == ("int", ["int"] * 9 + ["ptr"])
+    # the plan arrays' named indices: the Python field tuples follow the header's numbering
+    text = (ROOT / "include" / "tdx.h").read_text()
+    index = {n.lower(): int(v) for n, v in re.findall(r"^#define TDX_RESIZE_PLAN_(\w+) (\d+)$", text, flags=re.M)}
+    assert index.pop("ints") == _lib.RESIZE_PLAN_INTS == len(_lib.RESIZE_PLAN_FIELDS)
+    assert index == {k: i for i, k in enumerate(_lib.RESIZE_PLAN_FIELDS)}
+    kernels = {n.lower(): int(v) for n, v in re.findall(r"^#define TDX_RESIZE_(GATHER|PAIRS|TILED|GENERIC) (\d+)$", text, flags=re.M)}
+    assert [kernels[k] for k in _lib.RESIZE_FWD_KERNELS + _lib.RESIZE_BWD_KERNELS] == [0, 1, 0, 1]
 
 
 def test_product_refuses_cpu_tensors():

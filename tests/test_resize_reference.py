@@ -5,7 +5,9 @@ element is held to the bound derived in the docstring of resize_reference.py.  N
 element is left out of a comparison.
 
 Without a GPU: the reference against float64 F.interpolate and its autograd, the adjoint identity, the exactness preconditions
-of every dyadic row, the route of every row and what the table reaches as a whole, and E_a against the float32 taps.
+of every dyadic row, the route of every row and what the table reaches as a whole, E_a against the float32 taps, and the
+restated routing against the library's own plan query (tdx_resize_plan) on every row, the earlier tests' shapes and 300
+generated ones.
 """
 
 from fractions import Fraction
@@ -127,6 +129,81 @@ def test_error_matrices_cover_the_float32_taps(case):
         assert E.max().item() <= 2.0 * R.U * max(i - 1, 0) * (1.0 + R.U)  # and E is no more than delta
 
 
+# ------------------------------------------------------------------------ the library's own answers (no GPU: nothing launches)
+
+CODES = {"f32": 0, "bf16": 1, "f16": 3}  # TDX_F32, TDX_BF16, TDX_F16
+EINVAL, ESHAPE, EDTYPE = -1, -2, -3  # TDX_EINVAL, TDX_ESHAPE, TDX_EDTYPE
+
+
+def _ask(B, C, src, dst, dname):
+    """tdx_resize_plan answers what resize_cases.route restates: both kernels, their tiles and tile counts, K, the spans"""
+    from turbdiff_amd import _lib as L
+
+    q = L.resize_plan(B, C, src, dst, CODES[dname])
+    r = cases.route(B, C, src, dst)
+    what = (B, C, src, dst, dname, q)
+    grid = lambda h: (tuple(q[f"{h}_t{a}"] for a in "xyz"), tuple(q[f"{h}_n{a}"] for a in "xyz"))
+    assert q["status"] == 0, what
+    assert (q["fwd_kernel"], *grid("fwd")) == (r.fwd, r.fwd_tiles.tile, r.fwd_tiles.count), what
+    if r.bwd == cases.GENERIC:
+        assert (q["bwd_kernel"], q["bwd_k"], *grid("bwd")) == ("generic", 0, (0, 0, 0), (0, 0, 0)), what
+    else:
+        assert (q["bwd_kernel"], q["bwd_k"], *grid("bwd")) == ("tiled", r.bwd, r.bwd_tiles.tile, r.bwd_tiles.count), what
+    assert tuple(q[f"span_{a}"] for a in "xyz") == r.spans, what
+    return r
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_library_plans_every_row_as_restated(case):
+    for dname in DTYPES:  # the format moves nothing
+        r = _ask(case.B, case.C, case.src, case.dst, dname)
+        assert (r.fwd, r.fwd_tiles.tile, r.bwd, None if r.bwd_tiles is None else r.bwd_tiles.tile, r.spans) == cases.expected(case)
+
+
+def _generated(n=300, seed=30):
+    """(B, C, src, dst): extents 1..40, every width class of make_tiles, B = 64 for every tenth so that the ~1024-workgroup
+    rule of make_tiles is met from both sides"""
+    g = torch.Generator().manual_seed(seed)
+    draw = lambda hi, k=1: [int(v) for v in torch.randint(0, hi, (k,), generator=g)]
+    widths = (8, 16, 24, 64, 128, 512)
+    return [(64 if i % 10 == 9 else 1 + draw(2)[0], widths[draw(6)[0]], tuple(1 + v for v in draw(40, 3)), tuple(1 + v for v in draw(40, 3)))
+            for i in range(n)]
+
+
+def test_library_plans_earlier_and_generated_shapes_as_restated():
+    shapes = _generated()
+    assert len(shapes) == 300
+    routes = [_ask(*s, ("f32", "bf16", "f16")[i % 3]) for i, s in enumerate(cases.EARLIER + shapes)][len(cases.EARLIER):]
+    assert {r.fwd for r in routes} == {cases.PAIRS, cases.GATHER}
+    assert {r.bwd for r in routes} == {2, 4, 6, 12, cases.GENERIC}
+    # tiles that the workgroup rule shrank, and tiles it left alone although the tensor is wide enough to have a choice
+    shrunk = [cases.make_tiles(*dst, C, B)[0] != cases.make_tiles(*dst, C, 0)[0] for B, C, _, dst in shapes]
+    assert any(shrunk) and any(not s and B == 64 and C <= 64 for s, (B, C, _, _) in zip(shrunk, shapes))
+
+
+def test_library_plan_statuses():
+    import ctypes
+
+    from turbdiff_amd import _lib as L
+
+    status = lambda B, C, src, dst, code=L.BF16: L.resize_plan(B, C, src, dst, code)["status"]
+    assert status(1, 8, (3, 3, 3), (5, 5, 5)) == 0
+    assert status(1, 12, (3, 3, 3), (5, 5, 5)) == ESHAPE and status(1, 8 * 257, (3, 3, 3), (5, 5, 5)) == ESHAPE
+    assert status(1, 8 * 256, (3, 3, 3), (5, 5, 5)) == 0
+    for bad in ((0, 8, (3, 3, 3), (5, 5, 5)), (1, 8, (3, 0, 3), (5, 5, 5)), (1, 8, (3, 3, 3), (5, 5, 0)), (1, 0, (3, 3, 3), (5, 5, 5)),
+                (1, 12, (3, 3, 3), (0, 5, 5))):  # the last: a bad extent comes before a bad width
+        assert status(*bad) == EINVAL
+    assert L.load().tdx_resize_plan(1, 3, 3, 3, 5, 5, 5, 8, L.BF16, None) == EINVAL
+    # a code that is no tensor format (2: TDX_F32_SPLIT, a pack code): what tdx_resize_fwd / _bwd return for it, before any launch
+    x, y = (ctypes.c_float * 8)(), (ctypes.c_float * 8)()
+    at = lambda buf: ctypes.cast(buf, ctypes.c_void_p)
+    assert L.load().tdx_resize_fwd(at(x), at(y), 1, 1, 1, 1, 1, 1, 1, 8, 2, None) == EDTYPE
+    assert L.load().tdx_resize_bwd(at(y), None, at(x), 1, 1, 1, 1, 1, 1, 1, 8, 2, None) == EDTYPE
+    assert status(1, 8, (1, 1, 1), (1, 1, 1), 2) == EDTYPE and status(1, 12, (1, 1, 1), (1, 1, 1), 2) == ESHAPE
+    plan = L.resize_plan(1, 12, (3, 3, 3), (5, 5, 5), L.BF16)
+    assert all(v == 0 for k, v in plan.items() if k not in ("status", "fwd_kernel", "bwd_kernel"))  # an error leaves zeros
+
+
 # ---------------------------------------------------------------------------------------------------------------- on the GPU
 
 
@@ -137,6 +214,8 @@ def _dev():
 def _assert_route(case):
     _, got = cases.routed(case)
     assert got == cases.expected(case), f"{cases.case_id(case)} no longer takes its route: {got}"
+    for dname in case.dtypes:  # and the library names the row's kernels and tiles itself
+        _ask(case.B, case.C, case.src, case.dst, dname)
 
 
 def _where(t, flat):

@@ -1,4 +1,4 @@
-"""time tdx_resize_fwd on the U-Net's up-sampling shapes (TDX_RESIZE_PAIRS=0: one output per lane)"""
+"""time tdx_resize_fwd on the U-Net's up-sampling shapes, bf16 (TDX_LIB=<another build's libtdx_hip.so> for an A/B run)"""
 import sys, os, torch
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "..", "generative-turbulence_amd"))
 from turbdiff_amd import ops

@@ -1,4 +1,5 @@
-"""time tdx_resize_bwd (adjoint of the up path's trilinear up-sampling) on the U-Net's shapes; TDX_RESIZE_BWD_TILES=0: eight-pass tiles"""
+"""time tdx_resize_bwd (adjoint of the up path's trilinear up-sampling) on the U-Net's shapes, bf16 (TDX_LIB=<another build's
+libtdx_hip.so> for an A/B run)"""
 import sys, os, torch
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "..", "generative-turbulence_amd"))
 from turbdiff_amd import _lib as L
