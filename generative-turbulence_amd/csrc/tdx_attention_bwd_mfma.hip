@@ -25,17 +25,14 @@
 //
 // 6 + 8 MFMAs per 32 x 32 tile against the forward's 4; no atomics, no running maximum.
 #include "tdx_attention.h"
-#include "tdx_runtime.h"
 #include <type_traits>
-#include <stdlib.h>
 
-#define FB_RB 256          // resident rows per workgroup
 // TW = resident 32-row tiles per wave: 2 (the default: 4 waves per workgroup, 2 waves per SIMD, ~250 / 230 registers) or 1
 // (round 6 experiment: 8 waves per workgroup, 3-4 waves per SIMD at <= 168 / 128 registers, as the forward kernel since round 5).
 // The ablations (profiles/r13_attention_bwd_ablation.txt) put 2.4 of the 11.5 ms in vector-ALU work next to a 9.1-ms floor of
 // the 14 MFMAs per tile pair; more waves per SIMD do not hide it (10.99-12.3 ms): kept as an A/B knob (TDX_ATTN_BWD_TW).
 // The walked side is staged in tiles of FB_T(TW) rows, one 16-B piece per thread.
-#define FB_WAVES(TW) (FB_RB / (32 * (TW)))
+// (FB_RB = 256 resident rows per workgroup and FB_WAVES(TW) = its waves: tdx_attention.h, the plan's grid needs them)
 // waves per SIMD the one-tile-per-wave kernels are compiled for (HIP: the second __launch_bounds__ argument is waves per
 // execution unit): 4 = at most 128 registers, 3 = at most 168
 #ifndef FB_MINW_DQ
@@ -74,9 +71,8 @@ attn_bwd_dq_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E:
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hh = lane >> 5;
-    const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
-    const int ld = 3 * H * FA_D;
-    const typename E::T* base = qkv + (int64_t)b * N * ld;
+    const AttnHead<FA_D> hd(blockIdx.y, N, H);
+    const typename E::T* base = hd.batch(qkv);
     const int q0 = blockIdx.x * FB_RB + wave * RW;
     const float sm_scale = rsqrtf((float)FA_D);
 
@@ -91,10 +87,10 @@ attn_bwd_dq_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E:
         const int q = min(q0 + qt * 32 + r, N - 1);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            qf[qt][ks] = row_frag<E>(base + (int64_t)q * ld + h * FA_D + ks * 16 + hh * 8, FB_LOG2E * sm_scale);
-            gf[qt][ks] = row_frag<E>(dout + ((int64_t)b * N + q) * (H * FA_D) + h * FA_D + ks * 16 + hh * 8, 1.0f);
+            qf[qt][ks] = row_frag<E>(hd.q(base, q) + ks * 16 + hh * 8, FB_LOG2E * sm_scale);
+            gf[qt][ks] = row_frag<E>(hd.out_row(dout, q) + ks * 16 + hh * 8, 1.0f);
         }
-        const float ml = -lse[((int64_t)b * H + h) * N + q] * FB_LOG2E, md = -delta[((int64_t)b * H + h) * N + q];
+        const float ml = -lse[hd.stat(q)] * FB_LOG2E, md = -delta[hd.stat(q)];
 #pragma unroll
         for (int i = 0; i < 16; ++i) { dq[qt][i] = 0.f; nl[qt][i] = ml; nd[qt][i] = md; }
     }
@@ -103,7 +99,8 @@ attn_bwd_dq_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E:
     uint4 kreg, vreg;
     auto load_tile = [&](int k0) {
         const int key = min(k0 + st_row, N - 1);
-        const typename E::T* kp = base + (int64_t)key * ld + H * FA_D + h * FA_D + st_c * 8;
+        // (hd.k(base, key), written out: through the helper the two-tile instances schedule their prologue differently)
+        const typename E::T* kp = base + (int64_t)key * hd.ld + H * FA_D + hd.h * FA_D + st_c * 8;
         kreg = *reinterpret_cast<const uint4*>(kp);
         vreg = *reinterpret_cast<const uint4*>(kp + H * FA_D);
     };
@@ -124,14 +121,12 @@ attn_bwd_dq_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E:
             bf16x8 kf[2], vf[2], ktf[2];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                kf[ks] = *reinterpret_cast<const bf16x8*>(sK + sw64(kb * 32 + r, 2 * ks + hh));
-                vf[ks] = *reinterpret_cast<const bf16x8*>(sV + sw64(kb * 32 + r, 2 * ks + hh));
+                kf[ks] = attn_row_frag(sK, kb, r, ks, hh);
+                vf[ks] = attn_row_frag(sV, kb, r, ks, hh);
             }
 #pragma unroll
-            for (int s = 0; s < 2; ++s) {  // K^T: rows = d, k = key 16 s + 8 (j >> 2) + 4 hh + (j & 3)
-                const unsigned char* kp = sKp + (kb * 32 + 16 * s + 4 * (g >> 1) + tq) * 64 + t_col;
-                ktf[s] = (FB_ABL & 16) ? kf[s] : tr_frag(kp, kp + 8 * 64);
-            }
+            for (int s = 0; s < 2; ++s)  // K^T: rows = d, k = key 16 s + 8 (j >> 2) + 4 hh + (j & 3)
+                ktf[s] = (FB_ABL & 16) ? kf[s] : attn_tr_frag(sKp, kb, s, g, tq, t_col);
 #pragma unroll
             for (int qt = 0; qt < TW; ++qt) {
                 f32x16 st = E::mfma(kf[0], qf[qt][0], nl[qt]);   // S^T - lse
@@ -165,7 +160,7 @@ attn_bwd_dq_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E:
     for (int qt = 0; qt < TW; ++qt) {
         const int q = q0 + qt * 32 + r;
         if (q < N) {
-            typename E::T* op = dqkv + ((int64_t)b * N + q) * ld + h * FA_D;
+            typename E::T* op = hd.dq(dqkv, q);
 #pragma unroll
             for (int j = 0; j < 4; ++j) attn_store_row_piece<E>(op, dq[qt], j, sm_scale, hh);
         }
@@ -188,9 +183,8 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hh = lane >> 5;
-    const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
-    const int ld = 3 * H * FA_D;
-    const typename E::T* base = qkv + (int64_t)b * N * ld;
+    const AttnHead<FA_D> hd(blockIdx.y, N, H);
+    const typename E::T* base = hd.batch(qkv);
     const int j0 = blockIdx.x * FB_RB + wave * RW;
     const float qscale = FB_LOG2E * rsqrtf((float)FA_D);
     const float dk_scale = 0.6931471805599453f;  // ln 2 = (1/sqrt(D)) / (log2(e)/sqrt(D)): the staged Q carries the rest
@@ -202,8 +196,8 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
         const int key = min(j0 + kt * 32 + r, N - 1);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            kf[kt][ks] = row_frag<E>(base + (int64_t)key * ld + H * FA_D + h * FA_D + ks * 16 + hh * 8, 1.0f);
-            vf[kt][ks] = row_frag<E>(base + (int64_t)key * ld + 2 * H * FA_D + h * FA_D + ks * 16 + hh * 8, 1.0f);
+            kf[kt][ks] = row_frag<E>(hd.k(base, key) + ks * 16 + hh * 8, 1.0f);
+            vf[kt][ks] = row_frag<E>(hd.v(base, key) + ks * 16 + hh * 8, 1.0f);
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) dk[kt][i] = dv[kt][i] = 0.f;
@@ -214,12 +208,12 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
     float lreg = 0.f, dreg = 0.f;
     auto load_tile = [&](int i0) {
         const int q = min(i0 + st_row, N - 1);
-        qreg = *reinterpret_cast<const uint4*>(base + (int64_t)q * ld + h * FA_D + st_c * 8);
-        greg = *reinterpret_cast<const uint4*>(dout + ((int64_t)b * N + q) * (H * FA_D) + h * FA_D + st_c * 8);
+        qreg = *reinterpret_cast<const uint4*>(hd.q(base, q) + st_c * 8);
+        greg = *reinterpret_cast<const uint4*>(hd.out_row(dout, q) + st_c * 8);
         if (tid < T) {
             const int qq = i0 + tid;
-            lreg = qq < N ? -lse[((int64_t)b * H + h) * N + qq] * FB_LOG2E : -INFINITY;  // exp2(s - inf) = 0: no query there
-            dreg = qq < N ? -delta[((int64_t)b * H + h) * N + qq] : 0.f;
+            lreg = qq < N ? -lse[hd.stat(qq)] * FB_LOG2E : -INFINITY;  // exp2(s - inf) = 0: no query there
+            dreg = qq < N ? -delta[hd.stat(qq)] : 0.f;
         }
     };
     const int g = lane >> 4, i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;
@@ -244,12 +238,12 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
             bf16x8 qa[2], ga[2], qtf[2], gtf[2];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {  // A operands: row = query r, k = d
-                qa[ks] = *reinterpret_cast<const bf16x8*>(sQ + sw64(qb * 32 + r, 2 * ks + hh));
-                ga[ks] = *reinterpret_cast<const bf16x8*>(sG + sw64(qb * 32 + r, 2 * ks + hh));
+                qa[ks] = attn_row_frag(sQ, qb, r, ks, hh);
+                ga[ks] = attn_row_frag(sG, qb, r, ks, hh);
             }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {  // Q^T, dO^T: rows = d, k = query 16 s + 8 (j >> 2) + 4 hh + (j & 3)
-                const int off = (qb * 32 + 16 * s + 4 * (g >> 1) + tq) * 64 + t_col;
+                const int off = (qb * 32 + 16 * s + 4 * (g >> 1) + tq) * 64 + t_col;  // (attn_tr_frag's address, once for two tiles)
                 qtf[s] = (FB_ABL & 16) ? qa[s] : tr_frag(sQp + off, sQp + off + 8 * 64);
                 gtf[s] = (FB_ABL & 16) ? ga[s] : tr_frag(sGp + off, sGp + off + 8 * 64);
             }
@@ -292,7 +286,7 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
     for (int kt = 0; kt < TW; ++kt) {
         const int key = j0 + kt * 32 + r;
         if (key < N) {
-            typename E::T* okp = dqkv + ((int64_t)b * N + key) * ld + H * FA_D + h * FA_D;
+            typename E::T* okp = hd.dk(dqkv, key);
             typename E::T* ovp = okp + H * FA_D;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -303,26 +297,28 @@ attn_bwd_dkv_mfma_kernel(const typename E::T* __restrict__ qkv, const typename E
     }
 }
 
-int attn_bwd_mfma_launch(const void* qkv, const void* dout, const float* lse, const float* delta, void* dqkv, int B, int N,
-                         int H, int dtype, hipStream_t st) {
-    dim3 grid(ceil_div(N, FB_RB), B * H);
-    // TDX_ATTN_BWD_TW (A/B knob): tiles per wave of the dQ / dK-dV kernel, "<dq><dkv>", e.g. 21.  Default 22
-    // (two tiles per wave, two waves per SIMD): one tile per wave at three or four waves per SIMD measured 10.99-12.3 ms
-    // against 11.4-11.5 (profiles/r13_attention_bwd_ablation.txt) -- more waves do not hide the vector work either
-    const int tw = tdx_switch(SW_ATTN_BWD_TW);
-    const int twq = tw / 10, twk = tw % 10;
-#define FB_GO(E, T)                                                                                                            \
-    do {                                                                                                                       \
-        if (twq == 2) hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<E, 2>), grid, dim3(64 * FB_WAVES(2)), 0, st, (const T*)qkv,   \
-                                         (const T*)dout, lse, delta, (T*)dqkv, N, H);                                          \
-        else hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<E, 1>), grid, dim3(64 * FB_WAVES(1)), 0, st, (const T*)qkv,            \
-                                (const T*)dout, lse, delta, (T*)dqkv, N, H);                                                   \
-        if (twk == 2) hipLaunchKernelGGL((attn_bwd_dkv_mfma_kernel<E, 2>), grid, dim3(64 * FB_WAVES(2)), 0, st, (const T*)qkv,  \
-                                         (const T*)dout, lse, delta, (T*)dqkv, N, H);                                          \
-        else hipLaunchKernelGGL((attn_bwd_dkv_mfma_kernel<E, 1>), grid, dim3(64 * FB_WAVES(1)), 0, st, (const T*)qkv,           \
-                                (const T*)dout, lse, delta, (T*)dqkv, N, H);                                                   \
-    } while (0)
-    if (dtype == TDX_F16) FB_GO(AttnF16, f16); else FB_GO(AttnBf16, bf16);
-#undef FB_GO
+// the plan's instance (tiles per wave) of each of the two kernels on the plan's grid
+template <typename E, int TWQ, int TWK>
+static int attn_bwd_mfma_go(const AttnBwdCall& c, const AttnPlan& p) {
+    using T = typename E::T;
+    const dim3 grid(p.bwd_gx, p.bwd_gy);
+    hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<E, TWQ>), grid, dim3(64 * FB_WAVES(TWQ)), 0, c.st, (const T*)c.qkv,
+                       (const T*)c.dout, c.lse, c.delta, (T*)c.dqkv, c.N, c.H);
+    hipLaunchKernelGGL((attn_bwd_dkv_mfma_kernel<E, TWK>), grid, dim3(64 * FB_WAVES(TWK)), 0, c.st, (const T*)c.qkv,
+                       (const T*)c.dout, c.lse, c.delta, (T*)c.dqkv, c.N, c.H);
     return tdx_launch_status();
+}
+
+int attn_bwd_mfma_launch(const AttnBwdCall& c, const AttnPlan& p) {
+    if (p.bwd != TDX_ATTN_MFMA) return TDX_EINVAL;
+    return attn_h16_dispatch(c.dtype, [&](auto e) {
+        using E = decltype(e);
+        switch (10 * p.twq + p.twk) {
+            case 11: return attn_bwd_mfma_go<E, 1, 1>(c, p);
+            case 12: return attn_bwd_mfma_go<E, 1, 2>(c, p);
+            case 21: return attn_bwd_mfma_go<E, 2, 1>(c, p);
+            case 22: return attn_bwd_mfma_go<E, 2, 2>(c, p);
+        }
+        return (int)TDX_EINVAL;
+    });
 }

@@ -22,13 +22,6 @@
 // matrix cores: 4 MFMAs (128 pipe cycles) per 32x32 tile against 16 quarter-rate v_exp_f32 (256
 // cycles) + ~60 plain VALU instructions (v_max3, packed f32 sub / sum, packed bf16 conversion).
 #include "tdx_attention.h"
-#include "tdx_runtime.h"
-#include <type_traits>
-
-#define FA_KT 64          // keys per staged tile
-#define FA_QW 32          // queries per wave (one 32-query tile: <= 128 registers, four waves per SIMD)
-#define FA_THREADS 512    // 8 waves
-#define FA_QB (8 * FA_QW) // queries per workgroup
 
 // ---------------------------------------------------------------------------------------------------------------
 // Forward kernel, round 5.  What bound the round-3 kernel (0.21 of the matrix peak at N = 73 728): per 32 x 32 score tile
@@ -64,7 +57,6 @@ struct AttnSkArgs {
     float* part;               // [nwg][2 slots][FA_QB][34] f32 partials (O[32], m, l), or nullptr when chunk == ntile
     const float* kmax2;        // [B * H] max_k |k|^2 of each head's keys (attn_kmax_kernel), or nullptr: always check
 };
-#define FA_PART_STRIDE (FA_QB * 34)
 
 template <typename E>
 __global__ void __launch_bounds__(FA_THREADS, 4)
@@ -77,7 +69,6 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hh = lane >> 5;
     const int N = a.N, H = a.H;
-    const int ld = 3 * H * FA_D;
     // XCD x (= hardware workgroup id mod 8) owns the x-th contiguous eighth of the iteration space
     int w = blockIdx.x;
     if ((a.nwg & 7) == 0) w = (w & 7) * (a.nwg >> 3) + (w >> 3);
@@ -100,8 +91,8 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
         const int t0 = (int)(it - (long long)blk * a.ntile);
         const int t1 = (int)((long long)a.ntile - t0 <= it_end - it ? a.ntile : t0 + (it_end - it));
         const int bh = blk / a.nqb, qb = blk - bh * a.nqb;
-        const int b = bh / H, h = bh - b * H;
-        const T* base = qkv + (int64_t)b * N * ld;
+        const AttnHead<FA_D> hd(bh, N, H);
+        const T* base = hd.batch(qkv);
         const int q0 = qb * FA_QB + wave * FA_QW;
 
         // ---- Q fragments (B operand: col = query r, k = d), pre-scaled by log2(e)/sqrt(D)
@@ -109,7 +100,7 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
         {
             const int q = min(q0 + r, N - 1);
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) qf[ks] = row_frag<E>(base + (int64_t)q * ld + h * FA_D + ks * 16 + hh * 8, qscale);
+            for (int ks = 0; ks < 2; ++ks) qf[ks] = row_frag<E>(hd.q(base, q) + ks * 16 + hh * 8, qscale);
         }
         // |q|^2 of the lane's (rounded, pre-scaled) query: 16 of its 32 components here, the rest in lane ^ 32
         float bound = INFINITY;  // upper bound of every score of this query against this head's keys (log2 units)
@@ -139,7 +130,7 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
         uint4 sreg;
         auto load_tile = [&](int k0) {
             const int key = min(k0 + st_key, N - 1);
-            sreg = *reinterpret_cast<const uint4*>(base + (int64_t)key * ld + (1 + st_v) * H * FA_D + h * FA_D + st_c * 8);
+            sreg = *reinterpret_cast<const uint4*>(hd.kv(base, key, st_v) + st_c * 8);
         };
         auto stage = [&](int t) {  // tile t: registers -> LDS, next tile's loads in flight
             __syncthreads();
@@ -183,13 +174,9 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
         };
         auto frags = [&](int kb, bf16x8 (&kf)[2], bf16x8 (&vf)[2]) {
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-                kf[ks] = *reinterpret_cast<const bf16x8*>(sK + sw64(kb * 32 + r, 2 * ks + hh));
+            for (int ks = 0; ks < 2; ++ks) kf[ks] = attn_row_frag(sK, kb, r, ks, hh);
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const unsigned char* vp = sV + (kb * 32 + 16 * s2 + 4 * (g >> 1) + tq) * 64 + v_col;
-                vf[s2] = tr_frag(vp, vp + 8 * 64);
-            }
+            for (int s2 = 0; s2 < 2; ++s2) vf[s2] = attn_tr_frag(sV, kb, s2, g, tq, v_col);
         };
         auto accumulate = [&](f32x16& st, const bf16x8 (&vf)[2]) {  // P = 2^st; O^T += V^T P^T; l += sum P
 #pragma unroll
@@ -214,7 +201,7 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
             for (int i = 0; i < 16; ++i) s0[i] = 0.f;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                s0 = E::mfma(*reinterpret_cast<const bf16x8*>(sK + sw64(r, 2 * ks + hh)), qf[ks], s0);
+                s0 = E::mfma(attn_row_frag(sK, 0, r, ks, hh), qf[ks], s0);
             if (t0 * FA_KT + 32 > N) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i)
@@ -292,10 +279,10 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
         if (t0 == 0 && t1 == a.ntile) {  // the whole key range: final result
             if (q < N) {
                 const float inv = 1.0f / lq;
-                T* op = out + ((int64_t)b * N + q) * (H * FA_D) + h * FA_D;
+                T* op = hd.out_row(out, q);
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) attn_store_row_piece<E>(op, o, jj, inv, hh);
-                if (hh == 0) lse[((int64_t)b * H + h) * N + q] = (m + log2f(lq)) * 0.6931471805599453f;
+                if (hh == 0) lse[hd.stat(q)] = (m + log2f(lq)) * 0.6931471805599453f;
             }
         } else {
             // part of the key range: (O, m, l) relative to this segment's m; slot 0 = the block began in an earlier
@@ -317,13 +304,13 @@ attn_fwd_mfma_kernel(const typename E::T* __restrict__ qkv, typename E::T* __res
 template <typename T>
 __global__ void __launch_bounds__(256)
 attn_kmax_kernel(const T* __restrict__ qkv, float* __restrict__ kmax2, int N, int H) {
-    const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
-    const int ld = 3 * H * FA_D;
-    const T* base = qkv + (int64_t)b * N * ld + H * FA_D + h * FA_D;
+    const int bh = blockIdx.y;
+    const AttnHead<FA_D> hd(bh, N, H);
+    const T* base = hd.k(hd.batch(qkv), 0);  // the head's first key
     float mx = 0.f;
     for (int key = blockIdx.x * 64 + (threadIdx.x >> 2); key < N; key += gridDim.x * 64) {
         Vec8<T> v;
-        v.load(base + (int64_t)key * ld + (threadIdx.x & 3) * 8);
+        v.load(base + (int64_t)key * hd.ld + (threadIdx.x & 3) * 8);
         float s2 = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) s2 = __builtin_fmaf(v.v[e], v.v[e], s2);
@@ -345,7 +332,7 @@ attn_fwd_merge_kernel(typename E::T* __restrict__ out, float* __restrict__ lse, 
     const int w_lo = (int)(lo / a.chunk), w_hi = (int)((hi - 1) / a.chunk);
     if (w_lo == w_hi) return;  // one workgroup had the whole block and wrote the result
     const int bh = blk / a.nqb, qb = blk - bh * a.nqb;
-    const int b = bh / a.H, h = bh - b * a.H;
+    const AttnHead<FA_D> hd(bh, a.N, a.H);
     const int ql = threadIdx.x, q = qb * FA_QB + ql;
     if (q >= a.N) return;
     float mt = -INFINITY;
@@ -366,57 +353,37 @@ attn_fwd_merge_kernel(typename E::T* __restrict__ out, float* __restrict__ lse, 
         }
     }
     const float inv = 1.0f / l;
-    typename E::T* op = out + ((int64_t)b * a.N + q) * (a.H * FA_D) + h * FA_D;
+    typename E::T* op = hd.out_row(out, q);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
         *reinterpret_cast<uint4*>(op + 8 * j) =
             make_uint4(E::pack2(acc[8 * j] * inv, acc[8 * j + 1] * inv), E::pack2(acc[8 * j + 2] * inv, acc[8 * j + 3] * inv),
                        E::pack2(acc[8 * j + 4] * inv, acc[8 * j + 5] * inv), E::pack2(acc[8 * j + 6] * inv, acc[8 * j + 7] * inv));
-    lse[((int64_t)b * a.H + h) * a.N + q] = (mt + log2f(l)) * 0.6931471805599453f;
+    lse[hd.stat(q)] = (mt + log2f(l)) * 0.6931471805599453f;
 }
 
-bool attn_mfma_supported(int N, int D) { return D == FA_D && N >= 128; }  // incl. the U-Net bottleneck (N = 144 at 192x64x48)
-
-// Persistent stream-K schedule when the launch is big enough to care about whole rounds of workgroups (and the stream's
-// scratch arena can hold the partials: 2 slots x 512 workgroups x 34 816 B = 35.7 MB behind its zero block and the key-norm
-// table); otherwise one workgroup per query block.
-#define FA_KMAX_BYTES 1024  // max_k |k|^2 of up to 256 (b, h) pairs, right behind the arena's zero block
-int attn_fwd_mfma_launch(const void* qkv, void* out, float* lse, int B, int N, int H, int dtype, hipStream_t st) {
+// What the plan says, launched: the key-norm pre-pass into its table (bound), the flash kernel on the plan's grid, and under
+// stream-K the merge of the blocks that were split over workgroups.
+int attn_fwd_mfma_launch(const AttnFwdCall& c, const AttnPlan& p) {
+    if (p.fwd != TDX_ATTN_MFMA) return TDX_EINVAL;
     AttnSkArgs a;
-    a.N = N; a.H = H;
-    a.nqb = ceil_div(N, FA_QB);
-    a.ntile = ceil_div(N, FA_KT);
-    const int nblk = B * H * a.nqb;
-    a.total = (long long)nblk * a.ntile;
-    const int slots = 512;  // 256 CUs x 2 workgroups
-    const size_t head = TDX_SCRATCH_ZERO_BYTES + FA_KMAX_BYTES;
-    const bool want = tdx_switch(SW_ATTN_STREAMK) != 0 && nblk > slots && (nblk % slots) != 0 && a.ntile >= 16;
-    a.part = want ? reinterpret_cast<float*>(tdx_scratch_region(head, (size_t)slots * 2 * FA_PART_STRIDE * sizeof(float))) : nullptr;
-    if (a.part != nullptr) {
-        a.nwg = slots;
-        a.chunk = (int)((a.total + slots - 1) / slots);
-    } else {
-        a.nwg = nblk;
-        a.chunk = a.ntile;
-    }
-    a.kmax2 = nullptr;
-    float* km = reinterpret_cast<float*>(tdx_scratch_region(TDX_SCRATCH_ZERO_BYTES, FA_KMAX_BYTES));
-    if (tdx_switch(SW_ATTN_BOUND) != 0 && km != nullptr && B * H <= 256 && a.ntile >= 8) {
-        if (tdx_zero_async(km, (size_t)B * H * sizeof(float), st) != TDX_OK) return TDX_EINVAL;
-        const dim3 kg(min(ceil_div(N, 64), 64), B * H);
-        if (dtype == TDX_F16) hipLaunchKernelGGL(attn_kmax_kernel<f16>, kg, dim3(256), 0, st, (const f16*)qkv, km, N, H);
-        else hipLaunchKernelGGL(attn_kmax_kernel<bf16>, kg, dim3(256), 0, st, (const bf16*)qkv, km, N, H);
-        a.kmax2 = km;
-    }
-    if (dtype == TDX_F16)
-        hipLaunchKernelGGL(attn_fwd_mfma_kernel<AttnF16>, dim3(a.nwg), dim3(FA_THREADS), 0, st, (const f16*)qkv, (f16*)out, lse, a);
-    else
-        hipLaunchKernelGGL(attn_fwd_mfma_kernel<AttnBf16>, dim3(a.nwg), dim3(FA_THREADS), 0, st, (const bf16*)qkv, (bf16*)out, lse, a);
-    if (a.part != nullptr) {
-        if (dtype == TDX_F16)
-            hipLaunchKernelGGL(attn_fwd_merge_kernel<AttnF16>, dim3(nblk), dim3(FA_QB), 0, st, (f16*)out, lse, a);
-        else
-            hipLaunchKernelGGL(attn_fwd_merge_kernel<AttnBf16>, dim3(nblk), dim3(FA_QB), 0, st, (bf16*)out, lse, a);
-    }
-    return tdx_launch_status();
+    a.N = c.N; a.H = c.H;
+    a.nqb = p.nqb; a.ntile = p.ntile;
+    a.total = (long long)p.nblk * p.ntile;
+    a.chunk = p.chunk; a.nwg = p.nwg;
+    a.part = p.streamk ? reinterpret_cast<float*>(tdx_scratch_region(FA_PART_OFFSET, FA_PART_BYTES)) : nullptr;
+    float* km = p.bound ? reinterpret_cast<float*>(tdx_scratch_region(FA_KMAX_OFFSET, FA_KMAX_BYTES)) : nullptr;
+    a.kmax2 = km;
+    if ((p.streamk && a.part == nullptr) || (p.bound && km == nullptr)) return TDX_EINVAL;  // not this arena's plan
+    if (p.bound && tdx_zero_async(km, (size_t)c.B * c.H * sizeof(float), c.st) != TDX_OK) return TDX_EINVAL;
+    return attn_h16_dispatch(c.dtype, [&](auto e) {
+        using E = decltype(e);
+        using T = typename E::T;
+        if (p.bound)
+            hipLaunchKernelGGL(attn_kmax_kernel<T>, dim3(min(ceil_div(c.N, 64), 64), c.B * c.H), dim3(256), 0, c.st, (const T*)c.qkv,
+                               km, c.N, c.H);
+        hipLaunchKernelGGL(attn_fwd_mfma_kernel<E>, dim3(a.nwg), dim3(FA_THREADS), 0, c.st, (const T*)c.qkv, (T*)c.out, c.lse, a);
+        if (p.streamk) hipLaunchKernelGGL(attn_fwd_merge_kernel<E>, dim3(p.nblk), dim3(FA_QB), 0, c.st, (T*)c.out, c.lse, a);
+        return tdx_launch_status();
+    });
 }

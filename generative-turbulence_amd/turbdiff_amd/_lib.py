@@ -86,6 +86,7 @@ SIGNATURES = {
     "tdx_attn_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tdx_attn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "tdx_attn_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "tdx_attn_plan": (_i, [_i] * 5 + [_vp]),
     "tdx_cell_mask": (_i, [_vp, _i64, _vp, _i64, _vp]),
     "tdx_q_sample": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i64, _vp]),
     "tdx_p_sample_step": (_i, [_vp] * 7 + [_i, _vp, _i, _i, _vp, _i, _i, _i64, _vp]),
@@ -536,6 +537,26 @@ def resize_plan(B, C, src, dst, dtype: int) -> dict:
     plan = {k: int(buf[i]) for i, k in enumerate(RESIZE_PLAN_FIELDS)}
     plan["fwd_kernel"] = RESIZE_FWD_KERNELS[plan["fwd_kernel"]]
     plan["bwd_kernel"] = RESIZE_BWD_KERNELS[plan["bwd_kernel"]]
+    plan["status"] = status
+    return plan
+
+
+ATTN_KERNELS = ("vector", "mfma")  # TDX_ATTN_VECTOR, TDX_ATTN_MFMA
+ATTN_PLAN_INTS = 13  # TDX_ATTN_PLAN_INTS
+ATTN_PLAN_FIELDS = ("fwd", "bwd", "nqb", "ntile", "nwg", "chunk", "streamk", "bound", "tw_dq", "tw_dkv", "bwd_gx", "bwd_gy",
+                    "workspace")  # TDX_ATTN_PLAN_*
+
+
+def attn_plan(B, N, H, D, dtype: int) -> dict:
+    """What tdx_attn_fwd and tdx_attn_bwd would launch for qkv (B, N, 3 H D), as the library's own host function plans both:
+    {"status": the code those calls would return, "fwd" and "bwd": names of ATTN_KERNELS, and the other ATTN_PLAN_FIELDS
+    (0 where they do not apply; all 0, family "vector", unless the status is 0)}.  Launches nothing; reads the library switches
+    as of now and the bound arena's size (`call` binds the launching stream's before tdx_attn_fwd: bind it first --
+    ensure_scratch -- to ask about a call on this stream)."""
+    buf = (_i * ATTN_PLAN_INTS)()
+    status = int(load().tdx_attn_plan(B, N, H, D, dtype, buf))
+    plan = {k: int(buf[i]) for i, k in enumerate(ATTN_PLAN_FIELDS)}
+    plan["fwd"], plan["bwd"] = ATTN_KERNELS[plan["fwd"]], ATTN_KERNELS[plan["bwd"]]
     plan["status"] = status
     return plan
 

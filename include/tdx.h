@@ -492,6 +492,39 @@ int tdx_attn_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, in
 int tdx_attn_bwd(const void* qkv, const void* out, const float* lse, const void* dout, void* dqkv, int B, int N, int H,
                  int D, int dtype, void* workspace, void* stream);
 size_t tdx_attn_bwd_workspace_bytes(int B, int N, int H, int D);
+/* What tdx_attn_fwd and tdx_attn_bwd launch for these arguments, from the host function that plans both.  The
+ * TDX_ATTN_* switches and the claimed size of the bound scratch arena (tdx_set_scratch) are read as of now.  Nothing is
+ * launched.  Returns the status those calls would return (plan == NULL or a size <= 0: TDX_EINVAL) and fills
+ * plan[0 .. TDX_ATTN_PLAN_INTS) (zeros unless the status is TDX_OK; fields that do not apply to the family are 0):
+ *   FWD, BWD             TDX_ATTN_VECTOR (row-wise vector-ALU kernels) or TDX_ATTN_MFMA (matrix-core flash kernels: bf16 /
+ *                        fp16 tensors, N >= 128, TDX_ATTN_IMPL not "vector")
+ *   NQB, NTILE           matrix-core forward: 256-query blocks per (b, h), 64-key tiles per block
+ *   NWG, CHUNK           its workgroups and (query block, key tile) iterations per workgroup: B H NQB and NTILE, or under
+ *                        stream-K 512 and ceil(B H NQB NTILE / 512)
+ *   STREAMK              1: persistent stream-K schedule, partials in the arena, merge launch (TDX_ATTN_STREAMK, more than
+ *                        512 blocks and no multiple of 512, NTILE >= 16, and an arena that holds the partials)
+ *   BOUND                1: key-norm pre-pass, check-free loop where the bound allows (TDX_ATTN_BOUND, B H <= 256, NTILE >= 8,
+ *                        and an arena that holds the table)
+ *   TW_DQ, TW_DKV        matrix-core backward: 32-row tiles per wave of the dQ and the dK/dV kernel (TDX_ATTN_BWD_TW)
+ *   BWD_GX, BWD_GY       grid of the backward's two kernels: ceil(N / 256) or, vector, ceil(N / 64); B H
+ *   WORKSPACE            tdx_attn_bwd_workspace_bytes (at most INT_MAX here) */
+#define TDX_ATTN_VECTOR 0
+#define TDX_ATTN_MFMA 1
+#define TDX_ATTN_PLAN_FWD 0
+#define TDX_ATTN_PLAN_BWD 1
+#define TDX_ATTN_PLAN_NQB 2
+#define TDX_ATTN_PLAN_NTILE 3
+#define TDX_ATTN_PLAN_NWG 4
+#define TDX_ATTN_PLAN_CHUNK 5
+#define TDX_ATTN_PLAN_STREAMK 6
+#define TDX_ATTN_PLAN_BOUND 7
+#define TDX_ATTN_PLAN_TW_DQ 8
+#define TDX_ATTN_PLAN_TW_DKV 9
+#define TDX_ATTN_PLAN_BWD_GX 10
+#define TDX_ATTN_PLAN_BWD_GY 11
+#define TDX_ATTN_PLAN_WORKSPACE 12
+#define TDX_ATTN_PLAN_INTS 13
+int tdx_attn_plan(int B, int N, int H, int D, int dtype, int* plan);
 
 /* ------------------------------------------------------------------ DDPM arithmetic ---- */
 /* All tensors here are the reference's NCDHW (B, F, V) f32 tensors; t is int64 on device:

@@ -1,4 +1,4 @@
-"""Pinned-bits fixtures: what the case modules (reverse_step_cases, gn_cases, conv3_cases, convg_cases, conv1_bits_cases, resize_bits_cases), their tests and the recorder
+"""Pinned-bits fixtures: what the case modules (reverse_step_cases, gn_cases, conv3_cases, convg_cases, conv1_bits_cases, resize_bits_cases, attention_bits_cases), their tests and the recorder
 tests/golden/make_golden_bits.py share.
 
 A case module has GROUPS, FIXTURE (the file name under tests/golden/) and run(group) -> {case name: record}.  A record is

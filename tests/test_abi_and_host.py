@@ -76,6 +76,12 @@ def test_header_symbols_are_bound_and_exported():
     assert index == {k: i for i, k in enumerate(_lib.RESIZE_PLAN_FIELDS)}
     kernels = {n.lower(): int(v) for n, v in re.findall(r"^#define TDX_RESIZE_(GATHER|PAIRS|TILED|GENERIC) (\d+)$", text, flags=re.M)}
     assert [kernels[k] for k in _lib.RESIZE_FWD_KERNELS + _lib.RESIZE_BWD_KERNELS] == [0, 1, 0, 1]
+    assert protos["tdx_attn_plan"] == ("int", ["int"] * 5 + ["ptr"])
+    index = {n.lower(): int(v) for n, v in re.findall(r"^#define TDX_ATTN_PLAN_(\w+) (\d+)$", text, flags=re.M)}
+    assert index.pop("ints") == _lib.ATTN_PLAN_INTS == len(_lib.ATTN_PLAN_FIELDS)
+    assert index == {k: i for i, k in enumerate(_lib.ATTN_PLAN_FIELDS)}
+    kernels = {n.lower(): int(v) for n, v in re.findall(r"^#define TDX_ATTN_(VECTOR|MFMA) (\d+)$", text, flags=re.M)}
+    assert [kernels[k] for k in _lib.ATTN_KERNELS] == [0, 1]
 
 
 def test_product_refuses_cpu_tensors():

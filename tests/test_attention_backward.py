@@ -176,6 +176,14 @@ def abi_backward(qkv, out, lse, go, dqkv, H):
     torch.cuda.synchronize()
 
 
+def planned(B, N, H, dtype):
+    """what the library plans for a call on this stream, under the switches as they are now (its arena bound first)"""
+    from turbdiff_amd import _lib as L
+
+    L.ensure_scratch()
+    return L.attn_plan(B, N, H, D, L.dtype_code(dtype))
+
+
 @pytest.fixture(autouse=True)
 def _attention_env(monkeypatch):
     for name in ("TDX_ATTN_IMPL", "TDX_ATTN_BWD_TW", "TDX_ATTN_STREAMK", "TDX_ATTN_BOUND"):
@@ -213,22 +221,16 @@ def test_every_shipped_instance(N, dtype, tw, monkeypatch):
     if tw is not None:
         monkeypatch.setenv("TDX_ATTN_BWD_TW", tw)
     qkv, go, ref, model = dense_case("1", dtype, 2, 4, N)
+    p = planned(2, N, 4, dtype)  # the instance the switch names is the one that runs
+    assert (p["bwd"], 10 * p["tw_dq"] + p["tw_dkv"]) == ("mfma", int(tw or "22"))
     check(f"instance TW={tw} {_tag(dtype)} N={N}", run_autograd(qkv, go, 4), ref, model, ABS_TOL[dtype])
 
 
 # ---- (c) large logits
-@pytest.mark.parametrize("streamk", [None, "0"])
-@pytest.mark.parametrize("dtype", DTYPES, ids=_tag)
-@pytest.mark.parametrize("regime", ["grow", "3"])
-@pytest.mark.parametrize("N", [1000, 4096 + 64 * 37 + 5])
-def test_large_logits(N, regime, dtype, streamk, monkeypatch):
-    """|q| |k| / sqrt(D) up to ~200 (the growing-scores inputs) and 3 N(0,1) q, k (largest score ~50): the recomputed
-    probabilities are only as good as the agreement of the backward's scores with the forward's, whose log-sum-exp they are
-    normalised by.  All three gradients at the model bounds, and sum_keys dV = sum_queries dO per (b, h, d) -- the rows of P
-    sum to one -- at twice the model's own residual."""
+def _large_logits(B, H, N, regime, dtype, streamk, monkeypatch, streamk_runs):
     if streamk is not None:
         monkeypatch.setenv("TDX_ATTN_STREAMK", streamk)
-    B, H = 2, 4
+    assert planned(B, N, H, dtype)["streamk"] == int(streamk_runs)
     qkv, go, ref, model = dense_case(regime, dtype, B, H, N)
     got = run_autograd(qkv, go, H)
     sum_go = heads_first(go.double(), H).sum(2)
@@ -237,6 +239,30 @@ def test_large_logits(N, regime, dtype, streamk, monkeypatch):
     print(f"ATTN_BWD {tag} sum_keys dV: residual {res:.2e} model {res_m:.2e} ratio {res / res_m:.2f}")
     check(tag, got, ref, model)
     assert res <= 2 * res_m, (tag, res, res_m)
+
+
+@pytest.mark.parametrize("streamk", [None, "0"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=_tag)
+@pytest.mark.parametrize("regime", ["grow", "3"])
+@pytest.mark.parametrize("N", [1000, 4096 + 64 * 37 + 5])
+def test_large_logits(N, regime, dtype, streamk, monkeypatch):
+    """|q| |k| / sqrt(D) up to ~200 (the growing-scores inputs) and 3 N(0,1) q, k (largest score ~50): the recomputed
+    probabilities are only as good as the agreement of the backward's scores with the forward's, whose log-sum-exp they are
+    normalised by.  All three gradients at the model bounds, and sum_keys dV = sum_queries dO per (b, h, d) -- the rows of P
+    sum to one -- at twice the model's own residual.  (B = 2, H = 4 is at most 208 query blocks: the forward runs one
+    workgroup per block in both `streamk` arms, as its plan says; test_large_logits_stream_k has the shape that splits.)"""
+    _large_logits(2, 4, N, regime, dtype, streamk, monkeypatch, streamk_runs=False)
+
+
+@pytest.mark.parametrize("streamk", [None, "0"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=_tag)
+@pytest.mark.parametrize("regime", ["grow", "3"])
+def test_large_logits_stream_k(regime, dtype, streamk, monkeypatch):
+    """The same at B = 33, H = 4, N = 1000, the smallest shape whose forward the stream-K schedule takes: 528 query blocks on
+    512 workgroups of 17 (block, key tile) iterations, so segments start on every one of the 16 key tiles, the ragged last one
+    included, and every block is merged from partials.  The plan says stream-K runs in one arm and not in the other; the
+    backward consumes either forward's log-sum-exp at the same bounds."""
+    _large_logits(33, 4, 1000, regime, dtype, streamk, monkeypatch, streamk_runs=streamk is None)
 
 
 # ---- (d) overwrite, not accumulate; nothing outside
@@ -250,6 +276,8 @@ def test_overwrites_its_output_and_nothing_else(N, dtype, impl, monkeypatch):
         monkeypatch.setenv("TDX_ATTN_IMPL", "vector")
     B, H, G = 2, 4, 256
     ld = 3 * H * D
+    p = planned(B, N, H, dtype)
+    assert (p["fwd"], p["bwd"]) == (impl, impl)
     qkv, go = make_inputs("1", dtype, B, H, N)
     out, lse = abi_forward(qkv, H)
     buf = torch.full((G + B * N + G, ld), -1234.0, dtype=dtype, device=dev())
@@ -295,11 +323,13 @@ def test_lse_handover_between_kernel_families(dtype, fwd_impl, bwd_impl, monkeyp
     qkv, go, ref, model = dense_case("1", dtype, B, H, N)
     if fwd_impl == "vector":
         monkeypatch.setenv("TDX_ATTN_IMPL", "vector")
+    assert planned(B, N, H, dtype)["fwd"] == fwd_impl
     out, lse = abi_forward(qkv, H)
     torch.cuda.synchronize()
     monkeypatch.delenv("TDX_ATTN_IMPL", raising=False)
     if bwd_impl == "vector":
         monkeypatch.setenv("TDX_ATTN_IMPL", "vector")
+    assert planned(B, N, H, dtype)["bwd"] == bwd_impl
     dqkv = torch.empty_like(qkv)
     abi_backward(qkv, out, lse, go, dqkv, H)
     check(f"handover {_tag(dtype)} fwd={fwd_impl} bwd={bwd_impl}", split_grad(dqkv, H), ref, model, ABS_TOL[dtype])

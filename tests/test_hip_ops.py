@@ -585,18 +585,25 @@ def test_conv3_with_fused_gn_statistics(case, dtype, impl, exact, monkeypatch):
 
 @pytest.mark.parametrize("N", [256, 257, 319, 511, 1000, 1023, 4096])
 def test_attention_mfma_forward(N, monkeypatch):
-    """bf16 MFMA flash attention (used for N >= 256) vs the oracle on the same bf16 inputs"""
-    from turbdiff_amd import ops
+    """bf16 MFMA flash attention (used for N >= 128) vs the oracle on the same bf16 inputs"""
+    from turbdiff_amd import _lib as L, ops
 
     B, H, D = 2, 4, 32
+
+    def family():  # what a call on this stream runs under the switches as they are now
+        L.ensure_scratch()
+        return L.attn_plan(B, N, H, D, L.BF16)["fwd"]
+
     qkv = q(rnd(B, N, 3 * H * D, seed=1), torch.bfloat16)
     qq, kk, vv = (p.reshape(B, N, H, D).transpose(1, 2).double() for p in qkv.chunk(3, dim=-1))
     ref = O.sdpa(qq, kk, vv).transpose(1, 2).reshape(B, N, H * D)
     qd = qkv.to(dev()).bfloat16()
+    assert family() == "mfma"
     out = ops.attention(qd, H)
     assert rel_l2(out.float().cpu(), ref) < 1e-2
     # the vector-ALU kernel on the same input (exact fp32 softmax): agree to bf16 rounding
     monkeypatch.setenv("TDX_ATTN_IMPL", "vector")
+    assert family() == "vector"
     out_v = ops.attention(qd, H)
     assert rel_l2(out.float(), out_v.float()) < 1e-2
     # backward (vector-ALU kernels, driven by the MFMA forward's out / lse)
@@ -696,6 +703,11 @@ def test_attention_fp16_operands(N, monkeypatch):
     for impl in ("mfma", "vector"):
         if impl == "vector":
             monkeypatch.setenv("TDX_ATTN_IMPL", "vector")
+        from turbdiff_amd import _lib as L
+
+        L.ensure_scratch()
+        plan = L.attn_plan(B, N, H, D, L.F16)
+        assert (plan["fwd"], plan["bwd"]) == (impl, impl)
         qd = qkv.to(dev()).requires_grad_()
         out = ops.attention(qd, H)
         assert out.dtype == torch.float16
@@ -706,26 +718,31 @@ def test_attention_fp16_operands(N, monkeypatch):
     monkeypatch.delenv("TDX_ATTN_IMPL")
 
 
-@pytest.mark.parametrize("dtype,tol", [(torch.bfloat16, 8e-3), (torch.float16, 2e-3)])
-@pytest.mark.parametrize("N", [1000, 4096 + 64 * 37 + 5])
-def test_attention_growing_scores_and_loose_norm_bound(dtype, tol, N, monkeypatch):
+def _growing_scores_and_loose_norm_bound(B, H, N, dtype, tol, monkeypatch, streamk_runs, ref_device="cpu"):
     """The matrix-core forward's lazy running maximum (round 5): scores that keep GROWING along the key index (every
     tile outgrows the stale maximum: the raise path runs over and over), an outlier key of huge norm that no query
     aligns with (the Cauchy-Schwarz bound |q| max|k| is loose by far more than the allowance: the per-tile check must
     stay on), queries of very different norms in one wave, and a ragged last tile -- against the fp64 oracle on the same
     rounded inputs; with the norm bound switched off (TDX_ATTN_BOUND=0: always checking) and with the stream-K schedule
-    forced off, bit-identical results are not required, the tolerance is."""
-    from turbdiff_amd import ops
+    forced off, bit-identical results are not required, the tolerance is.  The library's plan must say what each
+    environment asks for: the bound off under TDX_ATTN_BOUND=0, stream-K on only where `streamk_runs` and not under
+    TDX_ATTN_STREAMK=0.  ref_device: where the fp64 reference is evaluated."""
+    from turbdiff_amd import _lib as L, ops
 
-    B, H, D = 2, 4, 32
+    D = 32
     q, k, v = growing_scores_qkv(B, N, H, D, seed=5)
     qkv = torch.cat([t.reshape(B, N, H * D) for t in (q, k, v)], dim=-1).to(dtype)
-    qd, kd, vd = (t.reshape(B, N, H, D).transpose(1, 2).double() for t in qkv.chunk(3, dim=-1))
-    ref = O.sdpa(qd, kd, vd).transpose(1, 2).reshape(B, N, H * D)
-    lse_ref = torch.logsumexp(qd @ kd.transpose(-1, -2) / D**0.5, dim=-1)  # (B, H, N)
+    qd, kd, vd = (t.reshape(B, N, H, D).transpose(1, 2).double().to(ref_device) for t in qkv.chunk(3, dim=-1))
+    ref = O.sdpa(qd, kd, vd).transpose(1, 2).reshape(B, N, H * D).cpu()
+    lse_ref = torch.logsumexp(qd @ kd.transpose(-1, -2) / D**0.5, dim=-1).cpu()  # (B, H, N)
+    qd, kd, vd = qd.cpu(), kd.cpu(), vd.cpu()
     for env in ({}, {"TDX_ATTN_BOUND": "0"}, {"TDX_ATTN_STREAMK": "0"}):
         for kk, vv in env.items():
             monkeypatch.setenv(kk, vv)
+        L.ensure_scratch()
+        plan = L.attn_plan(B, N, H, D, L.dtype_code(dtype))
+        assert (plan["fwd"], plan["bound"], plan["streamk"]) == ("mfma", int("TDX_ATTN_BOUND" not in env and B * H <= 256),
+                                                                 int(streamk_runs and "TDX_ATTN_STREAMK" not in env)), (env, plan)
         x = qkv.to(dev()).requires_grad_()
         out = ops.attention(x, H)
         assert torch.isfinite(out).all()
@@ -733,8 +750,6 @@ def test_attention_growing_scores_and_loose_norm_bound(dtype, tol, N, monkeypatc
         out.backward(torch.ones_like(out))
         assert torch.isfinite(x.grad).all()
         # the log-sum-exp the backward pass consumes, straight from the entry point
-        from turbdiff_amd import _lib as L
-
         xd = qkv.to(dev())
         o2 = torch.empty(B, N, H * D, dtype=dtype, device=dev())
         lse = torch.empty(B, H, N, dtype=torch.float32, device=dev())
@@ -753,6 +768,20 @@ def test_attention_growing_scores_and_loose_norm_bound(dtype, tol, N, monkeypatc
         assert (lse.cpu().double() - lse_same).abs().max().item() < 1e-2, env
         for kk in env:
             monkeypatch.delenv(kk)
+
+
+@pytest.mark.parametrize("dtype,tol", [(torch.bfloat16, 8e-3), (torch.float16, 2e-3)])
+@pytest.mark.parametrize("N", [1000, 4096 + 64 * 37 + 5])
+def test_attention_growing_scores_and_loose_norm_bound(dtype, tol, N, monkeypatch):
+    """B = 2, H = 4: at most 208 query blocks, one workgroup each in every environment (see the helper)"""
+    _growing_scores_and_loose_norm_bound(2, 4, N, dtype, tol, monkeypatch, streamk_runs=False)
+
+
+@pytest.mark.parametrize("dtype,tol", [(torch.bfloat16, 8e-3), (torch.float16, 2e-3)])
+def test_attention_growing_scores_stream_k(dtype, tol, monkeypatch):
+    """B = 33, H = 4, N = 1000: the smallest shape the stream-K schedule takes (528 query blocks on 512 workgroups, segments
+    starting on every key tile, every block merged from partials), at the same tolerances; reference on the device"""
+    _growing_scores_and_loose_norm_bound(33, 4, 1000, dtype, tol, monkeypatch, streamk_runs=True, ref_device=dev())
 
 
 def test_attention_config5_rows_vs_oracle_fp16():

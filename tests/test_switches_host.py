@@ -160,6 +160,74 @@ def test_conv1_queries_follow_the_switches_between_two_calls(L, monkeypatch):
         L._ACTIVE = None  # a later GPU test in this process binds its real arena again
 
 
+# (B, N, H) on both sides of every threshold of the attention plan.  nblk = B H ceil(N / 256), ntile = ceil(N / 64).
+ATTN_SHAPES = [
+    (2, 8, 4), (2, 127, 4), (2, 128, 4), (2, 144, 4),    # vector / matrix core at N = 128
+    (2, 448, 4), (2, 449, 4),                             # ntile 7 / 8: norm bound
+    (64, 1000, 4), (257, 1000, 1),                        # B H = 256 / 257: norm bound (nblk 1024, 1028)
+    (32, 1000, 4), (27, 4700, 1), (64, 1000, 4),          # nblk 512 / 513 / 1024: stream-K only at 513
+    (33, 960, 4), (33, 961, 4), (33, 1000, 4),            # nblk 528 at ntile 15 / 16 / 16: stream-K
+    (1, 96 * 32 * 24, 4),                                 # BASELINE configs[4]: 1152 blocks
+]
+
+
+def test_attn_plan_follows_switches_and_arena_between_two_calls(L, monkeypatch):
+    """attn_plan (csrc/tdx_attention.hip) is the ONE reader of the four TDX_ATTN_* switches and the one place that asks for the
+    arena's size; the entry points and tdx_attn_plan ask it per call.  The library's answer against the Python restatement
+    (attention_cases.expected_plan) on both sides of every threshold, for every dtype, switch setting and arena size -- the same
+    queries again after each change.  A host buffer stands in for the arena: the plan looks at the claimed size only."""
+    import attention_cases as A
+
+    for sw in ("IMPL", "STREAMK", "BOUND", "BWD_TW"):
+        uses = [(f.name, n) for f in sorted(CSRC.glob("tdx_attention*")) if (n := len(re.findall(rf"\bSW_ATTN_{sw}\b", f.read_text())))]
+        assert uses == [("tdx_attention.hip", 1)], (sw, uses)
+    lib = L.load()
+    fake = ctypes.create_string_buffer(256)
+    arenas = (0, A.ARENA_ZERO + A.ARENA_KMAX - 1, A.ARENA_ZERO + A.ARENA_KMAX, A.ARENA_STREAMK - 1, A.ARENA_STREAMK, 96 << 20)
+    envs = [{}, {"TDX_ATTN_IMPL": "vector"}, {"TDX_ATTN_IMPL": "1"}, {"TDX_ATTN_STREAMK": "0"}, {"TDX_ATTN_BOUND": "0"},
+            {"TDX_ATTN_STREAMK": "0", "TDX_ATTN_BOUND": "0"}] + [{"TDX_ATTN_BWD_TW": tw} for tw in ("11", "12", "21", "22")] + [{}]
+    seen = set()
+    try:
+        for arena in arenas:
+            assert lib.tdx_set_scratch(ctypes.addressof(fake) if arena else None, arena) == 0
+            for env in envs:
+                for k in A.PLAN_ENV:
+                    monkeypatch.delenv(k, raising=False) if k not in env else monkeypatch.setenv(k, env[k])
+                for B, N, H in ATTN_SHAPES:
+                    for dt in (L.F32, L.BF16, L.F16):
+                        got, want = L.attn_plan(B, N, H, 32, dt), A.expected_plan(B, N, H, 32, dt, env, arena)
+                        assert got == want, (arena, env, B, N, H, dt)
+                        assert L.query("tdx_attn_bwd_workspace_bytes", B, N, H, 32) == 4 * B * N * H == got["workspace"]
+                        seen.add((got["fwd"], got["streamk"], got["bound"], got["tw_dq"], got["tw_dkv"]))
+        # every outcome was met, and the numbers of the smallest shape that engages stream-K (tests/attention_bits_cases.py)
+        assert {s[:3] for s in seen} == {("vector", 0, 0), ("mfma", 0, 0), ("mfma", 0, 1), ("mfma", 1, 0), ("mfma", 1, 1)}
+        assert {s[3:] for s in seen} == {(0, 0), (1, 1), (1, 2), (2, 1), (2, 2)}
+        p = L.attn_plan(33, 1000, 4, 32, L.BF16)  # the last arena and environment: 96 MB, defaults
+        assert (p["nqb"], p["ntile"], p["nwg"], p["chunk"], p["streamk"], p["bound"]) == (4, 16, 512, 17, 1, 1)
+        assert lib.tdx_set_scratch(ctypes.addressof(fake), A.ARENA_STREAMK - 1) == 0  # the silent fall-back, now reported
+        p = L.attn_plan(33, 1000, 4, 32, L.BF16)
+        assert (p["nwg"], p["chunk"], p["streamk"], p["bound"]) == (528, 16, 0, 1)
+    finally:
+        lib.tdx_set_scratch(None, 0)
+        L._ACTIVE = None  # a later GPU test in this process binds its real arena again
+
+
+def test_attn_plan_statuses(L):
+    """The statuses of tdx_attn_fwd / tdx_attn_bwd before they launch anything, from the plan: D != 32 is TDX_ESHAPE (before
+    the dtype is looked at), a dtype code that is no tensor format TDX_EDTYPE, a non-positive size or no plan TDX_EINVAL; the
+    plan array is zeroed unless the status is TDX_OK."""
+    import attention_cases as A
+
+    for D in (16, 31, 33, 64):
+        for dt in (L.F32, L.BF16, L.F16, 2, 7):
+            assert L.attn_plan(2, 144, 4, D, dt) == A.expected_plan(2, 144, 4, D, dt) and L.attn_plan(2, 144, 4, D, dt)["status"] == -2
+    for dt in (2, 4, -1):
+        assert L.attn_plan(2, 144, 4, 32, dt) == A.expected_plan(2, 144, 4, 32, dt) and L.attn_plan(2, 144, 4, 32, dt)["status"] == -3
+    for B, N, H in ((0, 144, 4), (2, 0, 4), (2, 144, 0), (-1, 144, 4)):
+        assert L.attn_plan(B, N, H, 32, L.BF16)["status"] == -1
+    assert L.load().tdx_attn_plan(2, 144, 4, 32, L.BF16, None) == -1
+
+
 def test_python_and_library_agree_on_deterministic(L, monkeypatch):
     assert L.deterministic() is False
     for s, want in (("", False), ("0", False), ("1", True), ("2", False), ("off", False)):
