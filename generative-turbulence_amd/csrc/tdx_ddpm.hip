@@ -513,7 +513,7 @@ extern "C" int tdx_randn_batched(float* out, int B, int64_t n, uint64_t seed, co
     return tdx_launch_status();
 }
 
-// ------------------------------------------------------------------ reverse step: three rules over two skeletons ---
+// ------------------------------------------------------------------ reverse step: five rules over two skeletons ----
 // One launch takes the state from one timestep of its sequence to the one before.  A RULE says which tables a step reads
 // and what it does to one element:
 //   Coef          the step's coefficients (block-uniform scalars); `last` = the step that writes the mean and fixes the BC cells
@@ -521,7 +521,9 @@ extern "C" int tdx_randn_batched(float* out, int B, int64_t n, uint64_t seed, co
 //   load(i)       column i
 //   draws_z(c)    does the interior consume z at this step?
 //   update(...)   one element; w, z, z2 and xb arrive as 0 where the step does not use them
-//   reads_w       eps is the decoder's [eps_hat | w], 2F planes per sample, and w feeds the update
+//   eps_planes    1: eps is (B, F, V); 2: it is the decoder's [eps_hat | w], 2F planes per sample -- the LAYOUT
+//   reads_w       w feeds the update (needs eps_planes == 2).  A rule with eps_planes == 2 and reads_w == false steps over the
+//                 w half without loading it
 // The two SKELETONS own everything else -- indexing, the mask, which operands are read, where the noise comes from -- so the
 // tensor-noise and the in-kernel-noise entry of a rule agree bit for bit by construction of `update`: the DDIM and the
 // learned-variance rule spell every multiply-add as an fmaf because, left to the compiler, the contraction of a * b + c * d
@@ -535,6 +537,7 @@ extern "C" int tdx_randn_batched(float* out, int B, int64_t n, uint64_t seed, co
 struct AncestralRule {
     const float* sched;
     int T;
+    static constexpr int eps_planes = 1;
     static constexpr bool reads_w = false;
     struct Coef {
         float recip, recipm1, c1, c2, sigma, sa, sb;
@@ -573,6 +576,7 @@ struct AncestralRule {
 struct LvRule {
     const float *sched, *plv;
     int T;
+    static constexpr int eps_planes = 2;
     static constexpr bool reads_w = true;
     struct Coef {
         float recip, recipm1, c1, c2, lb, dl, sa, sb;  // dl = plv - lb
@@ -617,6 +621,7 @@ struct LvRule {
 struct DdimRule {
     const float* tab;
     int S;
+    static constexpr int eps_planes = 1;
     static constexpr bool reads_w = false;
     struct Coef {
         float recip, recipm1, sp, dir, sigma, sbp;
@@ -650,6 +655,40 @@ struct DdimRule {
     }
 };
 
+// LvRule's step over an increasing subsequence tau[0..S-1] of the training timesteps, from tau[k] to tau[k-1]: the ancestral
+// step of the SHORTER chain whose cumulative products are a = abar[tau[k]] (Nichol & Dhariwal 2021, the SpacedDiffusion
+// construction).  tab = 8 rows of S floats (schedules.RESPACED_PACKED_ORDER), column k: the respaced beta' = 1 - a / p and
+// beta~' = beta' (1 - p) / (1 - a) take the places of beta_t and the posterior variance.  The element is LvRule's own
+// function, not a restatement: a table that holds the training chain's columns gives the training chain's bits.  BC cells
+// under noise_bcs are re-noised at the level of the state PRODUCED (sa = sqrt(p), sb = sqrt(1 - p)), as DdimRule does.
+struct LvRespacedRule {
+    const float* tab;
+    int S;
+    static constexpr int eps_planes = 2;
+    static constexpr bool reads_w = true;
+    using Coef = LvRule::Coef;
+    __device__ __forceinline__ bool valid(int64_t k) const { return k >= 0 && k < S; }
+    __device__ __forceinline__ Coef load(int64_t k) const {
+        Coef c;
+        c.recip = tab[k]; c.recipm1 = tab[S + k]; c.c1 = tab[2 * S + k]; c.c2 = tab[3 * S + k];
+        c.lb = tab[4 * S + k]; c.dl = tab[5 * S + k] - c.lb;
+        c.sa = tab[6 * S + k]; c.sb = tab[7 * S + k];
+        c.last = (k == 0);
+        return c;
+    }
+    static __device__ __forceinline__ bool draws_z(const Coef& c) { return LvRule::draws_z(c); }
+    static __device__ __forceinline__ float update(const Coef& c, float xt, float eps, float w, float z, float z2, float xb,
+                                                   bool inside, int noise_bcs, int clip) {
+        return LvRule::update(c, xt, eps, w, z, z2, xb, inside, noise_bcs, clip);
+    }
+};
+
+// DdimRule on the eps_hat half of a learned-variance model's output: the same table, coefficients and update, eps_hat read
+// at the 2F stride, w never loaded (the DDIM variance is the table's sigma).
+struct DdimLvRule : DdimRule {
+    static constexpr int eps_planes = 2;
+};
+
 // Skeleton 1: z and z2 are tensors.  One block row per (b, f) plane, one element per lane and trip.  A NULL noise tensor
 // reads as "no noise" rather than being dereferenced (the host cannot see the step index); x_bcs, z, z2 and w are read
 // only where the step uses them.
@@ -665,7 +704,7 @@ reverse_step_kernel(Rule rule, const float* __restrict__ x_t, const float* __res
     const int plane = blockIdx.y;
     const int64_t base = (int64_t)plane * V;
     int64_t ebase = base, wbase = 0;
-    if (Rule::reads_w) {  // sample b: F planes of eps_hat, then F of w
+    if (Rule::eps_planes == 2) {  // sample b: F planes of eps_hat, then F of w
         const int b = plane / F, f = plane - b * F;
         ebase = ((int64_t)b * 2 * F + f) * V;
         wbase = ebase + (int64_t)F * V;
@@ -700,8 +739,8 @@ reverse_step_rng_kernel(Rule rule, const float* __restrict__ x_t, const float* _
     const int64_t base4 = (int64_t)blockIdx.y * n4;
     const int64_t v4 = V >> 2;
     const float4* xt4 = reinterpret_cast<const float4*>(x_t) + base4;
-    const float4* e4 = reinterpret_cast<const float4*>(eps) + (Rule::reads_w ? 2 : 1) * base4;
-    const float4* w4 = e4 + n4;  // reads_w: sample b holds F planes of eps_hat, then F of w
+    const float4* e4 = reinterpret_cast<const float4*>(eps) + Rule::eps_planes * base4;
+    const float4* w4 = e4 + n4;  // eps_planes == 2: sample b holds F planes of eps_hat, then F of w
     const float4* xb4 = reinterpret_cast<const float4*>(x_bcs) + base4;
     const uchar4* m4 = reinterpret_cast<const uchar4*>(mask);
     float4* o4 = reinterpret_cast<float4*>(out) + base4;
@@ -865,6 +904,44 @@ extern "C" int tdx_ddim_step_rng(const float* x_t, const float* eps, const float
     TDX_CHECK_ARG(tab && S > 0 && tau && t);
     return reverse_step_rng_launch(DdimRule{tab, S}, x_t, eps, x_bcs, mask, k, noise_bcs, clip, out, B, F, V, seed, stream_ids,
                                    offset_dev, stream, [&](uint64_t by) {
+        hipLaunchKernelGGL(advance_ddim_step, dim3(1), dim3(1), 0, as_stream(stream), offset_dev, by, k, tau, S, t);
+    });
+}
+
+extern "C" int tdx_p_sample_step_lv_respaced(const float* x_t, const float* model_out, const float* z, const float* z2,
+                                             const float* x_bcs, const uint8_t* mask, const float* tab, int S,
+                                             const int64_t* k, const int64_t* tau, const int64_t* t, int noise_bcs, int clip,
+                                             float* out, int B, int F, int64_t V, void* stream) {
+    TDX_CHECK_ARG(tab && S > 0 && tau && t);
+    return reverse_step_launch(LvRespacedRule{tab, S}, x_t, model_out, z, z2, x_bcs, mask, k, noise_bcs, clip, out, B, F, V,
+                               stream);
+}
+extern "C" int tdx_p_sample_step_lv_respaced_rng(const float* x_t, const float* model_out, const float* x_bcs,
+                                                 const uint8_t* mask, const float* tab, int S, int64_t* k, const int64_t* tau,
+                                                 int64_t* t, int noise_bcs, int clip, float* out, int B, int F, int64_t V,
+                                                 uint64_t seed, const uint64_t* stream_ids, uint64_t* offset_dev,
+                                                 void* stream) {
+    TDX_CHECK_ARG(tab && S > 0 && tau && t);
+    return reverse_step_rng_launch(LvRespacedRule{tab, S}, x_t, model_out, x_bcs, mask, k, noise_bcs, clip, out, B, F, V, seed,
+                                   stream_ids, offset_dev, stream, [&](uint64_t by) {
+        hipLaunchKernelGGL(advance_ddim_step, dim3(1), dim3(1), 0, as_stream(stream), offset_dev, by, k, tau, S, t);
+    });
+}
+
+extern "C" int tdx_ddim_step_lv(const float* x_t, const float* model_out, const float* z, const float* z2, const float* x_bcs,
+                                const uint8_t* mask, const float* tab, int S, const int64_t* k, const int64_t* tau,
+                                const int64_t* t, int noise_bcs, int clip, float* out, int B, int F, int64_t V, void* stream) {
+    TDX_CHECK_ARG(tab && S > 0 && tau && t);
+    return reverse_step_launch(DdimLvRule{{tab, S}}, x_t, model_out, z, z2, x_bcs, mask, k, noise_bcs, clip, out, B, F, V,
+                               stream);
+}
+extern "C" int tdx_ddim_step_lv_rng(const float* x_t, const float* model_out, const float* x_bcs, const uint8_t* mask,
+                                    const float* tab, int S, int64_t* k, const int64_t* tau, int64_t* t, int noise_bcs,
+                                    int clip, float* out, int B, int F, int64_t V, uint64_t seed, const uint64_t* stream_ids,
+                                    uint64_t* offset_dev, void* stream) {
+    TDX_CHECK_ARG(tab && S > 0 && tau && t);
+    return reverse_step_rng_launch(DdimLvRule{{tab, S}}, x_t, model_out, x_bcs, mask, k, noise_bcs, clip, out, B, F, V, seed,
+                                   stream_ids, offset_dev, stream, [&](uint64_t by) {
         hipLaunchKernelGGL(advance_ddim_step, dim3(1), dim3(1), 0, as_stream(stream), offset_dev, by, k, tau, S, t);
     });
 }

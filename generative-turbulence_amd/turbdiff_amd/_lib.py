@@ -95,6 +95,10 @@ SIGNATURES = {
     "tdx_p_sample_step_lv_rng": (_i, [_vp] * 6 + [_i, _vp, _i, _i, _vp, _i, _i, _i64, _u64, _vp, _vp, _vp]),
     "tdx_ddim_step": (_i, [_vp] * 7 + [_i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i64, _vp]),
     "tdx_ddim_step_rng": (_i, [_vp] * 5 + [_i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i64, _u64, _vp, _vp, _vp]),
+    "tdx_p_sample_step_lv_respaced": (_i, [_vp] * 7 + [_i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i64, _vp]),
+    "tdx_p_sample_step_lv_respaced_rng": (_i, [_vp] * 5 + [_i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i64, _u64, _vp, _vp, _vp]),
+    "tdx_ddim_step_lv": (_i, [_vp] * 7 + [_i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i64, _vp]),
+    "tdx_ddim_step_lv_rng": (_i, [_vp] * 5 + [_i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i64, _u64, _vp, _vp, _vp]),
     "tdx_masked_loss": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _i, _i64, _vp, _vp]),
     "tdx_masked_loss_dyn": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _vp, _vp]),
     "tdx_masked_loss_workspace_bytes": (_sz, []),

@@ -717,15 +717,22 @@ class GaussianDiffusion(nn.Module):
 
     @torch.no_grad()
     def p_sample_loop(self, x_bcs, C, cell_idx, pbar=False, start_from: int | None = None, noise_fn=None, seed=None,
-                      trajectory_ids=None, sampling_timesteps: int | None = None, eta: float = 0.0):
+                      trajectory_ids=None, sampling_timesteps: int | None = None, eta: float = 0.0,
+                      sampling_method: str | None = None):
         """Ancestral sampling (reference ddpm.py:767-816), or with `sampling_timesteps = S` the generalized DDIM sampler
         (Song et al. 2021) over S of the training timesteps, `schedules.ddim_timesteps`: eta = 0 deterministic given
         x_T, eta = 1 the posterior variance of the sub-sampled chain (NOT the fixed-large variance of the ancestral loop, so
         S = T, eta = 1 is not expected to reproduce it).  Same routes, same noise order (z is consumed at eta = 0 too, and
-        ignored); ValueError with learned variances, S outside [1, start_from or T] or eta outside [0, 1].
+        ignored); ValueError for S outside [1, start_from or T] or eta outside [0, 1].
         With learned variances the ancestral loop scales the noise per voxel (ddpm.py:732-741), on the same routes: the
         default call draws its noise from the counter-based generator below, not from `torch.randn_like` (which only
-        TDX_GRAPH_SAMPLER=0 still uses), and takes `seed` / `trajectory_ids` like the fixed-variance model.
+        TDX_GRAPH_SAMPLER=0 still uses), and takes `seed` / `trajectory_ids` like the fixed-variance model.  Over S of T
+        steps such a model is sampled only on request: `sampling_timesteps = S` alone raises ValueError, as it always has;
+        `sampling_method="respaced"` (eta must be 0) takes the ancestral step of the shorter chain over the same tau, the
+        learned variance interpolating between that chain's beta' and beta~' (Nichol & Dhariwal 2021);
+        `sampling_method="ddim"` takes the DDIM step on the eps_hat half of the output and never reads w.  Both re-noise BC
+        cells under noise_bcs at the level of the state produced, as DDIM does.  For a fixed-variance model
+        `sampling_method` may be None or "ddim" (the same sampler); the whole table is `sampling.check_sampling_arguments`.
 
         Default (`noise_fn is None`): the hipGraph-captured reverse step of `sampling.GraphSampler`, replayed T times --
         this is what `DiffusionTrainer.sample`, `tools/eval_ckpt.py` and a `dropin` user get.  Noise comes from the
@@ -737,24 +744,28 @@ class GaussianDiffusion(nn.Module):
         input shape and pointed at the new batch / geometry by copies (`GraphSampler.rebind`); a weight update re-captures.
         With `noise_fn(like)` -- injected noise in the reference's drawing order (x_T; then per step t > 0: z, and z' if
         noise_bcs), the golden tests -- or TDX_GRAPH_SAMPLER=0 the loop runs eagerly, one launch sequence per step."""
-        if sampling_timesteps is not None:
-            from ..sampling import check_ddim_arguments
+        update = None
+        if sampling_timesteps is not None or sampling_method is not None:
+            from ..sampling import check_sampling_arguments
 
-            check_ddim_arguments(self, sampling_timesteps, eta, start_from)
+            update = check_sampling_arguments(self, sampling_timesteps, eta, start_from, sampling_method)
         if noise_fn is None and GRAPH_SAMPLER and x_bcs.is_cuda and hasattr(self.model, "encode_local"):
-            return self._graph_sample(x_bcs, C, cell_idx, pbar, start_from, seed, trajectory_ids, sampling_timesteps, eta)
+            return self._graph_sample(x_bcs, C, cell_idx, pbar, start_from, seed, trajectory_ids, sampling_timesteps, eta,
+                                      sampling_method)
+        if update is not None:
+            return self._eager_ddim_sample(x_bcs, C, cell_idx, pbar, start_from, noise_fn, int(sampling_timesteps), float(eta),
+                                           update)
         if self.learned_variances:
             return self._general_sample(x_bcs, C, cell_idx, pbar, start_from, noise_fn)
-        if sampling_timesteps is not None:
-            return self._eager_ddim_sample(x_bcs, C, cell_idx, pbar, start_from, noise_fn, int(sampling_timesteps), float(eta))
         return self._eager_sample(x_bcs, C, cell_idx, pbar, start_from, noise_fn)
 
-    def _graph_sample(self, x_bcs, C, cell_idx, pbar, start_from, seed, trajectory_ids, sampling_timesteps=None, eta=0.0):
+    def _graph_sample(self, x_bcs, C, cell_idx, pbar, start_from, seed, trajectory_ids, sampling_timesteps=None, eta=0.0,
+                      sampling_method=None):
         from ..sampling import GraphSampler
 
         nonce = int(torch.randint(0, 2**31 - 1, (1,)).item()) if seed is None else int(seed) % (2**31 - 1)
         x_bcs = x_bcs.contiguous().float()
-        sig = GraphSampler.signature_of(self, x_bcs, C, sampling_timesteps, eta)
+        sig = GraphSampler.signature_of(self, x_bcs, C, sampling_timesteps, eta, sampling_method)
         cache = self.graph_samplers()
         gs = cache.get(sig)
         if gs is None:
@@ -762,7 +773,8 @@ class GaussianDiffusion(nn.Module):
             # captured sampler each; all of them capture on ONE stream, hence share one scratch arena
             shared = next(iter(cache.values()))._capture_stream if cache else None
             gs = cache[sig] = GraphSampler(self, x_bcs, C, cell_idx, seed=0, trajectory_ids=trajectory_ids, nonce=nonce,
-                                           capture_stream=shared, sampling_timesteps=sampling_timesteps, eta=eta)
+                                           capture_stream=shared, sampling_timesteps=sampling_timesteps, eta=eta,
+                                           sampling_method=sampling_method)
             while len(cache) > MAX_GRAPH_SAMPLERS:
                 cache.popitem(last=False)
         else:
@@ -843,14 +855,20 @@ class GaussianDiffusion(nn.Module):
             x_t, eps, z, z2, xb, mask, self.step_tables, self.num_timesteps, ts[t : t + 1], self.noise_bcs, self.clip_denoised)
         return self._eager_loop(x_bcs, C, cell_idx, pbar, start_from, noise_fn, ts, step)
 
-    def _eager_ddim_sample(self, x_bcs, C, cell_idx, pbar, start_from, noise_fn, S, eta):
-        """The DDIM loop over `ops.ddim_step`; noise in the ancestral order."""
+    def _eager_ddim_sample(self, x_bcs, C, cell_idx, pbar, start_from, noise_fn, S, eta, update="ddim"):
+        """The loop over S of the training timesteps on the noise-tensor entry of `update` (sampling.
+        check_sampling_arguments): `ops.ddim_step`, or for a learned-variance model `ops.p_sample_step_lv_respaced` /
+        `ops.ddim_step_lv` on the decoder's [eps_hat | w]; noise in the ancestral order."""
         dev = x_bcs.device
         taus = schedules.ddim_timesteps(self.num_timesteps, S, start_from)
-        tab = schedules.ddim_tables(self.beta_schedule, self.num_timesteps, taus, eta).to(dev)
+        if update == "lv-respaced":
+            tab = schedules.respaced_tables(self.beta_schedule, self.num_timesteps, taus).to(dev)
+        else:
+            tab = schedules.ddim_tables(self.beta_schedule, self.num_timesteps, taus, eta).to(dev)
+        entry = {"ddim": ops.ddim_step, "lv-respaced": ops.p_sample_step_lv_respaced, "lv-ddim": ops.ddim_step_lv}[update]
         tau = torch.tensor(taus, dtype=torch.long, device=dev)
         ks = torch.arange(S, dtype=torch.long, device=dev)
-        step = lambda x_t, eps, z, z2, xb, mask, k: ops.ddim_step(
+        step = lambda x_t, eps, z, z2, xb, mask, k: entry(
             x_t, eps, z, z2, xb, mask, tab, ks[k : k + 1], tau, tau[k : k + 1], self.noise_bcs, self.clip_denoised)
         return self._eager_loop(x_bcs, C, cell_idx, pbar, start_from, noise_fn, tau, step)
 

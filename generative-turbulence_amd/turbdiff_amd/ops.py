@@ -12,6 +12,7 @@ the reference's shapes and float32 (so state_dicts round-trip). 
     attention        F.scaled_dot_product_attention                       attention.py:9-15
     q_sample / p_sample_step / masked_loss                                ddpm.py:745-852
     p_sample_step_lv / elbo_loss (learned variances)                      ddpm.py:732-741,853-870
+    ddim_step, p_sample_step_lv_respaced / ddim_step_lv (S of T steps)    not in the reference
 
 There is no CPU implementation: tensors must live on the GPU.
 """
@@ -988,7 +989,7 @@ def q_sample(x0, noise, sqrt_ac, sqrt_1mac, t, mask=None, keep_bcs=False):
 
 
 def _reverse_step(entry, lead, noise_bcs, clip, out, rng=()):
-    """What the six reverse-step entries share: B, F, V of the state, `out` made unless given (it may be x_t), and the
+    """What the ten reverse-step entries share: B, F, V of the state, `out` made unless given (it may be x_t), and the
     argument list -- `lead` (the entry's operands from the state x_t to its step index; tensors go as pointers), noise_bcs,
     clip, out, B, F, V, then `rng` = (seed, stream_ids, offset_dev) for the entries that draw their noise, and the stream."""
     x_t = lead[0]
@@ -1056,11 +1057,49 @@ def ddim_step_rng(x_t, eps, x_bcs, mask, tab, k_dev, tau_dev, t_dev, noise_bcs, 
                          (seed, stream_ids, offset_dev))
 
 
-def _ddim_steps(tab, tau_dev) -> int:
-    """S of a [6, S] float32 coefficient table and its int64 subsequence (the kernels index both by the device-side k)."""
-    if tab.dtype != torch.float32 or tab.ndim != 2 or tab.shape[0] != 6 or tau_dev.dtype != torch.int64 or tau_dev.numel() != tab.shape[1]:
-        raise ValueError(f"DDIM step: table {tuple(tab.shape)} {tab.dtype} and tau {tuple(tau_dev.shape)} {tau_dev.dtype} do not fit")
+def _ddim_steps(tab, tau_dev, rows: int = 6, what: str = "DDIM") -> int:
+    """S of a [rows, S] float32 coefficient table and its int64 subsequence (the kernels index both by the device-side k)."""
+    if tab.dtype != torch.float32 or tab.ndim != 2 or tab.shape[0] != rows or tau_dev.dtype != torch.int64 or tau_dev.numel() != tab.shape[1]:
+        raise ValueError(f"{what} step: table {tuple(tab.shape)} {tab.dtype} and tau {tuple(tau_dev.shape)} {tau_dev.dtype} do not fit")
     return tab.shape[1]
+
+
+def p_sample_step_lv_respaced(x_t, model_out, z, z2, x_bcs, mask, tab, k_dev, tau_dev, t_dev, noise_bcs, clip, out=None):
+    """The learned-variance update from tau[k] to tau[k-1] of the respaced chain: p_sample_step_lv's element with the
+    coefficients of tab = schedules.respaced_tables(...) on the device ([8, S]); model_out = (B, 2F, X, Y, Z) = [eps_hat | w];
+    k_dev / tau_dev / t_dev as for ddim_step.  z / z2 may be None where unused."""
+    _check_lv_output(x_t, model_out)
+    S = _ddim_steps(tab, tau_dev, 8, "respaced")
+    return _reverse_step("tdx_p_sample_step_lv_respaced", (x_t, model_out, z, z2, x_bcs, mask, tab, S, k_dev, tau_dev, t_dev),
+                         noise_bcs, clip, out)
+
+
+def p_sample_step_lv_respaced_rng(x_t, model_out, x_bcs, mask, tab, k_dev, tau_dev, t_dev, noise_bcs, clip, seed, stream_ids,
+                                  offset_dev, out=None):
+    """p_sample_step_lv_respaced with z (and z2) drawn in the kernel (layouts: p_sample_step_rng_supported); on the device it
+    then advances offset_dev, decrements k_dev and sets t_dev = tau[k] while a step is left."""
+    _check_lv_output(x_t, model_out)
+    S = _ddim_steps(tab, tau_dev, 8, "respaced")
+    return _reverse_step("tdx_p_sample_step_lv_respaced_rng", (x_t, model_out, x_bcs, mask, tab, S, k_dev, tau_dev, t_dev),
+                         noise_bcs, clip, out, (seed, stream_ids, offset_dev))
+
+
+def ddim_step_lv(x_t, model_out, z, z2, x_bcs, mask, tab, k_dev, tau_dev, t_dev, noise_bcs, clip, out=None):
+    """ddim_step on the eps_hat half of a learned-variance model's output (B, 2F, X, Y, Z) = [eps_hat | w]; the kernel strides
+    over w and never loads it.  tab = schedules.ddim_tables(...), as for ddim_step."""
+    _check_lv_output(x_t, model_out)
+    S = _ddim_steps(tab, tau_dev)
+    return _reverse_step("tdx_ddim_step_lv", (x_t, model_out, z, z2, x_bcs, mask, tab, S, k_dev, tau_dev, t_dev), noise_bcs,
+                         clip, out)
+
+
+def ddim_step_lv_rng(x_t, model_out, x_bcs, mask, tab, k_dev, tau_dev, t_dev, noise_bcs, clip, seed, stream_ids, offset_dev,
+                     out=None):
+    """ddim_step_lv with z (and z2) drawn in the kernel (layouts: p_sample_step_rng_supported); scalar updates as ddim_step_rng."""
+    _check_lv_output(x_t, model_out)
+    S = _ddim_steps(tab, tau_dev)
+    return _reverse_step("tdx_ddim_step_lv_rng", (x_t, model_out, x_bcs, mask, tab, S, k_dev, tau_dev, t_dev), noise_bcs, clip,
+                         out, (seed, stream_ids, offset_dev))
 
 
 class _MaskedLoss(torch.autograd.Function):

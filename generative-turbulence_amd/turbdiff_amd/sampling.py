@@ -18,6 +18,10 @@ table live in device memory next to t, so a replay still needs no new arguments.
 
 A model with learned variances (`diffusion.learned_variances`, Nichol & Dhariwal 2021) runs the same captured ancestral
 step with `tdx_p_sample_step_lv_rng` as its update: the decoder emits [eps_hat | w] and the noise is scaled per voxel.
+Over S of T steps such a model is sampled on request, `sampling_method=`: "respaced" is the ancestral step of the shorter
+chain over tau with the learned variance interpolating between its own beta' and beta~' (`tdx_p_sample_step_lv_respaced_rng`,
+an [8, S] table), "ddim" the DDIM step on the eps_hat half of the output (`tdx_ddim_step_lv_rng`, w never read).
+`check_sampling_arguments` is the one place that decides which update a call gets.
 """
 
 from __future__ import annotations
@@ -46,6 +50,41 @@ def check_ddim_arguments(diffusion, sampling_timesteps, eta, start_from=None):
     schedules.ddim_timesteps(diffusion.num_timesteps, sampling_timesteps, start_from)
 
 
+SAMPLING_METHODS = ("ddim", "respaced")
+
+
+def check_sampling_arguments(diffusion, sampling_timesteps, eta, start_from=None, sampling_method=None):
+    """Which update a sampling call gets: None = the ancestral loop over all T steps (fixed or learned variances), "ddim" =
+    the DDIM step of a fixed-variance model, "lv-respaced" / "lv-ddim" = the two samplers of a learned-variance model over
+    `sampling_timesteps` steps.  ValueError for every combination outside that: a method without a step count; a
+    learned-variance model with a step count and no method (a call that raised before the two samplers existed keeps
+    raising: they are opt-in); "respaced" for fixed variances (DDIM with eta covers the stochastic case there) or with
+    eta != 0 (it has no meaning there); an unknown method; S, start_from or eta out of range."""
+    if sampling_method is not None and sampling_method not in SAMPLING_METHODS:
+        raise ValueError(f"sampling_method = {sampling_method!r} is none of {SAMPLING_METHODS}")
+    if sampling_timesteps is None:
+        if sampling_method is not None:
+            raise ValueError(f"sampling_method = {sampling_method!r} needs sampling_timesteps")
+        return None
+    learned = bool(getattr(diffusion, "learned_variances", False))
+    if not learned:
+        if sampling_method == "respaced":
+            raise ValueError('sampling_method="respaced" is the sampler of a model with learned variances; a fixed-variance '
+                             'model is sampled over fewer steps by "ddim" (eta > 0 for a stochastic chain)')
+        check_ddim_arguments(diffusion, sampling_timesteps, eta, start_from)
+        return "ddim"
+    if sampling_method is None:
+        raise ValueError("sampling_timesteps with learned_variances=True needs a choice of sampler: "
+                         'sampling_method="respaced" (the ancestral step of the shorter chain, learned variance kept) or '
+                         'sampling_method="ddim" (DDIM on the eps_hat half of the output)')
+    if sampling_method == "respaced" and float(eta) != 0.0:
+        raise ValueError(f'eta = {eta} has no meaning for sampling_method="respaced": its variance is the learned one')
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError(f"eta = {eta} outside [0, 1]")
+    schedules.ddim_timesteps(diffusion.num_timesteps, sampling_timesteps, start_from)
+    return "lv-" + sampling_method
+
+
 # ---- the update rules of a GraphSampler `s`: (ops entry that draws its noise, ops entry on noise tensors, the operands
 # between the mask and noise_bcs, the scalar advance the second entry leaves to its caller).  Plain functions of the sampler:
 # stored on it they close over nothing, so they add no reference cycle that would keep its captured graph and pool alive.
@@ -64,6 +103,10 @@ _LEARNED_VARIANCES = (ops.p_sample_step_lv_rng, ops.p_sample_step_lv,
                       lambda s: (s.d.step_tables, s.d.posterior_log_var, s.d.num_timesteps, s.t), _advance_t)
 # x_{tau_k} -> x_{tau_{k-1}}, then k -= 1 and t = tau[k] on the device
 _DDIM = (ops.ddim_step_rng, ops.ddim_step, lambda s: (s.ddim_table, s.k, s.tau, s.t), _advance_ddim)
+# the same walk for a model with learned variances (the table is [8, S] for the first, [6, S] for the second)
+_LV_RESPACED = (ops.p_sample_step_lv_respaced_rng, ops.p_sample_step_lv_respaced, _DDIM[2], _advance_ddim)
+_LV_DDIM = (ops.ddim_step_lv_rng, ops.ddim_step_lv, _DDIM[2], _advance_ddim)
+_RULES = {"ddim": _DDIM, "lv-respaced": _LV_RESPACED, "lv-ddim": _LV_DDIM}
 
 
 class GraphSampler:
@@ -73,12 +116,13 @@ class GraphSampler:
     p_sample_loop` keeps one sampler per input shape and re-uses its graph from call to call."""
 
     def __init__(self, diffusion, x_bcs, C, cell_idx, seed: int = 0, trajectory_ids=None, use_graph: bool = True, nonce: int = 0,
-                 capture_stream=None, sampling_timesteps: int | None = None, eta: float = 0.0):
+                 capture_stream=None, sampling_timesteps: int | None = None, eta: float = 0.0,
+                 sampling_method: str | None = None):
         self.d = diffusion
         self.sampling_timesteps = None if sampling_timesteps is None else int(sampling_timesteps)
         self.eta = float(eta)
-        if self.sampling_timesteps is not None:
-            check_ddim_arguments(diffusion, self.sampling_timesteps, self.eta)
+        self.sampling_method = sampling_method
+        update = check_sampling_arguments(diffusion, self.sampling_timesteps, self.eta, None, sampling_method)
         self.x_bcs = x_bcs.detach().float().contiguous().clone()
         self.C = {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in C.items()} if isinstance(C, dict) else C
         B = self.x_bcs.shape[0]
@@ -94,12 +138,15 @@ class GraphSampler:
         self.stream_ids = torch.tensor(self._sids(ids, nonce), dtype=torch.int64, device=dev)
         self.offset = torch.zeros(1, dtype=torch.int64, device=dev)
         self.t = torch.zeros(1, dtype=torch.int64, device=dev)
-        # DDIM: step index k into the subsequence tau and the [6, S] coefficient table, all on the device (the shapes are
-        # fixed by S, so `reset(start_from)` refills them under a captured graph)
+        # S of T steps: step index k into the subsequence tau and the coefficient table ([6, S] DDIM rows, or the [8, S]
+        # rows of the respaced chain), all on the device (the shapes are fixed by S, so `reset(start_from)` refills them
+        # under a captured graph)
         S = self.sampling_timesteps
+        self._update = update
+        rows = len(schedules.RESPACED_PACKED_ORDER if update == "lv-respaced" else schedules.DDIM_PACKED_ORDER)
         self.k = None if S is None else torch.zeros(1, dtype=torch.int64, device=dev)
         self.tau = None if S is None else torch.zeros(S, dtype=torch.int64, device=dev)
-        self.ddim_table = None if S is None else torch.zeros(len(schedules.DDIM_PACKED_ORDER), S, dtype=torch.float32, device=dev)
+        self.ddim_table = None if S is None else torch.zeros(rows, S, dtype=torch.float32, device=dev)
         self._taus = None  # host copy of what self.tau / self.ddim_table hold
         self.x_t = torch.empty_like(self.x_bcs)
         # noise drawn inside the update kernel (tdx_p_sample_step_rng) unless the layout rules that out; only then do the
@@ -115,7 +162,8 @@ class GraphSampler:
             self.enc = diffusion.model.encode_local(self.C)
         self.c_table = None  # (T, c_dim) conditioning vectors per timestep (DenoisingModel.conditioning_table) or None
         self._table_versions = None
-        rule = _DDIM if S is not None else (_LEARNED_VARIANCES if getattr(diffusion, "learned_variances", False) else _ANCESTRAL)
+        rule = _RULES[update] if update is not None else (
+            _LEARNED_VARIANCES if getattr(diffusion, "learned_variances", False) else _ANCESTRAL)
         self._fused, self._plain, self._operands, self._advance = rule  # the update, chosen once
         self._refresh_tables()
         self.reset()
@@ -126,22 +174,28 @@ class GraphSampler:
         return [(int(nonce) << 32) | int(i) for i in ids]
 
     @staticmethod
-    def signature_of(diffusion, x_bcs, C, sampling_timesteps=None, eta=0.0):
+    def signature_of(diffusion, x_bcs, C, sampling_timesteps=None, eta=0.0, sampling_method=None):
         """What must match for `rebind`: shapes / dtypes of everything the captured step reads, and the switches the
         captured step was built under.  The last two entries name the update the step applies: None = the ancestral step
         with fixed variances, "learned-variances" = the ancestral step with the per-voxel variance (read with getattr:
-        stand-ins for a diffusion need not carry the attribute), an int = the DDIM subsequence length (which excludes
-        learned variances, `check_ddim_arguments`); and eta."""
+        stand-ins for a diffusion need not carry the attribute), an int = the DDIM subsequence length of a fixed-variance
+        model, ("learned-variances", method, S) = one of the two samplers of a learned-variance model over S steps; and
+        eta.  `sampling_method` changes the signature of no call that leaves it out."""
         c = tuple(sorted((str(k), tuple(v.shape), str(v.dtype)) for k, v in C.items() if torch.is_tensor(v))) \
             if isinstance(C, dict) else None
         m = diffusion.model
+        learned = getattr(diffusion, "learned_variances", False)
+        if sampling_timesteps is None:
+            update = "learned-variances" if learned else None
+        elif learned and sampling_method is not None:
+            update = ("learned-variances", str(sampling_method), int(sampling_timesteps))
+        else:
+            update = int(sampling_timesteps)
         return (tuple(x_bcs.shape), str(x_bcs.device), c, getattr(m, "compute_dtype", None), getattr(m, "conv_impl", None),
-                L.conv_impl(), diffusion.noise_bcs, diffusion.clip_denoised, diffusion.num_timesteps,
-                int(sampling_timesteps) if sampling_timesteps is not None
-                else ("learned-variances" if getattr(diffusion, "learned_variances", False) else None), float(eta))
+                L.conv_impl(), diffusion.noise_bcs, diffusion.clip_denoised, diffusion.num_timesteps, update, float(eta))
 
     def signature(self):
-        return self.signature_of(self.d, self.x_bcs, self.C, self.sampling_timesteps, self.eta)
+        return self.signature_of(self.d, self.x_bcs, self.C, self.sampling_timesteps, self.eta, self.sampling_method)
 
     @torch.no_grad()
     def rebind(self, x_bcs, C, cell_idx, nonce=None, trajectory_ids=None):
@@ -206,8 +260,8 @@ class GraphSampler:
 
     @torch.no_grad()
     def reset(self, start_from: int | None = None):
-        """x_T ~ N(0, I) (or q_sample(x_bcs, start_from - 1)); t <- T - 1; RNG offset <- 0.  DDIM: tau and the table are
-        refilled when `start_from` changes them; k <- S - 1, t <- tau[S - 1]."""
+        """x_T ~ N(0, I) (or q_sample(x_bcs, start_from - 1)); t <- T - 1; RNG offset <- 0.  S of T steps: tau and the
+        table are refilled when `start_from` changes them; k <- S - 1, t <- tau[S - 1]."""
         d = self.d
         self.offset.zero_()
         T = d.num_timesteps if start_from is None else start_from
@@ -219,7 +273,9 @@ class GraphSampler:
             taus = schedules.ddim_timesteps(d.num_timesteps, steps, start_from)
             if taus != self._taus:
                 self.tau.copy_(torch.tensor(taus, dtype=torch.int64))
-                self.ddim_table.copy_(schedules.ddim_tables(d.beta_schedule, d.num_timesteps, taus, self.eta))
+                self.ddim_table.copy_(
+                    schedules.respaced_tables(d.beta_schedule, d.num_timesteps, taus) if self._update == "lv-respaced"
+                    else schedules.ddim_tables(d.beta_schedule, d.num_timesteps, taus, self.eta))
                 self._taus = taus
             self.k.fill_(steps - 1)
             self.t.fill_(taus[-1])

@@ -133,9 +133,7 @@ def ddim_tables(beta_schedule: str, T: int, taus, eta: float, dtype: torch.dtype
     eta = float(eta)
     if not 0.0 <= eta <= 1.0:
         raise ValueError(f"eta = {eta} outside [0, 1]")
-    taus = [int(t) for t in taus]
-    if not taus or taus[0] < 0 or taus[-1] >= T or any(b <= a for a, b in zip(taus, taus[1:])):
-        raise ValueError(f"taus must be a strictly increasing subsequence of 0 .. {T - 1}")
+    taus = _checked_taus(taus, T)
     abar = torch.cumprod(1.0 - betas_for(beta_schedule, T).to(torch.float64), dim=0)
     a = abar[torch.tensor(taus, dtype=torch.int64)]
     p = torch.nn.functional.pad(a[:-1], (1, 0), value=1.0)
@@ -150,6 +148,54 @@ def ddim_tables(beta_schedule: str, T: int, taus, eta: float, dtype: torch.dtype
         "sqrt_one_minus_p": torch.sqrt(1.0 - p),
     }
     return torch.stack([rows[k] for k in DDIM_PACKED_ORDER]).to(dtype).contiguous()
+
+
+# order of the 8 rows of the packed [8, S] array consumed by tdx_p_sample_step_lv_respaced (column k = step k of the
+# subsequence): the step tables of the SHORTER chain whose cumulative products are a = abar[tau_k], p = abar[tau_{k-1}]
+# (1 at k = 0), i.e. beta' = 1 - a / p and beta~' = beta' (1 - p) / (1 - a) (Nichol & Dhariwal 2021, respacing)
+RESPACED_PACKED_ORDER = (
+    "sqrt_recip_a",       # rsqrt(a)
+    "sqrt_recipm1_a",     # sqrt(1 / a - 1)
+    "coef1",              # beta' sqrt(p) / (1 - a)
+    "coef2",              # (1 - p) sqrt(a / p) / (1 - a)
+    "log_beta",           # log beta'
+    "posterior_log_var",  # log beta~' for k >= 1; column 0 = log_beta[0] (beta~'_0 = 0, and step 0 reads no variance)
+    "sqrt_p",             # sqrt(p)
+    "sqrt_one_minus_p",   # sqrt(1 - p)
+)
+
+
+def _checked_taus(taus, T: int) -> list[int]:
+    taus = [int(t) for t in taus]
+    if not taus or taus[0] < 0 or taus[-1] >= T or any(b <= a for a, b in zip(taus, taus[1:])):
+        raise ValueError(f"taus must be a strictly increasing subsequence of 0 .. {T - 1}")
+    return taus
+
+
+def respaced_tables(beta_schedule: str, T: int, taus, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """[8, S] coefficients of the learned-variance ancestral step over the subsequence `taus` (rows: RESPACED_PACKED_ORDER),
+    evaluated in float64 and rounded once.  taus = range(T) gives the training chain's own tables up to float64 rounding
+    (beta' = 1 - abar_t / abar_{t-1} against beta_t), except posterior_log_var[0], which the training chain extrapolates
+    and no step reads."""
+    taus = _checked_taus(taus, T)
+    abar = torch.cumprod(1.0 - betas_for(beta_schedule, T).to(torch.float64), dim=0)
+    a = abar[torch.tensor(taus, dtype=torch.int64)]
+    p = torch.nn.functional.pad(a[:-1], (1, 0), value=1.0)
+    beta = 1.0 - a / p
+    lb = torch.log(beta)
+    plv = torch.log(beta * (1.0 - p) / (1.0 - a))
+    plv[0] = lb[0]  # log 0 otherwise
+    rows = {
+        "sqrt_recip_a": torch.rsqrt(a),
+        "sqrt_recipm1_a": torch.sqrt(1.0 / a - 1),
+        "coef1": beta * torch.sqrt(p) / (1.0 - a),
+        "coef2": (1.0 - p) * torch.sqrt(a / p) / (1.0 - a),
+        "log_beta": lb,
+        "posterior_log_var": plv,
+        "sqrt_p": torch.sqrt(p),
+        "sqrt_one_minus_p": torch.sqrt(1.0 - p),
+    }
+    return torch.stack([rows[k] for k in RESPACED_PACKED_ORDER]).to(dtype).contiguous()
 
 
 def nyquist_embedding_tables(dim: int, timesteps: int) -> tuple[torch.Tensor, torch.Tensor]:

@@ -159,9 +159,11 @@ class DiffusionTrainer(nn.Module):
         # backward pass, 2 (eps_hat - eps) / (B F n_cells), lands near 2^-3 (initial_loss_scale)
         self.loss_scale = None
         # sampling: None = the full ancestral chain; S = DDIM over S of the training timesteps with `sampling_eta`
-        # (GaussianDiffusion.p_sample_loop); what sample / sample_cells / validation_step / measure_sample_time use
+        # (GaussianDiffusion.p_sample_loop); what sample / sample_cells / validation_step / measure_sample_time use.
+        # `sampling_method`: None, or for a model with learned variances the sampler that S steps need, "respaced" / "ddim"
         self.sampling_timesteps = None
         self.sampling_eta = 0.0
+        self.sampling_method = None
         self._opt = self._sched = None
         self.ddp = None  # set to a parallel.BucketedDataParallel(self) for multi-GPU training
         self.stats = None
@@ -256,27 +258,30 @@ class DiffusionTrainer(nn.Module):
         return loss
 
     @torch.no_grad()
-    def sample(self, batch, start_from=None, noise_fn=None, sampling_timesteps=None, eta=None):
-        """diffusion.py:152-158: dense denormalised samples (B, F, X, Y, Z).  `sampling_timesteps` / `eta`, when given, stand in for
-        the trainer's `sampling_timesteps` / `sampling_eta` for this call."""
-        x = self._sample_normalized(batch, start_from, noise_fn, sampling_timesteps, eta)
+    def sample(self, batch, start_from=None, noise_fn=None, sampling_timesteps=None, eta=None, sampling_method=None):
+        """diffusion.py:152-158: dense denormalised samples (B, F, X, Y, Z).  `sampling_timesteps` / `eta` / `sampling_method`,
+        when given, stand in for the trainer's `sampling_timesteps` / `sampling_eta` / `sampling_method` for this call."""
+        x = self._sample_normalized(batch, start_from, noise_fn, sampling_timesteps, eta, sampling_method)
         if self._is_openfoam_batch(batch):
             return self.normalization.denormalize_grid(x, batch.stats)
         return self.denormalize_grid(x, batch.mean, batch.std)
 
     @torch.no_grad()
-    def sample_cells(self, batch, start_from=None, noise_fn=None, sampling_timesteps=None, eta=None):
+    def sample_cells(self, batch, start_from=None, noise_fn=None, sampling_timesteps=None, eta=None, sampling_method=None):
         """The samples as ``SampleStore.add_samples`` stores them (metrics.py:52-58): per variable the
         denormalised in-domain values, channels-last (B, n_cells, dims) -- one fused egress kernel."""
-        x = self._sample_normalized(batch, start_from, noise_fn, sampling_timesteps, eta)
+        x = self._sample_normalized(batch, start_from, noise_fn, sampling_timesteps, eta, sampling_method)
         return self.normalization.denormalized_cells(x, batch.data.metadata, batch.stats)
 
-    def _sample_normalized(self, batch, start_from, noise_fn, sampling_timesteps=None, eta=None):
+    def _sample_normalized(self, batch, start_from, noise_fn, sampling_timesteps=None, eta=None, sampling_method=None):
         x, C = self._model_input(batch)
         steps = self.sampling_timesteps if sampling_timesteps is None else sampling_timesteps
+        method = self.sampling_method if sampling_method is None else sampling_method
         kw = {}
         if steps is not None:
             kw.update(sampling_timesteps=steps, eta=self.sampling_eta if eta is None else eta)
+        if method is not None:
+            kw.update(sampling_method=method)  # without a step count p_sample_loop raises: a method needs one
         if noise_fn is None:
             # identically seeded ranks draw the same per-call nonce: the trajectory ids keep their noise streams apart
             # (rank r samples trajectories r B ... r B + B - 1 of the global set, whatever the sharding)

@@ -613,6 +613,45 @@ int tdx_ddim_step_rng(const float* x_t, const float* eps, const float* x_bcs, co
                       int64_t* k, const int64_t* tau, int64_t* t, int noise_bcs, int clip, float* out, int B, int F,
                       int64_t V, uint64_t seed, const uint64_t* stream_ids, uint64_t* offset_dev, void* stream);
 
+/* The learned-variance step over an increasing subsequence tau[0..S-1] of the training timesteps, from tau[k] to tau[k-1]:
+ * the ancestral step of the shorter chain whose cumulative products are abar[tau[.]] (Nichol & Dhariwal 2021, respacing); not
+ * in the reference.  model_out = (B, 2F, V) = [eps_hat | w] as for tdx_p_sample_step_lv.  tab = 8 consecutive f32 rows of
+ * length S, column k, with a = abar[tau[k]], p = abar[tau[k-1]] (1 at k = 0), beta' = 1 - a / p:
+ *   recip = rsqrt(a), recipm1 = sqrt(1/a - 1), c1 = beta' sqrt(p) / (1 - a), c2 = (1 - p) sqrt(a / p) / (1 - a),
+ *   lb = log beta', plv = log(beta' (1 - p) / (1 - a)) (plv[0] = lb[0]), sa = sqrt(p), sb = sqrt(1 - p)
+ * Per element, tdx_p_sample_step_lv's own function with these coefficients (same operations, same bits):
+ *   x0   = recip x_t - recipm1 eps_hat;  [!noise_bcs: x0 = x_t outside mask];  [clip +-1];   mean = c1 x0 + c2 x_t
+ *   k == 0:  out = mean, then out = x_bcs outside the mask
+ *   k  > 0:  inside the mask out = mean + exp((lb + sigmoid(w) (plv - lb)) / 2) z
+ *            noise_bcs: outside the mask out = sa x_bcs + sb z2
+ * i.e. boundary cells are re-noised at the level of the state PRODUCED, tau[k-1], as tdx_ddim_step does and for its reason.
+ * k, tau, t as for tdx_ddim_step; k outside [0, S) writes nothing.  Any V, any alignment.  z, z2 may be NULL when unused. */
+int tdx_p_sample_step_lv_respaced(const float* x_t, const float* model_out, const float* z, const float* z2,
+                                  const float* x_bcs, const uint8_t* mask, const float* tab, int S, const int64_t* k,
+                                  const int64_t* tau, const int64_t* t, int noise_bcs, int clip, float* out, int B, int F,
+                                  int64_t V, void* stream);
+
+/* The same step with its noise drawn inside the kernel (needs V % 4 == 0 and 16-byte aligned tensors): bit-identical to
+ * tdx_randn_batched(z, ...); [tdx_randn_batched(z2, ...) if noise_bcs;] tdx_p_sample_step_lv_respaced(...) with the same
+ * seed, stream ids and offset; counters as tdx_p_sample_step_lv_rng (n4 = F V / 4 over the F planes of the STATE).
+ * Afterwards, on the device: *offset_dev += (noise_bcs ? 2 : 1) * n4; *k -= 1; if (*k >= 0) *t = tau[*k]. */
+int tdx_p_sample_step_lv_respaced_rng(const float* x_t, const float* model_out, const float* x_bcs, const uint8_t* mask,
+                                      const float* tab, int S, int64_t* k, const int64_t* tau, int64_t* t, int noise_bcs,
+                                      int clip, float* out, int B, int F, int64_t V, uint64_t seed,
+                                      const uint64_t* stream_ids, uint64_t* offset_dev, void* stream);
+
+/* tdx_ddim_step on the eps_hat half of a learned-variance model's output: model_out = (B, 2F, V) = [eps_hat | w], eps_hat
+ * read at the 2F stride, w NEVER loaded (the variance is the table's sigma; w may hold anything).  Table, arithmetic and bits
+ * are tdx_ddim_step's on eps = model_out[:, :F]. */
+int tdx_ddim_step_lv(const float* x_t, const float* model_out, const float* z, const float* z2, const float* x_bcs,
+                     const uint8_t* mask, const float* tab, int S, const int64_t* k, const int64_t* tau, const int64_t* t,
+                     int noise_bcs, int clip, float* out, int B, int F, int64_t V, void* stream);
+
+/* ... with its noise drawn inside the kernel: tdx_ddim_step_rng's layout rules, counters and scalar updates. */
+int tdx_ddim_step_lv_rng(const float* x_t, const float* model_out, const float* x_bcs, const uint8_t* mask, const float* tab,
+                         int S, int64_t* k, const int64_t* tau, int64_t* t, int noise_bcs, int clip, float* out, int B, int F,
+                         int64_t V, uint64_t seed, const uint64_t* stream_ids, uint64_t* offset_dev, void* stream);
+
 /* Masked loss (ddpm.py:845-852): loss = mean_b mean_{f, cells} err(eps_hat, noise),
  * err = squared (l1 = 0) or absolute (l1 = 1) error.  n_cells = number of mask ones.
  * Writes loss[0] and, if grad != NULL, d loss / d eps_hat (zero outside the mask). */

@@ -16,7 +16,8 @@ paper table reports; ``--sample-metrics`` adds the reference's own ``SampleMetri
 expensive one (``tke-front``, ``tke-middle``, ``tke-back``, ``tke``, ``max-mean-tke-pos``, as the reference's
 eval_ckpt.py computes them with ``expensive_metrics=False``), ``--expensive-metrics`` also ``wasserstein`` (exact W2 by
 the batched device auction).  ``--sampling-steps N [--eta E]`` draws the samples with the DDIM sampler over N of the training
-timesteps instead of the full ancestral chain (what that does to the metrics has not been measured).  Their side files (``regions.npz``, ``max-mean-tke.npy``, ``mean-flow.h5``) come from an
+timesteps instead of the full ancestral chain (what that does to the metrics has not been measured); a checkpoint with
+learned variances also needs ``--sampling-method respaced|ddim`` for that (equally unmeasured).  Their side files (``regions.npz``, ``max-mean-tke.npy``, ``mean-flow.h5``) come from an
 optional ``side`` entry of the ``--cases`` blob, ``{case_name: {file name: value}}``; ``--synthetic`` cases bring their
 own (channel-aligned region blocks, a nominal max-mean-TKE position).  Those stand-ins are not the reference's regions, so
 ``wasserstein`` on them is not the paper's metric: for real cases ``tools/prepare_dataset.py`` writes the three side files
@@ -131,9 +132,10 @@ def sample_metrics(store, cases, stats, device, *, side=None, expensive=False, p
 
 def evaluate(ckpt: dict, cases, stats, device, *, overrides=(), seed=2883413570083077179, samples_path=None,
              eval_batch_size=None, val_samples=2, discard_first_seconds=0.0, start_from=None, compute_mode=None,
-             sampling_steps=None, eta=0.0):
+             sampling_steps=None, eta=0.0, sampling_method=None):
     """The body of eval_ckpt.py:43-76.  Returns (store, metrics dict, task).  `sampling_steps`: sample with the DDIM
-    sampler over that many of the training timesteps (and `eta`) instead of the full ancestral chain."""
+    sampler over that many of the training timesteps (and `eta`) instead of the full ancestral chain; `sampling_method`:
+    the sampler a learned-variance model takes for that ("respaced" / "ddim", GaussianDiffusion.p_sample_loop)."""
     from turbdiff_amd.data.ofles import InMemoryRepository, OpenFOAMDataset, OpenFOAMEvaluationSampler
     from turbdiff_amd.data.staging import DeviceStager
     from turbdiff_amd.models.metrics import LogTKESpectrumL2Distance, SampleStore
@@ -146,7 +148,7 @@ def evaluate(ckpt: dict, cases, stats, device, *, overrides=(), seed=28834135700
     task = DiffusionTrainer.from_config(config, max_train_steps=1, compute_mode=compute_mode)
     task.load_state_dict(ckpt["state_dict"], strict=True)
     task = task.to(device).eval()
-    task.sampling_timesteps, task.sampling_eta = sampling_steps, eta
+    task.sampling_timesteps, task.sampling_eta, task.sampling_method = sampling_steps, eta, sampling_method
 
     dataset = OpenFOAMDataset(InMemoryRepository(cases), stats, discard_first_seconds)
     bs = eval_batch_size or int(config["model"].get("eval_batch_size", 8))
@@ -195,6 +197,8 @@ def main():
     ap.add_argument("--sampling-steps", type=int, default=None,
                     help="DDIM sampling over this many of the training timesteps instead of the full ancestral chain")
     ap.add_argument("--eta", type=float, default=0.0, help="with --sampling-steps: 0 = deterministic DDIM ... 1 = posterior variance")
+    ap.add_argument("--sampling-method", default=None, choices=["ddim", "respaced"],
+                    help="with --sampling-steps on a model with learned variances: the respaced ancestral step or DDIM on eps_hat")
     ap.add_argument("--compute-mode", default=None, choices=[None, "f32", "f32s", "bf16", "fp16"])
     ap.add_argument("--sample-metrics", action="store_true", help="also print the reference's cheap sample metrics")
     ap.add_argument("--expensive-metrics", action="store_true", help="with --sample-metrics, also the Wasserstein metric")
@@ -219,7 +223,7 @@ def main():
     device = torch.device(args.device)
     store, metrics, _ = evaluate(ckpt, cases, stats, device, overrides=args.overrides, seed=args.seed,
                                  samples_path=samples_path, start_from=args.start_from, compute_mode=args.compute_mode,
-                                 sampling_steps=args.sampling_steps, eta=args.eta)
+                                 sampling_steps=args.sampling_steps, eta=args.eta, sampling_method=args.sampling_method)
     if args.sample_metrics or args.expensive_metrics:
         metrics.update(sample_metrics(store, cases, stats, device, side=side, expensive=args.expensive_metrics))
     for key in sorted(metrics):

@@ -13,6 +13,11 @@ one hipGraph-captured reverse step per replay (no collective inside the loop).
       # alternating: this captured step, the eager torch loop it replaces on the default route (`general_loop`, what
       # TDX_GRAPH_SAMPLER=0 runs) and the fixed-variance captured step (`fixed_variance`)
 
+  python tools/sample_bench.py --trajectories 8 --learned-variances --sampling-steps 50 --sampling-method respaced
+      # the learned-variance model over 50 of the 1000 timesteps (`respaced`: tdx_p_sample_step_lv_respaced_rng, `ddim`:
+      # tdx_ddim_step_lv_rng); its captured step and the captured T-step learned-variance step (`ancestral`) alternate in
+      # this process, --rounds times each
+
   python tools/sample_bench.py --trajectories 8 --actfn gelu --steps 50 --ab 3
       # the U-Net built with another of the reference's activations; --ab N: the captured step with models.ddpm.FUSE_ACTFNS on
       # (activation inside the GroupNorm kernels) and off (act = 0 pass + torch module per Block), N times each, alternating
@@ -35,12 +40,14 @@ ap.add_argument("--steps", type=int, default=0, help="time only this many revers
 ap.add_argument("--sampling-steps", type=int, default=None,
                 help="DDIM sampling over this many of the training timesteps; the ancestral loop is timed first, as `ancestral`")
 ap.add_argument("--eta", type=float, default=0.0, help="with --sampling-steps: 0 = deterministic DDIM ... 1 = posterior variance")
+ap.add_argument("--sampling-method", default=None, choices=["ddim", "respaced"],
+                help="with --learned-variances --sampling-steps: the sampler over the subsequence; see above")
 ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "f32", "f32s"])
 ap.add_argument("--no-graph", action="store_true")
 ap.add_argument("--learned-variances", action="store_true", help="out_features = 2F, learned_variances=True; see above")
 ap.add_argument("--actfn", default="silu", choices=["silu", "gelu", "relu", "softplus", "tanh"], help="activation of the U-Net")
 ap.add_argument("--ab", type=int, default=0, help="with --actfn: time FUSE_ACTFNS on and off alternately, this many times each")
-ap.add_argument("--rounds", type=int, default=3, help="with --learned-variances: how often the three sides are timed in turn")
+ap.add_argument("--rounds", type=int, default=3, help="with --learned-variances: how often the sides are timed in turn")
 a = ap.parse_args()
 if a.dtype == "f32s":  # fp32 tensors, split-precision convs
     import os
@@ -52,8 +59,8 @@ fixed = bench.build_model(dev, bench.MODE_DTYPE[a.dtype], timesteps=a.timesteps)
 diff = fixed
 if a.learned_variances:
     from turbdiff_amd.models.ddpm import DenoisingModel, GaussianDiffusion
-    if a.sampling_steps is not None:
-        ap.error("--sampling-steps needs fixed variances")
+    if (a.sampling_steps is None) != (a.sampling_method is None):
+        ap.error("--learned-variances takes --sampling-steps and --sampling-method together")
     torch.manual_seed(0)
     net = DenoisingModel(in_features=4, out_features=8, c_local_features=4, c_global_features=0, timesteps=a.timesteps, dim=32,
                          u_net_levels=4, norm_type="group")
@@ -110,7 +117,24 @@ def measure_general_loop(n):
 
 total = a.timesteps if a.sampling_steps is None else a.sampling_steps
 extra = {}
-if a.learned_variances:
+if a.learned_variances and a.sampling_steps is not None:
+    # the S-step sampler and the T-step learned-variance step it stands in for, alternating; both per-step figures are of
+    # min(--steps, S) replays (0 = S) of one captured step each
+    kw = dict(sampling_timesteps=a.sampling_steps, eta=a.eta, sampling_method=a.sampling_method)
+    dt, n, s = measure(total, **kw)
+    _, _, sa = measure(total)
+    sides = {a.sampling_method: [], "ancestral": []}
+    for _ in range(a.rounds):
+        dt, n, s = measure(total, s=s)
+        sides[a.sampling_method].append(1e3 * dt / n)
+        sides["ancestral"].append(1e3 * measure(total, s=sa)[0] / n)
+    med = lambda v: sorted(v)[len(v) // 2]
+    anc = med(sides["ancestral"])
+    extra = {"learned_variances": True, "sampling_steps": a.sampling_steps, "eta": a.eta, "sampling_method": a.sampling_method,
+             "rounds_ms_per_reverse_step": sides,
+             "ancestral": {"timed_steps": n, "ms_per_reverse_step": anc, "seconds_per_batch": 1e-3 * anc * a.timesteps}}
+    dt = 1e-3 * med(sides[a.sampling_method]) * n
+elif a.learned_variances:
     n_gen = min(a.steps, total) if a.steps > 0 else total
     measure_general_loop(2)  # warm-up
     dt, n, s = measure(total)
